@@ -36,6 +36,7 @@ Extra objects on the JSON line:
   cpu_baseline  the CPU oracle (C + OpenMP restatement of the reference kernels, oracle/) and the PyTorch-CPU splat
                 (oracle/torch_splat.py) timed on this box's host cores on a bounded sample (rank 0, N = 1 only), with
                 the parity of the GPU frames against the oracle (first / middle / last frame of the orbit).
+  dump_outputs  with ``--dump-outputs DIR``: the arrays of the last timed step written to DIR (names, shapes, sampling).
 """
 from __future__ import annotations
 
@@ -161,6 +162,7 @@ class Bench:
         self.extra = None
         self.layers = None
         self.model = None
+        self.keep_last, self.last = False, None   # --dump-outputs: the arrays of the last consumed step
         if key == "c4":   # the per-Gaussian normals SuGaR renders beside the colours (sugar_model.py:2174-2183)
             n = self.cloud.means3D / self.cloud.means3D.norm(dim=1, keepdim=True)
             self.extra = (n * 0.5 + 0.5).contiguous()
@@ -201,12 +203,14 @@ class Bench:
             return out["render"][:3], out["depth"][None], out["render"][3:4], out["radii"]
         if self.extra is not None:
             _n, color, depth, alpha, radii, _g, _b, _i, normal = out
+            if self.keep_last:
+                self.last_normal = normal
             return color, depth, alpha, radii
         return out
 
     def consume(self, slot, result, rgba, composed=None):
         from autovfx_amd.frame_parallel import pack_rgba8
-        color, _depth, alpha, _radii = result
+        color, depth, alpha, radii = result
         pack_rgba8(color, alpha, out=rgba[slot])
         if self.layers is not None:   # C5: the frame is the background layer of the composite (blend_all.py:236-300)
             from autovfx_amd.compositor import composite_frame
@@ -214,6 +218,12 @@ class Bench:
             bg_c = rgba[slot].permute(1, 2, 0).contiguous()   # planar RGBA8 -> the interleaved layout image files have
             composite_frame(bg_c, L["o_c"], L["o_d"], L["s_c"], L["s_d"], L["o_s_c"], L["o_gs_c"], L["o_gs_d"],
                             L["s_f_c"], L["s_f_d"], L["s_f_c_pre"], out=composed[slot])
+        if self.keep_last:   # (views of rgba / composed: copied out before the next run overwrites them)
+            self.last = [("color", color), ("depth", depth), ("alpha", alpha), ("radii", radii), ("rgba8", rgba[slot])]
+            if self.extra is not None:
+                self.last.append(("normal", self.last_normal))
+            if self.layers is not None:
+                self.last.append(("composed", composed[slot]))
 
     def run(self, frames, rgba, streams, side, composed=None):
         """Render `frames` (orbit indices) into rgba[0..]; S > 1: one host thread keeps S split calls in flight."""
@@ -354,6 +364,34 @@ def timed_regions(fn, regions, distributed, device, local=None):
     return out
 
 
+DUMP_BUDGET_BYTES = 64 * 10**6   # --dump-outputs: all files together
+DUMP_SAMPLE = 1 << 20            # elements kept of an array that does not fit the budget whole
+
+
+def dump_outputs(out_dir, arrays):
+    """``--dump-outputs DIR``: every (name, array) as DIR/<name>.npy in float32 (float64 stays float64), in the given
+    order.  An array is written whole while the running total stays within DUMP_BUDGET_BYTES, else as DUMP_SAMPLE elements
+    of its flattened values at indices drawn with a fixed seed, the same in every run and build.  Returns, per name, the
+    array's shape and the number of sampled elements (None: written whole)."""
+    os.makedirs(out_dir, exist_ok=True)
+    used, info = 0, {}
+    for name, t in arrays:
+        a = t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+        shape = list(a.shape)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+        sampled = None
+        if used + a.nbytes > DUMP_BUDGET_BYTES:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=min(a.size, DUMP_SAMPLE), replace=False))
+            a = a.reshape(-1)[idx]
+            sampled = int(a.size)
+            if used + a.nbytes > DUMP_BUDGET_BYTES:
+                raise SystemExit(f"--dump-outputs: {name} does not fit the {DUMP_BUDGET_BYTES} B budget even as a sample")
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        used += a.nbytes
+        info[name] = {"shape": shape, "sampled": sampled}
+    return info
+
+
 def quick(key, device, side, streams, steps, warmup, regions, boundary="op", gaussians=0):
     """A short run of another workload for the `also` object: median-region frames/s, single-stream stage times."""
     from autovfx_amd import _lib
@@ -455,6 +493,10 @@ def main():
                     help="add `frames_digest` to the line: SHA-256 of the RGBA8 frames rank 0 holds after the last timed region "
                          "(the gathered stack in frame order with N > 1 ranks / --force-distributed), so that the N > 1 code "
                          "path can be checked byte for byte against the N = 1 path (tests/test_rccl_gpu.py)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed regions, write what the last timed step computed (the forward call's colour, depth, "
+                         "alpha and radii, the packed RGBA8 frame; N > 1 ranks: the gathered frames) as DIR/<name>.npy, "
+                         "float32, at most 64 MB in all (a fixed, seeded sample of an array that does not fit)")
     ap.add_argument("--profile-run", action="store_true",
                     help="for rocprofv3: only warm-up + ONE timed region of uniform calls (no replay, statistics, baselines)")
     args = ap.parse_args()
@@ -589,7 +631,15 @@ def main():
             region()   # the gather path's own rehearsal: frame stack, receive buffers, RCCL's first gather (untimed)
         _lib.set_stage_timing(False)
         local_secs = []
+        b.keep_last = args.dump_outputs is not None
         secs = timed_regions(region, R, distributed, device, local=local_secs)
+        b.keep_last = False
+    dumped = None
+    if args.dump_outputs is not None and rank == 0:   # before anything else renders into rgba / composed
+        torch.cuda.synchronize()
+        arrays = b.last if b.last is not None else [("frames", frames_in_order(*last_frames[0]))]   # (the gather paths)
+        dumped = dump_outputs(args.dump_outputs, arrays)
+        b.last = arrays = None
     # what RCCL saw: the group's size and every rank's own rate over its own median region (all-gathered)
     n_ranks_seen, per_rank_fps = 1, None
     my_frames = len(my_ids) if strong else K
@@ -776,6 +826,8 @@ def main():
                                         "last_region_render_s": round(gather_stats.get("render_s", 0.0), 5),
                                         "last_region_gather_tail_ms": round(gather_stats.get("gather_tail_s", 0.0) * 1e3, 3),
                                         "per_rank_frames_per_s_rank0": round(K / max(1e-9, gather_stats.get("render_s", 0.0)), 1)}
+        if dumped is not None:
+            line["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if reference_on_gpu is not None:
             line["reference_on_gpu"] = reference_on_gpu
         if also is not None:

@@ -81,6 +81,33 @@ def test_bench_finds_the_committed_pmc_traffic():
     assert bench.pmc_traffic("c2") is None and bench.pmc_traffic(None) is None   # only the C3 passes are kept
 
 
+def test_bench_dump_outputs_keeps_to_its_budget_and_samples_the_same_elements(tmp_path):
+    """bench.py --dump-outputs: float32 .npy files, whole while they fit 64 MB, then a fixed seeded sample that two runs
+    (or two builds) draw at the same indices; the C3 frame's arrays come to at most 64 MB."""
+    import bench
+    H, W, P = 1080, 1920, 3_000_000
+    g = torch.Generator().manual_seed(0)
+    arrays = [("color", torch.rand(3, H, W, generator=g)), ("depth", torch.rand(1, H, W, generator=g)),
+              ("alpha", torch.rand(1, H, W, generator=g)), ("radii", torch.randint(0, 50, (P,), dtype=torch.int32, generator=g)),
+              ("rgba8", torch.randint(0, 256, (4, H, W), dtype=torch.uint8, generator=g))]
+    info = bench.dump_outputs(str(tmp_path / "a"), arrays)
+    again = bench.dump_outputs(str(tmp_path / "b"), arrays)
+    assert info == again and [n for n, _ in arrays] == list(info)
+    assert all(info[n]["sampled"] is None for n in ("color", "depth", "alpha", "radii")) and info["rgba8"]["sampled"] == bench.DUMP_SAMPLE
+    assert info["rgba8"]["shape"] == [4, H, W]
+    total = 0
+    for name, t in arrays:
+        a, b = np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy"))
+        assert a.dtype == np.float32 and np.array_equal(a, b)
+        total += (tmp_path / "a" / (name + ".npy")).stat().st_size
+        flat = t.numpy().reshape(-1).astype(np.float32)
+        if info[name]["sampled"] is None:
+            assert a.shape == tuple(t.shape) and np.array_equal(a.reshape(-1), flat)
+        else:
+            assert a.shape == (bench.DUMP_SAMPLE,) and np.isin(a, flat).all()
+    assert total <= 64 * 10**6
+
+
 def test_slab_policy_is_host_logic():
     """Which inference calls are cut into depth slabs (gsr_plan_slabs; no device needed): the measured configurations
     land where the A/B runs put them, and the knobs do what include/gsr.h says."""

@@ -1,6 +1,7 @@
 """autovfx_amd.install(): the import hook that puts this package's render() behind an unchanged AutoVFX process, and the
 gate that decides whether a model may be rendered from its raw parameter tensors.  CPU only: nothing here launches a kernel."""
 import importlib
+import json
 import os
 import subprocess
 import sys
@@ -181,7 +182,6 @@ def test_raw_parameter_gate(monkeypatch):
     assert renderer.raw_parameters(_Model(M=1)) is not None        # degree 0 only: an empty [P,0,3] rest tensor
 
 
-@pytest.mark.skipif(not os.path.isdir(GS), reason="reference tree not mounted")
 def test_a_subclass_that_overrides_one_getter_is_not_rendered_from_its_raw_tensors(monkeypatch):
     """render() on the raw path calls no getter; a subclass with, say, a masked ``get_opacity`` would be rendered
     (and differentiated) from ``_opacity`` as if the override were not there.  The gate sends such a model down the getters path."""
@@ -211,18 +211,61 @@ def test_a_subclass_that_overrides_one_getter_is_not_rendered_from_its_raw_tenso
     assert renderer.raw_parameters(Insists(*args)) is not None
 
 
+GATE_FACTS = os.path.join(ROOT, "tests", "golden", "reference_gaussian_model_gate.json")
+
+
+def _gate_facts(cls, inst):
+    """What raw_parameters() reads from a model: which class of the MRO defines each getter and as what, which activation
+    attributes hold the stock functions, which raw tensor attributes the constructor sets."""
+    getters = {}
+    for name in renderer._GETTERS:
+        owner = next((c for c in cls.__mro__ if name in c.__dict__), None)
+        if owner is not None:
+            getters[name] = type(owner.__dict__[name]).__name__ if owner is cls else f"inherited from {owner.__name__}"
+    return {"class": cls.__name__, "getters": getters,
+            "stock_activations": [a for a, fn in renderer._RAW_ACTIVATIONS if getattr(inst, a, None) is fn],
+            "raw_attributes": [a for a in renderer._RAW_ATTRS if hasattr(inst, a)]}
+
+
+def _class_from_gate_facts(facts):
+    """A class with exactly those facts (getter bodies are never called by the gate)."""
+    stock = dict(renderer._RAW_ACTIVATIONS)
+
+    def __init__(self, sh_degree):
+        for a in facts["stock_activations"]:
+            setattr(self, a, stock[a])
+        for a in facts["raw_attributes"]:
+            setattr(self, a, torch.empty(0))
+
+    ns = {"__init__": __init__}
+    for name, kind in facts["getters"].items():
+        assert kind in ("property", "function"), (name, kind)
+        ns[name] = property(lambda self: None) if kind == "property" else (lambda self, *a: None)
+    return type(facts["class"], (), ns)
+
+
 def test_the_references_own_gaussian_model_passes_the_gate(monkeypatch):
     """The class AutoVFX instantiates (scene/gaussian_model.py), imported unchanged: its attribute names, shapes and
-    activation functions are what raw_parameters() looks for."""
-    from test_render_mirror import _import_reference
-    ref = _import_reference("scene.gaussian_model")
-    r = ref.GaussianModel(3)
-    src = _Model(P=7)
-    for k, v in vars(src).items():
-        setattr(r, k, v)
+    activation functions are what raw_parameters() looks for.  What the gate reads from that class is committed in
+    tests/golden/reference_gaussian_model_gate.json; a class with those facts passes the gate, and wherever the reference tree
+    is mounted the reference's own class passes it too and its facts are the committed ones."""
+    with open(GATE_FACTS) as f:
+        facts = json.load(f)
+    facts.pop("what")
+    models = [_class_from_gate_facts(facts)]
+    if os.path.isdir(GS):
+        from test_render_mirror import _import_reference
+        ref = _import_reference("scene.gaussian_model")
+        assert _gate_facts(ref.GaussianModel, ref.GaussianModel(3)) == facts, "the committed snapshot is stale"
+        models.append(ref.GaussianModel)
     monkeypatch.setattr(torch.Tensor, "is_cuda", property(lambda self: True))
-    got = renderer.raw_parameters(r)
-    assert got is not None and got[0] is r._xyz and got[5] is r._features_rest
+    for cls in models:
+        r = cls(3)
+        src = _Model(P=7)
+        for k, v in vars(src).items():
+            setattr(r, k, v)
+        got = renderer.raw_parameters(r)
+        assert got is not None and got[0] is r._xyz and got[5] is r._features_rest, cls
 
 
 @pytest.mark.skipif(not os.path.isdir(GS), reason="reference tree not mounted")
