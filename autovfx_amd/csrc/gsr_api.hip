@@ -903,6 +903,25 @@ int gsr_png_encode(const uint8_t* pixels, int width, int height, int channels, i
     return GSR_OK;
 }
 
+int gsr_cube_to_equirect(const float* const* faces, int face_size, int channels, const float* const* depth_faces, const float* grid_u,
+                         const float* grid_v, const int32_t* grid_ceil, int height, int width, float* out, uint8_t* out_u8, float* out_depth,
+                         void* stream_) {
+    if (width <= 0 || width % 8 != 0) return fail(GSR_ERR_INVALID_ARG, "gsr_cube_to_equirect: the width (%d) must be a positive multiple of 8", width);
+    if (height < 2 || height > 65535) return fail(GSR_ERR_INVALID_ARG, "gsr_cube_to_equirect: bad height %d (2 .. 65535)", height);
+    if (face_size < 2 || face_size > 32768) return fail(GSR_ERR_INVALID_ARG, "gsr_cube_to_equirect: bad face size %d (2 .. 32768)", face_size);
+    if (channels < 1 || channels > 4) return fail(GSR_ERR_INVALID_ARG, "gsr_cube_to_equirect: %d channels (1 .. 4)", channels);
+    if (!faces || !grid_u || !grid_v || !grid_ceil || (!out && !out_u8 && !out_depth) || (out_depth && !depth_faces))
+        return fail(GSR_ERR_INVALID_ARG, "null pointer");
+    gsr::CubeFacePointers f = {}, d = {};
+    for (int k = 0; k < 6; ++k) {
+        if (!(f.p[k] = faces[k])) return fail(GSR_ERR_INVALID_ARG, "gsr_cube_to_equirect: face %d is null", k);
+        if (out_depth && !(d.p[k] = depth_faces[k])) return fail(GSR_ERR_INVALID_ARG, "gsr_cube_to_equirect: depth face %d is null", k);
+    }
+    GSR_HIP(gsr::launch_cube_to_equirect(f, d, face_size, channels, grid_u, grid_v, grid_ceil, height, width, out, out_u8, out_depth,
+                                         (hipStream_t)stream_));
+    return GSR_OK;
+}
+
 int gsr_pack_rgba8(const float* color, const float* alpha, uint8_t* rgba8, int width, int height, void* stream_) {
     if (width <= 0 || height <= 0) return fail(GSR_ERR_INVALID_ARG, "bad image size %dx%d", width, height);
     if (!color || !alpha || !rgba8) return fail(GSR_ERR_INVALID_ARG, "null pointer");

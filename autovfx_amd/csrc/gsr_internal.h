@@ -364,6 +364,15 @@ hipError_t launch_resize_rgba8_bilinear(const uint8_t* src, int src_w, int src_h
                                         hipStream_t stream);
 hipError_t launch_resize_f32_nearest(const float* src, int src_w, int src_h, float* dst, int dst_w, int dst_h, hipStream_t stream);
 
+// ---- panoramas (gsr_panorama.hip) ----
+// The six faces of a cube map, in the reference's dict order (front, right, back, left, up, down): planar [C,S,S] colour or [S,S] depth.
+struct CubeFacePointers { const float* p[6]; };
+// c2e(..., mode='bilinear') of the reference (gsr.h: gsr_cube_to_equirect); grid_u [W], grid_v [H], grid_ceil [W/4] as the host computes
+// them; any of out [H,W,C] / out_u8 [H,W,C] / out_depth [H,W] may be null (depth.p is read only when out_depth is set).
+hipError_t launch_cube_to_equirect(const CubeFacePointers& faces, const CubeFacePointers& depth, int S, int C, const float* grid_u,
+                                   const float* grid_v, const int* grid_ceil, int H, int W, float* out, uint8_t* out_u8, float* out_depth,
+                                   hipStream_t stream);
+
 // ---- the compositor's input files (gsr_layerio.hip) ----
 // The inflated IDAT stream of an 8-bit RGB / RGBA, non-interlaced PNG (device memory) -> RGBA8 [H,W,4] (alpha 255 for RGB).
 // scratch: png_unfilter_scratch_bytes(W, H) bytes, 16-byte aligned (0: the width is not supported).

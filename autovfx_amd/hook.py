@@ -21,7 +21,10 @@ AutoVFX reaches the rasterizer through two imports (paths under the reference tr
    frame, several frames are in flight, the four files of a frame are built on the GPU;
 4. a module named ``...sugar_model`` gets ``SuGaR.render_image_gaussian_rasterizer`` (two rasterizer calls over the same geometry) run with
    the binding's geometry reuse switched on for its duration: the second call costs one blend launch, same bits;
-5. every module named ``...gaussian_renderer`` -- already imported or imported later (a ``sys.meta_path`` hook) -- gets its
+5. a module named ``...render_panorama`` (``sugar/gaussian_splatting/render_panorama.py``) gets its ``render_panorama`` replaced by
+   ``autovfx_amd.panorama.render_panorama`` (same arguments, files and return value; the six faces in flight, the cube-to-equirect
+   resample and the PNG files on the GPU); the original stays reachable as ``<module>.reference_render_panorama``;
+6. every module named ``...gaussian_renderer`` -- already imported or imported later (a ``sys.meta_path`` hook) -- gets its
    ``render`` replaced by ``autovfx_amd.renderer.render`` (same signature, same result dictionary; the original stays
    reachable as ``<module>.reference_render``), and every already-imported module that holds the original function under
    any name (``from ... import render [as gs_render]``) is rebound too.
@@ -48,6 +51,7 @@ _TARGET_LEAF = "gaussian_renderer"
 _BLEND_LEAF = "blend_all"                # blender/blend_all.py: its blend_frames() is called at scene_representation.py:232
 _SCENE_LEAF = "scene_representation"     # scene_representation.py: SceneRepresentation.render_from_3DGS is the frame loop (:337-447)
 _SUGAR_LEAF = "sugar_model"              # sugar/sugar_scene/sugar_model.py: SuGaR.render_image_gaussian_rasterizer calls the rasterizer twice (:2141,2174)
+_PANO_LEAF = "render_panorama"           # sugar/gaussian_splatting/render_panorama.py: render_panorama() (:100-145), imported directly by its users
 _installed: Optional["_RendererHook"] = None
 patched_modules: List[str] = []          # names of the modules whose ``render`` was replaced (introspection / tests)
 _strict = True                           # install(strict=...): may a failure to load the render path break the importing process?
@@ -55,7 +59,8 @@ _gave_up = False                         # lenient mode: the render path could n
 
 
 def _is_target(fullname: str) -> bool:
-    return any(fullname == leaf or fullname.endswith("." + leaf) for leaf in (_TARGET_LEAF, _BLEND_LEAF, _SCENE_LEAF, _SUGAR_LEAF))
+    return any(fullname == leaf or fullname.endswith("." + leaf) for leaf in (_TARGET_LEAF, _BLEND_LEAF, _SCENE_LEAF, _SUGAR_LEAF,
+                                                                                  _PANO_LEAF))
 
 
 def _is_blend_module(name: str) -> bool:
@@ -131,6 +136,37 @@ def _patch_sugar_module(module: types.ModuleType) -> None:
         patched_modules.append(module.__name__)
 
 
+def _is_panorama_module(name: str) -> bool:
+    return name == _PANO_LEAF or name.endswith("." + _PANO_LEAF)
+
+
+def _our_render_panorama() -> Callable:
+    from .panorama import render_panorama
+    return render_panorama
+
+
+def _patch_panorama_module(module: types.ModuleType) -> None:
+    """``render_panorama`` (render_panorama.py:100-145) becomes autovfx_amd.panorama.render_panorama: same arguments, the same seven
+    files and the same return value.  The reference's function stays reachable as ``<module>.reference_render_panorama``."""
+    global _gave_up
+    original = module.__dict__.get("render_panorama")
+    if original is None or (getattr(original, "__module__", None) or "").startswith("autovfx_amd") or _gave_up:
+        return
+    try:
+        ours = _our_render_panorama()
+    except Exception as e:
+        if _strict:
+            raise
+        _gave_up = True
+        sys.stderr.write(f"[autovfx_amd] {module.__name__}.render_panorama left as the reference's: the panorama path could not be loaded "
+                         f"({e!r})\n")
+        return
+    module.reference_render_panorama = original
+    module.render_panorama = ours
+    if module.__name__ not in patched_modules:
+        patched_modules.append(module.__name__)
+
+
 def _our_render() -> Callable:
     from .renderer import render   # imports torch and loads libgsr_hip.so: only when a renderer module really appears
     return render
@@ -148,6 +184,9 @@ def _patch_renderer_module(module: types.ModuleType) -> None:
         return
     if _is_sugar_module(module.__name__):
         _patch_sugar_module(module)
+        return
+    if _is_panorama_module(module.__name__):
+        _patch_panorama_module(module)
         return
     if _is_blend_module(module.__name__):
         # the compositing step of the edit loop: ``blend_all.blend_frames(results_dir, cfg_path)`` (scene_representation.py:232) becomes
@@ -272,6 +311,9 @@ def uninstall() -> None:
             module.render = module.reference_render
         if module is not None and hasattr(module, "reference_blend_frames"):
             module.blend_frames = module.reference_blend_frames
+        if module is not None and "reference_render_panorama" in module.__dict__:
+            module.render_panorama = module.reference_render_panorama
+            del module.reference_render_panorama
         cls = getattr(module, "SceneRepresentation", None) if module is not None else None
         if isinstance(cls, type) and "reference_render_from_3DGS" in cls.__dict__:
             cls.render_from_3DGS = cls.reference_render_from_3DGS

@@ -42,10 +42,11 @@
 extern "C" {
 #endif
 
-/* 14 (round 6): + the compositor's input files -- gsr_png_unfilter(_batch), gsr_exr_unpack_channel, gsr_inflate_zlib_blocks, the host-side
+/* 15: + panoramas (gsr_cube_to_equirect).
+ * 14 (round 6): + the compositor's input files -- gsr_png_unfilter(_batch), gsr_exr_unpack_channel, gsr_inflate_zlib_blocks, the host-side
  * gsr_png_file_* / gsr_exr_file_* readers, gsr_upload.  13: + compressed frame files (gsr_png_encode_deflate, gsr_frame_files_deflate).
  * Additions only: a binding written against 12 works unchanged apart from the version it checks. */
-#define GSR_ABI_VERSION 14
+#define GSR_ABI_VERSION 15
 
 #if defined(__GNUC__)
 #define GSR_API __attribute__((visibility("default")))
@@ -287,6 +288,26 @@ GSR_API int gsr_frame_files_deflate(const float* color, const float* alpha, cons
                                     const uint8_t* turbo_lut, int width, int height, uint8_t* png_rgba, uint8_t* png_depth_preview,
                                     uint8_t* png_normal, float* npy_plane, uint8_t* work, uint8_t* png_scratch, uint64_t* png_lengths,
                                     void* stream);
+
+/* Panoramas (render_panorama.py:100-145, utils/py360_utils.py:7-65,201-239) -- ABI 15.  The six faces of a cube map rendered with a
+ * 90-degree field of view -> the equirectangular image c2e(faces, height, width, mode='bilinear', cube_format='dict') of the reference:
+ * its face type per pixel, its face coordinates (fp32 in its operation order, renormalised in fp64), its seam padding (two rows, then
+ * two columns taken from the neighbouring faces, with its index quirks: zeros in the first and last row of the up / down faces' column
+ * pads, the down face's column pads read from the first row pad of the right / left faces) and map_coordinates' bilinear weights, fp64
+ * sums.  faces[6]: a HOST array of six device pointers to planar fp32 [C,S,S] images (render()["render"]) in the reference's dict order
+ * front, right, back, left, up, down; C = 1 .. 4.  grid_u [width] / grid_v [height]: the fp32 angles equirect_uvgrid makes
+ * (linspace(-pi, pi, width), linspace(pi, -pi, height) / 2); grid_ceil [width / 4]: the int32 up-face ceiling per column of a quarter
+ * (height / 2 - round(arctan(cos(linspace(-pi, pi, width / 4) / 4)) * height / pi)); device memory, computed by the caller in numpy's
+ * arithmetic (autovfx_amd/panorama.py) so that the face type is the reference's bit for bit.  Outputs, each nullable, at least one:
+ * out [height,width,C] fp32; out_u8 [height,width,C] = uint8(clip(x * 255, 0, 255)) of the fp32 value, truncated, as the reference
+ * quantises the panorama it saves; out_depth [height,width] the radial distance: the same taps and weights over depth * sqrt(1 + (2 cx)^2
+ * + (2 cy)^2) of each tap's source texel (cx, cy: its pixel centre on the face plane, in [-0.5, 0.5]), from depth_faces[6] (a host array
+ * of six device pointers to [S,S] fp32 depth planes; required with out_depth, ignored without).  Refused (GSR_ERR_INVALID_ARG, nothing
+ * launched): width % 8 != 0, height < 2 or > 65535, S < 2 or > 32768, C outside 1 .. 4, a null pointer.  One launch on `stream`, no scratch, no
+ * host synchronisation. */
+GSR_API int gsr_cube_to_equirect(const float* const* faces, int face_size, int channels, const float* const* depth_faces,
+                                 const float* grid_u, const float* grid_v, const int32_t* grid_ceil, int height, int width, float* out,
+                                 uint8_t* out_u8, float* out_depth, void* stream);
 
 /* The compositor's input side (blender/blend_all.py:21-28,217-234: every Blender layer of every frame is brought to the size of
  * the rendered frame with PIL -- Image.resize(new_size, BILINEAR) for the RGBA8 layers, Image.resize(new_size, NEAREST) for the
