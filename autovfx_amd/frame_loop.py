@@ -34,6 +34,7 @@ import copy
 import glob
 import os
 import sys
+import time
 from collections import deque
 from typing import Callable, Dict, Iterable, List, Optional, Sequence
 
@@ -54,6 +55,11 @@ def _render_begin(view, model, pipe, bg):
 def _render(view, model, pipe, bg):
     from . import renderer
     return renderer.render(view, model, pipe, bg)
+
+
+def _can_begin(model, pipe):
+    from . import renderer
+    return renderer.can_begin(model, pipe)
 
 
 def _make_writer(out_dir: str, writer_threads: int, slots: int):
@@ -103,63 +109,65 @@ def render_frames(views: Sequence, names: Sequence[str], model_for_frame: Callab
             for i in it:
                 writer.submit(names[i], _render(views[i], model_for_frame(i, 0), pipe, bg))
             return len(ids)
-        device = bg.device
-        side, q = _side_streams(device, S), deque()
-        for st in side:                # what the caller queued on its stream (the model's upload, the scene buffers) comes first
-            st.wait_stream(torch.cuda.current_stream(device))
-
         stats = LAST_LOOP_STATS if os.environ.get("AUTOVFX_AMD_LOOP_STATS") else None
         if stats is not None:          # where the host thread's time goes: begin (compose + first half), finish (wait + second half), submit (files)
-            import time
-            clock = time.perf_counter
             stats.clear()
             stats.update(frames=len(ids), streams=S, begin_s=0.0, finish_s=0.0, submit_s=0.0, loop_s=0.0)
-            t_loop = clock()
-
-        def finish_oldest():
-            st, name, pending = q.popleft()
-            with torch.cuda.stream(st):
-                if stats is None:
-                    writer.submit(name, pending.finish())
-                else:
-                    t0 = clock()
-                    result = pending.finish()
-                    t1 = clock()
-                    writer.submit(name, result)
-                    stats["finish_s"] += t1 - t0
-                    stats["submit_s"] += clock() - t1
-
-        # (One host thread on purpose.  Handing the file kernels of a frame to a second thread was tried: its Python parts take the
-        # interpreter lock from this one for milliseconds at a time -- profiles/r06_loop_filer_thread_ab.txt.)
-        split = True       # render() in two halves; a model / pipeline it cannot split gets one blocking render() per frame instead
-        for k, i in enumerate(it):
-            while len(q) == S:
-                finish_oldest()
-            st = side[k % S]
-            with torch.cuda.stream(st):
-                t0 = clock() if stats is not None else 0.0
-                model = model_for_frame(i, k % S)
-                pending = None
-                if split:
-                    try:
-                        pending = _render_begin(views[i], model, pipe, bg)
-                    except RuntimeError as e:
-                        if "render_begin needs" not in str(e):
-                            raise
-                        split = False          # (same kernels, the same library: only the frames no longer overlap)
-                if pending is not None:
-                    q.append((st, names[i], pending))
-                else:
-                    writer.submit(names[i], _render(views[i], model, pipe, bg))
-                if stats is not None:
-                    stats["begin_s"] += clock() - t0
-        while q:
-            finish_oldest()
-        if stats is not None:
-            stats["loop_s"] = clock() - t_loop
-        for st in side:
-            torch.cuda.current_stream(device).wait_stream(st)
+        _frames_in_flight(bg.device, S, it, lambda i, slot: (views[i], model_for_frame(i, slot)), pipe, bg,
+                          lambda i, result: writer.submit(names[i], result), stats)
     return len(ids)
+
+
+def _frames_in_flight(device, streams: int, items: Iterable, frame: Callable, pipe, bg, consume: Callable,
+                      stats: Optional[dict] = None) -> None:
+    """The frames-in-flight loop of ``render_frames`` and ``panorama.render_cube_faces``: ``frame(item, slot)`` gives the
+    ``(view, model)`` of each item, made and begun (``render_begin``) on side stream ``slot`` (0 .. streams-1), at most
+    ``streams`` items queued; the oldest is finished first and ``consume(item, result)`` runs on its stream, in item order.  A
+    model ``render_begin`` cannot split (``renderer.can_begin``) gets one blocking ``render()`` instead (same kernels, the same
+    library: only that frame does not overlap).  The side streams wait for the caller's stream first, and the caller's stream
+    for them at the end.  ``stats``: host seconds spent in begin / finish / consume are added to its ``begin_s`` / ``finish_s`` /
+    ``submit_s``; ``loop_s`` is set to the whole loop's."""
+    clock = time.perf_counter
+    main = torch.cuda.current_stream(device)
+    side, q = _side_streams(device, streams), deque()
+    for st in side:                # what the caller queued on its stream (the model's upload, the scene buffers) comes first
+        st.wait_stream(main)
+    t_loop = clock()
+
+    def finish_oldest():
+        st, item, finish = q.popleft()
+        with torch.cuda.stream(st):
+            t0 = clock()
+            result = finish()
+            t1 = clock()
+            consume(item, result)
+            if stats is not None:
+                stats["finish_s"] += t1 - t0
+                stats["submit_s"] += clock() - t1
+
+    # (One host thread on purpose.  Handing the file kernels of a frame to a second thread was tried: its Python parts take the
+    # interpreter lock from this one for milliseconds at a time -- profiles/r06_loop_filer_thread_ab.txt.)
+    for k, item in enumerate(items):
+        if len(q) == streams:
+            finish_oldest()
+        st = side[k % streams]
+        with torch.cuda.stream(st):
+            t0 = clock()
+            view, model = frame(item, k % streams)
+            if _can_begin(model, pipe):
+                finish = _render_begin(view, model, pipe, bg).finish
+            else:              # queued all the same: slot k % streams must be free when it comes round again
+                result = _render(view, model, pipe, bg)
+                finish = lambda result=result: result
+            q.append((st, item, finish))
+            if stats is not None:
+                stats["begin_s"] += clock() - t0
+    while q:
+        finish_oldest()
+    if stats is not None:
+        stats["loop_s"] = clock() - t_loop
+    for st in side:
+        main.wait_stream(st)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------
@@ -287,7 +295,6 @@ def render_from_3DGS(self, render_video=False, post_rendering=False):
     rank, world, dist = _rank_world()
     streams = DEFAULT_STREAMS
     names = [view.image_name for view in camera_views]
-    import time
     with torch.no_grad():
         t0 = time.perf_counter()
         plan = _plan(self, mod, len(camera_views), streams)

@@ -276,11 +276,11 @@ def cube_to_equirect(faces, h: int, w: int, depth=None, out_uint8: bool = False,
 # the faces, in flight
 # ------------------------------------------------------------------------------------------------------------------------------------
 def render_cube_faces(gaussians, pipeline, background, center, size: int = 1024, streams: Optional[int] = None) -> Dict[str, dict]:
-    """The six ``render()`` results of the cube map around ``center`` (``VIEW_ORDER``), rendered in flight: ``render_begin`` on the
-    frame loop's side streams, ``finish`` oldest first, at most ``streams`` faces queued.  The images are those of six blocking
-    ``render()`` calls, bit for bit; the caller's stream is ordered behind them when this returns.  A model / pipeline the split
-    path does not take gets blocking ``render()`` calls instead (same kernels)."""
-    from . import frame_loop, renderer
+    """The six ``render()`` results of the cube map around ``center`` (``VIEW_ORDER``), rendered in flight by the frame loop's
+    driver (``frame_loop._frames_in_flight``): ``render_begin`` on side streams, ``finish`` oldest first, at most ``streams`` faces
+    queued.  The images are those of six blocking ``render()`` calls, bit for bit; the caller's stream is ordered behind them when
+    this returns.  A model / pipeline the split path does not take gets blocking ``render()`` calls instead (same kernels)."""
+    from . import frame_loop
     device = background.device
     if device.type != "cuda":
         raise RuntimeError("render_cube_faces: the background must live on a HIP device (there is no CPU fallback)")
@@ -288,39 +288,10 @@ def render_cube_faces(gaussians, pipeline, background, center, size: int = 1024,
     views = dict(zip(VIEW_ORDER, Camera.batch_to([cams[n] for n in VIEW_ORDER], device)))
     S = max(1, int(frame_loop.DEFAULT_STREAMS if streams is None else streams))
     main = torch.cuda.current_stream(device)
-    side = frame_loop._side_streams(device, S)
     results: Dict[str, dict] = {}
     with torch.no_grad():
-        for st in side:
-            st.wait_stream(main)
-        queue, split = [], True
-
-        def finish_oldest():
-            st, name, pending = queue.pop(0)
-            with torch.cuda.stream(st):
-                results[name] = pending.finish()
-
-        for k, name in enumerate(VIEW_ORDER):
-            if len(queue) == S:
-                finish_oldest()
-            st = side[k % S]
-            with torch.cuda.stream(st):
-                pending = None
-                if split:
-                    try:
-                        pending = renderer.render_begin(views[name], gaussians, pipeline, background)
-                    except RuntimeError as e:
-                        if "render_begin needs" not in str(e):
-                            raise
-                        split = False
-                if pending is not None:
-                    queue.append((st, name, pending))
-                else:
-                    results[name] = renderer.render(views[name], gaussians, pipeline, background)
-        while queue:
-            finish_oldest()
-        for st in side:
-            main.wait_stream(st)
+        frame_loop._frames_in_flight(device, S, VIEW_ORDER, lambda name, slot: (views[name], gaussians), pipeline, background,
+                                     results.__setitem__)
         for res in results.values():       # made on a side stream, read on the caller's: keep the memory until that stream is done
             for t in res.values():
                 if isinstance(t, torch.Tensor) and t.is_cuda:

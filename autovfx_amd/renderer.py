@@ -301,18 +301,40 @@ class PendingRender:
         return tail()
 
 
+# The paths render() can take (_path); render_begin splits the two that end in one inference call of the rasterizer.
+_SPLIT_PATHS = ("raw", "fused")
+
+
+def _path(pc, pipe, override_color, xyz):
+    """How ``render()`` renders ``pc`` under the current grad mode and module flags: ``("raw_autograd", raw)`` / ``("raw", raw)``
+    -- from the model's raw tensors ``raw`` (``raw_parameters``) with / without autograd --, ``("fused", None)`` -- activated inputs,
+    fused elementwise kernels, one rasterizer call -- or ``("reference", None)``, the reference's structure.  ``xyz`` is
+    ``pc.get_xyz``."""
+    grad = torch.is_grad_enabled()
+    if (RAW_PARAMETERS and FUSE_ELEMENTWISE and override_color is None and not pipe.convert_SHs_python
+            and not pipe.compute_cov3D_python and (RAW_AUTOGRAD or not grad)):
+        raw = raw_parameters(pc)
+        if raw is not None:
+            return ("raw_autograd" if grad else "raw"), raw
+    if FUSE_ELEMENTWISE and not grad and xyz.is_cuda and xyz.dtype == torch.float32 and hasattr(pc, "get_minimum_axis"):
+        return "fused", None
+    return "reference", None
+
+
+def can_begin(pc, pipe=PipelineParams, override_color: Optional[torch.Tensor] = None) -> bool:
+    """Would ``render_begin`` split a render of ``pc`` with these arguments now (grad mode, module flags), rather than refuse?"""
+    return _path(pc, pipe, override_color, pc.get_xyz)[0] in _SPLIT_PATHS
+
+
 def render_begin(viewpoint_camera, pc, pipe=PipelineParams, bg_color: Optional[torch.Tensor] = None,
                  scaling_modifier: float = 1.0, override_color: Optional[torch.Tensor] = None) -> PendingRender:
     """``render`` in two halves for inference loops that keep several frames in flight from one host thread
     (``frame_parallel.render_shard(driver="pipelined")``): the per-Gaussian normals, the projection and the depth
     sort are queued on the current stream and the call returns without waiting for the GPU; ``finish()`` (same
     thread, same current stream) queues the rest.  Needs what the fused single-pass path needs: autograd off, data on
-    the GPU, a model with the six raw parameter tensors or with ``get_minimum_axis``.  Images are those of ``render``, bit for bit."""
-    out = _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, split=True)
-    if not isinstance(out, PendingRender):
-        raise RuntimeError("render_begin needs torch.no_grad(), float32 data on the GPU and a model with the raw parameter "
-                           "tensors or get_minimum_axis")
-    return out
+    the GPU, a model with the six raw parameter tensors or with ``get_minimum_axis`` (``can_begin``).  Images are those of
+    ``render``, bit for bit."""
+    return _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, split=True)
 
 
 def render(viewpoint_camera, pc, pipe=PipelineParams, bg_color: Optional[torch.Tensor] = None,
@@ -322,9 +344,13 @@ def render(viewpoint_camera, pc, pipe=PipelineParams, bg_color: Optional[torch.T
 
 
 def _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, split):
-    from diff_gaussian_rasterization import GaussianRasterizationSettings, GaussianRasterizer
+    from diff_gaussian_rasterization import GaussianRasterizationSettings, GaussianRasterizer, _C
 
     xyz = pc.get_xyz
+    path, raw = _path(pc, pipe, override_color, xyz)
+    if split and path not in _SPLIT_PATHS:
+        raise RuntimeError("render_begin needs torch.no_grad(), float32 data on the GPU and a model with the raw parameter "
+                           "tensors or get_minimum_axis")
     if torch.is_grad_enabled():
         # (the reference writes ``torch.zeros_like(..., requires_grad=True) + 0`` and retain_grad(): a zero fill, an add and a graph
         # node per frame for a tensor that is only ever read through ``.grad``; a zero leaf carries the same values and the same .grad)
@@ -352,12 +378,27 @@ def _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_col
     if c2w is None:
         c2w = viewpoint_camera.world_view_transform.inverse()
 
-    # Straight from the model's raw parameters (gsr_forward_raw): no getter is called, nothing is activated in PyTorch.
-    raw = None
-    if (RAW_PARAMETERS and FUSE_ELEMENTWISE and override_color is None and not pipe.convert_SHs_python
-            and not pipe.compute_cov3D_python and (RAW_AUTOGRAD or not torch.is_grad_enabled())):
-        raw = raw_parameters(pc)
-    if raw is not None and torch.is_grad_enabled():
+    def result(rendered_image, depth_image, normal_image, pseudo_normal, radii):
+        return {"render": rendered_image, "depth": depth_image, "normal": normal_image, "pseudo_normal": pseudo_normal,
+                "viewspace_points": screenspace_points, "visibility_filter": radii > 0, "radii": radii}
+
+    def inference_call(begin, once, *args, **kwargs):
+        """The raw and fused paths: one inference call of the rasterizer whose third image is the normal image, in two halves
+        with ``split``."""
+        def assemble(out):
+            (_n, rendered_image, depth_image, alpha_image, radii, _g, _b, _i, normal_image) = out
+            rendered_image = _C.rgba_planes(rendered_image, alpha_image)   # torch.cat((colour, alpha)) without the copy
+            depth_image = depth_image.squeeze(0)
+            normal_image, pseudo_normal = _fused_normal_maps(normal_image, depth_image, c2w, fx, fy, w / 2, h / 2)
+            return result(rendered_image, depth_image, normal_image, pseudo_normal, radii)
+
+        if split:
+            pending = begin(*args, **kwargs)
+            return PendingRender(lambda: assemble(pending.finish()), pending.ready)
+        return assemble(once(*args, **kwargs))
+
+    s_ = settings
+    if path == "raw_autograd":
         # one differentiable rasterizer call from the raw tensors; the per-pixel post-processing stays in PyTorch (:186-208),
         # so whatever the loss reads -- RGBA, depth, normal map, pseudo normals -- carries its gradient back
         rendered_image, depth_image, radii, normal_image = _RasterizeRaw.apply(*raw, screenspace_points, settings)
@@ -366,27 +407,12 @@ def _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_col
             normal_image, pseudo_normal = _NormalMaps.apply(normal_image, depth_image, c2w, h, w, fx, fy)
         else:
             normal_image, pseudo_normal = _normal_maps_torch(normal_image, depth_image, c2w, h, w, fx, fy)
-        return {"render": rendered_image, "depth": depth_image, "normal": normal_image, "pseudo_normal": pseudo_normal,
-                "viewspace_points": screenspace_points, "visibility_filter": radii > 0, "radii": radii}
-    if raw is not None:
-        from diff_gaussian_rasterization import _C
-        s_ = settings
-        raw_args = (s_.bg, *raw, s_.scale_modifier, s_.viewmatrix, s_.projmatrix, s_.tanfovx, s_.tanfovy, s_.image_height,
-                    s_.image_width, s_.sh_degree, s_.campos, s_.prefiltered, s_.debug)
-
-        def assemble_raw(result):
-            (_n, rendered_image, depth_image, alpha_image, radii, _g, _b, _i, normal_image) = result
-            rendered_image = _C.rgba_planes(rendered_image, alpha_image)
-            depth_image = depth_image.squeeze(0)
-            normal_image, pseudo_normal = _fused_normal_maps(normal_image, depth_image, c2w, fx, fy, w / 2, h / 2)
-            return {"render": rendered_image, "depth": depth_image, "normal": normal_image,
-                    "pseudo_normal": pseudo_normal, "viewspace_points": screenspace_points,
-                    "visibility_filter": radii > 0, "radii": radii}
-
-        if split:
-            pending = _C.rasterize_gaussians_raw_begin(*raw_args, want_normal=True, inference=True)
-            return PendingRender(lambda: assemble_raw(pending.finish()), pending.ready)
-        return assemble_raw(_C.rasterize_gaussians_raw(*raw_args, want_normal=True, inference=True))
+        return result(rendered_image, depth_image, normal_image, pseudo_normal, radii)
+    if path == "raw":
+        # Straight from the model's raw parameters (gsr_forward_raw): no getter is called, nothing is activated in PyTorch.
+        return inference_call(_C.rasterize_gaussians_raw_begin, _C.rasterize_gaussians_raw, s_.bg, *raw, s_.scale_modifier,
+                              s_.viewmatrix, s_.projmatrix, s_.tanfovx, s_.tanfovy, s_.image_height, s_.image_width, s_.sh_degree,
+                              s_.campos, s_.prefiltered, s_.debug, want_normal=True, inference=True)
 
     means3D, means2D, opacity = xyz, screenspace_points, pc.get_opacity
     scales = rotations = cov3D_precomp = None
@@ -398,9 +424,8 @@ def _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_col
     # With autograd off and the data on the GPU, the elementwise work around the passes runs as two fused kernels
     # (gsr_view_normals / gsr_normal_maps) instead of ~40 PyTorch launches, and the normal pass is folded into the
     # first one (gsr_forward_extra); same formulas, same images (tests).
-    fused = FUSE_ELEMENTWISE and (not torch.is_grad_enabled()) and xyz.is_cuda and xyz.dtype == torch.float32 and hasattr(pc, "get_minimum_axis")
     dir_pp_normalized = None
-    if not fused or (override_color is None and pipe.convert_SHs_python):
+    if path == "reference" or (override_color is None and pipe.convert_SHs_python):
         dir_pp = xyz - viewpoint_camera.camera_center.repeat(xyz.shape[0], 1)
         dir_pp_normalized = dir_pp / dir_pp.norm(dim=1, keepdim=True)
 
@@ -413,50 +438,27 @@ def _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_col
     else:
         colors_precomp = override_color
 
-    if fused:
+    if path == "fused":
         # One pass: the per-Gaussian normals ride through the SAME walk of the per-tile lists as a second feature
         # set (gsr_forward_extra); the normal image is what the reference's second pass (:176-184) returns, bit for bit.
-        from diff_gaussian_rasterization import _C
         normal_normed = _fused_view_normals(xyz, pc.get_minimum_axis, viewpoint_camera.camera_center)
         absent = torch.Tensor([])
-        s_ = settings
-        call_args = (
+        return inference_call(
+            _C.rasterize_gaussians_begin, _C.rasterize_gaussians_extra,
             s_.bg, means3D, absent if colors_precomp is None else colors_precomp, opacity,
             absent if scales is None else scales, absent if rotations is None else rotations, s_.scale_modifier,
             absent if cov3D_precomp is None else cov3D_precomp, s_.viewmatrix, s_.projmatrix, s_.tanfovx, s_.tanfovy,
             s_.image_height, s_.image_width, absent if shs is None else shs, s_.sh_degree, s_.campos, s_.prefiltered,
-            s_.debug, normal_normed)
+            s_.debug, normal_normed, inference=True)
 
-        def assemble(result):
-            (_n, rendered_image, depth_image, alpha_image, radii, _g, _b, _i, normal_image) = result
-            rendered_image = _C.rgba_planes(rendered_image, alpha_image)   # torch.cat((colour, alpha)) without the copy
-            depth_image = depth_image.squeeze(0)
-            normal_image, pseudo_normal = _fused_normal_maps(normal_image, depth_image, c2w, fx, fy, w / 2, h / 2)
-            return {"render": rendered_image, "depth": depth_image, "normal": normal_image,
-                    "pseudo_normal": pseudo_normal, "viewspace_points": screenspace_points,
-                    "visibility_filter": radii > 0, "radii": radii}
-
-        if split:
-            pending = _C.rasterize_gaussians_begin(*call_args, inference=True)   # (fused: autograd is off)
-            return PendingRender(lambda: assemble(pending.finish()), pending.ready)
-        return assemble(_C.rasterize_gaussians_extra(*call_args, inference=True))
-    else:
-        rasterizer = GaussianRasterizer(raster_settings=settings)
-        rendered_image, depth_image, alpha_image, radii = rasterizer(
-            means3D=means3D, means2D=means2D, shs=shs, colors_precomp=colors_precomp, opacities=opacity, scales=scales,
-            rotations=rotations, cov3D_precomp=cov3D_precomp)
-        rendered_image = torch.cat((rendered_image, alpha_image), dim=0)
-        depth_image = depth_image.squeeze(0)
-        normal_normed = pc.get_normal(dir_pp_normalized=dir_pp_normalized) * 0.5 + 0.5
-        normal_image = rasterizer(means3D=means3D, means2D=means2D, shs=None, colors_precomp=normal_normed,
-                                  opacities=opacity, scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp)[0]
-        normal_image = (normal_image - 0.5) * 2.0
-        normal_image = torch.nn.functional.normalize(normal_image.permute(1, 2, 0), p=2, dim=-1)
-        directions = get_ray_directions(h, w, fx, fy, w / 2, h / 2, depth_image.device)
-        rays_d = directions @ c2w[:3, :3].T
-        rays_o = c2w[:3, 3].expand_as(rays_d)
-        points3D = rays_o + rays_d * depth_image.unsqueeze(-1)
-        pseudo_normal = depth_pcd2normal(points3D)
-
-    return {"render": rendered_image, "depth": depth_image, "normal": normal_image, "pseudo_normal": pseudo_normal,
-            "viewspace_points": screenspace_points, "visibility_filter": radii > 0, "radii": radii}
+    rasterizer = GaussianRasterizer(raster_settings=settings)
+    rendered_image, depth_image, alpha_image, radii = rasterizer(
+        means3D=means3D, means2D=means2D, shs=shs, colors_precomp=colors_precomp, opacities=opacity, scales=scales,
+        rotations=rotations, cov3D_precomp=cov3D_precomp)
+    rendered_image = torch.cat((rendered_image, alpha_image), dim=0)
+    depth_image = depth_image.squeeze(0)
+    normal_normed = pc.get_normal(dir_pp_normalized=dir_pp_normalized) * 0.5 + 0.5
+    normal_image = rasterizer(means3D=means3D, means2D=means2D, shs=None, colors_precomp=normal_normed,
+                              opacities=opacity, scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp)[0]
+    normal_image, pseudo_normal = _normal_maps_torch(normal_image, depth_image, c2w, h, w, fx, fy)
+    return result(rendered_image, depth_image, normal_image, pseudo_normal, radii)

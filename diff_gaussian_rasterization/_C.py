@@ -210,7 +210,7 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
     may cut the lists into depth slabs and skip what finished tiles no longer need (``GSR_FORWARD_INFERENCE``); the
     images, radii and the returned count are bit-identical either way, the scratch buffers are only good for a second
     blend, not for ``rasterize_gaussians_backward``."""
-    return _rasterize(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
+    return _rasterize(False, background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
                       viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
                       prefiltered, debug, None, inference)[:8]
 
@@ -222,36 +222,65 @@ def rasterize_gaussians_extra(background, means3D, colors, opacity, scales, rota
     (``gsr_forward_extra``): returns the 8-tuple and ``extra_image[3,H,W]``, which equals the colour image of a
     second call with ``colors = extra_colors`` bit for bit.  Not part of the reference surface; used by
     ``autovfx_amd.renderer.render`` for the normal map."""
-    if extra_colors is None or extra_colors.dim() != 2 or extra_colors.shape != (means3D.size(0), 3):
+    if extra_colors is None:
         raise RuntimeError("extra_colors must have dimensions (num_points, 3)")
-    return _rasterize(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
+    return _rasterize(False, background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
                       viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
                       prefiltered, debug, extra_colors, inference)
 
 
-def _rasterize(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
+def rasterize_gaussians_begin(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
+                              viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
+                              prefiltered, debug, extra_colors=None, *, inference: bool = False) -> PendingForward:
+    """First half of ``rasterize_gaussians`` (same 19 arguments): everything up to the point where the host has to
+    learn the pair count is queued on the current stream and the call returns without waiting.  ``finish()`` on the
+    result queues the rest.  One host thread can so keep a frame in flight on each of several streams; results are
+    those of the one-shot call, bit for bit.  Not part of the reference surface (its forward is one blocking call,
+    ``DGR/rasterize_points.cu:36-119``); used by ``autovfx_amd.frame_parallel``."""
+    return _rasterize(True, background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
+                      viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
+                      prefiltered, debug, extra_colors, inference)
+
+
+def rasterize_gaussians_raw(background, xyz, log_scales, rotations, opacity_logits, features_dc, features_rest,
+                            scale_modifier, viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, degree,
+                            campos, prefiltered, debug, *, want_normal: bool = True, inference: bool = True):
+    """The forward pass straight from a model's RAW parameter tensors (``gsr_forward_raw``): ``_xyz``, ``_scaling`` (log),
+    ``_rotation`` (unnormalised), ``_opacity`` (logit), ``_features_dc [P,1,3]``, ``_features_rest [P,M-1,3]`` as
+    ``GaussianModel`` stores them (``scene/gaussian_model.py:95-128``).  ``exp`` / ``sigmoid`` / ``F.normalize``, the
+    ``cat(dc, rest)`` and -- with ``want_normal`` -- ``get_normal(dir) * 0.5 + 0.5`` happen inside the kernels, rounded as
+    PyTorch rounds them on this GPU: the result is bit-identical to activating in PyTorch and calling
+    ``rasterize_gaussians_extra``.  Returns that function's 9-tuple (the last entry is the normal image or None).  Not
+    part of the reference surface; ``autovfx_amd.renderer.render`` uses it for any model that exposes the six tensors."""
+    return _rasterize_raw(False, background, xyz, log_scales, rotations, opacity_logits, features_dc, features_rest,
+                          scale_modifier, viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, degree, campos,
+                          prefiltered, debug, want_normal, inference)
+
+
+def rasterize_gaussians_raw_begin(background, xyz, log_scales, rotations, opacity_logits, features_dc, features_rest,
+                                  scale_modifier, viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width,
+                                  degree, campos, prefiltered, debug, *, want_normal: bool = True,
+                                  inference: bool = True) -> PendingForward:
+    """``rasterize_gaussians_raw`` in two halves (``gsr_forward_raw_begin``): see ``rasterize_gaussians_begin``."""
+    return _rasterize_raw(True, background, xyz, log_scales, rotations, opacity_logits, features_dc, features_rest,
+                          scale_modifier, viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, degree, campos,
+                          prefiltered, debug, want_normal, inference)
+
+
+def _rasterize(begin, background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
                viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
-               prefiltered, debug, extra_colors, inference=False):
+               prefiltered, debug, extra_colors, inference):
+    """A forward call from activated inputs: ``gsr_forward_begin`` with ``begin``, else ``gsr_forward`` -- or
+    ``gsr_forward_extra`` when there is a third image or ``inference`` -- behind the geometry cache."""
     if means3D.dim() != 2 or means3D.size(1) != 3:
         raise RuntimeError("means3D must have dimensions (num_points, 3)")
     device = _require_gpu(means3D, "means3D")
     P, H, W = int(means3D.size(0)), int(image_height), int(image_width)
-
-    # The reference zero-fills its outputs (rasterize_points.cu:68-71), which only matters for P == 0:
-    # with P > 0 every pixel and every radius is written by the kernels, so the fills are skipped.
-    make = (lambda shape, dtype, device: torch.zeros(shape, dtype=dtype, device=device)) if P == 0 else _new
-    # colour and alpha are the first three and the fourth plane of ONE buffer, so a caller that wants RGBA
-    # (render() does: gaussian_renderer/__init__.py:161) gets it without a copy (rgba_planes below)
-    rgba = make((4, H, W), dtype=torch.float32, device=device)
-    out_color, out_alpha = rgba[:3], rgba[3:4]
-    out_depth = make((1, H, W), dtype=torch.float32, device=device)
-    radii = make((P,), dtype=torch.int32, device=device)
-    out_extra = make((3, H, W), dtype=torch.float32, device=device) if extra_colors is not None else None
-    scratch = _CallScratch(device)
-    rendered = 0
-    geometry_inputs = (means3D, opacity, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, campos)
+    if extra_colors is not None and (extra_colors.dim() != 2 or extra_colors.shape != (P, 3)):
+        raise RuntimeError("extra_colors must have dimensions (num_points, 3)")
     key = None
-    if P != 0 and _GEOMETRY_CACHE:
+    if P != 0 and _GEOMETRY_CACHE and not begin:
+        geometry_inputs = (means3D, opacity, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, campos)
         key = _geometry_key(geometry_inputs, (float(scale_modifier), float(tan_fovx), float(tan_fovy), H, W,
                                               bool(prefiltered), _lib.get_option(_lib.OPT_TILE_CULL), bool(inference),
                                               torch.cuda.current_stream(device).cuda_stream))
@@ -259,45 +288,119 @@ def _rasterize(background, means3D, colors, opacity, scales, rotations, scale_mo
         _tls.cache = None   # whatever happens next, the entry has had its one chance
         if hit is not None and hit["key"] == key and colors.numel() != 0 and sh.numel() == 0 and extra_colors is None:
             cache_stats["hits"] += 1
-            return _blend_cached(hit, background, colors, device, H, W, out_color, out_depth, out_alpha)
+            return _blend_cached(hit, background, colors, device, P, H, W)
         del hit
         cache_stats["misses"] += 1
-    if P != 0:
-        M = int(sh.size(1)) if sh.numel() != 0 else 0
-        tensors = [_f32c(n, t, device) for n, t in (
-            ("background", background), ("means3D", means3D), ("sh", sh), ("colors", colors), ("opacity", opacity),
-            ("scales", scales), ("rotations", rotations), ("cov3D_precomp", cov3D_precomp),
-            ("viewmatrix", viewmatrix), ("projmatrix", projmatrix), ("campos", campos))]
-        bg_, m3_, sh_, col_, op_, sc_, rot_, cov_, vm_, pm_, cp_ = tensors
-        _tls.call = scratch
-        try:
-            with torch.cuda.device(device):
-                stream = torch.cuda.current_stream(device).cuda_stream
-                head = (_GEOM_CB, None, _BINNING_CB, None, _IMAGE_CB, None, P, int(degree), M, _ptr(bg_), W, H,
-                        _ptr(m3_), _ptr(sh_), _ptr(col_), _ptr(op_), _ptr(sc_), float(scale_modifier), _ptr(rot_),
-                        _ptr(cov_), _ptr(vm_), _ptr(pm_), _ptr(cp_), float(tan_fovx), float(tan_fovy),
-                        1 if prefiltered else 0, out_color.data_ptr(), out_depth.data_ptr(), out_alpha.data_ptr(),
-                        radii.data_ptr())
-                flags = _lib.FORWARD_INFERENCE if inference else 0
-                if extra_colors is None and not flags:
-                    rendered = _lib.lib.gsr_forward(*head, 1 if debug else 0, ctypes.c_void_p(stream))
-                else:
-                    ext_ = None if extra_colors is None else _f32c("extra_colors", extra_colors, device)
-                    rendered = _lib.lib.gsr_forward_extra(*head, _ptr(ext_), None if ext_ is None else out_extra.data_ptr(),
-                                                          flags, 1 if debug else 0, ctypes.c_void_p(stream))
-        finally:
-            _tls.call = None
-        if rendered < 0:
-            raise RuntimeError(f"gsr_forward failed ({rendered}): {_lib.last_error()}")
-        # per-thread: the library keeps these per calling thread too, and streams are driven by separate threads
-        # (the pair counts are fetched by last_layout() on demand: they would cost a wait for the stream here)
-        _tls.last_layout = {"geom": _lib.offsets("geom"), "binning": _lib.offsets("binning"), "image": _lib.offsets("image")}
-        if key is not None and extra_colors is None:   # (a fused two-feature call has no second pass to wait for)
-            _tls.cache = {"key": key, "inputs": geometry_inputs,
-                          "rendered": rendered, "radii": radii, "geom": scratch.buffers["geom"],
-                          "binning": scratch.buffers["binning"], "image": scratch.buffers["image"]}
-    return (rendered, out_color, out_depth, out_alpha, radii, scratch.buffers["geom"], scratch.buffers["binning"],
-            scratch.buffers["image"], out_extra)
+    M = int(sh.size(1)) if sh.numel() != 0 else 0
+    flags = _lib.FORWARD_INFERENCE if inference else 0
+    extended = begin or extra_colors is not None or bool(flags)   # (gsr_forward has no extra image and no flags)
+    symbol = (_lib.lib.gsr_forward_begin if begin else _lib.lib.gsr_forward_extra) if extended else _lib.lib.gsr_forward
+    inputs = {"background": background, "means3D": means3D, "sh": sh, "colors": colors, "opacity": opacity, "scales": scales,
+              "rotations": rotations, "cov3D_precomp": cov3D_precomp, "viewmatrix": viewmatrix, "projmatrix": projmatrix,
+              "campos": campos, "extra_colors": extra_colors}
+
+    def args(p, out):
+        head = (P, int(degree), M, p["background"], W, H, p["means3D"], p["sh"], p["colors"], p["opacity"], p["scales"],
+                float(scale_modifier), p["rotations"], p["cov3D_precomp"], p["viewmatrix"], p["projmatrix"], p["campos"],
+                float(tan_fovx), float(tan_fovy), 1 if prefiltered else 0, *out[:4])
+        return head + (p["extra_colors"], out[4], flags) if extended else head
+
+    result = _forward(symbol, begin, device, P, H, W, extra_colors is not None, inputs, args, debug)
+    if key is not None and extra_colors is None:   # (a fused two-feature call has no second pass to wait for)
+        rendered, _c, _d, _a, radii, geom, binning, image, _e = result
+        _tls.cache = {"key": key, "inputs": geometry_inputs, "rendered": rendered, "radii": radii, "geom": geom,
+                      "binning": binning, "image": image}
+    return result
+
+
+def _raw_params(p) -> _lib.RawParams:
+    return _lib.RawParams(p["xyz"], p["log_scales"], p["rotations"], p["opacity_logits"], p["features_dc"], p["features_rest"])
+
+
+def _rasterize_raw(begin, background, xyz, log_scales, rotations, opacity_logits, features_dc, features_rest, scale_modifier,
+                   viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, degree, campos, prefiltered, debug,
+                   want_normal, inference):
+    """A forward call from raw parameters: ``gsr_forward_raw`` / ``gsr_forward_raw_begin``."""
+    if xyz.dim() != 2 or xyz.size(1) != 3:
+        raise RuntimeError("xyz must have dimensions (num_points, 3)")
+    device = _require_gpu(xyz, "xyz")
+    P, H, W = int(xyz.size(0)), int(image_height), int(image_width)
+    if features_dc.dim() != 3 or tuple(features_dc.shape) != (P, 1, 3):
+        raise RuntimeError("features_dc must have dimensions (num_points, 1, 3)")
+    if features_rest.dim() != 3 or features_rest.size(0) != P or features_rest.size(2) != 3:
+        raise RuntimeError("features_rest must have dimensions (num_points, M - 1, 3)")
+    if tuple(log_scales.shape) != (P, 3) or tuple(rotations.shape) != (P, 4) or opacity_logits.numel() != P:
+        raise RuntimeError("log_scales / rotations / opacity_logits must have dimensions (num_points, 3 / 4 / 1)")
+    M = 1 + int(features_rest.size(1))
+    inputs = {"background": background, "xyz": xyz, "log_scales": log_scales, "rotations": rotations,
+              "opacity_logits": opacity_logits, "features_dc": features_dc, "features_rest": features_rest,
+              "viewmatrix": viewmatrix, "projmatrix": projmatrix, "campos": campos}
+
+    def args(p, out):
+        return (P, int(degree), M, p["background"], W, H, ctypes.byref(_raw_params(p)), float(scale_modifier), p["viewmatrix"],
+                p["projmatrix"], p["campos"], float(tan_fovx), float(tan_fovy), 1 if prefiltered else 0, *out,
+                _lib.FORWARD_INFERENCE if inference else 0)
+
+    symbol = _lib.lib.gsr_forward_raw_begin if begin else _lib.lib.gsr_forward_raw
+    return _forward(symbol, begin, device, P, H, W, want_normal, inputs, args, debug)
+
+
+def _outputs(device, P, H, W, third):
+    """Colour, depth, alpha, radii and the optional third image ``[3,H,W]`` of one forward call."""
+    # The reference zero-fills its outputs (rasterize_points.cu:68-71), which only matters for P == 0:
+    # with P > 0 every pixel and every radius is written by the kernels, so the fills are skipped.
+    make = (lambda shape, dtype, device: torch.zeros(shape, dtype=dtype, device=device)) if P == 0 else _new
+    # colour and alpha are the first three and the fourth plane of ONE buffer, so a caller that wants RGBA
+    # (render() does: gaussian_renderer/__init__.py:161) gets it without a copy (rgba_planes)
+    rgba = make((4, H, W), torch.float32, device)
+    depth = make((1, H, W), torch.float32, device)
+    radii = make((P,), torch.int32, device)
+    return rgba[:3], depth, rgba[3:4], radii, make((3, H, W), torch.float32, device) if third else None
+
+
+def _forward(symbol, begin, device, P, H, W, third, inputs, args, debug):
+    """The one forward routine behind every public forward function.  Allocates the outputs (``third``: with a third image),
+    converts ``inputs`` (name -> tensor or None) to float32 device pointers ``p[name]``, installs the scratch and calls the
+    library's ``symbol`` with ``args(p, out)`` -- its arguments between the three allocator pairs and ``debug, stream``, where
+    ``out`` holds the pointers of colour, depth, alpha, radii and the third image.  Returns the 9-tuple of
+    ``rasterize_gaussians_extra``, or with ``begin`` a ``PendingForward``."""
+    outputs = _outputs(device, P, H, W, third)
+    scratch = _CallScratch(device)
+    stream = torch.cuda.current_stream(device).cuda_stream
+    if P == 0:   # nothing to launch: the (zero-filled) outputs are the result
+        pending = PendingForward(None, device, stream, scratch, None, outputs)
+        return pending if begin else pending.finish()
+    tensors = {n: None if t is None else _f32c(n, t, device) for n, t in inputs.items()}
+    p = {n: _ptr(t) for n, t in tensors.items()}
+    out = [None if t is None else t.data_ptr() for t in outputs]
+    _tls.call = scratch
+    try:
+        with torch.cuda.device(device):
+            rc = symbol(_GEOM_CB, None, _BINNING_CB, None, _IMAGE_CB, None, *args(p, out), 1 if debug else 0,
+                        ctypes.c_void_p(stream))
+    finally:
+        _tls.call = None
+    if not begin:
+        return _completed(rc, symbol.__name__, scratch, outputs)
+    if not rc:
+        raise RuntimeError(f"{symbol.__name__} failed: {_lib.last_error()}")
+    return PendingForward(rc, device, stream, scratch, tensors, outputs)
+
+
+def _completed(rendered, what, scratch, outputs):
+    """The epilogue of a full forward call, one-shot or finished: raise on failure, record the layout, build the 9-tuple."""
+    if rendered < 0:
+        raise RuntimeError(f"{what} failed ({rendered}): {_lib.last_error()}")
+    # per-thread: the library keeps these per calling thread too, and streams are driven by separate threads
+    # (the pair counts are fetched by last_layout() on demand: they would cost a wait for the stream here)
+    _tls.last_layout = {"geom": _lib.offsets("geom"), "binning": _lib.offsets("binning"), "image": _lib.offsets("image")}
+    return _result(rendered, scratch, outputs)
+
+
+def _result(rendered, scratch, outputs):
+    color, depth, alpha, radii, third = outputs
+    b = scratch.buffers
+    return rendered, color, depth, alpha, radii, b["geom"], b["binning"], b["image"], third
 
 
 class PendingForward:
@@ -322,217 +425,31 @@ class PendingForward:
         and with the current stream that ``rasterize_gaussians_begin`` ran on."""
         if self._outputs is None:
             raise RuntimeError("PendingForward.finish() called twice")
-        out_color, out_depth, out_alpha, radii, out_extra = self._outputs
-        self._outputs = None
-        rendered = 0
-        if self._handle is not None:
-            if torch.cuda.current_stream(self._device).cuda_stream != self._stream:
-                _lib.lib.gsr_forward_cancel(ctypes.c_void_p(self._handle))
-                self._handle = None
-                raise RuntimeError("PendingForward.finish(): the current stream is not the one the call was begun on")
-            _tls.call = self._scratch
-            try:
-                with torch.cuda.device(self._device):
-                    rendered = _lib.lib.gsr_forward_finish(ctypes.c_void_p(self._handle))
-            finally:
-                _tls.call = None
-                self._handle = None
-            if rendered < 0:
-                raise RuntimeError(f"gsr_forward_finish failed ({rendered}): {_lib.last_error()}")
-            _tls.last_layout = {"geom": _lib.offsets("geom"), "binning": _lib.offsets("binning"),
-                                "image": _lib.offsets("image")}
-        b = self._scratch.buffers
+        outputs, self._outputs = self._outputs, None
+        if self._handle is None:   # P == 0: nothing was queued
+            return _result(0, self._scratch, outputs)
+        if torch.cuda.current_stream(self._device).cuda_stream != self._stream:
+            _lib.lib.gsr_forward_cancel(ctypes.c_void_p(self._handle))
+            self._handle = None
+            raise RuntimeError("PendingForward.finish(): the current stream is not the one the call was begun on")
+        _tls.call = self._scratch
+        try:
+            with torch.cuda.device(self._device):
+                rendered = _lib.lib.gsr_forward_finish(ctypes.c_void_p(self._handle))
+        finally:
+            _tls.call = None
+            self._handle = None
         self._inputs = None
-        return rendered, out_color, out_depth, out_alpha, radii, b["geom"], b["binning"], b["image"], out_extra
+        return _completed(rendered, "gsr_forward_finish", self._scratch, outputs)
 
     def __del__(self):
         if getattr(self, "_handle", None) is not None:
             _lib.lib.gsr_forward_cancel(ctypes.c_void_p(self._handle))
 
 
-def rasterize_gaussians_begin(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
-                              viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
-                              prefiltered, debug, extra_colors=None, *, inference: bool = False) -> PendingForward:
-    """First half of ``rasterize_gaussians`` (same 19 arguments): everything up to the point where the host has to
-    learn the pair count is queued on the current stream and the call returns without waiting.  ``finish()`` on the
-    result queues the rest.  One host thread can so keep a frame in flight on each of several streams; results are
-    those of the one-shot call, bit for bit.  Not part of the reference surface (its forward is one blocking call,
-    ``DGR/rasterize_points.cu:36-119``); used by ``autovfx_amd.frame_parallel``."""
-    if means3D.dim() != 2 or means3D.size(1) != 3:
-        raise RuntimeError("means3D must have dimensions (num_points, 3)")
-    device = _require_gpu(means3D, "means3D")
-    P, H, W = int(means3D.size(0)), int(image_height), int(image_width)
-    if extra_colors is not None and (extra_colors.dim() != 2 or extra_colors.shape != (P, 3)):
-        raise RuntimeError("extra_colors must have dimensions (num_points, 3)")
-    make = (lambda shape, dtype, device: torch.zeros(shape, dtype=dtype, device=device)) if P == 0 else _new
-    # colour and alpha are the first three and the fourth plane of ONE buffer, so a caller that wants RGBA
-    # (render() does: gaussian_renderer/__init__.py:161) gets it without a copy (rgba_planes below)
-    rgba = make((4, H, W), dtype=torch.float32, device=device)
-    out_color, out_alpha = rgba[:3], rgba[3:4]
-    out_depth = make((1, H, W), dtype=torch.float32, device=device)
-    radii = make((P,), dtype=torch.int32, device=device)
-    out_extra = make((3, H, W), dtype=torch.float32, device=device) if extra_colors is not None else None
-    scratch = _CallScratch(device)
-    outputs = (out_color, out_depth, out_alpha, radii, out_extra)
-    stream = torch.cuda.current_stream(device).cuda_stream
-    if P == 0:
-        return PendingForward(None, device, stream, scratch, None, outputs)
-    M = int(sh.size(1)) if sh.numel() != 0 else 0
-    tensors = [_f32c(n, t, device) for n, t in (
-        ("background", background), ("means3D", means3D), ("sh", sh), ("colors", colors), ("opacity", opacity),
-        ("scales", scales), ("rotations", rotations), ("cov3D_precomp", cov3D_precomp),
-        ("viewmatrix", viewmatrix), ("projmatrix", projmatrix), ("campos", campos))]
-    bg_, m3_, sh_, col_, op_, sc_, rot_, cov_, vm_, pm_, cp_ = tensors
-    ext_ = _f32c("extra_colors", extra_colors, device) if extra_colors is not None else None
-    _tls.call = scratch
-    try:
-        with torch.cuda.device(device):
-            handle = _lib.lib.gsr_forward_begin(
-                _GEOM_CB, None, _BINNING_CB, None, _IMAGE_CB, None, P, int(degree), M, _ptr(bg_), W, H,
-                _ptr(m3_), _ptr(sh_), _ptr(col_), _ptr(op_), _ptr(sc_), float(scale_modifier), _ptr(rot_),
-                _ptr(cov_), _ptr(vm_), _ptr(pm_), _ptr(cp_), float(tan_fovx), float(tan_fovy),
-                1 if prefiltered else 0, out_color.data_ptr(), out_depth.data_ptr(), out_alpha.data_ptr(),
-                radii.data_ptr(), _ptr(ext_), None if ext_ is None else out_extra.data_ptr(),
-                _lib.FORWARD_INFERENCE if inference else 0, 1 if debug else 0, ctypes.c_void_p(stream))
-    finally:
-        _tls.call = None
-    if not handle:
-        raise RuntimeError(f"gsr_forward_begin failed: {_lib.last_error()}")
-    return PendingForward(handle, device, stream, scratch, (tensors, ext_), outputs)
-
-
-def _raw_call(begin, background, xyz, log_scales, rotations, opacity_logits, features_dc, features_rest, scale_modifier,
-              viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, degree, campos, prefiltered, debug,
-              want_normal, inference):
-    """Common part of ``rasterize_gaussians_raw`` / ``rasterize_gaussians_raw_begin``."""
-    if xyz.dim() != 2 or xyz.size(1) != 3:
-        raise RuntimeError("xyz must have dimensions (num_points, 3)")
-    device = _require_gpu(xyz, "xyz")
-    P, H, W = int(xyz.size(0)), int(image_height), int(image_width)
-    if features_dc.dim() != 3 or tuple(features_dc.shape) != (P, 1, 3):
-        raise RuntimeError("features_dc must have dimensions (num_points, 1, 3)")
-    if features_rest.dim() != 3 or features_rest.size(0) != P or features_rest.size(2) != 3:
-        raise RuntimeError("features_rest must have dimensions (num_points, M - 1, 3)")
-    if tuple(log_scales.shape) != (P, 3) or tuple(rotations.shape) != (P, 4) or opacity_logits.numel() != P:
-        raise RuntimeError("log_scales / rotations / opacity_logits must have dimensions (num_points, 3 / 4 / 1)")
-    M = 1 + int(features_rest.size(1))
-    make = (lambda shape, dtype, device: torch.zeros(shape, dtype=dtype, device=device)) if P == 0 else _new
-    rgba = make((4, H, W), dtype=torch.float32, device=device)
-    out_color, out_alpha = rgba[:3], rgba[3:4]
-    out_depth = make((1, H, W), dtype=torch.float32, device=device)
-    radii = make((P,), dtype=torch.int32, device=device)
-    out_normal = make((3, H, W), dtype=torch.float32, device=device) if want_normal else None
-    scratch = _CallScratch(device)
-    outputs = (out_color, out_depth, out_alpha, radii, out_normal)
-    stream = torch.cuda.current_stream(device).cuda_stream
-    if P == 0:
-        return None, device, stream, scratch, None, outputs
-    tensors = [_f32c(n, t, device) for n, t in (
-        ("background", background), ("xyz", xyz), ("log_scales", log_scales), ("rotations", rotations),
-        ("opacity_logits", opacity_logits), ("features_dc", features_dc), ("features_rest", features_rest),
-        ("viewmatrix", viewmatrix), ("projmatrix", projmatrix), ("campos", campos))]
-    bg_, xyz_, ls_, rot_, op_, dc_, rest_, vm_, pm_, cp_ = tensors
-    raw = _lib.RawParams(_ptr(xyz_), _ptr(ls_), _ptr(rot_), _ptr(op_), _ptr(dc_), _ptr(rest_))
-    _tls.call = scratch
-    try:
-        with torch.cuda.device(device):
-            fn = _lib.lib.gsr_forward_raw_begin if begin else _lib.lib.gsr_forward_raw
-            rc = fn(_GEOM_CB, None, _BINNING_CB, None, _IMAGE_CB, None, P, int(degree), M, _ptr(bg_), W, H, ctypes.byref(raw),
-                    float(scale_modifier), _ptr(vm_), _ptr(pm_), _ptr(cp_), float(tan_fovx), float(tan_fovy),
-                    1 if prefiltered else 0, out_color.data_ptr(), out_depth.data_ptr(), out_alpha.data_ptr(), radii.data_ptr(),
-                    None if out_normal is None else out_normal.data_ptr(), _lib.FORWARD_INFERENCE if inference else 0,
-                    1 if debug else 0, ctypes.c_void_p(stream))
-    finally:
-        _tls.call = None
-    return rc, device, stream, scratch, tensors, outputs
-
-
-def rasterize_gaussians_raw(background, xyz, log_scales, rotations, opacity_logits, features_dc, features_rest,
-                            scale_modifier, viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, degree,
-                            campos, prefiltered, debug, *, want_normal: bool = True, inference: bool = True):
-    """The forward pass straight from a model's RAW parameter tensors (``gsr_forward_raw``): ``_xyz``, ``_scaling`` (log),
-    ``_rotation`` (unnormalised), ``_opacity`` (logit), ``_features_dc [P,1,3]``, ``_features_rest [P,M-1,3]`` as
-    ``GaussianModel`` stores them (``scene/gaussian_model.py:95-128``).  ``exp`` / ``sigmoid`` / ``F.normalize``, the
-    ``cat(dc, rest)`` and -- with ``want_normal`` -- ``get_normal(dir) * 0.5 + 0.5`` happen inside the kernels, rounded as
-    PyTorch rounds them on this GPU: the result is bit-identical to activating in PyTorch and calling
-    ``rasterize_gaussians_extra``.  Returns that function's 9-tuple (the last entry is the normal image or None).  Not
-    part of the reference surface; ``autovfx_amd.renderer.render`` uses it for any model that exposes the six tensors."""
-    rc, device, stream, scratch, tensors, outputs = _raw_call(
-        False, background, xyz, log_scales, rotations, opacity_logits, features_dc, features_rest, scale_modifier, viewmatrix,
-        projmatrix, tan_fovx, tan_fovy, image_height, image_width, degree, campos, prefiltered, debug, want_normal, inference)
-    out_color, out_depth, out_alpha, radii, out_normal = outputs
-    rendered = 0
-    if rc is not None:
-        if rc < 0:
-            raise RuntimeError(f"gsr_forward_raw failed ({rc}): {_lib.last_error()}")
-        rendered = rc
-        _tls.last_layout = {"geom": _lib.offsets("geom"), "binning": _lib.offsets("binning"), "image": _lib.offsets("image")}
-    b = scratch.buffers
-    return rendered, out_color, out_depth, out_alpha, radii, b["geom"], b["binning"], b["image"], out_normal
-
-
-def rasterize_gaussians_raw_begin(background, xyz, log_scales, rotations, opacity_logits, features_dc, features_rest,
-                                  scale_modifier, viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width,
-                                  degree, campos, prefiltered, debug, *, want_normal: bool = True,
-                                  inference: bool = True) -> PendingForward:
-    """``rasterize_gaussians_raw`` in two halves (``gsr_forward_raw_begin``): see ``rasterize_gaussians_begin``."""
-    handle, device, stream, scratch, tensors, outputs = _raw_call(
-        True, background, xyz, log_scales, rotations, opacity_logits, features_dc, features_rest, scale_modifier, viewmatrix,
-        projmatrix, tan_fovx, tan_fovy, image_height, image_width, degree, campos, prefiltered, debug, want_normal, inference)
-    if tensors is None:   # P == 0
-        return PendingForward(None, device, stream, scratch, None, outputs)
-    if not handle:
-        raise RuntimeError(f"gsr_forward_raw_begin failed: {_lib.last_error()}")
-    return PendingForward(handle, device, stream, scratch, (tensors, None), outputs)
-
-
-def rasterize_gaussians_raw_backward(background, xyz, log_scales, rotations, opacity_logits, features_dc, features_rest, radii,
-                                     scale_modifier, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, dL_dout_depth,
-                                     dL_dout_alpha, dL_dout_normal, degree, campos, geomBuffer, R, binningBuffer, imageBuffer,
-                                     out_alpha, debug):
-    """Gradients of a full ``rasterize_gaussians_raw`` call with respect to the model's raw tensors (``gsr_backward_raw``):
-    returns ``(dL_dmeans2D, dL_dxyz, dL_dlog_scales, dL_drotations, dL_dopacity_logits, dL_dfeatures_dc, dL_dfeatures_rest)``.
-    ``dL_dout_depth`` / ``dL_dout_alpha`` / ``dL_dout_normal`` may be None (no gradient for that image)."""
-    device = _require_gpu(xyz, "xyz")
-    P = int(xyz.size(0))
-    H, W = int(out_alpha.size(-2)), int(out_alpha.size(-1))
-    M = 1 + int(features_rest.size(1))
-    z = lambda *shape: _new(shape, torch.float32, device)
-    g2d, gxyz, gls, grot, gop = z(P, 3), z(P, 3), z(P, 3), z(P, 4), z(*opacity_logits.shape)
-    gdc, grest = z(P, 1, 3), z(P, M - 1, 3)
-    if P != 0:
-        f = lambda n, t: _f32c(n, t, device)
-        fn_ = lambda n, t: None if t is None else f(n, t)
-        if dL_dout_color is None:
-            dL_dout_color = torch.zeros((3, H, W), dtype=torch.float32, device=device)
-        if (dL_dout_depth is None) != (dL_dout_alpha is None):
-            dL_dout_depth = torch.zeros((1, H, W), dtype=torch.float32, device=device) if dL_dout_depth is None else dL_dout_depth
-            dL_dout_alpha = torch.zeros((1, H, W), dtype=torch.float32, device=device) if dL_dout_alpha is None else dL_dout_alpha
-        tensors = [f(n, t) for n, t in (("background", background), ("xyz", xyz), ("log_scales", log_scales), ("rotations", rotations),
-                                        ("opacity_logits", opacity_logits), ("features_dc", features_dc), ("features_rest", features_rest),
-                                        ("viewmatrix", viewmatrix), ("projmatrix", projmatrix), ("campos", campos),
-                                        ("out_alpha", out_alpha), ("dL_dout_color", dL_dout_color))]
-        bg_, xyz_, ls_, rot_, op_, dc_, rest_, vm_, pm_, cp_, oa_, gc_ = tensors
-        gd_, ga_, gn_ = fn_("dL_dout_depth", dL_dout_depth), fn_("dL_dout_alpha", dL_dout_alpha), fn_("dL_dout_normal", dL_dout_normal)
-        radii_ = radii.contiguous()
-        if radii_.dtype != torch.int32:
-            raise RuntimeError(f"radii: expected an int32 tensor, got {radii_.dtype}")
-        raw = _lib.RawParams(_ptr(xyz_), _ptr(ls_), _ptr(rot_), _ptr(op_), _ptr(dc_), _ptr(rest_))
-        accum = _new((P, 16), torch.float32, device)   # cleared by the library
-        with torch.cuda.device(device):
-            rc = _lib.lib.gsr_backward_raw(
-                P, int(degree), M, int(R), _ptr(bg_), W, H, ctypes.byref(raw), float(scale_modifier), _ptr(vm_), _ptr(pm_), _ptr(cp_),
-                float(tan_fovx), float(tan_fovy), _ptr(radii_), _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), _ptr(oa_),
-                _ptr(gc_), _ptr(gd_), _ptr(ga_), _ptr(gn_), g2d.data_ptr(), gxyz.data_ptr(), gls.data_ptr(), grot.data_ptr(),
-                gop.data_ptr(), gdc.data_ptr(), grest.data_ptr() if M > 1 else None, accum.data_ptr(), 1 if debug else 0,
-                ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError(f"gsr_backward_raw failed ({rc}): {_lib.last_error()}")
-    return g2d, gxyz, gls, grot, gop, gdc, grest
-
-
-def _blend_cached(hit, background, colors, device, H, W, out_color, out_depth, out_alpha):
+def _blend_cached(hit, background, colors, device, P, H, W):
     """Second pass over cached geometry: one blend launch over the first pass's lists (gsr_blend)."""
+    out_color, out_depth, out_alpha, _radii, _ = _outputs(device, P, H, W, False)
     geom, binning, image = hit["geom"], hit["binning"], hit["image"]
     bg_, col_ = _f32c("background", background, device), _f32c("colors", colors, device)
     with torch.cuda.device(device):
@@ -568,37 +485,74 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     dL_dopacity = z(P, 1)
     dL_dcov3D = z(P, 6) if want_cov else None
     dL_dsh, dL_dscales, dL_drotations = z(P, M, 3), z(P, 3), z(P, 4)
-    if P != 0:
-        f = lambda n, t: _f32c(n, t, device)
-        # (beyond the reference: dL_dout_depth / dL_dout_alpha may be None = all zeros -- a loss that only reads the colour image;
-        # the per-pixel pass then skips their terms.  One of them alone is completed with zeros.)
-        if (dL_dout_depth is None) != (dL_dout_alpha is None):
-            like = (H, W)
-            dL_dout_depth = torch.zeros((1, *like), dtype=torch.float32, device=device) if dL_dout_depth is None else dL_dout_depth
-            dL_dout_alpha = torch.zeros((1, *like), dtype=torch.float32, device=device) if dL_dout_alpha is None else dL_dout_alpha
-        fn_ = lambda n, t: None if t is None else f(n, t)
-        bg_, m3_, sh_, col_, sc_, rot_, cov_, vm_, pm_, cp_, oa_, gc_, gd_, ga_ = (
-            f("background", background), f("means3D", means3D), f("sh", sh), f("colors", colors), f("scales", scales),
-            f("rotations", rotations), f("cov3D_precomp", cov3D_precomp), f("viewmatrix", viewmatrix),
-            f("projmatrix", projmatrix), f("campos", campos), f("out_alpha", out_alpha),
-            f("dL_dout_color", dL_dout_color), fn_("dL_dout_depth", dL_dout_depth), fn_("dL_dout_alpha", dL_dout_alpha))
-        radii_ = radii.contiguous()
-        if radii_.dtype != torch.int32:
-            raise RuntimeError(f"radii: expected an int32 tensor, got {radii_.dtype}")
-        accum = _new((P, 16), torch.float32, device)   # cleared by the library
-        with torch.cuda.device(device):
-            rc = _lib.lib.gsr_backward(
-                P, int(degree), M, int(R), _ptr(bg_), W, H, _ptr(m3_), _ptr(sh_), _ptr(col_), _ptr(sc_),
-                float(scale_modifier), _ptr(rot_), _ptr(cov_), _ptr(vm_), _ptr(pm_), _ptr(cp_), float(tan_fovx),
-                float(tan_fovy), _ptr(radii_), _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), _ptr(oa_),
-                _ptr(gc_), _ptr(gd_), _ptr(ga_), dL_dmeans2D.data_ptr(), _ptr(dL_dconic), dL_dopacity.data_ptr(),
-                _ptr(dL_dcolors), _ptr(dL_ddepths), dL_dmeans3D.data_ptr(), _ptr(dL_dcov3D),
-                dL_dsh.data_ptr() if M else None, dL_dscales.data_ptr(), dL_drotations.data_ptr(), accum.data_ptr(),
-                1 if debug else 0,
-                ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError(f"gsr_backward failed ({rc}): {_lib.last_error()}")
+    inputs = {"background": background, "means3D": means3D, "sh": sh, "colors": colors, "scales": scales,
+              "rotations": rotations, "cov3D_precomp": cov3D_precomp, "viewmatrix": viewmatrix, "projmatrix": projmatrix,
+              "campos": campos, "out_alpha": out_alpha, "dL_dout_color": dL_dout_color, "dL_dout_depth": dL_dout_depth,
+              "dL_dout_alpha": dL_dout_alpha}
+    _backward(_lib.lib.gsr_backward, device, P, H, W, inputs, radii, lambda p: (
+        P, int(degree), M, int(R), p["background"], W, H, p["means3D"], p["sh"], p["colors"], p["scales"],
+        float(scale_modifier), p["rotations"], p["cov3D_precomp"], p["viewmatrix"], p["projmatrix"], p["campos"],
+        float(tan_fovx), float(tan_fovy), p["radii"], _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), p["out_alpha"],
+        p["dL_dout_color"], p["dL_dout_depth"], p["dL_dout_alpha"], dL_dmeans2D.data_ptr(), _ptr(dL_dconic),
+        dL_dopacity.data_ptr(), _ptr(dL_dcolors), _ptr(dL_ddepths), dL_dmeans3D.data_ptr(), _ptr(dL_dcov3D),
+        dL_dsh.data_ptr() if M else None, dL_dscales.data_ptr(), dL_drotations.data_ptr()), debug)
     return dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations
+
+
+def rasterize_gaussians_raw_backward(background, xyz, log_scales, rotations, opacity_logits, features_dc, features_rest, radii,
+                                     scale_modifier, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, dL_dout_depth,
+                                     dL_dout_alpha, dL_dout_normal, degree, campos, geomBuffer, R, binningBuffer, imageBuffer,
+                                     out_alpha, debug):
+    """Gradients of a full ``rasterize_gaussians_raw`` call with respect to the model's raw tensors (``gsr_backward_raw``):
+    returns ``(dL_dmeans2D, dL_dxyz, dL_dlog_scales, dL_drotations, dL_dopacity_logits, dL_dfeatures_dc, dL_dfeatures_rest)``.
+    ``dL_dout_depth`` / ``dL_dout_alpha`` / ``dL_dout_normal`` may be None (no gradient for that image)."""
+    device = _require_gpu(xyz, "xyz")
+    P = int(xyz.size(0))
+    H, W = int(out_alpha.size(-2)), int(out_alpha.size(-1))
+    M = 1 + int(features_rest.size(1))
+    z = lambda *shape: _new(shape, torch.float32, device)
+    g2d, gxyz, gls, grot, gop = z(P, 3), z(P, 3), z(P, 3), z(P, 4), z(*opacity_logits.shape)
+    gdc, grest = z(P, 1, 3), z(P, M - 1, 3)
+    inputs = {"background": background, "xyz": xyz, "log_scales": log_scales, "rotations": rotations,
+              "opacity_logits": opacity_logits, "features_dc": features_dc, "features_rest": features_rest,
+              "viewmatrix": viewmatrix, "projmatrix": projmatrix, "campos": campos, "out_alpha": out_alpha,
+              "dL_dout_color": dL_dout_color, "dL_dout_depth": dL_dout_depth, "dL_dout_alpha": dL_dout_alpha,
+              "dL_dout_normal": dL_dout_normal}
+    _backward(_lib.lib.gsr_backward_raw, device, P, H, W, inputs, radii, lambda p: (
+        P, int(degree), M, int(R), p["background"], W, H, ctypes.byref(_raw_params(p)), float(scale_modifier), p["viewmatrix"],
+        p["projmatrix"], p["campos"], float(tan_fovx), float(tan_fovy), p["radii"], _ptr(geomBuffer), _ptr(binningBuffer),
+        _ptr(imageBuffer), p["out_alpha"], p["dL_dout_color"], p["dL_dout_depth"], p["dL_dout_alpha"], p["dL_dout_normal"],
+        g2d.data_ptr(), gxyz.data_ptr(), gls.data_ptr(), grot.data_ptr(), gop.data_ptr(), gdc.data_ptr(),
+        grest.data_ptr() if M > 1 else None), debug)
+    return g2d, gxyz, gls, grot, gop, gdc, grest
+
+
+def _backward(symbol, device, P, H, W, inputs, radii, args, debug):
+    """The one backward call behind both backward functions; nothing runs for P == 0.  Converts ``inputs`` (name -> tensor or
+    None) to float32 device pointers ``p[name]``, adds ``p["radii"]`` and calls the library's ``symbol`` with ``args(p)`` -- its
+    arguments before the accumulator scratch, ``debug`` and the stream."""
+    if P == 0:
+        return
+    # (beyond the reference: an image gradient may be None = all zeros -- a loss that only reads some of the images; the
+    # per-pixel pass then skips its terms.  dL_dout_depth / dL_dout_alpha are skipped together: one of them alone is completed
+    # with zeros, as is a missing colour gradient.)
+    zeros = lambda c: torch.zeros((c, H, W), dtype=torch.float32, device=device)
+    if inputs["dL_dout_color"] is None:
+        inputs["dL_dout_color"] = zeros(3)
+    if (inputs["dL_dout_depth"] is None) != (inputs["dL_dout_alpha"] is None):
+        inputs["dL_dout_depth"] = zeros(1) if inputs["dL_dout_depth"] is None else inputs["dL_dout_depth"]
+        inputs["dL_dout_alpha"] = zeros(1) if inputs["dL_dout_alpha"] is None else inputs["dL_dout_alpha"]
+    tensors = {n: None if t is None else _f32c(n, t, device) for n, t in inputs.items()}
+    p = {n: _ptr(t) for n, t in tensors.items()}
+    radii_ = radii.contiguous()
+    if radii_.dtype != torch.int32:
+        raise RuntimeError(f"radii: expected an int32 tensor, got {radii_.dtype}")
+    p["radii"] = _ptr(radii_)
+    accum = _new((P, 16), torch.float32, device)   # cleared by the library
+    with torch.cuda.device(device):
+        rc = symbol(*args(p), accum.data_ptr(), 1 if debug else 0, ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream))
+    if rc != 0:
+        raise RuntimeError(f"{symbol.__name__} failed ({rc}): {_lib.last_error()}")
 
 
 def mark_visible(means3D, viewmatrix, projmatrix) -> torch.Tensor:
