@@ -62,6 +62,26 @@ struct Shared {                    // per stream; LDS on the device (38 KB)
     Code lit, dist;
 };
 
+// ---- the input window: both instantiations hold the stream's words 64 at a time, the current piece [base, base + 64) and the next --
+enum WindowStep { kStay = 0, kAdvance = 1, kReopen = 2 };
+
+// Where word i lies against the window at `base`, and `base` moved to hold it: in the current piece (stay), in the next (advance
+// one piece), or anywhere else -- far ahead behind a long stored block, or BEHIND `base`: bits_seek starts over at the word where a
+// stored block ends, and behind a short one (an empty block of a sync flush) the prefetch may already have moved to the next piece
+// (reopen at i & ~63).  One unsigned difference tells all three apart: i < base wraps to far ahead.
+GSR_HD inline WindowStep window_step(uint32_t& base, uint32_t i) {
+    const uint32_t d = i - base;
+    if (d >= 128u) {
+        base = i & ~63u;
+        return kReopen;
+    }
+    if (d >= 64u) {
+        base += 64u;
+        return kAdvance;
+    }
+    return kStay;
+}
+
 // ---- what differs between the two instantiations ------------------------------------------------------------------------------
 template <int kLanes>
 struct Exec;
@@ -72,9 +92,31 @@ struct Exec<1> {                                   // host: one lane does every 
     static GSR_HD void sync() {}
     static GSR_HD uint32_t uni(uint32_t v) { return v; }
     static GSR_HD uint64_t sum(uint64_t v) { return v; }
-    struct Input {};                               // the stream's words: read where they lie
-    static GSR_HD void input_open(Input&, const uint32_t*, uint32_t) {}
-    static GSR_HD uint32_t input_word(Input&, const uint32_t* words, uint32_t n_words, uint32_t i) { return i < n_words ? words[i] : 0u; }
+    // The device's input window, word for word (Exec<64>::Input: lane k of `cur` is word base + k), so that the CPU tests run the
+    // window logic the GPU runs.  i - base is in [0, 64) behind window_step; were it not, the host reads what the device's v_readlane
+    // would (the lane's low six bits: a wrong word, which the tests see as a refused or misread stream), never outside `cur`.
+    struct Input {
+        uint32_t cur[64], nxt[64], base;
+    };
+    static GSR_HD void piece(uint32_t* dst, const uint32_t* words, uint32_t n_words, uint32_t base) {
+        for (uint32_t k = 0; k < 64u; ++k) dst[k] = base + k < n_words ? words[base + k] : 0u;
+    }
+    static GSR_HD void input_open(Input& in, const uint32_t* words, uint32_t n_words) {
+        in.base = 0;
+        piece(in.cur, words, n_words, 0);
+        piece(in.nxt, words, n_words, 64);
+    }
+    static GSR_HD uint32_t input_word(Input& in, const uint32_t* words, uint32_t n_words, uint32_t i) {
+        const WindowStep step = window_step(in.base, i);
+        if (step == kReopen) {
+            piece(in.cur, words, n_words, in.base);
+            piece(in.nxt, words, n_words, in.base + 64u);
+        } else if (step == kAdvance) {
+            for (int k = 0; k < 64; ++k) in.cur[k] = in.nxt[k];
+            piece(in.nxt, words, n_words, in.base + 64u);
+        }
+        return in.cur[(i - in.base) & 63u];
+    }
 };
 
 #if defined(__HIPCC__)
@@ -109,13 +151,12 @@ struct Exec<64> {                                  // device: a single-wave work
         in.cur = piece(words, n_words, 0);
         in.nxt = piece(words, n_words, 64);
     }
-    static __device__ uint32_t input_word(Input& in, const uint32_t* words, uint32_t n_words, uint32_t i) {      // i: uniform, never behind in.base
-        if (i >= in.base + 128u) {                 // a jump (behind a long stored block)
-            in.base = i & ~63u;
+    static __device__ uint32_t input_word(Input& in, const uint32_t* words, uint32_t n_words, uint32_t i) {      // i: uniform
+        const WindowStep step = window_step(in.base, i);
+        if (step == kReopen) {
             in.cur = piece(words, n_words, in.base);
             in.nxt = piece(words, n_words, in.base + 64u);
-        } else if (i >= in.base + 64u) {
-            in.base += 64u;
+        } else if (step == kAdvance) {
             in.cur = in.nxt;
             in.nxt = piece(words, n_words, in.base + 64u);
         }

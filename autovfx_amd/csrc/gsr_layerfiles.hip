@@ -156,7 +156,7 @@ bool walk_exr(const uint8_t* f, size_t n, const char* want, ExrWalk* out) {
     if (chans.empty()) return false;
     int pick = -1;
     if (want && *want) {
-        for (size_t i = 0; i < chans.size(); ++i)
+        for (size_t i = 0; i < chans.size() && pick < 0; ++i)      // (a name listed twice: the first entry, as layer_io.py takes it)
             if (std::strcmp(chans[i].name, want) == 0) pick = (int)i;
     } else {
         // what cv2.imread(path, ANYCOLOR | ANYDEPTH)[:, :, 0] is: the B channel of a colour file, else the one grey-ish channel there is

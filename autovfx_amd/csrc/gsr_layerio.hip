@@ -86,15 +86,20 @@ __device__ __forceinline__ uint32_t dpp_keep(uint32_t old, uint32_t src) {
 }
 
 // Row bytes -> one aligned 32-bit word per pixel (alpha byte 0 for RGB), in a scratch image whose rows have kUnfPad pixels in front
-// and kUnfTail behind: the wavefront kernel's 16-byte loads are then in bounds for every lane at every step.
+// and kUnfTail behind: the wavefront kernel's 16-byte loads are then in bounds for every lane at every step.  A workgroup row takes
+// rows y, y + gridDim.y, ...: a PNG may be 2^24 rows tall, the grid's y extent stays within kMaxGridY, the common gridDim.y limit
+// (the MI355X's runtime also took a grid 70 000 high; the loop keeps the launch from depending on that).
+constexpr int kMaxGridY = 65535;
 __global__ void __launch_bounds__(256) png_rows_to_words_kernel(UnfBatch batch) {
     const UnfJob& j = batch.job[blockIdx.z];
-    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
-    if (x >= j.W || y >= j.H) return;
-    const uint8_t* p = j.stream + (size_t)y * ((size_t)j.W * j.C + 1) + 1 + (size_t)x * j.C;
-    uint32_t v = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);
-    if (j.C == 4) v |= (uint32_t)p[3] << 24;
-    j.words[(size_t)y * (j.W + kUnfPad + kUnfTail) + kUnfPad + x] = v;
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    if (x >= j.W) return;
+    for (int y = blockIdx.y; y < j.H; y += gridDim.y) {
+        const uint8_t* p = j.stream + (size_t)y * ((size_t)j.W * j.C + 1) + 1 + (size_t)x * j.C;
+        uint32_t v = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);
+        if (j.C == 4) v |= (uint32_t)p[3] << 24;
+        j.words[(size_t)y * (j.W + kUnfPad + kUnfTail) + kUnfPad + x] = v;
+    }
 }
 
 __global__ void __launch_bounds__(kUnfWaves * 64) png_unfilter_kernel(UnfBatch batch) {
@@ -322,7 +327,7 @@ hipError_t launch_png_unfilter_batch(int n, const PngUnfilterJob* jobs, hipStrea
             max_w = std::max(max_w, j.width);
             max_h = std::max(max_h, j.height);
         }
-        hipLaunchKernelGGL(png_rows_to_words_kernel, dim3((max_w + 255) / 256, max_h, m), dim3(256), 0, stream, batch);
+        hipLaunchKernelGGL(png_rows_to_words_kernel, dim3((max_w + 255) / 256, std::min(max_h, kMaxGridY), m), dim3(256), 0, stream, batch);
         const size_t lds = (size_t)kUnfWaves * 2 * ((max_w + kUnfTail + 3) & ~3) * 4;
         hipLaunchKernelGGL(png_unfilter_kernel, dim3(m), dim3(kUnfWaves * 64), lds, stream, batch);
     }

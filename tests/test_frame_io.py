@@ -280,9 +280,12 @@ def _test_images(shape, seed):
     return {"noise": noise, "ramp": ramp, "flat": flat, "mixed": mixed}
 
 
+DEFLATE_SHAPES = [(1, 1, 4), (1, 1, 3), (7, 5, 4), (64, 33, 3), (4, 4096, 4), (4, 4095, 4), (5, 3277, 3), (300, 100, 4),
+                  (540, 960, 4), (540, 960, 3), (1080, 1920, 4), (17, 1285, 3), (2, 21845, 3)]
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("shape", [(1, 1, 4), (1, 1, 3), (7, 5, 4), (64, 33, 3), (4, 4096, 4), (4, 4095, 4), (5, 3277, 3), (300, 100, 4),
-                                   (540, 960, 4), (540, 960, 3), (1080, 1920, 4), (17, 1285, 3), (2, 21845, 3)])
+@pytest.mark.parametrize("shape", DEFLATE_SHAPES)
 @pytest.mark.parametrize("planar", [False, True])
 def test_gpu_deflate_png_files_are_valid_and_decode_to_the_image(shape, planar):
     """gsr_png_encode_deflate: a compressed file comes off the GPU finished.  Checked like the stored files (chunk CRCs, zlib inflates

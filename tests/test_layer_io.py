@@ -221,15 +221,35 @@ def _exr_corpus(tmp_path):
     files.append(written({"B": g.random((16, 24)).astype(np.float32)}, compression="ZIP"))                          # stored block
     files += [_hand_made(W=300, H=5, compressed="rle")[0], _hand_made(W=300, H=5, compressed=True)[0], _hand_made()[0]]
     files += [b"not an exr file at all", b"", struct.pack("<ii", 20000630, 2), struct.pack("<ii", 20000630, 2 | 0x200) + files[0][8:]]
+    files.append(_repeated_channel_file(z))
     return files
+
+
+def _repeated_channel_file(first, second=None):
+    """A ZIP file whose channel list names ``Y`` twice: written as ``Y`` (``first``) and ``Z`` (``second``), then the second name patched
+    in the header (same length and type: the offsets stay valid).  Whoever takes the channel must take the first ``Y``."""
+    import tempfile
+    second = first * 2 + 1 if second is None else second
+    with tempfile.TemporaryDirectory() as d:
+        p = os.path.join(d, "f.exr")
+        exr.write_exr(p, {"Y": first, "Z": second}, compression="ZIP")
+        buf = bytearray(open(p, "rb").read())
+    entry = b"Z\x00" + struct.pack("<iB3xii", 2, 0, 1, 1)
+    at = bytes(buf).index(b"Y\x00" + struct.pack("<iB3xii", 2, 0, 1, 1) + entry) + 18
+    buf[at] = ord("Y")
+    assert [n for n, _p in exr.read_header(bytes(buf))["channels"]] == ["Y", "Y"]
+    return bytes(buf)
 
 
 def test_native_exr_reader_is_the_python_one(tmp_path):
     files = _exr_corpus(tmp_path)
     for k, buf in enumerate(files):
         assert _native_exr(buf) == _python_exr(buf), f"corpus file {k}"
-        for want in ("A", "G", "Z", "nope"):
+        for want in ("A", "G", "Z", "Y", "nope"):
             assert _native_exr(buf, want) == _python_exr(buf, want), f"corpus file {k}, channel {want}"
+    repeated = files[-1]                                   # a channel name listed twice: both readers take the first
+    for want in (None, "Y"):
+        assert _native_exr(repeated, want)[0]["channel_at"] == 0 and _python_exr(repeated, want)[0]["channel_at"] == 0, want
     good = files[0]
     assert _native_exr(good) is not None and _native_exr(good)[1] == "B"
     for cut in list(range(0, 700, 5)) + list(range(700, len(good), 97)):
@@ -272,6 +292,55 @@ def _zlib_corpus(sizes=(0, 1, 2, 5, 100, 4095, 4096, 4097, 70000), levels=(0, 1,
     return out
 
 
+def _spliced(segments):
+    """A zlib stream put together from byte-aligned, non-final segments: ``("deflate", data, level, strategy)`` -- a raw-deflate piece that
+    ends with a sync flush -- or ``("stored", data)`` -- a hand-made stored block.  ``(stream, its data)``."""
+    stream, data = b"\x78\x01", b""
+    for seg in segments:
+        if seg[0] == "deflate":
+            c = zlib.compressobj(seg[2], zlib.DEFLATED, -15, 8, seg[3])
+            stream += c.compress(seg[1]) + c.flush(zlib.Z_SYNC_FLUSH)
+        else:
+            stream += b"\x00" + struct.pack("<HH", len(seg[1]), len(seg[1]) ^ 0xFFFF) + seg[1]
+        data += seg[1]
+    return stream + b"\x01\x00\x00\xff\xff" + struct.pack(">I", zlib.adler32(data)), data
+
+
+def _zlib_seek_corpus():
+    """(stream, its data) where the reader seeks back behind a short stored block: after a stored block the wave's reader starts over
+    at the word of the block's end, which can lie in front of the 64-word piece its prefetch has already moved to.  Sync / full flushes
+    every 150 ... 399 bytes (empty stored blocks), and stored blocks of 0 ... 12 bytes whose LEN / NLEN sit at every byte offset from
+    200 to 330 -- across the first 256-byte piece boundary, and across the one behind a 16 KB stored block (a jump).  zlib accepts
+    every stream; the corpus is the streams' data as ``zlib.decompress`` gives it."""
+    g = np.random.default_rng(7)
+    out = []
+    texts = (bytes(g.integers(0, 256, 3000, dtype=np.uint8)), bytes((np.arange(3000) % 97).astype(np.uint8)),
+             (b"stored blocks, short and empty, between the coded ones. " * 60)[:3000])
+    for data in texts:
+        for step in range(150, 400):
+            for mode in (zlib.Z_SYNC_FLUSH, zlib.Z_FULL_FLUSH):
+                c, stream = zlib.compressobj(6), b""
+                for k in range(0, len(data), step):
+                    stream += c.compress(data[k:k + step]) + c.flush(mode)
+                out.append(stream + c.flush())
+    head = ("deflate", bytes(g.integers(0, 256, 100, dtype=np.uint8)), 6, zlib.Z_FIXED)
+    head_bytes = len(_spliced([head])[0]) - 2 - 9
+    tail = [("deflate", b"a fixed-code segment: " + bytes(g.integers(0, 256, 200, dtype=np.uint8)) * 2, 1, zlib.Z_FIXED),
+            ("deflate", (b"and a dynamic one, " * 30) + bytes((np.arange(400) % 23).astype(np.uint8)), 6, zlib.Z_DEFAULT_STRATEGY)]
+    for jump in (0, 16384):
+        lead = [("stored", bytes(g.integers(0, 256, jump, dtype=np.uint8)))] if jump else []
+        lead_bytes = 5 + jump if jump else 0
+        for at in range(200, 331):              # byte offset of the short block's LEN, behind the jump
+            fill = jump + at - 1 - 2 - lead_bytes - head_bytes - 5        # a stored block that puts it there
+            assert fill >= 0
+            for n in range(13):
+                stream, _ = _spliced(lead + [head, ("stored", bytes(g.integers(0, 256, fill, dtype=np.uint8))),
+                                             ("stored", bytes(g.integers(0, 256, n, dtype=np.uint8)))] + tail)
+                assert stream[jump + at:jump + at + 4] == struct.pack("<HH", n, n ^ 0xFFFF)
+                out.append(stream)
+    return [(s, zlib.decompress(s)) for s in out]
+
+
 def _host_lane_inflate(stream, n):
     import ctypes
     out = ctypes.create_string_buffer(max(n, 1))
@@ -311,6 +380,13 @@ def test_wave_inflate_on_one_host_lane_is_zlib():
                 assert (rc == 0) == (want is not None) and (rc != 0 or out == want), f"level {level}: bit {bit} of byte {at}"
 
 
+def test_wave_inflate_on_one_host_lane_seeks_back_behind_short_stored_blocks():
+    """The host lane reads through the device's 64-word input window: every stream of the seek corpus -- the reader moved back in
+    front of the piece it has prefetched -- inflates to what zlib makes of it."""
+    bad = [k for k, (stream, data) in enumerate(_zlib_seek_corpus()) if _host_lane_inflate(stream, len(data)) != (0, data)]
+    assert not bad, f"{len(bad)} streams refused or misread, the first {bad[:10]}"
+
+
 # ---- the kernels -----------------------------------------------------------------------------------------------------------------
 
 def _unfilter_on_gpu(data: bytes) -> np.ndarray:
@@ -326,10 +402,11 @@ def _rgba(img):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("c", [3, 4])
-@pytest.mark.parametrize("hw", [(1, 1), (1, 9), (9, 1), (3, 5), (64, 64), (65, 130), (63, 3), (130, 61), (257, 300), (300, 7), (7, 1100)])
+@pytest.mark.parametrize("hw", [(1, 1), (1, 9), (9, 1), (3, 5), (64, 64), (65, 130), (63, 3), (130, 61), (257, 300), (300, 7), (7, 1100),
+                                (70000, 1)])
 def test_unfilter_every_filter_type(hw, c):
     """Rows of all five types in a fixed rotation and in random order, on images that cross the 64-row bands (1, 2, 3 and 5 of them:
-    one and two rounds of the four waves) and the 4-pixel groups."""
+    one and two rounds of the four waves) and the 4-pixel groups, and on one taller than a launch grid's y extent (65535)."""
     h, w = hw
     img = _noise(h, w, c, h * 1000 + w + c)
     for types in ([y % 5 for y in range(h)], np.random.default_rng(w).integers(0, 5, h), [4] * h, [3] * h):
@@ -396,6 +473,45 @@ def test_load_rgba_many_is_one_batch_of_mixed_images(tmp_path):
 
 
 @pytest.mark.gpu
+def test_load_rgba_many_takes_pngs_taller_than_the_grid(tmp_path):
+    """PNGs of 70 000 and 66 000 rows (the native walker and ``png_scanlines`` cover up to 2^24) among small ones in one batch: the
+    kernel takes them, and each result is Pillow's."""
+    dev = torch.device("cuda", 0)
+    paths = []
+    for k, (h, w, c) in enumerate([(9, 13, 4), (70000, 1, 3), (1, 1, 3), (66000, 3, 4), (64, 65, 3)]):
+        p = str(tmp_path / f"{k}.png")
+        data = _png_file(_noise(h, w, c, 40 + k), [y % 5 for y in range(h)], level=1)
+        assert layer_io.png_scanlines(data) is not None and _native_png(data) is not None
+        open(p, "wb").write(data)
+        paths.append(p)
+    for p, got in zip(paths, layer_io.load_rgba_many(paths, dev)):
+        np.testing.assert_array_equal(got.cpu().numpy(), np.array(Image.open(p).convert("RGBA")), err_msg=p)
+
+
+@pytest.mark.gpu
+def test_load_depth_takes_the_first_of_a_repeated_channel():
+    """A channel list that names ``Y`` twice: the plane of the first ``Y``, whether the file's channel is picked by the default rule
+    or asked for by name, with the blocks inflated on the host or on the GPU."""
+    import tempfile
+    dev = torch.device("cuda", 0)
+    yy, xx = np.mgrid[0:40, 0:96].astype(np.float32)
+    first = (3.0 + np.sin(xx * 0.05) + yy * 0.01).astype(np.float32)
+    buf = _repeated_channel_file(first)
+    assert layer_io.exr_blocks(buf, "Y") is not None                 # covered: the kernels read it, not the host fall-back
+    with tempfile.TemporaryDirectory() as d:
+        p = os.path.join(d, "Image0001.exr")
+        open(p, "wb").write(buf)
+        for flag in (None, torch.zeros(1, dtype=torch.int32, device=dev)):
+            got = layer_io.load_depth(p, dev, None, flag)
+            assert flag is None or int(flag.cpu()) == 0
+            np.testing.assert_array_equal(got.cpu().numpy(), first)
+    host, L = layer_io.read_exr_blocks(buf, layer_io.Staging(), "Y")
+    got = layer_io._unpack_plane(layer_io._upload(host, dev), L, dev)
+    torch.cuda.synchronize()
+    np.testing.assert_array_equal(got.cpu().numpy(), first)
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("compression", ["ZIPS", "ZIP"])
 @pytest.mark.parametrize("half", [False, True])
 @pytest.mark.parametrize("shape", [(1, 2), (16, 7), (17, 33), (54, 96), (100, 3), (540, 960)])
@@ -422,7 +538,7 @@ def test_zlib_streams_inflated_on_the_gpu():
     """``gsr_inflate_zlib_blocks``: the whole corpus in one launch, good streams beside damaged ones -- each good one inflates to its
     data, each damaged one is refused with the host lane's verdict, and no stream disturbs its neighbours."""
     dev = torch.device("cuda", 0)
-    corpus = _zlib_corpus(sizes=(0, 1, 5, 100, 4096, 4097, 70000, 300000), levels=(0, 1, 9), windows=(15,))
+    corpus = _zlib_corpus(sizes=(0, 1, 5, 100, 4096, 4097, 70000, 300000), levels=(0, 1, 9), windows=(15,)) + _zlib_seek_corpus()[::211]
     streams, sizes, want = [], [], []
     for k, (stream, data) in enumerate(corpus):
         if k % 5 == 3 and len(stream) > 12:                      # damage some: a flipped bit in the middle, or a lost tail
@@ -441,6 +557,85 @@ def test_zlib_streams_inflated_on_the_gpu():
             refused += 1
         at += sizes[k]
     assert refused > 10 and refused < len(want) // 3
+
+
+def _inflated_on_the_gpu_as_zlib(streams, dev):
+    """``inflate_zlib_streams`` of streams zlib accepts, all in one launch: every status 0, every output zlib's, byte for byte."""
+    want = [zlib.decompress(s) for s in streams]
+    out, status = layer_io.inflate_zlib_streams(streams, [len(d) for d in want], dev)
+    out, status = out.cpu().numpy().tobytes(), status.cpu().numpy()
+    bad, at = [], 0
+    for k, data in enumerate(want):
+        if status[k] != 0 or out[at:at + len(data)] != data:
+            bad.append((k, int(status[k])))
+        at += len(data)
+    assert not bad, f"{len(bad)} of {len(streams)} streams refused or misread (stream, status): {bad[:10]}"
+
+
+@pytest.mark.gpu
+def test_zlib_seek_corpus_inflated_on_the_gpu():
+    """The wave's reader moved back behind short stored blocks, on the device: the whole seek corpus in one launch."""
+    _inflated_on_the_gpu_as_zlib([s for s, _d in _zlib_seek_corpus()], torch.device("cuda", 0))
+
+
+def _idat(png: bytes) -> bytes:
+    at, out = 8, b""
+    while at < len(png):
+        n, = struct.unpack_from(">I", png, at)
+        if png[at + 4:at + 8] == b"IDAT":
+            out += png[at + 8:at + 8 + n]
+        at += 12 + n
+    return out
+
+
+@pytest.mark.gpu
+def test_gpu_deflate_png_streams_inflate_on_the_gpu():
+    """The project's own deflate writer (``gsr_png_encode_deflate``: a short stored block behind every 16 KB block) read back by the
+    wave's decoder: the IDAT stream of every image of the encoder's test, inflated on the GPU, is zlib's inflation of it."""
+    from test_frame_io import DEFLATE_SHAPES, _test_images
+    streams = []
+    for shape in DEFLATE_SHAPES:
+        h, w, c = shape
+        for img in _test_images(shape, h * 131 + w + c).values():
+            streams.append(_idat(frame_io.encode_png_gpu_deflate(torch.from_numpy(img).cuda()).cpu().numpy().tobytes()))
+    _inflated_on_the_gpu_as_zlib(streams, torch.device("cuda", 0))
+
+
+@pytest.mark.gpu
+def test_load_depth_inflates_sync_flushed_blocks_on_the_gpu(tmp_path):
+    """A 1920-wide ZIP depth pass whose every block is rewritten as a stream of the same payload, sync-flushed every 150 ... 400 bytes:
+    the GPU inflates it without setting the error flag (no silent fall-back to the host), and the plane is the host reader's."""
+    dev = torch.device("cuda", 0)
+    g = np.random.default_rng(3)
+    H, W = 40, 1920
+    yy, xx = np.mgrid[0:H, 0:W].astype(np.float32)
+    depth = (3.0 + np.sin(xx * 0.01) + np.cos(yy * 0.05) + 0.001 * g.random((H, W))).astype(np.float32)
+    p = str(tmp_path / "Image0001.exr")
+    exr.write_exr(p, {"R": depth, "G": depth, "B": depth + 1, "A": np.ones_like(depth)}, compression="ZIP")
+    buf = open(p, "rb").read()
+    table_at = exr.read_header(buf)["offsets_at"]
+    n_blocks = (H + 15) // 16
+    blocks = []
+    for off in struct.unpack_from(f"<{n_blocks}Q", buf, table_at):
+        y, size = struct.unpack_from("<ii", buf, off)
+        raw = zlib.decompress(buf[off + 8:off + 8 + size])
+        c, z, at = zlib.compressobj(6), b"", 0
+        while at < len(raw):
+            step = int(g.integers(150, 401))
+            z += c.compress(raw[at:at + step]) + c.flush(zlib.Z_SYNC_FLUSH)
+            at += step
+        z += c.flush()
+        assert len(z) < len(raw) and zlib.decompress(z) == raw          # (a block that did not shrink would be read as stored)
+        blocks.append(struct.pack("<ii", y, len(z)) + z)
+    at, table = table_at + 8 * n_blocks, b""
+    for b in blocks:
+        table += struct.pack("<Q", at)
+        at += len(b)
+    open(p, "wb").write(buf[:table_at] + table + b"".join(blocks))
+    flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    got = layer_io.load_depth_many([p], dev, error_flag=flag)[0]
+    assert int(flag.cpu()) == 0
+    np.testing.assert_array_equal(got.cpu().numpy().view(np.uint32), exr.load_depth_exr(p).view(np.uint32))
 
 
 @pytest.mark.gpu
