@@ -25,7 +25,7 @@ GEOM_SLOTS = ("raster", "rgb", "splat_bins", "internal_radii", "depth_order", "p
 BIN_SLOTS = ("point_list", "tile_keys")
 IMG_SLOTS = ("ranges", "n_contrib")
 STAGES = ("preprocess", "depth_sort", "scan", "duplicate", "tile_sort", "ranges", "blend", "colour")
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 
 class PngFileInfo(ctypes.Structure):
@@ -54,7 +54,8 @@ SYMBOLS = ("gsr_forward", "gsr_mark_visible", "gsr_backward", "gsr_last_geom_off
            "gsr_abi_version", "gsr_target_arch", "gsr_set_option", "gsr_get_option", "gsr_pack_rgba8", "gsr_png_size", "gsr_png_room", "gsr_png_encode", "gsr_frame_files", "gsr_png_deflate_max_size", "gsr_png_deflate_room", "gsr_png_deflate_scratch", "gsr_png_encode_deflate", "gsr_frame_files_deflate", "gsr_resize_rgba8_bilinear", "gsr_resize_f32_nearest", "gsr_png_unfilter_scratch", "gsr_png_unfilter", "gsr_png_unfilter_batch", "gsr_exr_unpack_channel", "gsr_upload", "gsr_png_file_probe", "gsr_png_file_inflate", "gsr_exr_file_probe", "gsr_exr_file_inflate", "gsr_selftest_inflate_host", "gsr_exr_file_pack", "gsr_inflate_zlib_blocks", "gsr_last_pair_counts", "gsr_blend", "gsr_composite",
            "gsr_radix_scratch_bytes", "gsr_radix_sort_pairs", "gsr_selftest_exp", "gsr_view_normals", "gsr_normal_maps", "gsr_forward_extra", "gsr_get_call_times",
            "gsr_forward_begin", "gsr_forward_finish", "gsr_forward_ready", "gsr_forward_cancel", "gsr_last_slab_pairs", "gsr_plan_slabs", "gsr_selftest_lds_atomic_order", "gsr_get_backward_times", "gsr_place_object",
-           "gsr_forward_raw", "gsr_forward_raw_begin", "gsr_backward_raw", "gsr_place_object_subset", "gsr_cube_to_equirect")
+           "gsr_forward_raw", "gsr_forward_raw_begin", "gsr_backward_raw", "gsr_place_object_subset", "gsr_cube_to_equirect",
+           "gsr_knn3_scratch_bytes", "gsr_knn3_mean_dist")
 OPT_TILE_CULL = 0
 OPT_SLABS = 1
 OPT_SLAB_FIRST = 2
@@ -198,6 +199,10 @@ def _load() -> ctypes.CDLL:
     lib.gsr_cube_to_equirect.restype = ctypes.c_int
     lib.gsr_cube_to_equirect.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p),
                                          c_f, c_f, c_f, ctypes.c_int, ctypes.c_int, c_f, c_f, c_f, ctypes.c_void_p]
+    lib.gsr_knn3_scratch_bytes.restype = ctypes.c_size_t
+    lib.gsr_knn3_scratch_bytes.argtypes = [ctypes.c_uint32]
+    lib.gsr_knn3_mean_dist.restype = ctypes.c_int
+    lib.gsr_knn3_mean_dist.argtypes = [ctypes.c_uint32, c_f, c_f, c_f, ctypes.c_size_t, ctypes.c_void_p]
     lib.gsr_resize_rgba8_bilinear.restype = ctypes.c_int
     lib.gsr_resize_rgba8_bilinear.argtypes = [c_f, ctypes.c_int, ctypes.c_int, c_f, ctypes.c_int, ctypes.c_int, c_f, ctypes.c_void_p]
     lib.gsr_resize_f32_nearest.restype = ctypes.c_int

@@ -681,6 +681,22 @@ int gsr_radix_sort_pairs(uint32_t n, int bits, uint32_t* keys, uint32_t* keys_al
     return GSR_OK;
 }
 
+size_t gsr_knn3_scratch_bytes(uint32_t n) {
+    return n >= gsr::kKnn3MaxPoints ? 0 : gsr::knn3_layout(n).bytes;
+}
+
+int gsr_knn3_mean_dist(uint32_t n, const float* points, float* out, void* scratch, size_t scratch_bytes, void* stream_) {
+    if (n == 0) return GSR_OK;
+    if (n >= gsr::kKnn3MaxPoints) return fail(GSR_ERR_INVALID_ARG, "gsr_knn3_mean_dist: %u points (at most 2^30 - 1)", n);
+    if (!points || !out || !scratch) return fail(GSR_ERR_INVALID_ARG, "null pointer");
+    if (((uintptr_t)points & 3u) != 0u || ((uintptr_t)out & 3u) != 0u || ((uintptr_t)scratch & 255u) != 0u)
+        return fail(GSR_ERR_INVALID_ARG, "gsr_knn3_mean_dist: misaligned pointer (points / out: 4 bytes, scratch: 256 bytes)");
+    if (scratch_bytes < gsr_knn3_scratch_bytes(n))
+        return fail(GSR_ERR_INVALID_ARG, "gsr_knn3_mean_dist: scratch too small (%zu of %zu bytes)", scratch_bytes, gsr_knn3_scratch_bytes(n));
+    GSR_HIP(gsr::launch_knn3_mean_dist(n, points, out, scratch, (hipStream_t)stream_));
+    return GSR_OK;
+}
+
 int gsr_view_normals(int P, const float* means3D, const float* axis, const float* cam_pos, float* colors, void* stream_) {
     if (P < 0) return fail(GSR_ERR_INVALID_ARG, "bad size P=%d", P);
     if (P == 0) return GSR_OK;

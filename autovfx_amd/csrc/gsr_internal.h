@@ -373,6 +373,26 @@ hipError_t launch_cube_to_equirect(const CubeFacePointers& faces, const CubeFace
                                    const float* grid_v, const int* grid_ceil, int H, int W, float* out, uint8_t* out_u8, float* out_depth,
                                    hipStream_t stream);
 
+// ---- three nearest neighbours (gsr_knn.hip) ----
+// Boxes over the Morton-sorted points: level 0 = leaves of 64 points, every level above = 16 boxes of the one below, up to the first
+// level of at most 16 boxes (six levels for n < 2^30).  A box is two float4 (lo, hi; w unused) at boxes[2 * (offset[level] + i)].
+constexpr int kKnnMaxLevels = 6;
+constexpr uint32_t kKnn3MaxPoints = 1u << 30;   // refused from here on (the radix sort's limit)
+struct KnnTree {
+    const float4* boxes;
+    uint32_t count[kKnnMaxLevels];
+    uint32_t offset[kKnnMaxLevels];
+    int top;
+};
+// Byte offsets of the regions of the caller's scratch (each 256-byte aligned); bytes = the whole.
+struct KnnLayout {
+    size_t keys, keys_alt, vals, vals_alt, key_hi, radix, packed, boxes, partials, bytes;
+    KnnTree tree;
+};
+KnnLayout knn3_layout(uint32_t n);
+// gsr.h: gsr_knn3_mean_dist; scratch: knn3_layout(n).bytes bytes, 256-byte aligned, any content; 0 < n < 2^30
+hipError_t launch_knn3_mean_dist(uint32_t n, const float* points, float* out, void* scratch, hipStream_t stream);
+
 // ---- the compositor's input files (gsr_layerio.hip) ----
 // The inflated IDAT stream of an 8-bit RGB / RGBA, non-interlaced PNG (device memory) -> RGBA8 [H,W,4] (alpha 255 for RGB).
 // scratch: png_unfilter_scratch_bytes(W, H) bytes, 16-byte aligned (0: the width is not supported).

@@ -1,0 +1,358 @@
+// gsr_knn.hip -- the mean squared distance of every point to its three nearest neighbours (include/gsr.h: gsr_knn3_mean_dist).
+//
+// The drop-in for simple_knn's distCUDA2 (sugar/gaussian_splatting/submodules/simple-knn), which GaussianModel.create_from_pcd uses
+// to give every Gaussian its initial scale.  The result is a pointwise function of the input ("Nearest neighbours"):
+//   out[i] = fl(fl(fl(s0 + s1) + s2) / 3),  s0 <= s1 <= s2 the three smallest of { d(i, j) : j != i, d(i, j) < FLT_MAX }, missing = FLT_MAX,
+//   d(i, j) = fl(fl(fl(dx dx) + fl(dy dy)) + fl(dz dz)),  dx = fl(x_j - x_i), ...
+// so any exact search gives the same bits.  This one, all stream-ordered, no host synchronisation:
+//
+//   bounds  : min / max over the finite points, per-workgroup partials (kBoundsBlocks of them, no atomics, nothing to clear);
+//   codes   : 63-bit Morton codes on a (2^21)^3 grid of those bounds; a point with a non-finite coordinate gets 2^63 (sorts last).
+//             Far outliers stretch the bounds of a COLMAP cloud: with 10 bits per axis its dense part would share a handful of
+//             cells, the leaves would be random samples of it and the search quadratic;
+//   sort    : (code, index) by the library's radix sort, low word first (iota payload), then the high word (stable);
+//   pack    : the points gathered once in sorted order into float4 (x, y, z, index bits); one wave per leaf of 64 points reduces
+//             the leaf's box (finite members only: a leaf of non-finite points has an empty box, lo = +inf, hi = -inf);
+//   levels  : boxes of 16 children each, level over level, until at most 16 boxes are left (six levels below 2^30 points);
+//   search  : one wave per leaf, one lane per query.  The slots are seeded with the wave's own leaf; then a depth-first walk over the
+//             tree from the top, a wave-uniform stack in LDS: a node's children are kept only if some lane's lower bound is not
+//             above that lane's third slot (ballot), and pushed nearest-first by their distance to the wave's own box.  A leaf is
+//             re-tested when it is popped, streamed into LDS with one coalesced 1 KiB load and read back by all lanes at once.
+//
+// Exactness: a box's lower bound is formed with the rounded operations of d(i, j) (per axis the gap lo - q or q - hi, squared,
+// summed in the same order).  Rounding to nearest is monotone, so the bound never exceeds the computed distance of a member, and a
+// box is skipped only when its bound is strictly greater than the lane's third slot -- no member could then enter a slot.  A
+// distance enters a slot only when it is below FLT_MAX (NaN and inf map to FLT_MAX before the branch-free insertion, whose
+// fmaxf would otherwise duplicate a slot).
+#include "gsr_internal.h"
+
+#include <cfloat>
+
+namespace gsr {
+namespace {
+
+constexpr int kLeaf = 64;            // points per leaf: one wave
+constexpr int kFan = 16;             // children per box above the leaves
+constexpr int kStackDepth = 96;      // >= kFan + (kFan - 1) * (kKnnMaxLevels - 1)
+constexpr int kBoundsBlocks = 128;   // partial bounds
+constexpr uint32_t kCellMax = (1u << 21) - 1u;   // 21 bits per axis: a 63-bit Morton code, sorted as two 32-bit words
+constexpr uint32_t kNonFiniteKey = 1u << 31;     // (the high word of a point with a non-finite coordinate)
+static_assert(kStackDepth >= kFan + (kFan - 1) * (kKnnMaxLevels - 1), "stack too shallow for the tree");
+
+__device__ __forceinline__ void wave_sync() {   // a wave's LDS operations run in program order: keep the compiler to it
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+__device__ __forceinline__ float wave_min(float v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v = fminf(v, __shfl_xor(v, d, 64));
+    return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d, 64));
+    return v;
+}
+__device__ __forceinline__ float lane_value(float v, int lane) {   // lane: wave-uniform
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
+}
+
+__device__ __forceinline__ bool finite3(float x, float y, float z) {
+    return __builtin_isfinite(x) && __builtin_isfinite(y) && __builtin_isfinite(z);
+}
+
+// d(i, j) of the contract: candidate minus query, squares summed left to right (the build has -ffp-contract=off)
+__device__ __forceinline__ float sq_dist(const float4& c, float qx, float qy, float qz) {
+    const float dx = c.x - qx, dy = c.y - qy, dz = c.z - qz;
+    return (dx * dx + dy * dy) + dz * dz;
+}
+
+// The same operations on the gap to a box: never above sq_dist of a member (see the file comment).  An empty box gives +inf.
+__device__ __forceinline__ float box_bound(const float4& lo, const float4& hi, float qx, float qy, float qz) {
+    const float gx = fmaxf(fmaxf(lo.x - qx, qx - hi.x), 0.0f);
+    const float gy = fmaxf(fmaxf(lo.y - qy, qy - hi.y), 0.0f);
+    const float gz = fmaxf(fmaxf(lo.z - qz, qz - hi.z), 0.0f);
+    return (gx * gx + gy * gy) + gz * gz;
+}
+
+// s0 <= s1 <= s2 stay sorted; NaN / inf / FLT_MAX change nothing (as the reference's strict `knn[j] > dist`)
+__device__ __forceinline__ void insert3(float d, float& s0, float& s1, float& s2) {
+    d = d < FLT_MAX ? d : FLT_MAX;
+    s2 = fminf(s2, fmaxf(s1, d));
+    s1 = fminf(s1, fmaxf(s0, d));
+    s0 = fminf(s0, d);
+}
+
+__device__ __forceinline__ uint64_t spread21(uint32_t v) {   // bit k of v (k < 21) -> bit 3k
+    uint64_t x = v & 0x1FFFFFu;
+    x = (x | (x << 32)) & 0x001F00000000FFFFull;
+    x = (x | (x << 16)) & 0x001F0000FF0000FFull;
+    x = (x | (x << 8)) & 0x100F00F00F00F00Full;
+    x = (x | (x << 4)) & 0x10C30C30C30C30C3ull;
+    x = (x | (x << 2)) & 0x1249249249249249ull;
+    return x;
+}
+
+__device__ __forceinline__ uint32_t grid_cell(float x, float lo, float hi) {
+    const float extent = hi - lo;
+    const float t = extent > 0.0f ? (x - lo) / extent * (float)kCellMax : 0.0f;
+    return t >= 0.0f ? (uint32_t)fminf(t, (float)kCellMax) : 0u;   // (NaN -> 0: the code only steers the search, never its result)
+}
+
+// lo / hi of six floats reduced over the workgroup (256 lanes), result in every lane
+__device__ void block_minmax(float lo[3], float hi[3], float* s_red /* 6 * 4 floats */) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int a = 0; a < 3; ++a) { lo[a] = wave_min(lo[a]); hi[a] = wave_max(hi[a]); }
+    if (lane == 0)
+        for (int a = 0; a < 3; ++a) { s_red[a * 4 + wave] = lo[a]; s_red[(3 + a) * 4 + wave] = hi[a]; }
+    __syncthreads();
+    for (int a = 0; a < 3; ++a) {
+        lo[a] = fminf(fminf(s_red[a * 4], s_red[a * 4 + 1]), fminf(s_red[a * 4 + 2], s_red[a * 4 + 3]));
+        hi[a] = fmaxf(fmaxf(s_red[(3 + a) * 4], s_red[(3 + a) * 4 + 1]), fmaxf(s_red[(3 + a) * 4 + 2], s_red[(3 + a) * 4 + 3]));
+    }
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(256) void knn_bounds_kernel(uint32_t n, const float* __restrict__ points, float4* __restrict__ partials) {
+    __shared__ float s_red[24];
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += kBoundsBlocks * 256u) {
+        const float x = points[3 * (size_t)i], y = points[3 * (size_t)i + 1], z = points[3 * (size_t)i + 2];
+        if (finite3(x, y, z)) {
+            lo[0] = fminf(lo[0], x); lo[1] = fminf(lo[1], y); lo[2] = fminf(lo[2], z);
+            hi[0] = fmaxf(hi[0], x); hi[1] = fmaxf(hi[1], y); hi[2] = fmaxf(hi[2], z);
+        }
+    }
+    block_minmax(lo, hi, s_red);
+    if (threadIdx.x == 0) {
+        partials[2 * blockIdx.x] = make_float4(lo[0], lo[1], lo[2], 0.0f);
+        partials[2 * blockIdx.x + 1] = make_float4(hi[0], hi[1], hi[2], 0.0f);
+    }
+}
+
+__global__ __launch_bounds__(256) void knn_codes_kernel(uint32_t n, const float* __restrict__ points, const float4* __restrict__ partials,
+                                                        uint32_t* __restrict__ key_lo, uint32_t* __restrict__ key_hi) {
+    __shared__ float s_red[24];
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    if (threadIdx.x < kBoundsBlocks) {
+        const float4 a = partials[2 * threadIdx.x], b = partials[2 * threadIdx.x + 1];
+        lo[0] = a.x; lo[1] = a.y; lo[2] = a.z; hi[0] = b.x; hi[1] = b.y; hi[2] = b.z;
+    }
+    block_minmax(lo, hi, s_red);
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
+        const float x = points[3 * (size_t)i], y = points[3 * (size_t)i + 1], z = points[3 * (size_t)i + 2];
+        uint64_t code = (uint64_t)kNonFiniteKey << 32;
+        if (finite3(x, y, z))
+            code = spread21(grid_cell(x, lo[0], hi[0])) | (spread21(grid_cell(y, lo[1], hi[1])) << 1) |
+                   (spread21(grid_cell(z, lo[2], hi[2])) << 2);
+        key_lo[i] = (uint32_t)code;
+        key_hi[i] = (uint32_t)(code >> 32);
+    }
+}
+
+// the high words in the order of the first sort (by the low words), for the second
+__global__ __launch_bounds__(256) void knn_gather_kernel(uint32_t n, const uint32_t* __restrict__ order, const uint32_t* __restrict__ key_hi,
+                                                         uint32_t* __restrict__ out) {
+    const uint32_t s = blockIdx.x * 256u + threadIdx.x;
+    if (s < n) out[s] = key_hi[order[s]];
+}
+
+// one wave per leaf: the sorted points packed, the leaf's box (finite members)
+__global__ __launch_bounds__(256) void knn_pack_kernel(uint32_t n, const float* __restrict__ points, const uint32_t* __restrict__ order,
+                                                       float4* __restrict__ packed, float4* __restrict__ leaf_boxes) {
+    const uint32_t s = blockIdx.x * 256u + threadIdx.x;
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    if (s < n) {
+        const uint32_t idx = order[s];
+        const float x = points[3 * (size_t)idx], y = points[3 * (size_t)idx + 1], z = points[3 * (size_t)idx + 2];
+        packed[s] = make_float4(x, y, z, __uint_as_float(idx));
+        if (finite3(x, y, z)) { lo[0] = hi[0] = x; lo[1] = hi[1] = y; lo[2] = hi[2] = z; }
+    }
+    for (int a = 0; a < 3; ++a) { lo[a] = wave_min(lo[a]); hi[a] = wave_max(hi[a]); }
+    const uint32_t leaf = s / kLeaf;
+    if ((threadIdx.x & 63) == 0 && leaf * kLeaf < n) {
+        leaf_boxes[2 * leaf] = make_float4(lo[0], lo[1], lo[2], 0.0f);
+        leaf_boxes[2 * leaf + 1] = make_float4(hi[0], hi[1], hi[2], 0.0f);
+    }
+}
+
+__global__ __launch_bounds__(256) void knn_level_kernel(uint32_t n_parents, uint32_t n_children, const float4* __restrict__ children,
+                                                        float4* __restrict__ parents) {
+    const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+    if (p >= n_parents) return;
+    float4 lo = make_float4(INFINITY, INFINITY, INFINITY, 0.0f), hi = make_float4(-INFINITY, -INFINITY, -INFINITY, 0.0f);
+    const uint32_t end = min(n_children, (p + 1) * kFan);
+    for (uint32_t c = p * kFan; c < end; ++c) {
+        const float4 a = children[2 * c], b = children[2 * c + 1];
+        lo.x = fminf(lo.x, a.x); lo.y = fminf(lo.y, a.y); lo.z = fminf(lo.z, a.z);
+        hi.x = fmaxf(hi.x, b.x); hi.y = fmaxf(hi.y, b.y); hi.z = fmaxf(hi.z, b.z);
+    }
+    parents[2 * p] = lo;
+    parents[2 * p + 1] = hi;
+}
+
+struct Query {
+    float x, y, z;
+    bool active;   // in range and finite: the others answer (3 FLT_MAX) / 3 = +inf
+};
+
+// Children [first, first + cnt) of `level` kept by some lane, pushed farthest first so the nearest is popped next.
+__device__ __forceinline__ void push_children(const KnnTree& tree, int level, uint32_t first, int cnt, uint32_t own_leaf, const Query& q,
+                                              float s2, const float4& wlo, const float4& whi, uint32_t* stack, int& top, int lane) {
+    const float4* boxes = tree.boxes + 2 * (size_t)tree.offset[level];
+    float4 clo = make_float4(INFINITY, INFINITY, INFINITY, 0.0f), chi = make_float4(-INFINITY, -INFINITY, -INFINITY, 0.0f);
+    if (lane < cnt) { clo = boxes[2 * (first + lane)]; chi = boxes[2 * (first + lane) + 1]; }
+    uint32_t keep = 0u;
+    for (int j = 0; j < cnt; ++j) {
+        const float4 lo = make_float4(lane_value(clo.x, j), lane_value(clo.y, j), lane_value(clo.z, j), 0.0f);
+        const float4 hi = make_float4(lane_value(chi.x, j), lane_value(chi.y, j), lane_value(chi.z, j), 0.0f);
+        const float lb = box_bound(lo, hi, q.x, q.y, q.z);
+        if (__ballot(q.active && !(lb > s2)) != 0ull) keep |= 1u << j;
+    }
+    if (level == 0 && own_leaf - first < (uint32_t)cnt) keep &= ~(1u << (own_leaf - first));   // seeded already
+    if (keep == 0u) return;
+    // order key: the gap between the child's box and the wave's queries' box
+    const float gx = fmaxf(fmaxf(clo.x - whi.x, wlo.x - chi.x), 0.0f);
+    const float gy = fmaxf(fmaxf(clo.y - whi.y, wlo.y - chi.y), 0.0f);
+    const float gz = fmaxf(fmaxf(clo.z - whi.z, wlo.z - chi.z), 0.0f);
+    const float key = (gx * gx + gy * gy) + gz * gz;
+    int rank = 0;   // kept children farther than this one (ties: the higher index counts as farther)
+    for (int j = 0; j < cnt; ++j) {
+        const float kj = lane_value(key, j);
+        rank += ((keep >> j) & 1u) && (kj > key || (kj == key && j > lane)) ? 1 : 0;
+    }
+    if (lane < cnt && ((keep >> lane) & 1u)) stack[top + rank] = ((uint32_t)level << 29) | (first + lane);
+    top += __popc(keep);
+    wave_sync();
+}
+
+__global__ __launch_bounds__(256) void knn_search_kernel(uint32_t n, const float4* __restrict__ packed, KnnTree tree, float* __restrict__ out) {
+    __shared__ float4 s_leaf[4][kLeaf];
+    __shared__ uint32_t s_stack[4][kStackDepth];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t own = blockIdx.x * 4u + (uint32_t)wave;    // this wave's leaf
+    if (own * kLeaf >= n) return;
+    float4* leaf = s_leaf[wave];
+    uint32_t* stack = s_stack[wave];
+    const uint32_t s = own * kLeaf + lane;
+    const float4 p = s < n ? packed[s] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    Query q;
+    q.active = s < n && finite3(p.x, p.y, p.z);
+    q.x = q.active ? p.x : 0.0f; q.y = q.active ? p.y : 0.0f; q.z = q.active ? p.z : 0.0f;
+    float s0 = FLT_MAX, s1 = FLT_MAX, s2 = FLT_MAX;
+
+    // seed: the own leaf, every member but the lane itself
+    const int own_cnt = (int)min((uint32_t)kLeaf, n - own * kLeaf);
+    leaf[lane] = p;
+    wave_sync();
+    for (int c = 0; c < own_cnt; ++c) {
+        const float d = sq_dist(leaf[c], q.x, q.y, q.z);
+        insert3(c != lane ? d : FLT_MAX, s0, s1, s2);
+    }
+
+    if (__ballot(q.active) != 0ull) {
+        // the box of the wave's queries orders the walk
+        float4 wlo = make_float4(wave_min(q.active ? q.x : INFINITY), wave_min(q.active ? q.y : INFINITY),
+                                 wave_min(q.active ? q.z : INFINITY), 0.0f);
+        float4 whi = make_float4(wave_max(q.active ? q.x : -INFINITY), wave_max(q.active ? q.y : -INFINITY),
+                                 wave_max(q.active ? q.z : -INFINITY), 0.0f);
+        int top = 0;
+        push_children(tree, tree.top, 0u, (int)tree.count[tree.top], own, q, s2, wlo, whi, stack, top, lane);
+        while (top > 0) {
+            const uint32_t e = (uint32_t)__builtin_amdgcn_readfirstlane((int)stack[--top]);
+            const int level = (int)(e >> 29);
+            const uint32_t idx = e & ((1u << 29) - 1u);
+            if (level > 0) {
+                const uint32_t first = idx * kFan;
+                push_children(tree, level - 1, first, (int)min((uint32_t)kFan, tree.count[level - 1] - first), own, q, s2, wlo, whi, stack,
+                              top, lane);
+                continue;
+            }
+            const float4 lo = tree.boxes[2 * (size_t)idx], hi = tree.boxes[2 * (size_t)idx + 1];   // (leaves: level offset 0)
+            const float lb = box_bound(lo, hi, q.x, q.y, q.z);
+            if (__ballot(q.active && !(lb > s2)) == 0ull) continue;    // the slots have tightened since the push
+            const uint32_t base = idx * kLeaf;
+            const int cnt = (int)min((uint32_t)kLeaf, n - base);
+            wave_sync();
+            leaf[lane] = lane < cnt ? packed[base + lane] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            wave_sync();
+            for (int c = 0; c < cnt; ++c) insert3(sq_dist(leaf[c], q.x, q.y, q.z), s0, s1, s2);
+        }
+    }
+    if (s < n) {
+        if (!q.active) s0 = s1 = s2 = FLT_MAX;
+        out[__float_as_uint(p.w)] = ((s0 + s1) + s2) / 3.0f;
+    }
+}
+
+constexpr size_t kAlign = 256;
+size_t align_up(size_t v) { return (v + kAlign - 1) & ~(kAlign - 1); }
+
+}  // namespace
+
+KnnLayout knn3_layout(uint32_t n) {
+    KnnLayout L = {};
+    if (n == 0) return L;
+    uint32_t count = (n + kLeaf - 1) / kLeaf, boxes = 0;
+    for (int level = 0;; ++level) {
+        L.tree.count[level] = count;
+        L.tree.offset[level] = boxes;
+        boxes += count;
+        if (count <= (uint32_t)kFan || level + 1 == kKnnMaxLevels) { L.tree.top = level; break; }
+        count = (count + kFan - 1) / kFan;
+    }
+    size_t at = 0;
+    auto take = [&](size_t bytes) { const size_t here = at; at = align_up(at + bytes); return here; };
+    L.keys = take(4 * (size_t)n);
+    L.keys_alt = take(4 * (size_t)n);
+    L.vals = take(4 * (size_t)n);
+    L.vals_alt = take(4 * (size_t)n);
+    L.key_hi = take(4 * (size_t)n);
+    L.radix = take(radix_scratch_words(n) * sizeof(uint32_t));
+    L.packed = take(16 * (size_t)n);
+    L.boxes = take(32 * (size_t)boxes);
+    L.partials = take(32 * (size_t)kBoundsBlocks);
+    L.bytes = at;
+    return L;
+}
+
+hipError_t launch_knn3_mean_dist(uint32_t n, const float* points, float* out, void* scratch, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    KnnLayout L = knn3_layout(n);
+    if (L.tree.count[L.tree.top] > (uint32_t)kFan) return hipErrorInvalidValue;   // (n < 2^30 never gets here)
+    char* base = static_cast<char*>(scratch);
+    uint32_t* keys = reinterpret_cast<uint32_t*>(base + L.keys);
+    uint32_t* keys_alt = reinterpret_cast<uint32_t*>(base + L.keys_alt);
+    uint32_t* vals = reinterpret_cast<uint32_t*>(base + L.vals);
+    uint32_t* vals_alt = reinterpret_cast<uint32_t*>(base + L.vals_alt);
+    float4* packed = reinterpret_cast<float4*>(base + L.packed);
+    float4* boxes = reinterpret_cast<float4*>(base + L.boxes);
+    float4* partials = reinterpret_cast<float4*>(base + L.partials);
+
+    uint32_t* key_hi = reinterpret_cast<uint32_t*>(base + L.key_hi);
+    hipLaunchKernelGGL(knn_bounds_kernel, dim3(kBoundsBlocks), dim3(256), 0, stream, n, points, partials);
+    const uint32_t blocks = (n + 255u) / 256u;
+    hipLaunchKernelGGL(knn_codes_kernel, dim3(min(blocks, 2048u)), dim3(256), 0, stream, n, points, (const float4*)partials, keys, key_hi);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    // the 63-bit codes, least significant word first (both sorts are stable)
+    uint32_t* rscratch = reinterpret_cast<uint32_t*>(base + L.radix);
+    uint32_t *ks = nullptr, *vs = nullptr;
+    e = radix_sort_pairs(rscratch, n, 32, keys, keys_alt, vals, vals_alt, true, false, &ks, &vs, stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(knn_gather_kernel, dim3(blocks), dim3(256), 0, stream, n, (const uint32_t*)vs, (const uint32_t*)key_hi, keys);
+    e = radix_sort_pairs(rscratch, n, 32, keys, keys_alt, vs, vs == vals ? vals_alt : vals, false, false, &ks, &vs, stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(knn_pack_kernel, dim3(blocks), dim3(256), 0, stream, n, points, (const uint32_t*)vs, packed, boxes);
+    for (int level = 1; level <= L.tree.top; ++level)
+        hipLaunchKernelGGL(knn_level_kernel, dim3((L.tree.count[level] + 255u) / 256u), dim3(256), 0, stream, L.tree.count[level],
+                           L.tree.count[level - 1], (const float4*)(boxes + 2 * (size_t)L.tree.offset[level - 1]),
+                           boxes + 2 * (size_t)L.tree.offset[level]);
+    KnnTree tree = L.tree;
+    tree.boxes = boxes;
+    hipLaunchKernelGGL(knn_search_kernel, dim3((L.tree.count[0] + 3u) / 4u), dim3(256), 0, stream, n, (const float4*)packed, tree, out);
+    return hipGetLastError();
+}
+
+}  // namespace gsr

@@ -42,11 +42,12 @@
 extern "C" {
 #endif
 
-/* 15: + panoramas (gsr_cube_to_equirect).
+/* 16: + three nearest neighbours (gsr_knn3_scratch_bytes, gsr_knn3_mean_dist).
+ * 15: + panoramas (gsr_cube_to_equirect).
  * 14 (round 6): + the compositor's input files -- gsr_png_unfilter(_batch), gsr_exr_unpack_channel, gsr_inflate_zlib_blocks, the host-side
  * gsr_png_file_* / gsr_exr_file_* readers, gsr_upload.  13: + compressed frame files (gsr_png_encode_deflate, gsr_frame_files_deflate).
  * Additions only: a binding written against 12 works unchanged apart from the version it checks. */
-#define GSR_ABI_VERSION 15
+#define GSR_ABI_VERSION 16
 
 #if defined(__GNUC__)
 #define GSR_API __attribute__((visibility("default")))
@@ -402,6 +403,18 @@ GSR_API size_t gsr_radix_scratch_bytes(uint32_t n, int bits);
 GSR_API int gsr_radix_sort_pairs(uint32_t n, int bits, uint32_t* keys, uint32_t* keys_alt, uint32_t* vals,
                                  uint32_t* vals_alt, int iota_payload, void* scratch, size_t scratch_bytes,
                                  int* sorted_in_alt, void* stream);
+
+/* Three nearest neighbours (simple_knn's distCUDA2: GaussianModel.create_from_pcd's initial scales, gaussian_model.py:144) -- ABI 16.
+ * points [n,3] fp32 -> out [n] fp32, out[i] = fl(fl(fl(s0 + s1) + s2) / 3) with s0 <= s1 <= s2 the three smallest of
+ * { d(i, j) : j != i, d(i, j) < FLT_MAX } (missing ones: FLT_MAX), d(i, j) = fl(fl(fl(dx dx) + fl(dy dy)) + fl(dz dz)), dx = fl(x_j - x_i).
+ * The self is excluded by index (a duplicate is a neighbour at distance 0); a point with a non-finite coordinate is nobody's neighbour
+ * and gets +inf; n <= 2 gives +inf everywhere.  An exact search: the result does not depend on the traversal ("Nearest
+ * neighbours").  scratch: gsr_knn3_scratch_bytes(n) bytes of device memory (about 37 per point), 256-byte aligned, any content;
+ * gsr_knn3_scratch_bytes returns 0 for n >= 2^30.  n == 0 succeeds without touching anything.  Refused (GSR_ERR_INVALID_ARG, nothing
+ * launched): n >= 2^30, a null pointer, misaligned pointers, too little scratch.  Enqueues on `stream` only: no host synchronisation,
+ * no device-to-host copy. */
+GSR_API size_t gsr_knn3_scratch_bytes(uint32_t n);
+GSR_API int gsr_knn3_mean_dist(uint32_t n, const float* points, float* out, void* scratch, size_t scratch_bytes, void* stream);
 
 /* The elementwise work of the reference's per-frame render() around its two rasterizer passes
  * (sugar/gaussian_splatting/gaussian_renderer/__init__.py:118-146,169-208), as two kernels instead of ~40 framework
