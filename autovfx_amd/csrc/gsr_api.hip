@@ -697,6 +697,49 @@ int gsr_knn3_mean_dist(uint32_t n, const float* points, float* out, void* scratc
     return GSR_OK;
 }
 
+namespace {
+// the sizes gsr_ssim_* accept: every dimension > 0, n c h w < 2^31
+bool ssim_size_ok(int n, int c, int h, int w) {
+    if (n <= 0 || c <= 0 || h <= 0 || w <= 0) return false;
+    const int64_t nc = (int64_t)n * c, nch = nc * h;
+    return nc < (int64_t(1) << 31) && nch < (int64_t(1) << 31) && nch * w < (int64_t(1) << 31);
+}
+bool aligned4(const void* p) { return ((uintptr_t)p & 3u) == 0u; }
+gsr::SsimWindow ssim_window(const float* window11) {
+    gsr::SsimWindow win;
+    for (int k = 0; k < gsr::kSsimTaps; ++k) win.w[k] = window11[k];
+    return win;
+}
+}  // namespace
+
+size_t gsr_ssim_scratch_bytes(int n, int c, int h, int w) {
+    return ssim_size_ok(n, c, h, w) ? (size_t)gsr::ssim_shape(n, c, h, w).blocks * sizeof(float) : 0;
+}
+
+int gsr_ssim_forward(int n, int c, int h, int w, const float* x, const float* y, const float* window11, int per_image, float* out,
+                     float* coef_or_null, void* scratch, size_t scratch_bytes, void* stream_) {
+    if (!ssim_size_ok(n, c, h, w)) return fail(GSR_ERR_INVALID_ARG, "gsr_ssim_forward: bad size %d x %d x %d x %d (each > 0, product < 2^31)", n, c, h, w);
+    if (!x || !y || !window11 || !out || !scratch) return fail(GSR_ERR_INVALID_ARG, "gsr_ssim_forward: null pointer");
+    if (!aligned4(x) || !aligned4(y) || !aligned4(out) || !aligned4(coef_or_null) || !aligned4(scratch))
+        return fail(GSR_ERR_INVALID_ARG, "gsr_ssim_forward: misaligned pointer (4 bytes)");
+    if (scratch_bytes < gsr_ssim_scratch_bytes(n, c, h, w))
+        return fail(GSR_ERR_INVALID_ARG, "gsr_ssim_forward: scratch too small (%zu of %zu bytes)", scratch_bytes, gsr_ssim_scratch_bytes(n, c, h, w));
+    GSR_HIP(gsr::launch_ssim_forward(gsr::ssim_shape(n, c, h, w), ssim_window(window11), x, y, per_image ? 1 : 0, out, coef_or_null,
+                                     (float*)scratch, (hipStream_t)stream_));
+    return GSR_OK;
+}
+
+int gsr_ssim_backward(int n, int c, int h, int w, const float* x, const float* y, const float* coef, const float* window11, int per_image,
+                      const float* grad_out, float* grad_x, void* stream_) {
+    if (!ssim_size_ok(n, c, h, w)) return fail(GSR_ERR_INVALID_ARG, "gsr_ssim_backward: bad size %d x %d x %d x %d (each > 0, product < 2^31)", n, c, h, w);
+    if (!x || !y || !coef || !window11 || !grad_out || !grad_x) return fail(GSR_ERR_INVALID_ARG, "gsr_ssim_backward: null pointer");
+    if (!aligned4(x) || !aligned4(y) || !aligned4(coef) || !aligned4(grad_out) || !aligned4(grad_x))
+        return fail(GSR_ERR_INVALID_ARG, "gsr_ssim_backward: misaligned pointer (4 bytes)");
+    GSR_HIP(gsr::launch_ssim_backward(gsr::ssim_shape(n, c, h, w), ssim_window(window11), x, y, coef, per_image ? 1 : 0, grad_out, grad_x,
+                                      (hipStream_t)stream_));
+    return GSR_OK;
+}
+
 int gsr_view_normals(int P, const float* means3D, const float* axis, const float* cam_pos, float* colors, void* stream_) {
     if (P < 0) return fail(GSR_ERR_INVALID_ARG, "bad size P=%d", P);
     if (P == 0) return GSR_OK;

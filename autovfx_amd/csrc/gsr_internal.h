@@ -373,6 +373,25 @@ hipError_t launch_cube_to_equirect(const CubeFacePointers& faces, const CubeFace
                                    const float* grid_v, const int* grid_ceil, int H, int W, float* out, uint8_t* out_u8, float* out_depth,
                                    hipStream_t stream);
 
+// ---- structural similarity (gsr_ssim.hip) ----
+constexpr int kSsimTaps = 11;
+constexpr float kSsimC1 = (float)(0.01 * 0.01);   // the reference's Python constants, rounded to fp32 as its fp32 tensor ops do
+constexpr float kSsimC2 = (float)(0.03 * 0.03);
+struct SsimWindow {   // the separable window, passed by value
+    float w[kSsimTaps];
+};
+struct SsimShape {
+    int n, c, h, w;
+    int tiles_x;
+    uint32_t tiles_per_plane, blocks;   // blocks = n c tiles_per_plane (one partial sum each)
+};
+SsimShape ssim_shape(int n, int c, int h, int w);   // n c h w < 2^31
+// gsr.h: gsr_ssim_forward; partials: s.blocks floats; coef: null, or 3 n c h w floats (the maps a, b, c, one after the other)
+hipError_t launch_ssim_forward(const SsimShape& s, const SsimWindow& win, const float* x, const float* y, int per_image, float* out,
+                               float* coef, float* partials, hipStream_t stream);
+hipError_t launch_ssim_backward(const SsimShape& s, const SsimWindow& win, const float* x, const float* y, const float* coef,
+                                int per_image, const float* grad_out, float* grad_x, hipStream_t stream);
+
 // ---- three nearest neighbours (gsr_knn.hip) ----
 // Boxes over the Morton-sorted points: level 0 = leaves of 64 points, every level above = 16 boxes of the one below, up to the first
 // level of at most 16 boxes (six levels for n < 2^30).  A box is two float4 (lo, hi; w unused) at boxes[2 * (offset[level] + i)].

@@ -27,7 +27,12 @@ AutoVFX reaches the rasterizer through two imports (paths under the reference tr
 6. every module named ``...gaussian_renderer`` -- already imported or imported later (a ``sys.meta_path`` hook) -- gets its
    ``render`` replaced by ``autovfx_amd.renderer.render`` (same signature, same result dictionary; the original stays
    reachable as ``<module>.reference_render``), and every already-imported module that holds the original function under
-   any name (``from ... import render [as gs_render]``) is rebound too.
+   any name (``from ... import render [as gs_render]``) is rebound too;
+7. a module named ``...loss_utils`` that defines ``ssim``, ``_ssim`` and ``create_window`` (``utils/loss_utils.py``, its SuGaR copy
+   ``sugar_utils/loss_utils.py``) gets its ``ssim`` replaced by ``autovfx_amd.ssim.drop_in(<the original>)``: the fused HIP
+   forward and backward where they apply, the original for every other call; the original stays reachable as
+   ``<module>.reference_ssim``, and already-imported modules holding it under any name (``train.py``, ``metrics.py``, the SuGaR
+   trainers, ``scene_representation``) are rebound.
 
 Nothing else of the reference is touched: its ``GaussianModel``, cameras, scene editing and I/O run as they are.  With
 autograd off, ``render`` reads the model's six raw parameter tensors and activates them inside the HIP kernels
@@ -52,6 +57,7 @@ _BLEND_LEAF = "blend_all"                # blender/blend_all.py: its blend_frame
 _SCENE_LEAF = "scene_representation"     # scene_representation.py: SceneRepresentation.render_from_3DGS is the frame loop (:337-447)
 _SUGAR_LEAF = "sugar_model"              # sugar/sugar_scene/sugar_model.py: SuGaR.render_image_gaussian_rasterizer calls the rasterizer twice (:2141,2174)
 _PANO_LEAF = "render_panorama"           # sugar/gaussian_splatting/render_panorama.py: render_panorama() (:100-145), imported directly by its users
+_LOSS_LEAF = "loss_utils"                # utils/loss_utils.py, sugar_utils/loss_utils.py: ssim() (:33-62) of every training loop's loss
 _installed: Optional["_RendererHook"] = None
 patched_modules: List[str] = []          # names of the modules whose ``render`` was replaced (introspection / tests)
 _strict = True                           # install(strict=...): may a failure to load the render path break the importing process?
@@ -60,7 +66,7 @@ _gave_up = False                         # lenient mode: the render path could n
 
 def _is_target(fullname: str) -> bool:
     return any(fullname == leaf or fullname.endswith("." + leaf) for leaf in (_TARGET_LEAF, _BLEND_LEAF, _SCENE_LEAF, _SUGAR_LEAF,
-                                                                                  _PANO_LEAF))
+                                                                                  _PANO_LEAF, _LOSS_LEAF))
 
 
 def _is_blend_module(name: str) -> bool:
@@ -167,6 +173,47 @@ def _patch_panorama_module(module: types.ModuleType) -> None:
         patched_modules.append(module.__name__)
 
 
+def _is_loss_module(name: str) -> bool:
+    return name == _LOSS_LEAF or name.endswith("." + _LOSS_LEAF)
+
+
+def _rebind(original, ours, skip: types.ModuleType) -> None:
+    """Every imported module but ``skip`` that holds ``original`` under some name gets ``ours`` instead."""
+    for other in list(sys.modules.values()):
+        d = getattr(other, "__dict__", None)
+        if not isinstance(d, dict) or other is skip:
+            continue
+        for key, value in list(d.items()):
+            if value is original:
+                d[key] = ours
+
+
+def _patch_loss_module(module: types.ModuleType) -> None:
+    """``ssim`` (loss_utils.py:33-62) becomes autovfx_amd.ssim.drop_in(original): same signature and results, the fused kernels
+    where they apply and the original everywhere else.  The original stays reachable as ``<module>.reference_ssim``."""
+    global _gave_up
+    d = module.__dict__
+    original = d.get("ssim")
+    if not all(callable(d.get(k)) for k in ("ssim", "_ssim", "create_window")) or _gave_up:
+        return
+    if (getattr(original, "__module__", None) or "").startswith("autovfx_amd"):
+        return
+    try:
+        from .ssim import drop_in      # imports torch and loads libgsr_hip.so
+        ours = drop_in(original)
+    except Exception as e:
+        if _strict:
+            raise
+        _gave_up = True
+        sys.stderr.write(f"[autovfx_amd] {module.__name__}.ssim left as the reference's: the fused SSIM could not be loaded ({e!r})\n")
+        return
+    module.reference_ssim = original
+    module.ssim = ours
+    if module.__name__ not in patched_modules:
+        patched_modules.append(module.__name__)
+    _rebind(original, ours, module)
+
+
 def _our_render() -> Callable:
     from .renderer import render   # imports torch and loads libgsr_hip.so: only when a renderer module really appears
     return render
@@ -187,6 +234,9 @@ def _patch_renderer_module(module: types.ModuleType) -> None:
         return
     if _is_panorama_module(module.__name__):
         _patch_panorama_module(module)
+        return
+    if _is_loss_module(module.__name__):
+        _patch_loss_module(module)
         return
     if _is_blend_module(module.__name__):
         # the compositing step of the edit loop: ``blend_all.blend_frames(results_dir, cfg_path)`` (scene_representation.py:232) becomes
@@ -230,13 +280,7 @@ def _patch_renderer_module(module: types.ModuleType) -> None:
     if module.__name__ not in patched_modules:
         patched_modules.append(module.__name__)
     # importers that already bound the original under some name (``from ... import render as gs_render``)
-    for other in list(sys.modules.values()):
-        d = getattr(other, "__dict__", None)
-        if not isinstance(d, dict) or other is module:
-            continue
-        for key, value in list(d.items()):
-            if value is original:
-                d[key] = ours
+    _rebind(original, ours, module)
 
 
 class _PatchingLoader(importlib.abc.Loader):
@@ -298,8 +342,8 @@ def install(path: bool = True, strict: bool = True) -> None:
 
 
 def uninstall() -> None:
-    """Remove the import hook and put the reference's ``render`` back into the modules ``install`` patched (importers that
-    were rebound keep what they hold; meant for tests)."""
+    """Remove the import hook and put the reference's functions back into the modules ``install`` patched (importers of
+    ``render`` that were rebound keep what they hold, importers of ``ssim`` get the original again; meant for tests)."""
     global _installed, _strict, _gave_up
     if _installed is not None and _installed in sys.meta_path:
         sys.meta_path.remove(_installed)
@@ -311,6 +355,10 @@ def uninstall() -> None:
             module.render = module.reference_render
         if module is not None and hasattr(module, "reference_blend_frames"):
             module.blend_frames = module.reference_blend_frames
+        if module is not None and "reference_ssim" in module.__dict__:
+            ours, module.ssim = module.ssim, module.reference_ssim
+            del module.reference_ssim
+            _rebind(ours, module.ssim, module)
         if module is not None and "reference_render_panorama" in module.__dict__:
             module.render_panorama = module.reference_render_panorama
             del module.reference_render_panorama

@@ -42,12 +42,13 @@
 extern "C" {
 #endif
 
-/* 16: + three nearest neighbours (gsr_knn3_scratch_bytes, gsr_knn3_mean_dist).
+/* 17: + structural similarity (gsr_ssim_scratch_bytes, gsr_ssim_forward, gsr_ssim_backward).
+ * 16: + three nearest neighbours (gsr_knn3_scratch_bytes, gsr_knn3_mean_dist).
  * 15: + panoramas (gsr_cube_to_equirect).
  * 14 (round 6): + the compositor's input files -- gsr_png_unfilter(_batch), gsr_exr_unpack_channel, gsr_inflate_zlib_blocks, the host-side
  * gsr_png_file_* / gsr_exr_file_* readers, gsr_upload.  13: + compressed frame files (gsr_png_encode_deflate, gsr_frame_files_deflate).
  * Additions only: a binding written against 12 works unchanged apart from the version it checks. */
-#define GSR_ABI_VERSION 16
+#define GSR_ABI_VERSION 17
 
 #if defined(__GNUC__)
 #define GSR_API __attribute__((visibility("default")))
@@ -415,6 +416,26 @@ GSR_API int gsr_radix_sort_pairs(uint32_t n, int bits, uint32_t* keys, uint32_t*
  * no device-to-host copy. */
 GSR_API size_t gsr_knn3_scratch_bytes(uint32_t n);
 GSR_API int gsr_knn3_mean_dist(uint32_t n, const float* points, float* out, void* scratch, size_t scratch_bytes, void* stream);
+
+/* Structural similarity (the training loops' loss_utils.ssim, loss_utils.py:33-62, window 11, sigma 1.5) -- ABI 17.
+ * x, y: [n,c,h,w] fp32, contiguous, device memory.  Per plane, zero-padded outside the image: mx = w*x, my = w*y, Exx = w*x^2,
+ * Eyy = w*y^2, Exy = w*xy with the separable window window11[0..10] (HOST memory, read during the call: the caller's fp32 weights,
+ * those of the reference's gaussian(11, 1.5)); A1 = 2 mx my + C1, A2 = 2 (Exy - mx my) + C2, B1 = mx^2 + my^2 + C1,
+ * B2 = (Exx - mx^2) + (Eyy - my^2) + C2, S = A1 A2 / (B1 B2), C1 = 0.01^2, C2 = 0.03^2.
+ * gsr_ssim_forward: out[0] = the mean of S over n c h w (per_image == 0), or out[i] = the mean over image i's c h w (per_image != 0,
+ * n outputs).  coef_or_null: null, or 3 n c h w floats that receive the maps a = dS/dmx, b = dS/dExx, c = dS/dExy, one after the
+ * other, for gsr_ssim_backward.  scratch: gsr_ssim_scratch_bytes(n, c, h, w) bytes of device memory, 4-byte aligned, any content
+ * (one partial sum per 32 x 16 tile); gsr_ssim_scratch_bytes returns 0 for sizes the calls refuse.
+ * gsr_ssim_backward: grad_x = (g / M) (w*a + 2 x (w*b) + y (w*c)) from the maps of a forward on the same x, y, window and per_image;
+ * g = grad_out[0], or grad_out[i] for image i (device memory: read by the kernel), M = n c h w or c h w.  grad_x: [n,c,h,w] fp32.
+ * Both calls sum in a fixed order without atomics: the same inputs give the same bits.  Refused (GSR_ERR_INVALID_ARG, nothing
+ * launched, no device needed): a dimension <= 0, n c h w >= 2^31, a null pointer (but coef_or_null), a pointer not 4-byte aligned,
+ * too little scratch.  Enqueues on `stream` only: no host synchronisation, no device-to-host copy. */
+GSR_API size_t gsr_ssim_scratch_bytes(int n, int c, int h, int w);
+GSR_API int gsr_ssim_forward(int n, int c, int h, int w, const float* x, const float* y, const float* window11, int per_image, float* out,
+                             float* coef_or_null, void* scratch, size_t scratch_bytes, void* stream);
+GSR_API int gsr_ssim_backward(int n, int c, int h, int w, const float* x, const float* y, const float* coef, const float* window11,
+                              int per_image, const float* grad_out, float* grad_x, void* stream);
 
 /* The elementwise work of the reference's per-frame render() around its two rasterizer passes
  * (sugar/gaussian_splatting/gaussian_renderer/__init__.py:118-146,169-208), as two kernels instead of ~40 framework
