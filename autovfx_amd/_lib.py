@@ -25,7 +25,7 @@ GEOM_SLOTS = ("raster", "rgb", "splat_bins", "internal_radii", "depth_order", "p
 BIN_SLOTS = ("point_list", "tile_keys")
 IMG_SLOTS = ("ranges", "n_contrib")
 STAGES = ("preprocess", "depth_sort", "scan", "duplicate", "tile_sort", "ranges", "blend", "colour")
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 
 class PngFileInfo(ctypes.Structure):
@@ -45,6 +45,13 @@ class PngUnfilterJob(ctypes.Structure):
     """``GsrPngUnfilterJob`` (gsr.h)."""
     _fields_ = [("scanlines", ctypes.c_void_p), ("width", ctypes.c_int), ("height", ctypes.c_int), ("channels", ctypes.c_int),
                 ("out_rgba", ctypes.c_void_p), ("scratch", ctypes.c_void_p)]
+class AdamTensor(ctypes.Structure):
+    """``GsrAdamTensor`` (gsr.h)."""
+    _fields_ = [("param", ctypes.c_void_p), ("grad", ctypes.c_void_p), ("exp_avg", ctypes.c_void_p), ("exp_avg_sq", ctypes.c_void_p),
+                ("numel", ctypes.c_int64), ("step_size", ctypes.c_float), ("bias2_sqrt", ctypes.c_float)]
+
+
+ADAM_MAX_TENSORS = 16
 MAX_SLABS = 8
 FORWARD_INFERENCE = 1
 
@@ -55,7 +62,8 @@ SYMBOLS = ("gsr_forward", "gsr_mark_visible", "gsr_backward", "gsr_last_geom_off
            "gsr_radix_scratch_bytes", "gsr_radix_sort_pairs", "gsr_selftest_exp", "gsr_view_normals", "gsr_normal_maps", "gsr_forward_extra", "gsr_get_call_times",
            "gsr_forward_begin", "gsr_forward_finish", "gsr_forward_ready", "gsr_forward_cancel", "gsr_last_slab_pairs", "gsr_plan_slabs", "gsr_selftest_lds_atomic_order", "gsr_get_backward_times", "gsr_place_object",
            "gsr_forward_raw", "gsr_forward_raw_begin", "gsr_backward_raw", "gsr_place_object_subset", "gsr_cube_to_equirect",
-           "gsr_knn3_scratch_bytes", "gsr_knn3_mean_dist", "gsr_ssim_scratch_bytes", "gsr_ssim_forward", "gsr_ssim_backward")
+           "gsr_knn3_scratch_bytes", "gsr_knn3_mean_dist", "gsr_ssim_scratch_bytes", "gsr_ssim_forward", "gsr_ssim_backward",
+           "gsr_adam_step")
 OPT_TILE_CULL = 0
 OPT_SLABS = 1
 OPT_SLAB_FIRST = 2
@@ -210,6 +218,8 @@ def _load() -> ctypes.CDLL:
     lib.gsr_ssim_forward.argtypes = [c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_p, ctypes.c_size_t, c_p]
     lib.gsr_ssim_backward.restype = ctypes.c_int
     lib.gsr_ssim_backward.argtypes = [c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p]
+    lib.gsr_adam_step.restype = ctypes.c_int
+    lib.gsr_adam_step.argtypes = [ctypes.POINTER(AdamTensor), c_i, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, c_p]
     lib.gsr_resize_rgba8_bilinear.restype = ctypes.c_int
     lib.gsr_resize_rgba8_bilinear.argtypes = [c_f, ctypes.c_int, ctypes.c_int, c_f, ctypes.c_int, ctypes.c_int, c_f, ctypes.c_void_p]
     lib.gsr_resize_f32_nearest.restype = ctypes.c_int

@@ -740,6 +740,33 @@ int gsr_ssim_backward(int n, int c, int h, int w, const float* x, const float* y
     return GSR_OK;
 }
 
+int gsr_adam_step(const GsrAdamTensor* tensors, int count, float w, float b2, float c, float eps, void* stream_) {
+    if (count <= 0 || count > GSR_ADAM_MAX_TENSORS)
+        return fail(GSR_ERR_INVALID_ARG, "gsr_adam_step: bad count %d (1..%d)", count, GSR_ADAM_MAX_TENSORS);
+    if (!tensors) return fail(GSR_ERR_INVALID_ARG, "gsr_adam_step: null tensors");
+    if (!(w >= 0.0f && w < 0.5f)) return fail(GSR_ERR_INVALID_ARG, "gsr_adam_step: w = %g outside [0, 0.5) (ATen's small-weight lerp)", (double)w);
+    static_assert(GSR_ADAM_MAX_TENSORS == gsr::kAdamMaxTensors, "gsr.h and gsr_internal.h");
+    gsr::AdamBatch b{};
+    b.count = count;
+    b.w = w;
+    b.b2 = b2;
+    b.c = c;
+    b.eps = eps;
+    for (int i = 0; i < count; ++i) {
+        const GsrAdamTensor& t = tensors[i];
+        if (t.numel < 0) return fail(GSR_ERR_INVALID_ARG, "gsr_adam_step: tensor %d: numel %lld < 0", i, (long long)t.numel);
+        if (t.numel > 0 && (!t.param || !t.grad || !t.exp_avg || !t.exp_avg_sq))
+            return fail(GSR_ERR_INVALID_ARG, "gsr_adam_step: tensor %d: null pointer", i);
+        if (!aligned4(t.param) || !aligned4(t.grad) || !aligned4(t.exp_avg) || !aligned4(t.exp_avg_sq))
+            return fail(GSR_ERR_INVALID_ARG, "gsr_adam_step: tensor %d: misaligned pointer (4 bytes)", i);
+        const uintptr_t any = (uintptr_t)t.param | (uintptr_t)t.grad | (uintptr_t)t.exp_avg | (uintptr_t)t.exp_avg_sq;
+        b.t[i] = {t.param, t.grad, t.exp_avg, t.exp_avg_sq, t.numel, t.step_size, t.bias2_sqrt, (any & 15u) == 0u ? 1 : 0};
+        b.first_chunk[i + 1] = b.first_chunk[i] + gsr::adam_chunks(t.numel);   // numel == 0: no chunk, skipped
+    }
+    GSR_HIP(gsr::launch_adam_step(b, (hipStream_t)stream_));
+    return GSR_OK;
+}
+
 int gsr_view_normals(int P, const float* means3D, const float* axis, const float* cam_pos, float* colors, void* stream_) {
     if (P < 0) return fail(GSR_ERR_INVALID_ARG, "bad size P=%d", P);
     if (P == 0) return GSR_OK;

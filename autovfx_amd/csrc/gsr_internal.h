@@ -392,6 +392,26 @@ hipError_t launch_ssim_forward(const SsimShape& s, const SsimWindow& win, const 
 hipError_t launch_ssim_backward(const SsimShape& s, const SsimWindow& win, const float* x, const float* y, const float* coef,
                                 int per_image, const float* grad_out, float* grad_x, hipStream_t stream);
 
+// ---- one Adam step over many tensors (gsr_adam.hip) ----
+constexpr int kAdamMaxTensors = 16;   // gsr.h: GSR_ADAM_MAX_TENSORS
+struct AdamTensor {
+    float* p;
+    const float* g;
+    float* m;
+    float* v;
+    int64_t numel;
+    float a, s2;      // gsr.h: GsrAdamTensor::step_size, ::bias2_sqrt
+    int aligned16;    // p, g, m and v all 16-byte aligned
+};
+struct AdamBatch {    // passed by value (kernel arguments)
+    AdamTensor t[kAdamMaxTensors];
+    uint64_t first_chunk[kAdamMaxTensors + 1];   // prefix of adam_chunks(numel); first_chunk[count] = the total
+    int count;
+    float w, b2, c, eps;
+};
+uint64_t adam_chunks(int64_t numel);   // numel >= 0
+hipError_t launch_adam_step(const AdamBatch& b, hipStream_t stream);
+
 // ---- three nearest neighbours (gsr_knn.hip) ----
 // Boxes over the Morton-sorted points: level 0 = leaves of 64 points, every level above = 16 boxes of the one below, up to the first
 // level of at most 16 boxes (six levels for n < 2^30).  A box is two float4 (lo, hi; w unused) at boxes[2 * (offset[level] + i)].

@@ -32,9 +32,15 @@ AutoVFX reaches the rasterizer through two imports (paths under the reference tr
    ``sugar_utils/loss_utils.py``) gets its ``ssim`` replaced by ``autovfx_amd.ssim.drop_in(<the original>)``: the fused HIP
    forward and backward where they apply, the original for every other call; the original stays reachable as
    ``<module>.reference_ssim``, and already-imported modules holding it under any name (``train.py``, ``metrics.py``, the SuGaR
-   trainers, ``scene_representation``) are rebound.
+   trainers, ``scene_representation``) are rebound;
+8. a module named ``...gaussian_model`` whose ``GaussianModel`` defines both ``training_setup`` and ``replace_tensor_to_optimizer``
+   (the reference's ``scene/gaussian_model.py``, used by ``train.py`` and the inpainting re-train; not this package's
+   ``autovfx_amd.gaussian_model``) gets ``training_setup`` wrapped: after the original built ``self.optimizer``, a plain
+   ``torch.optim.Adam`` is replaced by ``autovfx_amd.optim.Adam`` over the same parameter groups and defaults (one HIP launch per
+   step, torch's bits; the state is still empty there, so ``restore()`` loads into it as before).  The original stays reachable as
+   ``GaussianModel.reference_training_setup``; torch and the library are imported at the first call, not at patch time.
 
-Nothing else of the reference is touched: its ``GaussianModel``, cameras, scene editing and I/O run as they are.  With
+Nothing else of the reference is touched: the rest of its ``GaussianModel``, cameras, scene editing and I/O run as they are.  With
 autograd off, ``render`` reads the model's six raw parameter tensors and activates them inside the HIP kernels
 (``gsr_forward_raw``); with autograd on it keeps the reference's structure (PyTorch activations, two rasterizer calls).
 
@@ -58,15 +64,21 @@ _SCENE_LEAF = "scene_representation"     # scene_representation.py: SceneReprese
 _SUGAR_LEAF = "sugar_model"              # sugar/sugar_scene/sugar_model.py: SuGaR.render_image_gaussian_rasterizer calls the rasterizer twice (:2141,2174)
 _PANO_LEAF = "render_panorama"           # sugar/gaussian_splatting/render_panorama.py: render_panorama() (:100-145), imported directly by its users
 _LOSS_LEAF = "loss_utils"                # utils/loss_utils.py, sugar_utils/loss_utils.py: ssim() (:33-62) of every training loop's loss
+_MODEL_LEAF = "gaussian_model"           # scene/gaussian_model.py: GaussianModel.training_setup builds the training loops' Adam (:159-177)
 _installed: Optional["_RendererHook"] = None
 patched_modules: List[str] = []          # names of the modules whose ``render`` was replaced (introspection / tests)
+patched_models: List[str] = []           # names of the modules whose ``GaussianModel.training_setup`` was wrapped (item 8)
 _strict = True                           # install(strict=...): may a failure to load the render path break the importing process?
 _gave_up = False                         # lenient mode: the render path could not be loaded once; do not try again
 
 
 def _is_target(fullname: str) -> bool:
     return any(fullname == leaf or fullname.endswith("." + leaf) for leaf in (_TARGET_LEAF, _BLEND_LEAF, _SCENE_LEAF, _SUGAR_LEAF,
-                                                                                  _PANO_LEAF, _LOSS_LEAF))
+                                                                                  _PANO_LEAF, _LOSS_LEAF)) or _is_model_module(fullname)
+
+
+def _is_model_module(name: str) -> bool:
+    return (name == _MODEL_LEAF or name.endswith("." + _MODEL_LEAF)) and not name.startswith("autovfx_amd.")
 
 
 def _is_blend_module(name: str) -> bool:
@@ -214,6 +226,44 @@ def _patch_loss_module(module: types.ModuleType) -> None:
     _rebind(original, ours, module)
 
 
+def _patch_model_module(module: types.ModuleType) -> None:
+    """``GaussianModel.training_setup`` (gaussian_model.py:159-177) runs as it is, then a plain ``torch.optim.Adam`` in
+    ``self.optimizer`` becomes autovfx_amd.optim.Adam over the same groups.  The original stays reachable as
+    ``GaussianModel.reference_training_setup``."""
+    cls = module.__dict__.get("GaussianModel")
+    d = getattr(cls, "__dict__", {}) if isinstance(cls, type) else {}
+    original = d.get("training_setup")
+    if not (callable(original) and callable(d.get("replace_tensor_to_optimizer"))) or getattr(original, "_autovfx_amd_wrapped", False):
+        return
+    if _gave_up:
+        return
+
+    import functools
+
+    @functools.wraps(original)
+    def training_setup(self, *args, **kwargs):
+        global _gave_up
+        out = original(self, *args, **kwargs)
+        if _gave_up:
+            return out
+        try:
+            from .optim import from_torch_adam   # imports torch and loads libgsr_hip.so: at the first call, not at patch time
+        except Exception as e:
+            if _strict:
+                raise
+            _gave_up = True
+            sys.stderr.write(f"[autovfx_amd] {module.__name__}.GaussianModel keeps torch's Adam: the fused step could not be loaded ({e!r})\n")
+            return out
+        self.optimizer = from_torch_adam(self.optimizer)
+        return out
+
+    training_setup._autovfx_amd_wrapped = True
+    cls.reference_training_setup = original
+    cls.training_setup = training_setup
+    if module.__name__ not in patched_models:
+        patched_models.append(module.__name__)
+
+
 def _our_render() -> Callable:
     from .renderer import render   # imports torch and loads libgsr_hip.so: only when a renderer module really appears
     return render
@@ -237,6 +287,9 @@ def _patch_renderer_module(module: types.ModuleType) -> None:
         return
     if _is_loss_module(module.__name__):
         _patch_loss_module(module)
+        return
+    if _is_model_module(module.__name__):
+        _patch_model_module(module)
         return
     if _is_blend_module(module.__name__):
         # the compositing step of the edit loop: ``blend_all.blend_frames(results_dir, cfg_path)`` (scene_representation.py:232) becomes
@@ -371,3 +424,9 @@ def uninstall() -> None:
             cls.render_image_gaussian_rasterizer = cls.reference_render_image_gaussian_rasterizer
             del cls.reference_render_image_gaussian_rasterizer
     patched_modules.clear()
+    for name in list(patched_models):
+        cls = getattr(sys.modules.get(name), "GaussianModel", None)
+        if isinstance(cls, type) and "reference_training_setup" in cls.__dict__:
+            cls.training_setup = cls.reference_training_setup
+            del cls.reference_training_setup
+    patched_models.clear()

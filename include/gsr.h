@@ -42,13 +42,14 @@
 extern "C" {
 #endif
 
-/* 17: + structural similarity (gsr_ssim_scratch_bytes, gsr_ssim_forward, gsr_ssim_backward).
+/* 18: + one Adam step over many tensors (GsrAdamTensor, gsr_adam_step).
+ * 17: + structural similarity (gsr_ssim_scratch_bytes, gsr_ssim_forward, gsr_ssim_backward).
  * 16: + three nearest neighbours (gsr_knn3_scratch_bytes, gsr_knn3_mean_dist).
  * 15: + panoramas (gsr_cube_to_equirect).
  * 14 (round 6): + the compositor's input files -- gsr_png_unfilter(_batch), gsr_exr_unpack_channel, gsr_inflate_zlib_blocks, the host-side
  * gsr_png_file_* / gsr_exr_file_* readers, gsr_upload.  13: + compressed frame files (gsr_png_encode_deflate, gsr_frame_files_deflate).
  * Additions only: a binding written against 12 works unchanged apart from the version it checks. */
-#define GSR_ABI_VERSION 17
+#define GSR_ABI_VERSION 18
 
 #if defined(__GNUC__)
 #define GSR_API __attribute__((visibility("default")))
@@ -436,6 +437,33 @@ GSR_API int gsr_ssim_forward(int n, int c, int h, int w, const float* x, const f
                              float* coef_or_null, void* scratch, size_t scratch_bytes, void* stream);
 GSR_API int gsr_ssim_backward(int n, int c, int h, int w, const float* x, const float* y, const float* coef, const float* window11,
                               int per_image, const float* grad_out, float* grad_x, void* stream);
+
+/* One Adam step (torch.optim.Adam's default GPU path, torch/optim/adam.py _multi_tensor_adam, with amsgrad, maximize and weight decay
+ * off) over up to GSR_ADAM_MAX_TENSORS tensors in ONE launch -- ABI 18.  tensors: `count` descriptors in HOST memory, read during the
+ * call; param, grad, exp_avg, exp_avg_sq: `numel` contiguous fp32 values each, device memory.  Per element, every arrow one fp32
+ * rounding, in this order:
+ *   m <- fma(w, g - m, m)                    (ATen's lerp for a weight w < 0.5, i.e. beta1 > 0.5)
+ *   v <- v * b2,  v <- fma(c, g * g, v)
+ *   d <- sqrt(v) (correctly rounded),  d <- d / bias2_sqrt,  d <- d + eps
+ *   p <- fma(step_size, m / d, p)
+ * with the shared w = fl(1 - beta1), b2 = fl(beta2), c = fl(1 - beta2), eps = fl(eps) and, per tensor, step_size =
+ * fl(-lr / (1 - beta1^t)) and bias2_sqrt = fl(sqrt(1 - beta2^t)), both computed in double by the caller as torch does.  The fmas are
+ * those of ATen's foreach kernels as this PyTorch build compiles them (tests/test_adam_gpu.py probes them); denormals are kept.
+ * A tensor with numel == 0 is skipped (its pointers are not read).  Each element is read and written by one lane: no atomics, no
+ * scratch.  Refused (GSR_ERR_INVALID_ARG, nothing launched, no device needed): count <= 0 or > GSR_ADAM_MAX_TENSORS, a null
+ * `tensors`, w outside [0, 0.5) (ATen's other lerp branch), numel < 0, a null pointer with numel > 0, a pointer not 4-byte aligned.  Enqueues on `stream` only: no host
+ * synchronisation. */
+#define GSR_ADAM_MAX_TENSORS 16
+typedef struct GsrAdamTensor {
+    float* param;
+    const float* grad;
+    float* exp_avg;
+    float* exp_avg_sq;
+    int64_t numel;
+    float step_size;     /* fl(-lr / (1 - beta1^t)) */
+    float bias2_sqrt;    /* fl(sqrt(1 - beta2^t)) */
+} GsrAdamTensor;
+GSR_API int gsr_adam_step(const GsrAdamTensor* tensors, int count, float w, float b2, float c, float eps, void* stream);
 
 /* The elementwise work of the reference's per-frame render() around its two rasterizer passes
  * (sugar/gaussian_splatting/gaussian_renderer/__init__.py:118-146,169-208), as two kernels instead of ~40 framework
