@@ -6,7 +6,7 @@ AutoVFX process (autovfx_amd/hook.py).
 
 
 def install(path: bool = True) -> None:
-    """Route ``diff_gaussian_rasterization`` and every ``...gaussian_renderer.render`` of this process to this package."""
+    """Put this repository first on ``sys.path`` and patch the reference's modules in this process (the list is in hook.py)."""
     from .hook import install as _install
     _install(path)
 

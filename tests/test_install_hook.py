@@ -64,7 +64,48 @@ def test_install_after_import_rebinds_existing_importers(fake_autovfx):
     assert sum(1 for f in sys.meta_path if isinstance(f, hook._RendererHook)) == 1
     autovfx_amd.uninstall()
     assert sys.modules["sugar.gaussian_splatting.gaussian_renderer"].render(None, None, None, None) == "reference"
+    assert a.render is sys.modules["sugar.gaussian_splatting.gaussian_renderer"].render and b.gs_render is a.render
     assert not any(isinstance(f, hook._RendererHook) for f in sys.meta_path)
+
+
+# every target of install(): (module leaf name, owning class or None for the module, attribute, other callables it must define)
+HOOK_ROWS = [
+    ("gaussian_renderer", None, "render", ()),
+    ("blend_all", None, "blend_frames", ()),
+    ("scene_representation", "SceneRepresentation", "render_from_3DGS", ()),
+    ("sugar_model", "SuGaR", "render_image_gaussian_rasterizer", ()),
+    ("render_panorama", None, "render_panorama", ()),
+    ("loss_utils", None, "ssim", ("_ssim", "create_window")),
+    ("gaussian_model", "GaussianModel", "training_setup", ("replace_tensor_to_optimizer",)),
+]
+
+
+@pytest.mark.parametrize("leaf, cls, attr, needs", HOOK_ROWS, ids=[row[0] for row in HOOK_ROWS])
+def test_each_target_is_patched_once_and_uninstall_undoes_it(leaf, cls, attr, needs, monkeypatch):
+    """A minimal module of each target's leaf name: install() replaces the attribute and keeps the original as
+    ``reference_<attr>``, a second install() changes nothing, uninstall() puts the original back and removes ``reference_<attr>``."""
+    def original(*a, **k):
+        return "reference"
+
+    module = types.ModuleType("hook_rows." + leaf)
+    owner = module if cls is None else type(cls, (), {})
+    if cls is not None:
+        setattr(module, cls, owner)
+    for name in needs:
+        setattr(owner, name, lambda *a, **k: None)
+    setattr(owner, attr, original)
+    monkeypatch.setitem(sys.modules, module.__name__, module)
+    try:
+        autovfx_amd.install(path=False)
+        assert vars(owner)[attr] is not original and vars(owner)["reference_" + attr] is original
+        assert module.__name__ in (hook.patched_models if leaf == "gaussian_model" else hook.patched_modules)
+        state = lambda: (dict(vars(owner)), list(hook.patched_modules), list(hook.patched_models))
+        before = state()
+        autovfx_amd.install(path=False)
+        assert state() == before
+    finally:
+        autovfx_amd.uninstall()
+    assert vars(owner)[attr] is original and "reference_" + attr not in vars(owner)
 
 
 def test_install_patches_blend_all_blend_frames(fake_autovfx, monkeypatch):
