@@ -36,7 +36,7 @@ MODES = ("atomic", "deterministic", "slabs")
 
 
 def hip_backward(cloud, cam, pg, bg=(0.0, 0.0, 0.0), scale_modifier=1.0, sh_degree=None, cov3D_precomp=None,
-                 device="cuda:0", cull=True, tanfov=None, mode="atomic"):
+                 device="cuda:0", cull=True, tanfov=None, mode="atomic", slab_first=6):
     from autovfx_amd import _lib
     from diff_gaussian_rasterization import GaussianRasterizer
     c = cloud.to(device)
@@ -57,10 +57,11 @@ def hip_backward(cloud, cam, pg, bg=(0.0, 0.0, 0.0), scale_modifier=1.0, sh_degr
         kw["scales"], kw["rotations"] = scales, rots
     _lib.set_option(_lib.OPT_TILE_CULL, 1 if cull else 0)
     _lib.set_option(_lib.OPT_BACKWARD_DETERMINISTIC, 1 if mode == "deterministic" else 0)
-    _lib.set_option(_lib.OPT_GRAD_SLABS, 1 if mode == "slabs" else 0)
+    # ("default": the library's shipped options -- float atomics, a grad-mode forward is an inference call with the default slabs)
+    _lib.set_option(_lib.OPT_GRAD_SLABS, 1 if mode in ("slabs", "default") else 0)
     if mode == "slabs":
         _lib.set_option(_lib.OPT_SLABS, 0)
-        _lib.set_option(_lib.OPT_SLAB_FIRST, 6)
+        _lib.set_option(_lib.OPT_SLAB_FIRST, slab_first)
         _lib.set_option(_lib.OPT_SLAB_MIN_REST, 0)
     try:
         color, depth, alpha, radii = GaussianRasterizer(st)(means3D=means3D, means2D=means2D, opacities=opac, shs=shs,
@@ -70,7 +71,7 @@ def hip_backward(cloud, cam, pg, bg=(0.0, 0.0, 0.0), scale_modifier=1.0, sh_degr
         from diff_gaussian_rasterization import _C
         torch.cuda.synchronize()
         saved = color.grad_fn.saved_tensors   # (.., radii, sh, geom, binning, image, alpha): __init__.py save_for_backward
-        if mode == "slabs":
+        if mode in ("slabs", "default"):
             fwd = {"slab_pairs": _C.last_layout()["slab_pairs"]} if cloud.P else {}
         else:
             fwd = decode_scratch(_C.last_layout(), saved[7], saved[8], saved[9], cloud.P, cam.image_width, cam.image_height) if cloud.P else {}
@@ -104,7 +105,7 @@ def assert_forward_state(name, hip, fref):
     V = int(vis.sum())
     ids = np.nonzero(vis)[0]
     expect = ids[np.lexsort((ids, fref["depths"][ids].view(np.uint32)))]
-    if hip.get("mode") == "slabs":
+    if hip.get("mode") in ("slabs", "default"):
         pass   # (an inference call's scratch: its lists are compared with the full call's at every parity case of test_parity_gpu.py)
     elif not hip["cull"]:
         np.testing.assert_array_equal(f["depth_order"][:V], expect.astype(np.uint32), err_msg=f"{name}: depth order")
@@ -135,7 +136,7 @@ def assert_forward_state(name, hip, fref):
         assert bad <= int(np.ceil(FLIP_PPM * 1e-6 * npx)), f"{name}: forward {key} off on {bad} px (max {err.max():.3e})"
 
 
-_ORACLE_CACHE = {}
+_ORACLE_CACHE, _FORWARD_CACHE = {}, {}
 
 
 def oracles(name, kw, yardstick=False):
@@ -147,18 +148,28 @@ def oracles(name, kw, yardstick=False):
     return _ORACLE_CACHE[name]
 
 
+def oracle_forward(name, kw):
+    """The oracle's forward with intermediates of one case, computed once for every mode of the library (one case at a time)."""
+    if name not in _FORWARD_CACHE:
+        _FORWARD_CACHE.clear()
+        _FORWARD_CACHE[name] = cpu_oracle.forward(intermediates=True, **kw)
+    return _FORWARD_CACHE[name]
+
+
 def check_case(name, cloud, cam, pg, keys, mode, hip_kw=None, yardstick=False, **okw):
     """One backward case in one mode of the library: forward state first (integers bit-exact against the oracle), then every
     gradient against the truth; on any failure the inputs, the HIP results (with the decoded forward scratch) and the
     oracle's are dumped to gpurun_out/failures/.  In deterministic mode a second run must give the same bits."""
     kw = oracle_kwargs(cloud, cam, **okw)
     kw.update(pg)
-    ref, truth, noise = oracles(name, kw, yardstick)
+    ref, truth, noise = oracles(name, kw, bool(yardstick))
+    if noise is not None and yardstick is not True:   # yardstick = the names of the arrays whose bar takes it; the others keep the plain bar
+        noise = {k: v for k, v in noise.items() if k in yardstick}
     hkw = dict(bg=tuple(float(v) for v in okw.get("bg", (0.0, 0.0, 0.0))), scale_modifier=okw.get("scale_modifier", 1.0),
                sh_degree=okw.get("sh_degree"), cov3D_precomp=okw.get("cov3D_precomp"))
     hkw.update(hip_kw or {})
     hip = hip_backward(cloud, cam, pg, mode=mode, **hkw)
-    fref = cpu_oracle.forward(intermediates=True, **oracle_kwargs(cloud, cam, **okw))
+    fref = oracle_forward(name, oracle_kwargs(cloud, cam, **okw))
     with dump_on_failure(f"bw_{name}_{mode}", hip={k: v for k, v in hip.items() if k != "fwd"}, fwd=hip["fwd"], ref=ref, fref=fref, pg=pg,
                          cloud={"means3D": cloud.means3D, "opacities": cloud.opacities, "scales": cloud.scales,
                                 "rotations": cloud.rotations}):

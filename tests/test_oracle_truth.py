@@ -2,7 +2,8 @@
 
 * against float64 AUTOGRAD of an independently written dense splat (no tiles, no lists, every Gaussian against every pixel,
   cumprod transmittance) on a small scene built so that tiling, the near plane and saturation do not act -- the truth then is
-  simply d(loss)/d(parameters), and PyTorch differentiates a different program to get it;
+  simply d(loss)/d(parameters), and PyTorch differentiates a different program to get it -- and on a saturated one where only
+  the early stop acts (the dense splat then applies the reference's stop rule, decided in float64);
 * against the reference's own fp32 backward (the CPU oracle = backward.cu bit for bit, and the committed golden vectors) on
   well-conditioned scenes, where fp32 is within 3e-4 of it.
 """
@@ -22,8 +23,12 @@ from helpers import gradient_errors, oracle_kwargs
 from test_oracle_backward import GOLDEN_BW, load_bw_case, pixel_grads
 
 
-def dense_splat(means3D, opac, scales, rots, shs, cam, bg, deg):
-    """float64, differentiable, O(P * pixels): SURVEY.md appendix A.3 without tiles."""
+def dense_splat(means3D, opac, scales, rots, shs, cam, bg, deg, early_stop=False):
+    """float64, differentiable, O(P * pixels): SURVEY.md appendix A.3 without tiles.  ``early_stop``: each pixel also stops as the
+    reference's blend does (forward.cu renderCUDA) -- entries with alpha < 1/255 are skipped, and the first entry whose
+    T * (1 - alpha) would fall below 1e-4 is excluded with every entry behind it.  The stop is decided in float64 and held
+    constant for the derivative (the stop index is piecewise constant in the parameters); the fifth value returned is then the
+    stop record of early_stop_mask."""
     dt = torch.float64
     V, PM = cam.world_view_transform.to(dt), cam.full_proj_transform.to(dt)
     campos = cam.camera_center.to(dt)
@@ -63,11 +68,36 @@ def dense_splat(means3D, opac, scales, rots, shs, cam, bg, deg):
     power = -0.5 * (cxx[order, None, None] * dx * dx + cyy[order, None, None] * dy * dy) - cxy[order, None, None] * dx * dy
     alpha = torch.clamp_max(opac.reshape(-1)[order, None, None] * torch.exp(power), 0.99)
     alpha = torch.where((power > 0) | (alpha < 1.0 / 255.0), torch.zeros((), dtype=dt), alpha)
+    stop = None
+    if early_stop:
+        stop = early_stop_mask(alpha.detach())
+        alpha = alpha * stop["keep"]
     Tin = torch.cumprod(torch.cat((torch.ones(1, H, W, dtype=dt), 1 - alpha), 0), 0)
     w = alpha * Tin[:-1]
     color = torch.einsum("phw,pc->chw", w, rgb[order]) + Tin[-1][None] * bg.to(dt)[:, None, None]
     depth = (w * tz[order, None, None]).sum(0, keepdim=True)
-    return color, depth, (1 - Tin[-1])[None], float(Tin[-1].detach().min())
+    out = (color, depth, (1 - Tin[-1])[None], float(Tin[-1].detach().min()))
+    return out + (stop,) if early_stop else out
+
+
+def early_stop_mask(alpha):
+    """The reference's stop rule on alpha[P, H, W] (depth order, skipped entries already 0): a pixel's transmittance after an
+    entry is the running product of (1 - alpha); the first entry that takes it below 1e-4 stops the pixel and is not
+    composited, nor is any entry behind it.  Returns keep [P, H, W] (1.0 / 0.0), stopped [H, W] (the stop excluded an entry with
+    alpha > 0), last [H, W] (1-based position of the last composited entry: the forward's n_contrib when every Gaussian is in
+    every tile's list) and margin (the smallest relative distance of any tested T * (1 - alpha), up to and including each
+    pixel's stop, from 1e-4)."""
+    after = torch.cumprod(1 - alpha, 0)
+    live = alpha > 0
+    keep = after >= 1e-4          # non-increasing along the list: once below, below for good
+    stopped = ~keep[-1]
+    pos = torch.arange(1, alpha.shape[0] + 1, dtype=torch.int64)[:, None, None]
+    last = torch.where(keep & live, pos, torch.zeros((), dtype=torch.int64)).amax(0)
+    first_out = torch.cat((torch.ones_like(keep[:1]), keep[:-1]), 0)   # the entries a pixel still tested
+    tested = live & first_out
+    rel = (after / 1e-4 - 1).abs()
+    margin = float(rel[tested].min()) if bool(tested.any()) else math.inf
+    return {"keep": keep.to(alpha.dtype), "stopped": stopped, "last": last, "margin": margin}
 
 
 def small_smooth_scene(seed):
@@ -104,6 +134,60 @@ def test_truth_equals_float64_autograd_of_a_dense_splat(seed):
         want, got = leaf.grad.numpy().reshape(-1), truth[name].reshape(-1)
         scale = np.abs(want).max()
         # (the truth stands on the fp32 forward state -- means2D, conic, colours rounded to fp32 -- hence 1e-5, not 1e-12)
+        assert np.abs(got - want).max() <= 2e-5 * scale, (name, np.abs(got - want).max() / scale)
+
+
+def saturating_scene(seed):
+    """32 x 32 pixels (four tiles) and 160 big Gaussians 1.5 - 2.5 units in front of the camera, centred within a few pixels of
+    the image centre: every rectangle covers all four tiles, so every tile's list is the whole depth order.  40 % of them have
+    opacity 0.35 - 0.6, the rest 0.04 - 0.15: pixels near the centre stop after 20 - 30 entries, the corners after 120 - 160."""
+    g = torch.Generator().manual_seed(seed)
+    P = 160
+    cam = scenes.c1_camera(32, 32)   # at (0, 0, -4) looking down +z
+    means = torch.cat(((torch.rand(P, 2, generator=g) - 0.5) * 0.5, torch.rand(P, 1, generator=g) - 2.5), 1)
+    scales = torch.exp(torch.randn(P, 3, generator=g) * 0.15 + math.log(0.9))
+    rots = torch.nn.functional.normalize(torch.randn(P, 4, generator=g), dim=1)
+    opac = torch.where(torch.rand(P, 1, generator=g) < 0.4, torch.rand(P, 1, generator=g) * 0.25 + 0.35,
+                       torch.rand(P, 1, generator=g) * 0.11 + 0.04)
+    shs = torch.randn(P, 16, 3, generator=g) * torch.tensor([1.0] + [0.2] * 15)[None, :, None]
+    return GaussianCloud(means, opac, scales, rots, shs, None, 3), cam
+
+
+# (seeds whose stop decisions all keep the margin below; about one seed in four has a pixel whose product lands within 1e-4
+# of the threshold, where fp32 and fp64 may decide differently)
+@pytest.mark.parametrize("seed", [1, 7, 8])
+def test_truth_equals_float64_autograd_of_a_dense_splat_that_stops_early(seed):
+    """The truth on a saturated scene: the early stop (T * (1 - alpha) < 1e-4 ends a pixel's walk and excludes that entry) decides
+    which entries a pixel differentiates, and the dense splat's independently written stop rule must agree with it.  Only the stop
+    is new here: every Gaussian covers all four tiles (the tile cut cannot act), and opacity * G stays below 0.99 -- the clamp
+    is left out on purpose, because the reference's backward ignores it where autograd would not."""
+    cloud, cam = saturating_scene(seed)
+    assert float(cloud.opacities.max()) < 0.99
+    pg = pixel_grads(cam, seed)
+    bg = torch.tensor([0.3, 0.1, 0.2])
+    leaves = [t.to(torch.float64).requires_grad_(True) for t in (cloud.means3D, cloud.opacities, cloud.scales, cloud.rotations, cloud.shs)]
+    color, depth, alpha, _t_min, stop = dense_splat(*leaves, cam, bg, 3, early_stop=True)
+    kw = oracle_kwargs(cloud, cam, bg=bg.numpy())
+    fwd = cpu_oracle.forward(intermediates=True, **kw)
+    assert (fwd["tiles_touched"] == 4).all(), "a Gaussian misses a tile: the tile cut acts"
+    stopped, n_contrib = stop["stopped"].numpy(), fwd["n_contrib"]
+    # the fp64 stop is the fp32 forward's: no tested product within a relative 1e-4 of the threshold, and the oracle's last
+    # contributor of every pixel is the dense splat's
+    assert stop["margin"] > 1e-4, stop["margin"]
+    np.testing.assert_array_equal(n_contrib, stop["last"].numpy())
+    assert stopped.mean() >= 0.9, f"only {stopped.mean():.1%} of the pixels stop"
+    assert n_contrib[stopped].min() < 32 and n_contrib[stopped].max() > 64, (n_contrib[stopped].min(), n_contrib[stopped].max())
+    assert np.abs(fwd["color"] - color.detach().numpy()).max() < 2e-5
+    assert np.abs(fwd["alpha"] - alpha.detach().numpy()).max() < 2e-5
+    assert np.abs(fwd["depth"] - depth.detach().numpy()).max() < 2e-5 * float(np.abs(fwd["depth"]).max())
+    loss = ((color * torch.from_numpy(pg["dL_dcolor"])).sum() + (depth * torch.from_numpy(pg["dL_ddepth"])).sum()
+            + (alpha * torch.from_numpy(pg["dL_dalpha"])).sum())
+    loss.backward()
+    kw.update(pg)
+    truth = cpu_oracle.backward_f64(**kw)
+    for name, leaf in zip(("dL_dmeans3D", "dL_dopacity", "dL_dscales", "dL_drotations", "dL_dsh"), leaves):
+        want, got = leaf.grad.numpy().reshape(-1), truth[name].reshape(-1)
+        scale = np.abs(want).max()
         assert np.abs(got - want).max() <= 2e-5 * scale, (name, np.abs(got - want).max() / scale)
 
 
