@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- frames/s of the 3DGS forward render path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -22,10 +22,15 @@ gathered to rank 0 with RCCL inside the timed region, in pieces that travel behi
 owns the cloud, one broadcast, F frames dealt round-robin (shards may differ by one frame), pipelined gather.
 
 Workload (default ``c3``) = BASELINE.json configs[2] shape on one GPU: 3 M synthetic Gaussians, 1920x1080, 800-frame
-orbit, SH degree 3 (M = 16), bg = 0.  Other workloads (``--workload``; short runs of them also ride on the default
+orbit, SH degree 3 (M = 16), bg = 0.  Other workloads (``--workload``; short runs of them also ride on the ``--full``
 line under ``also``): ``c2`` 1 M / 960x540; ``heavy`` a trained-scene-like stress cloud (heavy-tailed sizes, 10:1
 anisotropy, bimodal opacity); ``c4`` 200 k flat SuGaR-style Gaussians, RGB + normal + depth in one fused call;
 ``c5`` C2 frames -> RGBA8 -> composited with synthetic Blender layers.  Data is synthetic by construction.
+
+A plain run sets up, warms up, times the regions, writes ``--dump-outputs`` and prints the line; everything else it can
+measure runs after the timed regions with ``--full`` only: ``serial`` (the caller's own blocking loop), ``roofline`` and
+the workload units (``config.visible_mean`` / ``num_rendered_mean``), ``cpu_baseline``, ``reference_on_gpu``, ``also``
+and, with N > 1 ranks, rank 0 alone (``config.frac_of_n_x_single_gpu``).  Left out, they are null or absent.
 
 Extra objects on the JSON line:
   roofline      dominant kernel of the frame (the blend): algorithmic bytes per launch / average launch time, measured
@@ -499,6 +504,9 @@ def main():
                          "float32, at most 64 MB in all (a fixed, seeded sample of an array that does not fit)")
     ap.add_argument("--profile-run", action="store_true",
                     help="for rocprofv3: only warm-up + ONE timed region of uniform calls (no replay, statistics, baselines)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed regions, also measure what the headline does not need: serial loop, roofline, "
+                         "CPU baseline, the reference's kernels, `also`, and with N > 1 ranks rank 0 alone")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args))
@@ -655,7 +663,7 @@ def main():
     # N x single-GPU, measured in THIS run: rank 0 renders the same frames alone -- no gather, the other ranks waiting at a
     # barrier -- so that the line carries its own yardstick (the driver computes efficiency from separate N = 1 runs as well)
     alone_fps = None
-    if distributed and not strong and not args.profile_run:
+    if args.full and distributed and not strong and not args.profile_run:
         with torch.no_grad():
             dist.barrier()
             if rank == 0:
@@ -672,119 +680,117 @@ def main():
             dist.destroy_process_group()
         return
 
-    # ---- stage breakdown: an untimed single-stream replay of the first timed frames, HIP events on the launch stream ----
-    with torch.no_grad():
-        _lib.set_stage_timing(True)
-        b.run(timed_frames[:min(K, 32)], rgba, 1, side, composed)
-        torch.cuda.synchronize()
-        stage_ms = _lib.stage_times_ms()
-        call_ms = sorted(_lib.call_times_ms())
-        slab_pairs = _lib.slab_pairs()
-        _lib.set_stage_timing(False)
-
     order = sorted(secs)
     med = order[len(order) // 2]
     total_frames = args.job_frames if strong else K * world
     fps = lambda s: total_frames / s
     ms_per_step = med / K * 1e3
 
-    # ---- the caller's own loop: one blocking GaussianRasterizer.forward (or render()) per frame, one stream ----
-    serial = None
-    if world == 1 and not distributed and not strong and b.extra is None and b.layers is None:
-        Ks = min(K, 100)
+    serial = units = roofline = cpu_baseline = reference_on_gpu = also = None
+    if args.full:
+        # ---- stage breakdown: an untimed single-stream replay of the first timed frames, HIP events on the launch stream ----
         with torch.no_grad():
-            b.run_blocking(timed_frames[:min(Ks, 8)], rgba)
-            ssecs = timed_regions(lambda: b.run_blocking(timed_frames[:Ks], rgba), min(R, 3), False, device)
-        smed = sorted(ssecs)[len(ssecs) // 2]
-        serial = {"value": round(Ks / smed, 2), "unit": "frames/s", "ms_per_step": round(smed / Ks * 1e3, 4), "steps": Ks,
-                  "regions": [round(Ks / x, 2) for x in ssecs], "streams": 1,
-                  "what": "what an unmodified caller gets (scene_representation.py:355-424): frames one at a time on the "
-                          "current stream, each a blocking " + ("render()" if args.boundary == "render" else "GaussianRasterizer.forward")
-                          + " + RGBA8 pack; host wall clock between synchronize()s, like `value`"}
+            _lib.set_stage_timing(True)
+            b.run(timed_frames[:min(K, 32)], rgba, 1, side, composed)
+            torch.cuda.synchronize()
+            stage_ms = _lib.stage_times_ms()
+            call_ms = sorted(_lib.call_times_ms())
+            slab_pairs = _lib.slab_pairs()
+            _lib.set_stage_timing(False)
 
-    # ---- per-frame workload statistics (untimed): the units of this rank's timed frames ----
-    units = b.units(timed_frames[::max(1, K // 8)])
-    V, D = units["V"], units["D"]
-    alg = algorithmic_bytes(P, V, D, T, W, H, M)
-    design = design_bytes(units, inference=True, deferred=_lib.get_option(_lib.OPT_DEFER_COLOUR) != 0)
+        # ---- the caller's own loop: one blocking GaussianRasterizer.forward (or render()) per frame, one stream ----
+        if world == 1 and not distributed and not strong and b.extra is None and b.layers is None:
+            Ks = min(K, 100)
+            with torch.no_grad():
+                b.run_blocking(timed_frames[:min(Ks, 8)], rgba)
+                ssecs = timed_regions(lambda: b.run_blocking(timed_frames[:Ks], rgba), min(R, 3), False, device)
+            smed = sorted(ssecs)[len(ssecs) // 2]
+            serial = {"value": round(Ks / smed, 2), "unit": "frames/s", "ms_per_step": round(smed / Ks * 1e3, 4), "steps": Ks,
+                      "regions": [round(Ks / x, 2) for x in ssecs], "streams": 1,
+                      "what": "what an unmodified caller gets (scene_representation.py:355-424): frames one at a time on the "
+                              "current stream, each a blocking " + ("render()" if args.boundary == "render" else "GaussianRasterizer.forward")
+                              + " + RGBA8 pack; host wall clock between synchronize()s, like `value`"}
 
-    calls = stage_ms.pop("calls")
-    traffic = pmc_traffic(T_key=args.workload if not args.gaussians else None)
-    counter = stage_counter_bytes(traffic)
-    # Per stage: this library's design bytes (design_bytes above: what its own layout has to move, measured units) and the
-    # HBM bytes the counters saw (profiles/, per stage) over the stage's time.  Both are <= what the hardware can move; the
-    # reference formula's bytes are NOT credited per stage -- the stages are not the reference's -- only
-    # for the frame (`frac_equiv`) and for the dominant kernel, as the contract asks.
-    stages = {}
-    for k, v in stage_ms.items():
-        ent = {"ms": round(v, 4), "design_bytes": int(design.get(k, 0)),
-               "design_GBps": round(design.get(k, 0) / (v * 1e-3) / 1e9, 1) if v > 0 else None}
-        if counter is not None and k in counter:
-            ent["counter_bytes"] = int(counter[k])
-            ent["counter_GBps"] = round(counter[k] / (v * 1e-3) / 1e9, 1) if v > 0 else None
-            ent["frac_of_hbm_peak"] = round(counter[k] / (v * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4) if v > 0 else None
-        stages[k] = ent
-    # the dominant kernel of the frame is the blend; an inference call launches it once per depth slab, so "per launch"
-    # figures are the frame's blend figures divided by the launches of a frame (what rocprofv3's per-kernel average is)
-    stage_alg = {"preprocess": alg["preprocess"], "depth_sort": 0, "scan": alg["scan"], "duplicate": alg["duplicate"],
-                 "tile_sort": alg["sort"], "ranges": alg["ranges"], "blend": alg["blend"], "colour": 0}
-    dom = max(stage_ms, key=stage_ms.get)
-    kernel_of = {"blend": "blend_quadrant_kernel", "preprocess": "preprocess_kernel", "duplicate": "expand_kernel",
-                 "ranges": "tile_ranges_kernel", "colour": "sh_colour_listed_kernel"}
-    launches = max(1, len(slab_pairs)) if dom in ("blend", "duplicate", "ranges", "colour", "tile_sort") else 1
-    dom_kernel = kernel_of.get(dom, dom)
-    dom_traffic = None
-    if traffic is not None and dom_kernel in traffic["kernels"]:
-        dom_traffic = int(traffic["kernels"][dom_kernel]["bytes_per_launch"])
-    dom_bytes = stage_alg[dom] if stage_alg[dom] else design[dom]
-    dom_gbps = dom_bytes / (stage_ms[dom] * 1e-3) / 1e9 if stage_ms[dom] > 0 else 0.0
-    equiv_gbps = alg["frame"] / (ms_per_step * 1e-3) / 1e9
-    design_gbps = design["frame"] / (ms_per_step * 1e-3) / 1e9
-    frame = {"ms_per_step": round(ms_per_step, 4),
-             # one frame alone on the GPU, first kernel to last (HIP events), over the per-stage replay
-             "single_stream_ms_p50": round(call_ms[len(call_ms) // 2], 4) if call_ms else None,
-             "single_stream_ms_p95": round(call_ms[min(len(call_ms) - 1, int(0.95 * len(call_ms)))], 4) if call_ms else None,
-             "design_bytes": int(design["frame"]), "achieved_design": round(design_gbps, 1),
-             "frac_design": round(design_gbps / HBM_PEAK_GBPS, 4),
-             # the reference formula's bytes (SURVEY.md 8d B_alg, 6 radix passes over 64-bit keys ...) over this frame time:
-             # an EQUIVALENCE figure -- this design does not move most of those bytes
-             "alg_bytes_reference_formula": int(alg["frame"]), "achieved_equiv": round(equiv_gbps, 1),
-             "frac_equiv": round(equiv_gbps / HBM_PEAK_GBPS, 4), "n_pass_ref_sort": alg["n_pass"]}
-    if traffic is not None:
-        tr_gbps = traffic["frame_bytes"] / (ms_per_step * 1e-3) / 1e9
-        # THE frame figure: HBM bytes the counters measured for one frame / the frame time of the timed regions / peak
-        frame.update({"traffic": int(traffic["frame_bytes"]), "achieved": round(tr_gbps, 1),
-                      "frac": round(tr_gbps / HBM_PEAK_GBPS, 4)})
-        if serial is not None:
-            frame["frac_serial"] = round(traffic["frame_bytes"] / (serial["ms_per_step"] * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)
-    else:
-        frame.update({"traffic": None, "achieved": round(design_gbps, 1), "frac": round(design_gbps / HBM_PEAK_GBPS, 4),
-                      "frac_is": "design bytes (no counter summary for this workload)"})
-    roofline = {
-        "bound": "hbm", "kernel": dom_kernel,
-        "achieved": round(dom_gbps, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-        "frac": round(dom_gbps / HBM_PEAK_GBPS, 4), "traffic": dom_traffic,
-        "traffic_source": None if traffic is None else traffic["source"],
-        "traffic_measured_at": None if traffic is None else traffic["commit"],
-        "launches_per_frame": launches, "avg_launch_ms": round(stage_ms[dom] / launches, 4),
-        "alg_bytes_per_launch": int(dom_bytes / launches), "per_frame_ms": round(stage_ms[dom], 4),
-        "alg_bytes_per_frame": int(dom_bytes), "design_bytes_per_frame": int(design[dom]), "stage_replay_calls": calls,
-        "note": "vector-instruction-issue bound, not HBM bound (DESIGN.md section 4): frac = SURVEY 8d's algorithmic bytes of the "
-                "kernel (44 B per reference pair + 24 B per pixel) over its time and the HBM peak",
-        "frame": frame, "stages": stages, "slab_pairs_last_frame": slab_pairs,
-        "units_mean": {k: (round(v, 1) if not isinstance(v, list) else [round(x, 1) for x in v]) for k, v in units.items()},
-    }
+        # ---- per-frame workload statistics (untimed): the units of this rank's timed frames ----
+        units = b.units(timed_frames[::max(1, K // 8)])
+        V, D = units["V"], units["D"]
+        alg = algorithmic_bytes(P, V, D, T, W, H, M)
+        design = design_bytes(units, inference=True, deferred=_lib.get_option(_lib.OPT_DEFER_COLOUR) != 0)
 
-    cpu_baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.boundary == "op" and b.key in ("c3", "c2", "heavy", "heavy1080"):
-        cpu_baseline = run_cpu_baseline(b)
-    reference_on_gpu = None
-    if rank == 0 and world == 1 and args.boundary == "op" and not args.no_reference_hip and b.extra is None and b.layers is None:
-        reference_on_gpu = run_reference_on_gpu(b.cloud, [b.cam(f) for f in timed_frames[:24]], b.bg)
+        calls = stage_ms.pop("calls")
+        traffic = pmc_traffic(T_key=args.workload if not args.gaussians else None)
+        counter = stage_counter_bytes(traffic)
+        # Per stage: this library's design bytes (design_bytes above: what its own layout has to move, measured units) and the
+        # HBM bytes the counters saw (profiles/, per stage) over the stage's time.  Both are <= what the hardware can move; the
+        # reference formula's bytes are NOT credited per stage -- the stages are not the reference's -- only
+        # for the frame (`frac_equiv`) and for the dominant kernel, as the contract asks.
+        stages = {}
+        for k, v in stage_ms.items():
+            ent = {"ms": round(v, 4), "design_bytes": int(design.get(k, 0)),
+                   "design_GBps": round(design.get(k, 0) / (v * 1e-3) / 1e9, 1) if v > 0 else None}
+            if counter is not None and k in counter:
+                ent["counter_bytes"] = int(counter[k])
+                ent["counter_GBps"] = round(counter[k] / (v * 1e-3) / 1e9, 1) if v > 0 else None
+                ent["frac_of_hbm_peak"] = round(counter[k] / (v * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4) if v > 0 else None
+            stages[k] = ent
+        # the dominant kernel of the frame is the blend; an inference call launches it once per depth slab, so "per launch"
+        # figures are the frame's blend figures divided by the launches of a frame (what rocprofv3's per-kernel average is)
+        stage_alg = {"preprocess": alg["preprocess"], "depth_sort": 0, "scan": alg["scan"], "duplicate": alg["duplicate"],
+                     "tile_sort": alg["sort"], "ranges": alg["ranges"], "blend": alg["blend"], "colour": 0}
+        dom = max(stage_ms, key=stage_ms.get)
+        kernel_of = {"blend": "blend_quadrant_kernel", "preprocess": "preprocess_kernel", "duplicate": "expand_kernel",
+                     "ranges": "tile_ranges_kernel", "colour": "sh_colour_listed_kernel"}
+        launches = max(1, len(slab_pairs)) if dom in ("blend", "duplicate", "ranges", "colour", "tile_sort") else 1
+        dom_kernel = kernel_of.get(dom, dom)
+        dom_traffic = None
+        if traffic is not None and dom_kernel in traffic["kernels"]:
+            dom_traffic = int(traffic["kernels"][dom_kernel]["bytes_per_launch"])
+        dom_bytes = stage_alg[dom] if stage_alg[dom] else design[dom]
+        dom_gbps = dom_bytes / (stage_ms[dom] * 1e-3) / 1e9 if stage_ms[dom] > 0 else 0.0
+        equiv_gbps = alg["frame"] / (ms_per_step * 1e-3) / 1e9
+        design_gbps = design["frame"] / (ms_per_step * 1e-3) / 1e9
+        frame = {"ms_per_step": round(ms_per_step, 4),
+                 # one frame alone on the GPU, first kernel to last (HIP events), over the per-stage replay
+                 "single_stream_ms_p50": round(call_ms[len(call_ms) // 2], 4) if call_ms else None,
+                 "single_stream_ms_p95": round(call_ms[min(len(call_ms) - 1, int(0.95 * len(call_ms)))], 4) if call_ms else None,
+                 "design_bytes": int(design["frame"]), "achieved_design": round(design_gbps, 1),
+                 "frac_design": round(design_gbps / HBM_PEAK_GBPS, 4),
+                 # the reference formula's bytes (SURVEY.md 8d B_alg, 6 radix passes over 64-bit keys ...) over this frame time:
+                 # an EQUIVALENCE figure -- this design does not move most of those bytes
+                 "alg_bytes_reference_formula": int(alg["frame"]), "achieved_equiv": round(equiv_gbps, 1),
+                 "frac_equiv": round(equiv_gbps / HBM_PEAK_GBPS, 4), "n_pass_ref_sort": alg["n_pass"]}
+        if traffic is not None:
+            tr_gbps = traffic["frame_bytes"] / (ms_per_step * 1e-3) / 1e9
+            # THE frame figure: HBM bytes the counters measured for one frame / the frame time of the timed regions / peak
+            frame.update({"traffic": int(traffic["frame_bytes"]), "achieved": round(tr_gbps, 1),
+                          "frac": round(tr_gbps / HBM_PEAK_GBPS, 4)})
+            if serial is not None:
+                frame["frac_serial"] = round(traffic["frame_bytes"] / (serial["ms_per_step"] * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)
+        else:
+            frame.update({"traffic": None, "achieved": round(design_gbps, 1), "frac": round(design_gbps / HBM_PEAK_GBPS, 4),
+                          "frac_is": "design bytes (no counter summary for this workload)"})
+        roofline = {
+            "bound": "hbm", "kernel": dom_kernel,
+            "achieved": round(dom_gbps, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+            "frac": round(dom_gbps / HBM_PEAK_GBPS, 4), "traffic": dom_traffic,
+            "traffic_source": None if traffic is None else traffic["source"],
+            "traffic_measured_at": None if traffic is None else traffic["commit"],
+            "launches_per_frame": launches, "avg_launch_ms": round(stage_ms[dom] / launches, 4),
+            "alg_bytes_per_launch": int(dom_bytes / launches), "per_frame_ms": round(stage_ms[dom], 4),
+            "alg_bytes_per_frame": int(dom_bytes), "design_bytes_per_frame": int(design[dom]), "stage_replay_calls": calls,
+            "note": "vector-instruction-issue bound, not HBM bound (DESIGN.md section 4): frac = SURVEY 8d's algorithmic bytes of the "
+                    "kernel (44 B per reference pair + 24 B per pixel) over its time and the HBM peak",
+            "frame": frame, "stages": stages, "slab_pairs_last_frame": slab_pairs,
+            "units_mean": {k: (round(v, 1) if not isinstance(v, list) else [round(x, 1) for x in v]) for k, v in units.items()},
+        }
 
-    also = None
-    if rank == 0 and world == 1 and not args.no_also and args.workload == "c3" and not args.gaussians and args.boundary == "op":
-        also = run_also(device, side, S, parity=not args.no_cpu_baseline)
+        if rank == 0 and world == 1 and not args.no_cpu_baseline and args.boundary == "op" and b.key in ("c3", "c2", "heavy", "heavy1080"):
+            cpu_baseline = run_cpu_baseline(b)
+        if rank == 0 and world == 1 and args.boundary == "op" and not args.no_reference_hip and b.extra is None and b.layers is None:
+            reference_on_gpu = run_reference_on_gpu(b.cloud, [b.cam(f) for f in timed_frames[:24]], b.bg)
+
+        if rank == 0 and world == 1 and not args.no_also and args.workload == "c3" and not args.gaussians and args.boundary == "op":
+            also = run_also(device, side, S, parity=not args.no_cpu_baseline)
 
     if rank == 0:
         metric = ("rendered frames/sec at 1920x1080, 3M Gaussians" if args.workload == "c3" and not args.gaussians
@@ -797,7 +803,8 @@ def main():
             "regions": {"count": R, "steps_each": K, "value_median": round(fps(med), 2), "value_min": round(fps(order[-1]), 2),
                         "value_max": round(fps(order[0]), 2), "values": [round(fps(s), 2) for s in secs]},
             "config": {"workload": b.name, "P": P, "sh_coeffs": M, "width": W, "height": H, "tiles": T,
-                       "visible_mean": round(V, 1), "num_rendered_mean": round(D, 1),
+                       "visible_mean": None if units is None else round(units["V"], 1),
+                       "num_rendered_mean": None if units is None else round(units["D"], 1),
                        "boundary": ("render(): activations, SH pass, normal pass (folded into the first), normal/pseudo-normal "
                                     "post-processing, RGBA8 pack per frame" if args.boundary == "render" else
                                     "GaussianRasterizer.forward + RGBA8 pack per frame")
@@ -835,13 +842,14 @@ def main():
         # scalars a reader of the driver's record needs, where that record keeps them (its copy of `roofline` and `config`
         # holds scalar fields only; the nested objects above stay for the full line)
         rf = line["roofline"]
-        rf["frame_frac_traffic"] = frame.get("frac") if traffic is not None else None
-        rf["frame_traffic_bytes"] = frame.get("traffic")
-        rf["frame_frac_design"] = frame["frac_design"]
-        rf["frame_frac_serial"] = frame.get("frac_serial")
-        rf["serial_ms_per_step"] = None if serial is None else serial["ms_per_step"]
-        rf["serial_value"] = None if serial is None else serial["value"]
-        rf["reference_on_gpu_ms"] = reference_on_gpu.get("ms_per_frame") if isinstance(reference_on_gpu, dict) else None
+        if rf is not None:
+            rf["frame_frac_traffic"] = frame.get("frac") if traffic is not None else None
+            rf["frame_traffic_bytes"] = frame.get("traffic")
+            rf["frame_frac_design"] = frame["frac_design"]
+            rf["frame_frac_serial"] = frame.get("frac_serial")
+            rf["serial_ms_per_step"] = None if serial is None else serial["ms_per_step"]
+            rf["serial_value"] = None if serial is None else serial["value"]
+            rf["reference_on_gpu_ms"] = reference_on_gpu.get("ms_per_frame") if isinstance(reference_on_gpu, dict) else None
         line["config"]["serial_frames_per_s"] = None if serial is None else serial["value"]
         line["config"]["n_ranks_seen"] = n_ranks_seen
         # the multi-GPU scalars where the driver's record keeps scalars: every rank's own rate (min / max; the list is `per_rank_frames_per_s`),

@@ -4,7 +4,7 @@
 mkdir -p gpurun_out/rank_ab
 for rep in 1 2; do
   for mode in 0 2; do
-    GSR_RADIX_RANK=$mode python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-also --no-reference-hip \
+    GSR_RADIX_RANK=$mode python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-also --no-reference-hip \
       > gpurun_out/rank_ab/mode${mode}_rep${rep}.json 2> gpurun_out/rank_ab/mode${mode}_rep${rep}.err
   done
 done

@@ -38,7 +38,7 @@ def _bench(*extra):
 
 def test_one_rank_rccl_group_gathers_the_bytes_of_the_single_process_path():
     plain = _bench("--steps", "8")
-    dist = _bench("--steps", "8", "--force-distributed", "--gather-chunks", "3")
+    dist = _bench("--steps", "8", "--force-distributed", "--gather-chunks", "3", "--full")   # --full: rank 0 alone as well
     assert dist["config"]["gather"]["gathered_shape"] == [1, 8, 4, 540, 960]
     assert "RCCL gather" in dist["config"]["boundary"]
     assert dist["frames_digest"] == plain["frames_digest"]
@@ -49,6 +49,8 @@ def test_one_rank_rccl_group_gathers_the_bytes_of_the_single_process_path():
     assert c["gather_tail_ms"] >= 0.0 and c["single_gpu_frames_per_s_same_run"] > 0
     assert 0.3 < c["frac_of_n_x_single_gpu"] < 1.5      # one rank: the gather's cost against the same frames without it
     assert plain["config"]["frac_of_n_x_single_gpu"] is None and plain["config"]["gather_tail_ms"] is None
+    # a plain run measures the headline only; the replay, serial loop and roofline come with --full
+    assert plain["roofline"] is None and plain["serial"] is None and dist["roofline"]["stages"]
 
 
 def test_one_rank_rccl_job_with_cloud_broadcast_and_uneven_pieces():
