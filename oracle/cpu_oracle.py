@@ -78,6 +78,43 @@ def mark_visible(means3D, viewmatrix, projmatrix) -> np.ndarray:
     return out.astype(bool)
 
 
+def preprocess(*, means3D, opacities, width: int, height: int, viewmatrix, projmatrix, campos, tanfovx: float,
+               tanfovy: float, sh_degree: int = 0, scale_modifier: float = 1.0, shs=None, colors_precomp=None, scales=None,
+               rotations=None, cov3D_precomp=None, **_unused) -> Dict[str, np.ndarray]:
+    """The per-Gaussian stage alone (gsro_preprocess: forward.cu:155-256).  Returns cov3D_out [P,6] (written where the
+    Gaussian passes the near-plane test and the covariance comes from scales / rotations), rgb [P,3] and clamped [P,3]
+    (written where radii > 0 and the colour comes from SHs), radii, means2D, depths and conic_opacity; rows the stage
+    does not write are zero."""
+    m = _f32(means3D)
+    P = 0 if m is None else int(m.shape[0])
+    out = {"cov3D_out": np.zeros((P, 6), np.float32), "rgb": np.zeros((P, 3), np.float32),
+           "clamped": np.zeros((P, 3), np.uint8), "radii": np.zeros(P, np.int32), "means2D": np.zeros((P, 2), np.float32),
+           "depths": np.zeros(P, np.float32), "conic_opacity": np.zeros((P, 4), np.float32)}
+    if P == 0:
+        return out
+    sh, col, sc, rot, cov = _f32(shs), _f32(colors_precomp), _f32(scales), _f32(rotations), _f32(cov3D_precomp)
+    if (sh is None) == (col is None):
+        raise ValueError("exactly one of shs / colors_precomp")
+    if ((sc is None or rot is None) and cov is None) or ((sc is not None or rot is not None) and cov is not None):
+        raise ValueError("exactly one of (scales, rotations) / cov3D_precomp")
+    M = 0 if sh is None else int(sh.shape[1])
+    op, vm, pm, cp = _f32(opacities), _f32(viewmatrix), _f32(projmatrix), _f32(campos)
+    tiles = np.zeros(P, np.uint32)
+    L = lib()
+    if not getattr(L, "_pre_ready", False):
+        L.gsro_preprocess.restype = None
+        L.gsro_preprocess.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, _F, _F, ctypes.c_float, _F, _F, _F, _F, _F,
+                                      _F, _F, _F, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float,
+                                      _I32, _F, _F, _F, _F, _F, _U32, _U8]
+        L._pre_ready = True
+    L.gsro_preprocess(P, int(sh_degree), M, _ptr(m, _F), _ptr(sc, _F), float(scale_modifier), _ptr(rot, _F), _ptr(op, _F),
+                      _ptr(sh, _F), _ptr(cov, _F), _ptr(col, _F), _ptr(vm, _F), _ptr(pm, _F), _ptr(cp, _F), int(width),
+                      int(height), float(tanfovx), float(tanfovy), _ptr(out["radii"], _I32), _ptr(out["means2D"], _F),
+                      _ptr(out["depths"], _F), _ptr(out["cov3D_out"], _F), _ptr(out["rgb"], _F),
+                      _ptr(out["conic_opacity"], _F), _ptr(tiles, _U32), _ptr(out["clamped"], _U8))
+    return out
+
+
 def forward(*, means3D, opacities, bg, width: int, height: int, viewmatrix, projmatrix, campos,
             tanfovx: float, tanfovy: float, sh_degree: int = 0, scale_modifier: float = 1.0, shs=None,
             colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None,
