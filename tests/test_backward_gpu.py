@@ -289,6 +289,20 @@ def test_backward_randomised_configurations(seed):
     check_case(f"rand{seed}", cloud, cam, pg, KEYS_SH, mode, hip_kw={"cull": bool(seed % 2)}, bg=bg, sh_degree=deg)
 
 
+@pytest.mark.parametrize("P", [256, 257, 65_536, 65_537], ids=lambda P: f"P{P}_idbits{(P - 1).bit_length()}")
+def test_deterministic_id_sort_at_its_width_boundaries(P):
+    """The deterministic backward sorts the point list by Gaussian id on ceil(log2 P) bits (gsr_api.hip: id_bits): 8, 9, 16 and
+    17 bits here, i.e. 1, 2, 2 and 3 radix passes, each side of a pass-count step.  The Gaussian with the highest id sits in
+    front of the cloud, so its id -- the only one with the top bit set at 257 and 65 537 -- is in the lists; the gradients
+    hold the bar against the truth and two calls give the same bits."""
+    cloud, cam = scenes.config_c1(P=P, seed=36), scenes.c1_camera(128, 96)
+    cloud.means3D[-1] = torch.tensor([0.05, -0.03, -1.0])
+    cloud.scales[-1] = 0.04
+    cloud.opacities[-1] = 0.8
+    hip, _ = check_case(f"id_sort_P{P}", cloud, cam, pixel_grads(cam, 9), KEYS_SH, "deterministic", hip_kw={"cull": False})
+    assert hip["radii"][-1] > 0 and int(hip["fwd"]["point_list"].max()) == P - 1
+
+
 @pytest.mark.parametrize("mode", MODES)
 def test_backward_c2_full_size_vs_oracle(mode):
     """BASELINE configs[1] stand-in at full size (1 M Gaussians, 960x540, orbit frame 100): every gradient against the

@@ -34,6 +34,12 @@ def fallbacks():
 
 
 def sort_pairs(keys, vals, bits, iota=False):
+    k, v, _ = sort_pairs_where(keys, vals, bits, iota)
+    return k, v
+
+
+def sort_pairs_where(keys, vals, bits, iota=False):
+    """``sort_pairs`` that also returns the ABI's ``sorted_in_alt``."""
     from autovfx_amd import _lib
     n = keys.numel()
     dev = keys.device
@@ -47,7 +53,7 @@ def sort_pairs(keys, vals, bits, iota=False):
                                        ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
     assert rc == 0, _lib.last_error()
     torch.cuda.synchronize()
-    return (k_alt, v_alt) if where.value else (keys, v)
+    return ((k_alt, v_alt) if where.value else (keys, v)) + (where.value,)
 
 
 @pytest.mark.parametrize("n", [1, 2, 63, 64, 65, 255, 4095, 4096, 4097, 8192, 12345, 100_000, 1_000_003, 8_500_000])
@@ -67,6 +73,107 @@ def test_sort_matches_stable_sort(n, bits):
     got_k, got_v = sort_pairs(k32, v32, bits)
     assert torch.equal(got_k.view(torch.uint32).to(torch.int64), want_k)
     assert torch.equal(got_v.to(torch.int64), want_v)
+
+
+# Every pass count and every digit split at its edges: radix_sort_pairs makes (bits + 7) // 8 passes, the first bits % passes
+# digits one bit wider than the rest, and every pass swaps the key / payload buffers, so the width decides where the result lands.
+WIDTHS = [1, 2, 7, 8, 9, 12, 15, 16, 17, 20, 23, 24, 25, 30, 31, 32]
+
+
+def passes_of(bits):
+    return (bits + 7) // 8
+
+
+def digit_widths(bits):
+    p = passes_of(bits)
+    return [bits // p + (1 if i < bits % p else 0) for i in range(p)]
+
+
+def width_id(bits):
+    return f"bits{bits}_passes{passes_of(bits)}"
+
+
+def as_u32(keys):
+    """int64 values in [0, 2^32) -> an int32 tensor holding the same 32 bits."""
+    return keys.to(torch.uint32).view(torch.int32).contiguous()
+
+
+def stable_on_low_bits(keys, vals, bits):
+    """The reference: torch's stable sort on key & (2^bits - 1), carrying the whole keys and the payloads along."""
+    order = torch.sort(keys & ((1 << bits) - 1), stable=True).indices
+    return keys[order], vals[order]
+
+
+def check_sort(keys, vals, bits):
+    got_k, got_v, where = sort_pairs_where(as_u32(keys), vals.to(torch.int32).contiguous(), bits)
+    assert where == passes_of(bits) % 2, f"{bits} bits: sorted_in_alt = {where} after {passes_of(bits)} passes"
+    want_k, want_v = stable_on_low_bits(keys, vals, bits)
+    assert torch.equal(got_k.view(torch.uint32).to(torch.int64), want_k), f"{bits} bits: keys"
+    assert torch.equal(got_v.to(torch.int64), want_v), f"{bits} bits: payloads"
+
+
+def test_the_widths_reach_every_pass_count_and_split():
+    assert {passes_of(b) for b in WIDTHS} == {1, 2, 3, 4}
+    assert digit_widths(13) == [7, 6] and digit_widths(17) == [6, 6, 5] and digit_widths(25) == [7, 6, 6, 6]
+    assert all(sum(digit_widths(b)) == b and max(digit_widths(b)) <= 8 for b in WIDTHS)
+
+
+@pytest.mark.parametrize("n", [1, 64, 4095, 4097, 300_007])
+@pytest.mark.parametrize("bits", WIDTHS, ids=width_id)
+def test_every_width_matches_stable_sort(bits, n):
+    """Keys over all of [0, 2^bits), both ends of it present and repeated, heavy duplicates; the result in the buffers the pass
+    count says (sorted_in_alt = passes % 2: what the tile sort's caller relies on to land a list in its slab's own buffer)."""
+    g = torch.Generator(device="cuda").manual_seed(1000 * bits + n)
+    hi = (1 << bits) - 1
+    keys = torch.randint(0, hi + 1, (n,), generator=g, device="cuda", dtype=torch.int64)
+    keys[::5] = keys[n // 2].clone()
+    keys[n // 3::7] = hi
+    keys[0] = hi
+    if n > 1:
+        keys[-1] = 0
+        keys[1::11] = 0
+    vals = torch.randint(0, 2**31 - 1, (n,), generator=g, device="cuda", dtype=torch.int64)
+    check_sort(keys, vals, bits)
+
+
+@pytest.mark.parametrize("bits", WIDTHS, ids=width_id)
+def test_only_the_top_digit_varies(bits):
+    """Every pass but the last sees one digit value (each carries whole tiles unchanged); the last one does all the sorting."""
+    n = 100_003
+    g = torch.Generator(device="cuda").manual_seed(7 * bits + 1)
+    top = digit_widths(bits)[-1]
+    shift = bits - top
+    low = int(torch.randint(0, 1 << shift, (1,), generator=g, device="cuda").item()) if shift else 0
+    digit = torch.randint(0, 1 << top, (n,), generator=g, device="cuda", dtype=torch.int64)
+    digit[::4] = (1 << top) - 1
+    vals = torch.arange(n, device="cuda", dtype=torch.int64)
+    check_sort((digit << shift) | low, vals, bits)
+
+
+@pytest.mark.parametrize("bits", [7, 13, 17, 25], ids=width_id)
+def test_bits_above_the_width_are_ignored_and_kept(bits):
+    """gsr.h: the sort is on the low `bits` key bits.  Keys with random bits above them: the order is the stable sort on the
+    low bits, and the returned keys are the input keys, high bits included."""
+    n = 200_003
+    g = torch.Generator(device="cuda").manual_seed(bits)
+    low = torch.randint(0, 1 << bits, (n,), generator=g, device="cuda", dtype=torch.int64)
+    low[::3] = low[1].clone()                   # equal low bits under different high bits: stability decides
+    high = torch.randint(0, 1 << (32 - bits), (n,), generator=g, device="cuda", dtype=torch.int64) << bits
+    vals = torch.randint(0, 2**31 - 1, (n,), generator=g, device="cuda", dtype=torch.int64)
+    check_sort(high | low, vals, bits)
+
+
+@pytest.mark.parametrize("n", [4096 * 3 + 17, 300_007])
+@pytest.mark.parametrize("bits", [8, 20, 32], ids=width_id)
+def test_iota_payload_at_one_three_and_four_passes(bits, n):
+    g = torch.Generator(device="cuda").manual_seed(bits + n)
+    keys = torch.randint(0, 1 << bits, (n,), generator=g, device="cuda", dtype=torch.int64)
+    keys[::4] = keys[2].clone()
+    want = torch.sort(keys, stable=True).indices
+    got_k, got, where = sort_pairs_where(as_u32(keys), None, bits, iota=True)
+    assert where == passes_of(bits) % 2
+    assert torch.equal(got.to(torch.int64), want)
+    assert torch.equal(got_k.view(torch.uint32).to(torch.int64), keys[want])
 
 
 @pytest.mark.parametrize("n", [5, 4096 * 3 + 17, 3_000_000])
