@@ -233,6 +233,46 @@ def test_bit_equal_to_torch_adam_over_many_steps_with_surgery(launches):
     assert ours.param_groups[-1]["params"][0] is offset and offset.data_ptr() % 16 == 4
 
 
+@pytest.mark.parametrize("stepped,counts,offset_at", [(17, [16, 1], 17), (35, [16, 16, 3], 20)])
+def test_more_tensors_than_one_launch_takes(launches, stepped, counts, offset_at):
+    """A launch takes 16 tensors (ADAM_MAX_TENSORS); optim.py cuts a longer list into launches of 16.  17 and 35 single-tensor groups
+    with a gradient, and one more without at index 3, so that the cut does not fall on parameter index 16: sizes 1, 3, 1023, 4096,
+    4097 and 70 001 in turn, one tensor of numel 0, and after the first cut one parameter 4 bytes into its allocation.  The empty
+    tensor has a gradient, so torch's _init_group hands it on and optim.py passes it as a descriptor of no chunks: it counts as one
+    of a launch's tensors.  After each of 12 steps every p, exp_avg and exp_avg_sq has torch.optim.Adam's bits; the second and third
+    launch step their own tensors (a launch that repeated the first 16 would leave the rest unstepped and step those twice), and
+    their chunk numbering starts again at their first tensor."""
+    assert _lib.ADAM_MAX_TENSORS == 16
+    gen = torch.Generator(device=DEV).manual_seed(17)
+    sizes = (1, 3, 1023, 4096, 4097, 70_001)
+    ga = []
+    for i in range(stepped + 1):
+        if i == offset_at:
+            p = torch.randn(MISALIGNED + 2, generator=gen, device=DEV)[1:1 + MISALIGNED]
+        else:
+            p = torch.randn(0 if i == 6 else sizes[i % len(sizes)], generator=gen, device=DEV)
+        ga.append({"params": [torch.nn.Parameter(p)], "lr": 1e-3 * (1 + i), "name": f"t{i}"})
+    gb = twin(ga)
+    assert offset_at > 16 and gb[offset_at]["params"][0].data_ptr() % 16 == 4 and gb[6]["params"][0].numel() == 0
+    numels = [gr["params"][0].numel() for i, gr in enumerate(gb) if i != 3]
+    assert all(max(numels[cut:cut + 16]) > 4096 for cut in range(16, stepped, 16))   # a tensor of several chunks after every cut
+    ref, ours = torch.optim.Adam(ga, lr=0.0, eps=1e-15), O.Adam(gb, lr=0.0, eps=1e-15)
+    for it in range(1, 13):
+        gen_a, gen_b = (torch.Generator(device=DEV).manual_seed(8000 + it) for _ in range(2))
+        for i, (gr_a, gr_b) in enumerate(zip(ref.param_groups, ours.param_groups)):
+            pa, pb = gr_a["params"][0], gr_b["params"][0]
+            g_a, g_b = nasty_grads(pa.shape, gen_a), nasty_grads(pb.shape, gen_b)
+            pa.grad, pb.grad = (None, None) if i == 3 else (g_a, g_b)
+        assert O.kernel_takes(ours.param_groups, ours.state)
+        ref.step()
+        before = len(launches)
+        ours.step()
+        assert [c[0] for c in launches[before:]] == counts and sum(counts) == stepped, launches[before:]
+        compare(ref, ours, it)
+    assert ours.state.get(gb[3]["params"][0]) is None and same_bits(ga[3]["params"][0], gb[3]["params"][0])
+    assert float(ours.state[gb[offset_at]["params"][0]]["step"]) == 12.0
+
+
 def test_misaligned_gradient_or_moment_with_an_aligned_parameter():
     """The vector path needs all four pointers 16-byte aligned: an aligned parameter with a gradient, or with moments, 4 bytes into
     their allocations runs element by element, with torch's bits."""
