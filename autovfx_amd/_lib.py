@@ -25,7 +25,7 @@ GEOM_SLOTS = ("raster", "rgb", "splat_bins", "internal_radii", "depth_order", "p
 BIN_SLOTS = ("point_list", "tile_keys")
 IMG_SLOTS = ("ranges", "n_contrib")
 STAGES = ("preprocess", "depth_sort", "scan", "duplicate", "tile_sort", "ranges", "blend", "colour")
-ABI_VERSION = 18
+ABI_VERSION = 19
 
 
 class PngFileInfo(ctypes.Structure):
@@ -52,6 +52,21 @@ class AdamTensor(ctypes.Structure):
 
 
 ADAM_MAX_TENSORS = 16
+
+
+class DensifyTensor(ctypes.Structure):
+    """``GsrDensifyTensor`` (gsr.h)."""
+    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("side", ctypes.c_void_p), ("floats_per_row", ctypes.c_int32),
+                ("is_moment", ctypes.c_int32)]
+
+
+class DensifyPlan(ctypes.Structure):
+    """``GsrDensifyPlan`` (gsr.h)."""
+    _fields_ = [("n_src", ctypes.c_int64), ("n_keep", ctypes.c_int64), ("n_front", ctypes.c_int64), ("n_out", ctypes.c_int64),
+                ("n_split", ctypes.c_int64), ("src_of", ctypes.c_void_p), ("child_rows", ctypes.c_void_p), ("split_idx", ctypes.c_void_p)]
+
+
+DENSIFY_MAX_TENSORS = 18
 MAX_SLABS = 8
 FORWARD_INFERENCE = 1
 
@@ -63,7 +78,7 @@ SYMBOLS = ("gsr_forward", "gsr_mark_visible", "gsr_backward", "gsr_last_geom_off
            "gsr_forward_begin", "gsr_forward_finish", "gsr_forward_ready", "gsr_forward_cancel", "gsr_last_slab_pairs", "gsr_plan_slabs", "gsr_selftest_lds_atomic_order", "gsr_get_backward_times", "gsr_place_object",
            "gsr_forward_raw", "gsr_forward_raw_begin", "gsr_backward_raw", "gsr_place_object_subset", "gsr_cube_to_equirect",
            "gsr_knn3_scratch_bytes", "gsr_knn3_mean_dist", "gsr_ssim_scratch_bytes", "gsr_ssim_forward", "gsr_ssim_backward",
-           "gsr_adam_step")
+           "gsr_adam_step", "gsr_densify_stats", "gsr_densify_plan_scratch_bytes", "gsr_densify_plan", "gsr_densify_apply")
 OPT_TILE_CULL = 0
 OPT_SLABS = 1
 OPT_SLAB_FIRST = 2
@@ -220,6 +235,15 @@ def _load() -> ctypes.CDLL:
     lib.gsr_ssim_backward.argtypes = [c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p]
     lib.gsr_adam_step.restype = ctypes.c_int
     lib.gsr_adam_step.argtypes = [ctypes.POINTER(AdamTensor), c_i, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, c_p]
+    c_f32, c_i64 = ctypes.c_float, ctypes.c_int64
+    lib.gsr_densify_stats.restype = ctypes.c_int
+    lib.gsr_densify_stats.argtypes = [c_i64, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p]
+    lib.gsr_densify_plan_scratch_bytes.restype = ctypes.c_size_t
+    lib.gsr_densify_plan_scratch_bytes.argtypes = [c_i64]
+    lib.gsr_densify_plan.restype = ctypes.c_int
+    lib.gsr_densify_plan.argtypes = [c_i64, c_p, c_p, c_p, c_p, c_f32, c_f32, c_f32, c_i, c_f32, c_p, c_p, c_p, c_p, ctypes.c_size_t, c_p]
+    lib.gsr_densify_apply.restype = ctypes.c_int
+    lib.gsr_densify_apply.argtypes = [ctypes.POINTER(DensifyTensor), c_i, ctypes.POINTER(DensifyPlan), c_p]
     lib.gsr_resize_rgba8_bilinear.restype = ctypes.c_int
     lib.gsr_resize_rgba8_bilinear.argtypes = [c_f, ctypes.c_int, ctypes.c_int, c_f, ctypes.c_int, ctypes.c_int, c_f, ctypes.c_void_p]
     lib.gsr_resize_f32_nearest.restype = ctypes.c_int

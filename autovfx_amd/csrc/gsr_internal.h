@@ -412,6 +412,56 @@ struct AdamBatch {    // passed by value (kernel arguments)
 uint64_t adam_chunks(int64_t numel);   // numel >= 0
 hipError_t launch_adam_step(const AdamBatch& b, hipStream_t stream);
 
+// ---- densification (gsr_densify.hip) ----
+constexpr int kDensifyBlockRows = 1024;       // source rows per workgroup of the plan's classify / scatter kernels
+constexpr int64_t kDensifyApplyChunk = 2048;  // output floats per workgroup iteration of the apply kernel
+constexpr int kDensifyMaxTensors = 18;        // gsr.h: GSR_DENSIFY_MAX_TENSORS (6 parameters, 12 moments)
+struct DensifyPlanArgs {   // gsr.h: gsr_densify_plan; passed by value
+    int64_t n;
+    const float *accum, *denom, *scaling, *opacity;
+    float max_grad, dense_bound, min_opacity, ws_bound;
+    int ws_test;
+    int32_t *src_of, *split_idx, *counts;
+    uint8_t* flags;                           // scratch: [n] class bits
+    uint32_t *block_counts, *block_offsets;   // scratch: [3][blocks] each
+    uint32_t blocks;
+};
+// Byte offsets of the regions of the plan's scratch (each 256-byte aligned); bytes = the whole.
+struct DensifyPlanLayout {
+    size_t flags, block_counts, block_offsets, bytes;
+    uint32_t blocks;
+};
+inline DensifyPlanLayout densify_plan_layout(int64_t n) {
+    DensifyPlanLayout l{};
+    l.blocks = (uint32_t)((n + kDensifyBlockRows - 1) / kDensifyBlockRows);
+    auto up = [](size_t x) { return (x + 255) & ~size_t(255); };
+    l.flags = 0;
+    l.block_counts = up((size_t)n);
+    l.block_offsets = l.block_counts + up((size_t)3 * l.blocks * sizeof(uint32_t));
+    l.bytes = l.block_offsets + up((size_t)3 * l.blocks * sizeof(uint32_t));
+    return l;
+}
+struct DensifyTensor {
+    const float* src;
+    float* dst;
+    const float* side;   // the children's rows of this tensor ([2 n_split, floats_per_row]); null: copied from the parent
+    int floats_per_row, is_moment;
+};
+struct DensifyApplyPlan {
+    int64_t n_src, n_keep, n_front, n_out, n_split;
+    const int32_t *src_of, *child_rows, *split_idx;
+};
+struct DensifyApplyBatch {   // passed by value (kernel arguments)
+    DensifyTensor t[kDensifyMaxTensors];
+    uint64_t first_chunk[kDensifyMaxTensors + 1];
+    DensifyApplyPlan plan;
+    int count;
+};
+hipError_t launch_densify_stats(int64_t n, const float* grad, int row_floats, const uint8_t* filter, float* accum, float* denom,
+                                const int* radii, float* max_radii, hipStream_t stream);
+hipError_t launch_densify_plan(const DensifyPlanArgs& p, hipStream_t stream);
+hipError_t launch_densify_apply(const DensifyApplyBatch& b, hipStream_t stream);
+
 // ---- three nearest neighbours (gsr_knn.hip) ----
 // Boxes over the Morton-sorted points: level 0 = leaves of 64 points, every level above = 16 boxes of the one below, up to the first
 // level of at most 16 boxes (six levels for n < 2^30).  A box is two float4 (lo, hi; w unused) at boxes[2 * (offset[level] + i)].

@@ -36,9 +36,16 @@ AutoVFX reaches the rasterizer through two imports (paths under the reference tr
    ``autovfx_amd.gaussian_model``) gets ``training_setup`` wrapped: after the original built ``self.optimizer``, a plain
    ``torch.optim.Adam`` is replaced by ``autovfx_amd.optim.Adam`` over the same parameter groups and defaults (one HIP launch per
    step, torch's bits; the state is still empty there, so ``restore()`` loads into it as before); torch and the library are
-   imported at the first call, not at patch time.
+   imported at the first call, not at patch time;
+9. the same class, when it also defines ``densification_postfix``, ``prune_points`` and ``cat_tensors_to_optimizer``, gets
+   ``add_densification_stats`` (``:415-417``, every iteration) and ``densify_and_prune`` (``:399-413``) replaced by
+   ``autovfx_amd.densify``'s: one HIP launch for the statistics, and a plan, one host read of three counts and one launch that writes
+   the six new parameters and twelve new moments instead of four rewrites of the model -- the reference's values, order, generator
+   state and optimizer surgery bit for bit; a call the kernels do not take exactly (a CPU model, ``max_grad <= 0``, other layouts)
+   runs ``GaussianModel.reference_<name>``.  The inline ``max_radii2D`` line of the loops cannot be reached by a hook and stays.
+   torch and the library are imported at the first call.
 
-Items 2-8 are the rows of ``_TARGETS``, applied by ``_patch`` to every matching module, whether it was imported before
+Items 2-9 are the rows of ``_TARGETS``, applied by ``_patch`` to every matching module, whether it was imported before
 ``install()`` or after (a ``sys.meta_path`` hook).  Each replaced attribute keeps the reference's original next to it as
 ``reference_<attr>`` on the module or class (``<module>.reference_render``, ``SceneRepresentation.reference_render_from_3DGS``, ...).
 ``uninstall()`` undoes every patch in reverse.
@@ -135,6 +142,26 @@ def _with_fused_adam(original: Callable) -> Callable:
     return _mark(training_setup)
 
 
+def _with_hip_densify(name: str) -> Callable:
+    """make() for ``GaussianModel.add_densification_stats`` / ``densify_and_prune``: the method of that name in autovfx_amd.densify,
+    imported (torch, libgsr_hip.so) at the first call; it runs ``reference_<name>`` itself for the calls its kernels do not take."""
+    def make(original: Callable) -> Callable:
+        @functools.wraps(original)
+        def method(self, *args, **kwargs):
+            if _gave_up:
+                return original(self, *args, **kwargs)
+            try:
+                ours = _load("densify", name)
+            except Exception as e:
+                _could_not_load(f"{original.__module__}.{original.__qualname__} left as the reference's: the HIP densification", e)
+                return original(self, *args, **kwargs)
+            return ours(self, *args, **kwargs)
+
+        return _mark(method)
+
+    return make
+
+
 class _Target(NamedTuple):
     leaf: str                            # the last component of the module's name
     cls: Optional[str]                   # the class in the module that owns ``attr``; None: the module itself
@@ -164,14 +191,19 @@ _TARGETS = (
     # item 8: scene/gaussian_model.py, GaussianModel.training_setup builds the training loops' Adam (:159-177)
     _Target("gaussian_model", "GaussianModel", "training_setup", _with_fused_adam, "the fused Adam step",
             needs=("training_setup", "replace_tensor_to_optimizer"), record=patched_models),
+    # item 9: the same class's densification (:399-417), rewritten around the optimizer surgery it must reproduce
+    _Target("gaussian_model", "GaussianModel", "add_densification_stats", _with_hip_densify("add_densification_stats"),
+            "the HIP densification", needs=("densification_postfix", "prune_points", "cat_tensors_to_optimizer"), record=patched_models),
+    _Target("gaussian_model", "GaussianModel", "densify_and_prune", _with_hip_densify("densify_and_prune"), "the HIP densification",
+            needs=("densification_postfix", "prune_points", "cat_tensors_to_optimizer"), record=patched_models),
 )
 
 
-def _target(name: str) -> Optional[_Target]:
-    """The row for a module of that name; this package's own modules (``autovfx_amd.gaussian_model``) are never targets."""
+def _target(name: str) -> Tuple[_Target, ...]:
+    """The rows for a module of that name; this package's own modules (``autovfx_amd.gaussian_model``) are never targets."""
     if name.startswith("autovfx_amd."):
-        return None
-    return next((t for t in _TARGETS if name == t.leaf or name.endswith("." + t.leaf)), None)
+        return ()
+    return tuple(t for t in _TARGETS if name == t.leaf or name.endswith("." + t.leaf))
 
 
 def _is_ours(value) -> bool:
@@ -193,9 +225,13 @@ def _rebind(original, ours, skip: Optional[types.ModuleType] = None) -> List[Tup
 
 
 def _patch(module: types.ModuleType) -> None:
-    """Apply the row of ``module``'s name to it, and log what was done for ``uninstall()``."""
-    t = _target(module.__name__)
-    if t is None or _gave_up:
+    """Apply every row of ``module``'s name whose ``needs`` hold to it, and log what was done for ``uninstall()``."""
+    for t in _target(module.__name__):
+        _patch_row(module, t)
+
+
+def _patch_row(module: types.ModuleType, t: _Target) -> None:
+    if _gave_up:
         return
     owner = module if t.cls is None else module.__dict__.get(t.cls)
     if t.cls is not None and not isinstance(owner, type):
@@ -237,7 +273,7 @@ class _RendererHook(importlib.abc.MetaPathFinder):
     right after the module body ran."""
 
     def find_spec(self, fullname, path=None, target=None):
-        if _target(fullname) is None:
+        if not _target(fullname):
             return None
         for finder in sys.meta_path:
             if finder is self or not hasattr(finder, "find_spec"):
@@ -271,7 +307,7 @@ def install(path: bool = True, strict: bool = True) -> None:
         _installed = _RendererHook()
         sys.meta_path.insert(0, _installed)
     for name, module in list(sys.modules.items()):
-        if module is not None and _target(name) is not None:
+        if module is not None and _target(name):
             _patch(module)
 
 

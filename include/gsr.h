@@ -42,14 +42,15 @@
 extern "C" {
 #endif
 
-/* 18: + one Adam step over many tensors (GsrAdamTensor, gsr_adam_step).
+/* 19: + densification (gsr_densify_stats, gsr_densify_plan_scratch_bytes, gsr_densify_plan, gsr_densify_apply).
+ * 18: + one Adam step over many tensors (GsrAdamTensor, gsr_adam_step).
  * 17: + structural similarity (gsr_ssim_scratch_bytes, gsr_ssim_forward, gsr_ssim_backward).
  * 16: + three nearest neighbours (gsr_knn3_scratch_bytes, gsr_knn3_mean_dist).
  * 15: + panoramas (gsr_cube_to_equirect).
  * 14 (round 6): + the compositor's input files -- gsr_png_unfilter(_batch), gsr_exr_unpack_channel, gsr_inflate_zlib_blocks, the host-side
  * gsr_png_file_* / gsr_exr_file_* readers, gsr_upload.  13: + compressed frame files (gsr_png_encode_deflate, gsr_frame_files_deflate).
  * Additions only: a binding written against 12 works unchanged apart from the version it checks. */
-#define GSR_ABI_VERSION 18
+#define GSR_ABI_VERSION 19
 
 #if defined(__GNUC__)
 #define GSR_API __attribute__((visibility("default")))
@@ -464,6 +465,54 @@ typedef struct GsrAdamTensor {
     float bias2_sqrt;    /* fl(sqrt(1 - beta2^t)) */
 } GsrAdamTensor;
 GSR_API int gsr_adam_step(const GsrAdamTensor* tensors, int count, float w, float b2, float c, float eps, void* stream);
+
+/* Densification of the reference's training loops (scene/gaussian_model.py:339-417) -- ABI 19, DESIGN.md §7e.  All pointers are device
+ * memory unless the name says host; every call enqueues on `stream` only (no host synchronisation, no float atomics), writes every
+ * output element it owns, returns 0 and touches nothing for n == 0, and refuses (GSR_ERR_INVALID_ARG, nothing launched, no device
+ * needed) a null or misaligned pointer (4 bytes for fp32 / int32 arrays, 256 for scratch), n < 0, n >= 2^31 and too little scratch.
+ *
+ * gsr_densify_stats: add_densification_stats (:415-417) in one launch.  For every i < n with filter[i] != 0 (one byte each):
+ *   accum[i] <- accum[i] + sqrt(fl(gx gx) + fl(gy gy)),  denom[i] <- denom[i] + 1,  gx, gy = grad[i * grad_row_floats + 0, 1]
+ * (torch.norm over a last dimension of 2 as PyTorch-ROCm rounds it), and, when radii (int32) and max_radii are both given,
+ * max_radii[i] <- max(max_radii[i], float(radii[i])); both null skips that.  grad_row_floats >= 2.
+ *
+ * gsr_densify_plan: densify_and_prune (:399-411) for max_grad > 0 as classes of the n source rows and their places in the result.
+ * With g = accum/denom (NaN -> 0), big = max(exp(scaling[i,0..2])) (a NaN wins), pruned = sigmoid(opacity[i]) < min_opacity ||
+ * (ws_test && big > ws_bound):  clone = sqrt(g g) >= max_grad && big <= dense_bound,  split = g >= max_grad && big > dense_bound.
+ * Outputs: counts[0] = K rows kept as they are (not split, not pruned), counts[1] = C clones that survive, counts[2] = S split
+ * parents, counts[3] = 0;  src_of[0..K) the kept rows and src_of[K..K+C) the cloned rows, split_idx[0..S) the parents, each in
+ * ascending source order.  src_of: room for 2 n, split_idx for n.  The scalars are the reference's Python doubles rounded to fp32.
+ * scratch: gsr_densify_plan_scratch_bytes(n) bytes (0 for an n the call refuses), any content.  Three launches; the prefix sums are
+ * this library's own, without spinning.
+ *
+ * gsr_densify_apply: ONE launch that writes the n_out rows of up to GSR_DENSIFY_MAX_TENSORS output tensors.  tensors, plan: HOST
+ * memory, read during the call.  Row j of dst is, for j < n_keep, row src_of[j] of src; for j < n_front, the same for a parameter
+ * and zeros for a moment; from n_front on, child c = child_rows[j - n_front] (0 <= c < 2 n_split, copy-major as repeat(2, 1) lays
+ * them out): zeros for a moment, row c of `side` when side is given (the children's xyz and scaling, computed by the caller), and
+ * otherwise row split_idx[c mod n_split] of src.  An index outside its source reads as zeros instead of out of bounds.
+ * floats_per_row == 0 tensors are skipped.  Refused in addition: count outside 1..GSR_DENSIFY_MAX_TENSORS, negative or unordered
+ * sizes (0 <= n_keep <= n_front <= n_out < 2^31), n_out floats_per_row >= 2^40. */
+GSR_API int gsr_densify_stats(int64_t n, const float* grad, int grad_row_floats, const uint8_t* filter, float* accum, float* denom,
+                              const int32_t* radii, float* max_radii, void* stream);
+GSR_API size_t gsr_densify_plan_scratch_bytes(int64_t n);
+GSR_API int gsr_densify_plan(int64_t n, const float* accum, const float* denom, const float* scaling, const float* opacity,
+                             float max_grad, float dense_bound, float min_opacity, int ws_test, float ws_bound, int32_t* src_of,
+                             int32_t* split_idx, int32_t* counts, void* scratch, size_t scratch_bytes, void* stream);
+#define GSR_DENSIFY_MAX_TENSORS 18
+typedef struct GsrDensifyTensor {
+    const float* src;
+    float* dst;
+    const float* side;     /* nullable */
+    int32_t floats_per_row;
+    int32_t is_moment;
+} GsrDensifyTensor;
+typedef struct GsrDensifyPlan {
+    int64_t n_src, n_keep, n_front, n_out, n_split;
+    const int32_t* src_of;       /* n_front entries */
+    const int32_t* child_rows;   /* n_out - n_front entries; may be null when there are none */
+    const int32_t* split_idx;    /* n_split entries; may be null when n_split == 0 */
+} GsrDensifyPlan;
+GSR_API int gsr_densify_apply(const GsrDensifyTensor* tensors, int count, const GsrDensifyPlan* plan, void* stream);
 
 /* The elementwise work of the reference's per-frame render() around its two rasterizer passes
  * (sugar/gaussian_splatting/gaussian_renderer/__init__.py:118-146,169-208), as two kernels instead of ~40 framework
