@@ -25,7 +25,7 @@ GEOM_SLOTS = ("raster", "rgb", "splat_bins", "internal_radii", "depth_order", "p
 BIN_SLOTS = ("point_list", "tile_keys")
 IMG_SLOTS = ("ranges", "n_contrib")
 STAGES = ("preprocess", "depth_sort", "scan", "duplicate", "tile_sort", "ranges", "blend", "colour")
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 
 class PngFileInfo(ctypes.Structure):
@@ -78,7 +78,8 @@ SYMBOLS = ("gsr_forward", "gsr_mark_visible", "gsr_backward", "gsr_last_geom_off
            "gsr_forward_begin", "gsr_forward_finish", "gsr_forward_ready", "gsr_forward_cancel", "gsr_last_slab_pairs", "gsr_plan_slabs", "gsr_selftest_lds_atomic_order", "gsr_get_backward_times", "gsr_place_object",
            "gsr_forward_raw", "gsr_forward_raw_begin", "gsr_backward_raw", "gsr_place_object_subset", "gsr_cube_to_equirect",
            "gsr_knn3_scratch_bytes", "gsr_knn3_mean_dist", "gsr_ssim_scratch_bytes", "gsr_ssim_forward", "gsr_ssim_backward",
-           "gsr_adam_step", "gsr_densify_stats", "gsr_densify_plan_scratch_bytes", "gsr_densify_plan", "gsr_densify_apply")
+           "gsr_adam_step", "gsr_densify_stats", "gsr_densify_plan_scratch_bytes", "gsr_densify_plan", "gsr_densify_apply",
+           "gsr_knn_points_scratch_bytes", "gsr_knn_points")
 OPT_TILE_CULL = 0
 OPT_SLABS = 1
 OPT_SLAB_FIRST = 2
@@ -226,6 +227,10 @@ def _load() -> ctypes.CDLL:
     lib.gsr_knn3_scratch_bytes.argtypes = [ctypes.c_uint32]
     lib.gsr_knn3_mean_dist.restype = ctypes.c_int
     lib.gsr_knn3_mean_dist.argtypes = [ctypes.c_uint32, c_f, c_f, c_f, ctypes.c_size_t, ctypes.c_void_p]
+    lib.gsr_knn_points_scratch_bytes.restype = ctypes.c_size_t
+    lib.gsr_knn_points_scratch_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int]
+    lib.gsr_knn_points.restype = ctypes.c_int
+    lib.gsr_knn_points.argtypes = [ctypes.c_int64, c_f, ctypes.c_int64, c_f, ctypes.c_int, c_f, c_f, c_f, ctypes.c_size_t, ctypes.c_void_p]
     c_i, c_p = ctypes.c_int, ctypes.c_void_p
     lib.gsr_ssim_scratch_bytes.restype = ctypes.c_size_t
     lib.gsr_ssim_scratch_bytes.argtypes = [c_i, c_i, c_i, c_i]

@@ -697,6 +697,33 @@ int gsr_knn3_mean_dist(uint32_t n, const float* points, float* out, void* scratc
     return GSR_OK;
 }
 
+size_t gsr_knn_points_scratch_bytes(int64_t n1, int64_t n2, int same) {
+    if (n1 < 0 || n2 < 0 || n1 >= (int64_t)gsr::kKnn3MaxPoints || n2 >= (int64_t)gsr::kKnn3MaxPoints) return 0;
+    return gsr::knn_points_scratch_bytes((uint32_t)n1, (uint32_t)n2, same != 0);
+}
+
+int gsr_knn_points(int64_t n1, const float* p1, int64_t n2, const float* p2, int K, float* dists, int64_t* idx, void* scratch,
+                   size_t scratch_bytes, void* stream_) {
+    if (n1 < 0 || n2 < 0) return fail(GSR_ERR_INVALID_ARG, "gsr_knn_points: negative count (n1 %lld, n2 %lld)", (long long)n1, (long long)n2);
+    if (n1 >= (int64_t)gsr::kKnn3MaxPoints || n2 >= (int64_t)gsr::kKnn3MaxPoints)
+        return fail(GSR_ERR_INVALID_ARG, "gsr_knn_points: %lld and %lld points (at most 2^30 - 1 each)", (long long)n1, (long long)n2);
+    if (K < 1 || K > gsr::kKnnPointsMaxK) return fail(GSR_ERR_INVALID_ARG, "gsr_knn_points: K = %d (1 to %d)", K, gsr::kKnnPointsMaxK);
+    if (n1 == 0) return GSR_OK;
+    if (n2 < K) return fail(GSR_ERR_INVALID_ARG, "gsr_knn_points: n2 = %lld is less than K = %d", (long long)n2, K);
+    if (!p1 || !p2 || !dists || !idx || !scratch) return fail(GSR_ERR_INVALID_ARG, "gsr_knn_points: null pointer");
+    // K = 4, 8, 16 rows are written with 16-byte stores; every other K element by element
+    const bool wide = K == 4 || K == 8 || K == 16;
+    if (((uintptr_t)p1 & 3u) != 0u || ((uintptr_t)p2 & 3u) != 0u || ((uintptr_t)dists & (wide ? 15u : 3u)) != 0u ||
+        ((uintptr_t)idx & (wide ? 15u : 7u)) != 0u || ((uintptr_t)scratch & 255u) != 0u)
+        return fail(GSR_ERR_INVALID_ARG, "gsr_knn_points: misaligned pointer (p1 / p2: 4 bytes; dists / idx: 16 bytes for K = 4, 8, 16, "
+                                         "else 4 / 8 bytes; scratch: 256 bytes)");
+    const size_t need = gsr_knn_points_scratch_bytes(n1, n2, p1 == p2 && n1 == n2);
+    if (scratch_bytes < need) return fail(GSR_ERR_INVALID_ARG, "gsr_knn_points: scratch too small (%zu of %zu bytes)", scratch_bytes, need);
+    GSR_HIP(gsr::launch_knn_points((uint32_t)n1, p1, (uint32_t)n2, p2, K, dists, reinterpret_cast<long long*>(idx), scratch,
+                                   (hipStream_t)stream_));
+    return GSR_OK;
+}
+
 namespace {
 // the sizes gsr_ssim_* accept: every dimension > 0, n c h w < 2^31
 bool ssim_size_ok(int n, int c, int h, int w) {

@@ -481,6 +481,13 @@ struct KnnLayout {
 KnnLayout knn3_layout(uint32_t n);
 // gsr.h: gsr_knn3_mean_dist; scratch: knn3_layout(n).bytes bytes, 256-byte aligned, any content; 0 < n < 2^30
 hipError_t launch_knn3_mean_dist(uint32_t n, const float* points, float* out, void* scratch, hipStream_t stream);
+// gsr.h: gsr_knn_points; the same tree over p2, K <= kKnnPointsMaxK slots per query.  same = (p1 == p2 && n1 == n2): the tree's own
+// leaves are the queries.  scratch: knn_points_scratch_bytes(n1, n2, same) bytes, 256-byte aligned; dists / idx 16-byte aligned for K = 4, 8, 16 (4 / 8 bytes otherwise);
+// 0 < K <= n2 < 2^30, n1 < 2^30
+constexpr int kKnnPointsMaxK = 16;
+size_t knn_points_scratch_bytes(uint32_t n1, uint32_t n2, bool same);
+hipError_t launch_knn_points(uint32_t n1, const float* p1, uint32_t n2, const float* p2, int K, float* dists, long long* idx, void* scratch,
+                             hipStream_t stream);
 
 // ---- the compositor's input files (gsr_layerio.hip) ----
 // The inflated IDAT stream of an 8-bit RGB / RGBA, non-interlaced PNG (device memory) -> RGBA8 [H,W,4] (alpha 255 for RGB).

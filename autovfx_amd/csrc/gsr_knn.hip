@@ -1,4 +1,5 @@
-// gsr_knn.hip -- the mean squared distance of every point to its three nearest neighbours (include/gsr.h: gsr_knn3_mean_dist).
+// gsr_knn.hip -- the mean squared distance of every point to its three nearest neighbours (include/gsr.h: gsr_knn3_mean_dist), and
+// the K nearest neighbours of every query with their indices (gsr_knn_points, further down: the same tree and walk, K slots).
 //
 // The drop-in for simple_knn's distCUDA2 (sugar/gaussian_splatting/submodules/simple-knn), which GaussianModel.create_from_pcd uses
 // to give every Gaussian its initial scale.  The result is a pointwise function of the input ("Nearest neighbours"):
@@ -286,6 +287,135 @@ __global__ __launch_bounds__(256) void knn_search_kernel(uint32_t n, const float
     }
 }
 
+// ---- K nearest neighbours with indices (gsr.h: gsr_knn_points) ----
+// A row is the K smallest candidates in ascending (d, j) order, j the index in p2: equal distances go by the lower index, so the
+// result is a pointwise function of the input for duplicates and lattices as well.  The self is a candidate like any other.
+
+// (d, j) < (sd, sj), lexicographic
+__device__ __forceinline__ bool slot_less(float d, uint32_t j, float sd, uint32_t sj) { return d < sd || (d == sd && j < sj); }
+
+// The slots stay sorted ascending; a candidate that is not below the last slot changes nothing.  Slot numbers are compile-time
+// constants after unrolling, so the arrays live in registers.
+template <int S>
+__device__ __forceinline__ void insert_slots(float d, uint32_t j, float (&sd)[S], uint32_t (&sj)[S]) {
+    bool below = slot_less(d, j, sd[S - 1], sj[S - 1]);   // below slot k
+#pragma unroll
+    for (int k = S - 1; k >= 1; --k) {
+        const bool below_prev = slot_less(d, j, sd[k - 1], sj[k - 1]);
+        sd[k] = below_prev ? sd[k - 1] : (below ? d : sd[k]);
+        sj[k] = below_prev ? sj[k - 1] : (below ? j : sj[k]);
+        below = below_prev;
+    }
+    sd[0] = below ? d : sd[0];
+    sj[0] = below ? j : sj[0];
+}
+
+// `cnt` candidates of a leaf in LDS against every lane's slots.  A distance that is not below FLT_MAX (NaN, inf) becomes the empty
+// slot's own value (FLT_MAX, ~0), which is below no slot.  Most candidates enter nobody's row: one ballot skips their insertion.
+template <int S>
+__device__ __forceinline__ void scan_leaf(const float4* leaf, int cnt, const Query& q, float (&sd)[S], uint32_t (&sj)[S]) {
+    for (int c = 0; c < cnt; ++c) {
+        const float4 cand = leaf[c];
+        float d = sq_dist(cand, q.x, q.y, q.z);
+        const bool ok = d < FLT_MAX;
+        d = ok ? d : FLT_MAX;
+        const uint32_t j = ok ? __float_as_uint(cand.w) : ~0u;
+        if (__ballot(q.active && slot_less(d, j, sd[S - 1], sj[S - 1])) == 0ull) continue;
+        insert_slots<S>(d, j, sd, sj);
+    }
+}
+
+// One wave per 64 queries, one lane per query, S = 4, 8 or 16 slots for K <= S neighbours.  The first S - K slots hold (-inf, 0),
+// below every candidate and never displaced, so the K-th best is always slot S - 1: the prune threshold and the early-out need
+// no run-time slot number.  kSelf: the queries are the tree's own points (queries == packed, n1 == n2); a wave takes the points of
+// its leaf and seeds its slots from that leaf, which the walk then leaves out.  Otherwise `queries` is p1 in the order of its
+// Morton codes on p2's grid, and nothing is seeded.
+// Prune rule: a box is skipped only when its bound is strictly above the lane's K-th slot for every lane; at equality a member
+// with a lower index could still enter (push_children and the re-test below both say !(lb > kth)).
+template <int S, bool kSelf>
+__global__ __launch_bounds__(256) void knn_points_search_kernel(uint32_t n1, const float4* __restrict__ queries, uint32_t n2,
+                                                                const float4* __restrict__ packed, KnnTree tree, int K,
+                                                                float* __restrict__ dists, long long* __restrict__ idx) {
+    __shared__ float4 s_leaf[4][kLeaf];
+    __shared__ uint32_t s_stack[4][kStackDepth];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t group = blockIdx.x * 4u + (uint32_t)wave;    // this wave's 64 queries; kSelf: its leaf
+    if (group * kLeaf >= n1) return;
+    float4* leaf = s_leaf[wave];
+    uint32_t* stack = s_stack[wave];
+    const uint32_t s = group * kLeaf + lane;
+    const float4 p = s < n1 ? queries[s] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    Query q;
+    q.active = s < n1 && finite3(p.x, p.y, p.z);
+    q.x = q.active ? p.x : 0.0f; q.y = q.active ? p.y : 0.0f; q.z = q.active ? p.z : 0.0f;
+    float sd[S];
+    uint32_t sj[S];
+#pragma unroll
+    for (int k = 0; k < S; ++k) {
+        const bool spare = k < S - K;
+        sd[k] = spare ? -INFINITY : FLT_MAX;
+        sj[k] = spare ? 0u : ~0u;
+    }
+    const uint32_t own = kSelf ? group : ~0u;   // (~0: no leaf is left out of the walk)
+    if (kSelf) {
+        leaf[lane] = p;
+        wave_sync();
+        scan_leaf<S>(leaf, (int)min((uint32_t)kLeaf, n2 - group * kLeaf), q, sd, sj);
+    }
+
+    if (__ballot(q.active) != 0ull) {
+        float4 wlo = make_float4(wave_min(q.active ? q.x : INFINITY), wave_min(q.active ? q.y : INFINITY),
+                                 wave_min(q.active ? q.z : INFINITY), 0.0f);
+        float4 whi = make_float4(wave_max(q.active ? q.x : -INFINITY), wave_max(q.active ? q.y : -INFINITY),
+                                 wave_max(q.active ? q.z : -INFINITY), 0.0f);
+        int top = 0;
+        push_children(tree, tree.top, 0u, (int)tree.count[tree.top], own, q, sd[S - 1], wlo, whi, stack, top, lane);
+        while (top > 0) {
+            const uint32_t e = (uint32_t)__builtin_amdgcn_readfirstlane((int)stack[--top]);
+            const int level = (int)(e >> 29);
+            const uint32_t node = e & ((1u << 29) - 1u);
+            if (level > 0) {
+                const uint32_t first = node * kFan;
+                push_children(tree, level - 1, first, (int)min((uint32_t)kFan, tree.count[level - 1] - first), own, q, sd[S - 1], wlo,
+                              whi, stack, top, lane);
+                continue;
+            }
+            const float4 lo = tree.boxes[2 * (size_t)node], hi = tree.boxes[2 * (size_t)node + 1];   // (leaves: level offset 0)
+            const float lb = box_bound(lo, hi, q.x, q.y, q.z);
+            if (__ballot(q.active && !(lb > sd[S - 1])) == 0ull) continue;    // the slots have tightened since the push
+            const uint32_t base = node * kLeaf;
+            const int cnt = (int)min((uint32_t)kLeaf, n2 - base);
+            wave_sync();
+            leaf[lane] = lane < cnt ? packed[base + lane] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            wave_sync();
+            scan_leaf<S>(leaf, cnt, q, sd, sj);
+        }
+    }
+    if (s >= n1) return;
+    // the row of the query's original index: empty slots (all of them for a non-finite query) are (+inf, -1)
+    float od[S];
+    long long oj[S];
+#pragma unroll
+    for (int k = 0; k < S; ++k) {
+        const bool filled = q.active && sd[k] < FLT_MAX;
+        od[k] = filled ? sd[k] : INFINITY;
+        oj[k] = filled ? (long long)sj[k] : -1ll;
+    }
+    const size_t row = (size_t)__float_as_uint(p.w) * (size_t)K;
+    if (K == S) {   // whole rows of 4 S and 8 S bytes, 16-byte aligned: 16-byte stores
+        float4* drow = reinterpret_cast<float4*>(dists + row);
+        longlong2* irow = reinterpret_cast<longlong2*>(idx + row);
+#pragma unroll
+        for (int k = 0; k < S; k += 4) drow[k / 4] = make_float4(od[k], od[k + 1], od[k + 2], od[k + 3]);
+#pragma unroll
+        for (int k = 0; k < S; k += 2) irow[k / 2] = make_longlong2(oj[k], oj[k + 1]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < S; ++k)
+            if (k >= S - K) { dists[row + (size_t)(k - (S - K))] = od[k]; idx[row + (size_t)(k - (S - K))] = oj[k]; }
+    }
+}
+
 constexpr size_t kAlign = 256;
 size_t align_up(size_t v) { return (v + kAlign - 1) & ~(kAlign - 1); }
 
@@ -317,41 +447,101 @@ KnnLayout knn3_layout(uint32_t n) {
     return L;
 }
 
-hipError_t launch_knn3_mean_dist(uint32_t n, const float* points, float* out, void* scratch, hipStream_t stream) {
-    if (n == 0) return hipSuccess;
-    KnnLayout L = knn3_layout(n);
-    if (L.tree.count[L.tree.top] > (uint32_t)kFan) return hipErrorInvalidValue;   // (n < 2^30 never gets here)
-    char* base = static_cast<char*>(scratch);
-    uint32_t* keys = reinterpret_cast<uint32_t*>(base + L.keys);
-    uint32_t* keys_alt = reinterpret_cast<uint32_t*>(base + L.keys_alt);
-    uint32_t* vals = reinterpret_cast<uint32_t*>(base + L.vals);
-    uint32_t* vals_alt = reinterpret_cast<uint32_t*>(base + L.vals_alt);
-    float4* packed = reinterpret_cast<float4*>(base + L.packed);
-    float4* boxes = reinterpret_cast<float4*>(base + L.boxes);
-    float4* partials = reinterpret_cast<float4*>(base + L.partials);
+namespace {
 
-    uint32_t* key_hi = reinterpret_cast<uint32_t*>(base + L.key_hi);
-    hipLaunchKernelGGL(knn_bounds_kernel, dim3(kBoundsBlocks), dim3(256), 0, stream, n, points, partials);
+struct KnnRegions {
+    uint32_t *keys, *keys_alt, *vals, *vals_alt, *key_hi, *radix;
+    float4 *packed, *boxes, *partials;
+};
+KnnRegions knn_regions(const KnnLayout& L, void* scratch) {
+    char* base = static_cast<char*>(scratch);
+    auto u32 = [&](size_t at) { return reinterpret_cast<uint32_t*>(base + at); };
+    auto f4 = [&](size_t at) { return reinterpret_cast<float4*>(base + at); };
+    return {u32(L.keys), u32(L.keys_alt), u32(L.vals), u32(L.vals_alt), u32(L.key_hi), u32(L.radix), f4(L.packed), f4(L.boxes), f4(L.partials)};
+}
+
+// `points` in the order of their Morton codes on the grid of `partials`, packed into r.packed with the boxes of every 64 in r.boxes
+hipError_t knn_sort_and_pack(uint32_t n, const float* points, const float4* partials, const KnnRegions& r, hipStream_t stream) {
     const uint32_t blocks = (n + 255u) / 256u;
-    hipLaunchKernelGGL(knn_codes_kernel, dim3(min(blocks, 2048u)), dim3(256), 0, stream, n, points, (const float4*)partials, keys, key_hi);
+    hipLaunchKernelGGL(knn_codes_kernel, dim3(min(blocks, 2048u)), dim3(256), 0, stream, n, points, partials, r.keys, r.key_hi);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     // the 63-bit codes, least significant word first (both sorts are stable)
-    uint32_t* rscratch = reinterpret_cast<uint32_t*>(base + L.radix);
     uint32_t *ks = nullptr, *vs = nullptr;
-    e = radix_sort_pairs(rscratch, n, 32, keys, keys_alt, vals, vals_alt, true, false, &ks, &vs, stream);
+    e = radix_sort_pairs(r.radix, n, 32, r.keys, r.keys_alt, r.vals, r.vals_alt, true, false, &ks, &vs, stream);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(knn_gather_kernel, dim3(blocks), dim3(256), 0, stream, n, (const uint32_t*)vs, (const uint32_t*)key_hi, keys);
-    e = radix_sort_pairs(rscratch, n, 32, keys, keys_alt, vs, vs == vals ? vals_alt : vals, false, false, &ks, &vs, stream);
+    hipLaunchKernelGGL(knn_gather_kernel, dim3(blocks), dim3(256), 0, stream, n, (const uint32_t*)vs, (const uint32_t*)r.key_hi, r.keys);
+    e = radix_sort_pairs(r.radix, n, 32, r.keys, r.keys_alt, vs, vs == r.vals ? r.vals_alt : r.vals, false, false, &ks, &vs, stream);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(knn_pack_kernel, dim3(blocks), dim3(256), 0, stream, n, points, (const uint32_t*)vs, packed, boxes);
+    hipLaunchKernelGGL(knn_pack_kernel, dim3(blocks), dim3(256), 0, stream, n, points, (const uint32_t*)vs, r.packed, r.boxes);
+    return hipGetLastError();
+}
+
+// bounds -> codes -> sort -> pack -> levels: the tree over `points` in the regions of L
+hipError_t knn_build_tree(uint32_t n, const float* points, const KnnLayout& L, const KnnRegions& r, hipStream_t stream) {
+    if (L.tree.count[L.tree.top] > (uint32_t)kFan) return hipErrorInvalidValue;   // (n < 2^30 never gets here)
+    hipLaunchKernelGGL(knn_bounds_kernel, dim3(kBoundsBlocks), dim3(256), 0, stream, n, points, r.partials);
+    hipError_t e = knn_sort_and_pack(n, points, r.partials, r, stream);
+    if (e != hipSuccess) return e;
     for (int level = 1; level <= L.tree.top; ++level)
         hipLaunchKernelGGL(knn_level_kernel, dim3((L.tree.count[level] + 255u) / 256u), dim3(256), 0, stream, L.tree.count[level],
-                           L.tree.count[level - 1], (const float4*)(boxes + 2 * (size_t)L.tree.offset[level - 1]),
-                           boxes + 2 * (size_t)L.tree.offset[level]);
+                           L.tree.count[level - 1], (const float4*)(r.boxes + 2 * (size_t)L.tree.offset[level - 1]),
+                           r.boxes + 2 * (size_t)L.tree.offset[level]);
+    return hipGetLastError();
+}
+
+template <int S>
+void launch_points_search(bool same, uint32_t n1, const float4* queries, uint32_t n2, const float4* packed, const KnnTree& tree, int K,
+                          float* dists, long long* idx, hipStream_t stream) {
+    const dim3 grid(((n1 + kLeaf - 1) / kLeaf + 3u) / 4u);
+    if (same)
+        hipLaunchKernelGGL((knn_points_search_kernel<S, true>), grid, dim3(256), 0, stream, n1, queries, n2, packed, tree, K, dists, idx);
+    else
+        hipLaunchKernelGGL((knn_points_search_kernel<S, false>), grid, dim3(256), 0, stream, n1, queries, n2, packed, tree, K, dists, idx);
+}
+
+}  // namespace
+
+hipError_t launch_knn3_mean_dist(uint32_t n, const float* points, float* out, void* scratch, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    const KnnLayout L = knn3_layout(n);
+    const KnnRegions r = knn_regions(L, scratch);
+    hipError_t e = knn_build_tree(n, points, L, r, stream);
+    if (e != hipSuccess) return e;
     KnnTree tree = L.tree;
-    tree.boxes = boxes;
-    hipLaunchKernelGGL(knn_search_kernel, dim3((L.tree.count[0] + 3u) / 4u), dim3(256), 0, stream, n, (const float4*)packed, tree, out);
+    tree.boxes = r.boxes;
+    hipLaunchKernelGGL(knn_search_kernel, dim3((L.tree.count[0] + 3u) / 4u), dim3(256), 0, stream, n, (const float4*)r.packed, tree, out);
+    return hipGetLastError();
+}
+
+// The tree's regions, then (a separate query set) the same regions again for p1: its codes, their sort, the packed queries.
+size_t knn_points_scratch_bytes(uint32_t n1, uint32_t n2, bool same) {
+    return knn3_layout(n2).bytes + (same ? 0 : knn3_layout(n1).bytes);
+}
+
+hipError_t launch_knn_points(uint32_t n1, const float* p1, uint32_t n2, const float* p2, int K, float* dists, long long* idx, void* scratch,
+                             hipStream_t stream) {
+    if (n1 == 0) return hipSuccess;
+    if (n2 == 0 || K < 1 || K > kKnnPointsMaxK) return hipErrorInvalidValue;
+    const bool same = p1 == p2 && n1 == n2;
+    const KnnLayout L = knn3_layout(n2);
+    const KnnRegions r = knn_regions(L, scratch);
+    hipError_t e = knn_build_tree(n2, p2, L, r, stream);
+    if (e != hipSuccess) return e;
+    const float4* queries = r.packed;
+    if (!same) {   // p1 on p2's grid (cells clamped: a query may lie outside the bounds), so that a wave's queries are neighbours
+        // (the regions of a tree over n1 points, for the sorts and the packed queries; the pack kernel also leaves the boxes of every
+        // 64 queries there, a by-product nobody reads -- the search forms its wave's box itself -- and `partials` stays unused)
+        const KnnRegions rq = knn_regions(knn3_layout(n1), static_cast<char*>(scratch) + L.bytes);
+        e = knn_sort_and_pack(n1, p1, r.partials, rq, stream);
+        if (e != hipSuccess) return e;
+        queries = rq.packed;
+    }
+    KnnTree tree = L.tree;
+    tree.boxes = r.boxes;
+    if (K <= 4) launch_points_search<4>(same, n1, queries, n2, r.packed, tree, K, dists, idx, stream);
+    else if (K <= 8) launch_points_search<8>(same, n1, queries, n2, r.packed, tree, K, dists, idx, stream);
+    else launch_points_search<16>(same, n1, queries, n2, r.packed, tree, K, dists, idx, stream);
     return hipGetLastError();
 }
 

@@ -45,7 +45,13 @@ AutoVFX reaches the rasterizer through two imports (paths under the reference tr
    runs ``GaussianModel.reference_<name>``.  The inline ``max_radii2D`` line of the loops cannot be reached by a hook and stays.
    torch and the library are imported at the first call.
 
-Items 2-9 are the rows of ``_TARGETS``, applied by ``_patch`` to every matching module, whether it was imported before
+10. a module named ``...knn`` that defines ``knn_points`` and ``knn_gather`` (``pytorch3d/ops/knn.py``; this repository ships no
+    ``pytorch3d``) gets its ``knn_points`` replaced by ``autovfx_amd.knn.drop_in(<the original>)``: the HIP search for CUDA float32
+    ``[N, P, 3]`` calls with ``K <= 16`` (SuGaR's neighbour searches, ``sugar_model.py:233``, ``:899``, ``:914``, ``:1213``, gradients
+    included), the original for every other call (the 2-D one of ``sugar_extractors/refined_mesh.py:147``); ``pytorch3d.ops.knn_points``
+    and every module that did ``from pytorch3d.ops import knn_points`` are rebound.
+
+Items 2-10 are the rows of ``_TARGETS``, applied by ``_patch`` to every matching module, whether it was imported before
 ``install()`` or after (a ``sys.meta_path`` hook).  Each replaced attribute keeps the reference's original next to it as
 ``reference_<attr>`` on the module or class (``<module>.reference_render``, ``SceneRepresentation.reference_render_from_3DGS``, ...).
 ``uninstall()`` undoes every patch in reverse.
@@ -69,7 +75,7 @@ from typing import Callable, List, NamedTuple, Optional, Tuple
 
 _REPO_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _installed: Optional["_RendererHook"] = None
-patched_modules: List[str] = []          # names of the modules patched by items 2-7 (introspection / tests)
+patched_modules: List[str] = []          # names of the modules patched by items 2-7 and 10 (introspection / tests)
 patched_models: List[str] = []           # names of the modules whose ``GaussianModel.training_setup`` was wrapped (item 8)
 _strict = True                           # install(strict=...): may a failure to load the render path break the importing process?
 _gave_up = False                         # lenient mode: a replacement could not be loaded once; patch nothing more
@@ -196,6 +202,9 @@ _TARGETS = (
             "the HIP densification", needs=("densification_postfix", "prune_points", "cat_tensors_to_optimizer"), record=patched_models),
     _Target("gaussian_model", "GaussianModel", "densify_and_prune", _with_hip_densify("densify_and_prune"), "the HIP densification",
             needs=("densification_postfix", "prune_points", "cat_tensors_to_optimizer"), record=patched_models),
+    # item 10: pytorch3d/ops/knn.py, knn_points() of SuGaR's neighbour searches (sugar_model.py:233, :899, :914, :1213)
+    _Target("knn", None, "knn_points", lambda original: _mark(_load("knn", "drop_in")(original)), "the HIP k-nearest-neighbour search",
+            needs=("knn_points", "knn_gather"), rebind=True),
 )
 
 

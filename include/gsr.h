@@ -42,7 +42,8 @@
 extern "C" {
 #endif
 
-/* 19: + densification (gsr_densify_stats, gsr_densify_plan_scratch_bytes, gsr_densify_plan, gsr_densify_apply).
+/* 20: + K nearest neighbours with indices (gsr_knn_points_scratch_bytes, gsr_knn_points).
+ * 19: + densification (gsr_densify_stats, gsr_densify_plan_scratch_bytes, gsr_densify_plan, gsr_densify_apply).
  * 18: + one Adam step over many tensors (GsrAdamTensor, gsr_adam_step).
  * 17: + structural similarity (gsr_ssim_scratch_bytes, gsr_ssim_forward, gsr_ssim_backward).
  * 16: + three nearest neighbours (gsr_knn3_scratch_bytes, gsr_knn3_mean_dist).
@@ -50,7 +51,7 @@ extern "C" {
  * 14 (round 6): + the compositor's input files -- gsr_png_unfilter(_batch), gsr_exr_unpack_channel, gsr_inflate_zlib_blocks, the host-side
  * gsr_png_file_* / gsr_exr_file_* readers, gsr_upload.  13: + compressed frame files (gsr_png_encode_deflate, gsr_frame_files_deflate).
  * Additions only: a binding written against 12 works unchanged apart from the version it checks. */
-#define GSR_ABI_VERSION 19
+#define GSR_ABI_VERSION 20
 
 #if defined(__GNUC__)
 #define GSR_API __attribute__((visibility("default")))
@@ -418,6 +419,22 @@ GSR_API int gsr_radix_sort_pairs(uint32_t n, int bits, uint32_t* keys, uint32_t*
  * no device-to-host copy. */
 GSR_API size_t gsr_knn3_scratch_bytes(uint32_t n);
 GSR_API int gsr_knn3_mean_dist(uint32_t n, const float* points, float* out, void* scratch, size_t scratch_bytes, void* stream);
+
+/* K nearest neighbours with indices (pytorch3d.ops.knn_points as SuGaR calls it, sugar_model.py:233, :899, :914, :1213) -- ABI 20.
+ * p1 [n1,3], p2 [n2,3] fp32 -> dists [n1,K] fp32, idx [n1,K] int64.  Row i holds the K smallest candidates in ascending (d, j) order,
+ * equal distances by the lower index; the candidates of query i are every j in 0 .. n2-1 with d(i, j) < FLT_MAX,
+ * d(i, j) = fl(fl(fl(dx dx) + fl(dy dy)) + fl(dz dz)), dx = fl(p2[j].x - p1[i].x).  The self is not excluded (p1 == p2 gives it first,
+ * at 0); NaN, inf and FLT_MAX distances never qualify; a row with fewer than K candidates ends in (+inf, -1).  An exact search: the
+ * result does not depend on the traversal.  p1 == p2 with n1 == n2 is the self query: no second sort.
+ * scratch: gsr_knn_points_scratch_bytes(n1, n2, same) bytes of device memory (about 37 per point of p2, and of p1 unless same),
+ * 256-byte aligned, any content; 0 for a count outside 0 .. 2^30 - 1.  n1 == 0 succeeds without touching anything.  Refused
+ * (GSR_ERR_INVALID_ARG, nothing launched): K outside 1..16, n2 < K, a negative count, a count >= 2^30, a null pointer, misaligned
+ * pointers (p1 / p2: 4 bytes; dists / idx: 16 bytes for K = 4, 8, 16, whose rows are written with 16-byte stores, else 4 / 8 bytes;
+ * scratch: 256), too little scratch.  Enqueues on `stream` only: no host
+ * synchronisation, no device-to-host copy, no atomics. */
+GSR_API size_t gsr_knn_points_scratch_bytes(int64_t n1, int64_t n2, int same);
+GSR_API int gsr_knn_points(int64_t n1, const float* p1, int64_t n2, const float* p2, int K, float* dists, int64_t* idx, void* scratch,
+                           size_t scratch_bytes, void* stream);
 
 /* Structural similarity (the training loops' loss_utils.ssim, loss_utils.py:33-62, window 11, sigma 1.5) -- ABI 17.
  * x, y: [n,c,h,w] fp32, contiguous, device memory.  Per plane, zero-padded outside the image: mx = w*x, my = w*y, Exx = w*x^2,
