@@ -79,7 +79,7 @@ SYMBOLS = ("gsr_forward", "gsr_mark_visible", "gsr_backward", "gsr_last_geom_off
            "gsr_forward_raw", "gsr_forward_raw_begin", "gsr_backward_raw", "gsr_place_object_subset", "gsr_cube_to_equirect",
            "gsr_knn3_scratch_bytes", "gsr_knn3_mean_dist", "gsr_ssim_scratch_bytes", "gsr_ssim_forward", "gsr_ssim_backward",
            "gsr_adam_step", "gsr_densify_stats", "gsr_densify_plan_scratch_bytes", "gsr_densify_plan", "gsr_densify_apply",
-           "gsr_knn_points_scratch_bytes", "gsr_knn_points")
+           "gsr_knn_points_scratch_bytes", "gsr_knn_points", "gsr_field_scratch_bytes", "gsr_field_forward", "gsr_field_backward")
 OPT_TILE_CULL = 0
 OPT_SLABS = 1
 OPT_SLAB_FIRST = 2
@@ -231,6 +231,13 @@ def _load() -> ctypes.CDLL:
     lib.gsr_knn_points_scratch_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int]
     lib.gsr_knn_points.restype = ctypes.c_int
     lib.gsr_knn_points.argtypes = [ctypes.c_int64, c_f, ctypes.c_int64, c_f, ctypes.c_int, c_f, c_f, c_f, ctypes.c_size_t, ctypes.c_void_p]
+    lib.gsr_field_scratch_bytes.restype = ctypes.c_size_t
+    lib.gsr_field_scratch_bytes.argtypes = [ctypes.c_int64]
+    field_inputs = [ctypes.c_int64, ctypes.c_int, ctypes.c_int64, c_f, c_f, c_f, c_f, c_f, c_f, ctypes.c_float]   # n K P x idx centers M strengths min_scaling factor
+    lib.gsr_field_forward.restype = ctypes.c_int
+    lib.gsr_field_forward.argtypes = field_inputs + [c_f, c_f, c_f, c_f, ctypes.c_size_t, ctypes.c_void_p]   # density opacities beta scratch bytes stream
+    lib.gsr_field_backward.restype = ctypes.c_int
+    lib.gsr_field_backward.argtypes = field_inputs + [c_f, c_f, c_f, c_f, c_f, c_f, ctypes.c_size_t, ctypes.c_void_p]   # g_density g_opacities g_beta dx accum scratch bytes stream
     c_i, c_p = ctypes.c_int, ctypes.c_void_p
     lib.gsr_ssim_scratch_bytes.restype = ctypes.c_size_t
     lib.gsr_ssim_scratch_bytes.argtypes = [c_i, c_i, c_i, c_i]

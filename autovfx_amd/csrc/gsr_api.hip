@@ -724,6 +724,57 @@ int gsr_knn_points(int64_t n1, const float* p1, int64_t n2, const float* p2, int
     return GSR_OK;
 }
 
+size_t gsr_field_scratch_bytes(int64_t P) {
+    return (P < 0 || P >= (int64_t)gsr::kKnn3MaxPoints) ? 0 : gsr::field_scratch_bytes(P);
+}
+
+namespace {
+// What gsr_field_forward and gsr_field_backward check alike; 1: n == 0, nothing to do.
+int field_check(const char* who, const gsr::FieldInputs& in, bool wants_beta, const void* scratch, size_t scratch_bytes) {
+    if (in.K < 1 || in.K > gsr::kFieldMaxK) return fail(GSR_ERR_INVALID_ARG, "%s: K = %d (1 to %d)", who, in.K, gsr::kFieldMaxK);
+    if (in.n < 0 || in.P < 0) return fail(GSR_ERR_INVALID_ARG, "%s: negative count (n %lld, P %lld)", who, (long long)in.n, (long long)in.P);
+    if (in.n >= (int64_t)gsr::kKnn3MaxPoints || in.P >= (int64_t)gsr::kKnn3MaxPoints)
+        return fail(GSR_ERR_INVALID_ARG, "%s: %lld samples and %lld Gaussians (at most 2^30 - 1 each)", who, (long long)in.n, (long long)in.P);
+    if (in.n == 0) return 1;
+    if (!in.x || !in.idx || !scratch || (in.P > 0 && (!in.centers || !in.M || !in.strengths)))
+        return fail(GSR_ERR_INVALID_ARG, "%s: null pointer", who);
+    if (wants_beta && !in.min_scaling) return fail(GSR_ERR_INVALID_ARG, "%s: beta needs min_scaling", who);
+    if ((((uintptr_t)in.x | (uintptr_t)in.centers | (uintptr_t)in.M | (uintptr_t)in.strengths | (uintptr_t)in.min_scaling) & 3u) != 0u ||
+        ((uintptr_t)in.idx & 7u) != 0u || ((uintptr_t)scratch & 255u) != 0u)
+        return fail(GSR_ERR_INVALID_ARG, "%s: misaligned pointer (floats: 4 bytes, idx: 8, scratch: 256)", who);
+    const size_t need = gsr::field_scratch_bytes(in.P);
+    if (scratch_bytes < need) return fail(GSR_ERR_INVALID_ARG, "%s: scratch too small (%zu of %zu bytes)", who, scratch_bytes, need);
+    return GSR_OK;
+}
+}  // namespace
+
+int gsr_field_forward(int64_t n, int K, int64_t P, const float* x, const int64_t* idx, const float* centers, const float* M,
+                      const float* strengths, const float* min_scaling, float density_factor, float* density, float* opacities, float* beta,
+                      void* scratch, size_t scratch_bytes, void* stream_) {
+    const gsr::FieldInputs in{n, K, P, x, reinterpret_cast<const long long*>(idx), centers, M, strengths, min_scaling, density_factor};
+    const int rc = field_check("gsr_field_forward", in, beta != nullptr, scratch, scratch_bytes);
+    if (rc != GSR_OK) return rc == 1 ? GSR_OK : rc;
+    if (!density) return fail(GSR_ERR_INVALID_ARG, "gsr_field_forward: null pointer");
+    if ((((uintptr_t)density | (uintptr_t)opacities | (uintptr_t)beta) & 3u) != 0u)
+        return fail(GSR_ERR_INVALID_ARG, "gsr_field_forward: misaligned pointer (density / opacities / beta: 4 bytes)");
+    GSR_HIP(gsr::launch_field_forward(in, density, opacities, beta, scratch, (hipStream_t)stream_));
+    return GSR_OK;
+}
+
+int gsr_field_backward(int64_t n, int K, int64_t P, const float* x, const int64_t* idx, const float* centers, const float* M,
+                       const float* strengths, const float* min_scaling, float density_factor, const float* g_density,
+                       const float* g_opacities, const float* g_beta, float* dx, float* accum, void* scratch, size_t scratch_bytes,
+                       void* stream_) {
+    const gsr::FieldInputs in{n, K, P, x, reinterpret_cast<const long long*>(idx), centers, M, strengths, min_scaling, density_factor};
+    const int rc = field_check("gsr_field_backward", in, g_beta != nullptr, scratch, scratch_bytes);
+    if (rc != GSR_OK) return rc == 1 ? GSR_OK : rc;
+    if (!accum && P > 0) return fail(GSR_ERR_INVALID_ARG, "gsr_field_backward: null pointer");
+    if ((((uintptr_t)g_density | (uintptr_t)g_opacities | (uintptr_t)g_beta | (uintptr_t)dx) & 3u) != 0u || ((uintptr_t)accum & 63u) != 0u)
+        return fail(GSR_ERR_INVALID_ARG, "gsr_field_backward: misaligned pointer (gradients: 4 bytes, accum: 64)");
+    GSR_HIP(gsr::launch_field_backward(in, g_density, g_opacities, g_beta, dx, accum, scratch, (hipStream_t)stream_));
+    return GSR_OK;
+}
+
 namespace {
 // the sizes gsr_ssim_* accept: every dimension > 0, n c h w < 2^31
 bool ssim_size_ok(int n, int c, int h, int w) {

@@ -489,6 +489,25 @@ size_t knn_points_scratch_bytes(uint32_t n1, uint32_t n2, bool same);
 hipError_t launch_knn_points(uint32_t n1, const float* p1, uint32_t n2, const float* p2, int K, float* dists, long long* idx, void* scratch,
                              hipStream_t stream);
 
+// ---- SuGaR's density field over a neighbour list (gsr_field.hip; gsr.h: gsr_field_forward, gsr_field_backward) ----
+constexpr int kFieldMaxK = 64;
+struct FieldInputs {
+    int64_t n;                   // samples, 0 < n < 2^30
+    int K;                       // neighbour slots per sample, 1 .. kFieldMaxK
+    int64_t P;                   // Gaussians, 0 <= P < 2^30
+    const float* x;              // [n,3]
+    const long long* idx;        // [n,K]; a slot outside [0, P) is skipped
+    const float *centers, *M, *strengths, *min_scaling;   // [P,3], [P,3,3], [P], [P] or null
+    float density_factor;
+};
+// scratch: field_scratch_bytes(P) bytes (one 64-byte record per Gaussian), 256-byte aligned, any content; both calls fill it themselves.
+size_t field_scratch_bytes(int64_t P);
+hipError_t launch_field_forward(const FieldInputs& in, float* density, float* opacities, float* beta, void* scratch, hipStream_t stream);
+// accum [P,16], zeroed by the caller, 64-byte aligned: floats 0-2 of a line dL/dcentre, 3-11 dL/dM row-major, 12 dL/dstrength,
+// 13 dL/dmin_scaling.
+hipError_t launch_field_backward(const FieldInputs& in, const float* g_density, const float* g_opacities, const float* g_beta, float* dx,
+                                 float* accum, void* scratch, hipStream_t stream);
+
 // ---- the compositor's input files (gsr_layerio.hip) ----
 // The inflated IDAT stream of an 8-bit RGB / RGBA, non-interlaced PNG (device memory) -> RGBA8 [H,W,4] (alpha 255 for RGB).
 // scratch: png_unfilter_scratch_bytes(W, H) bytes, 16-byte aligned (0: the width is not supported).

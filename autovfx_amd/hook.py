@@ -51,7 +51,14 @@ AutoVFX reaches the rasterizer through two imports (paths under the reference tr
     included), the original for every other call (the 2-D one of ``sugar_extractors/refined_mesh.py:147``); ``pytorch3d.ops.knn_points``
     and every module that did ``from pytorch3d.ops import knn_points`` are rebound.
 
-Items 2-10 are the rows of ``_TARGETS``, applied by ``_patch`` to every matching module, whether it was imported before
+11. the same ``...sugar_model`` module, when its ``SuGaR`` defines ``compute_density``, ``get_field_values``, ``get_beta`` and
+    ``get_covariance``, gets the first two (``sugar_model.py:1216-1239``, ``:1118-1187``: the density field of the regulariser, 1 M samples
+    x 16 neighbours per iteration, and of the mesh extraction) replaced by ``autovfx_amd.field``'s drop-ins: inputs built as the
+    reference builds them, the gather / 3x3 product / ``exp`` / sum over the neighbours and their backward in two HIP kernels, what
+    follows the sum in the reference's arithmetic; ``return_sdf_grad=True``, CPU tensors and other dtypes run
+    ``SuGaR.reference_<name>``.  torch and the library are imported at the first call.
+
+Items 2-11 are the rows of ``_TARGETS``, applied by ``_patch`` to every matching module, whether it was imported before
 ``install()`` or after (a ``sys.meta_path`` hook).  Each replaced attribute keeps the reference's original next to it as
 ``reference_<attr>`` on the module or class (``<module>.reference_render``, ``SceneRepresentation.reference_render_from_3DGS``, ...).
 ``uninstall()`` undoes every patch in reverse.
@@ -75,7 +82,7 @@ from typing import Callable, List, NamedTuple, Optional, Tuple
 
 _REPO_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _installed: Optional["_RendererHook"] = None
-patched_modules: List[str] = []          # names of the modules patched by items 2-7 and 10 (introspection / tests)
+patched_modules: List[str] = []          # names of the modules patched by items 2-7, 10 and 11 (introspection / tests)
 patched_models: List[str] = []           # names of the modules whose ``GaussianModel.training_setup`` was wrapped (item 8)
 _strict = True                           # install(strict=...): may a failure to load the render path break the importing process?
 _gave_up = False                         # lenient mode: a replacement could not be loaded once; patch nothing more
@@ -168,6 +175,29 @@ def _with_hip_densify(name: str) -> Callable:
     return make
 
 
+def _with_hip_field(name: str) -> Callable:
+    """make() for ``SuGaR.compute_density`` / ``get_field_values``: ``autovfx_amd.field.drop_in_<name>(original)``, built (torch,
+    libgsr_hip.so) at the first call; it runs ``original`` itself for the calls its kernels do not take."""
+    def make(original: Callable) -> Callable:
+        built = []
+
+        @functools.wraps(original)
+        def method(self, *args, **kwargs):
+            if not built:
+                if _gave_up:
+                    return original(self, *args, **kwargs)
+                try:
+                    built.append(_load("field", "drop_in_" + name)(original))
+                except Exception as e:
+                    _could_not_load(f"{original.__module__}.{original.__qualname__} left as the reference's: the HIP density field", e)
+                    return original(self, *args, **kwargs)
+            return built[0](self, *args, **kwargs)
+
+        return _mark(method)
+
+    return make
+
+
 class _Target(NamedTuple):
     leaf: str                            # the last component of the module's name
     cls: Optional[str]                   # the class in the module that owns ``attr``; None: the module itself
@@ -205,6 +235,11 @@ _TARGETS = (
     # item 10: pytorch3d/ops/knn.py, knn_points() of SuGaR's neighbour searches (sugar_model.py:233, :899, :914, :1213)
     _Target("knn", None, "knn_points", lambda original: _mark(_load("knn", "drop_in")(original)), "the HIP k-nearest-neighbour search",
             needs=("knn_points", "knn_gather"), rebind=True),
+    # item 11: sugar/sugar_scene/sugar_model.py, SuGaR's density field (:1118-1187, :1216-1239)
+    _Target("sugar_model", "SuGaR", "compute_density", _with_hip_field("compute_density"), "the HIP density field",
+            needs=("compute_density", "get_field_values", "get_beta", "get_covariance")),
+    _Target("sugar_model", "SuGaR", "get_field_values", _with_hip_field("get_field_values"), "the HIP density field",
+            needs=("compute_density", "get_field_values", "get_beta", "get_covariance")),
 )
 
 

@@ -42,7 +42,9 @@
 extern "C" {
 #endif
 
-/* 20: + K nearest neighbours with indices (gsr_knn_points_scratch_bytes, gsr_knn_points).
+/* Still 20: + SuGaR's density field (gsr_field_scratch_bytes, gsr_field_forward, gsr_field_backward).  They only add symbols
+ * behind the existing ones, so the version a binding checks did not move.
+ * 20: + K nearest neighbours with indices (gsr_knn_points_scratch_bytes, gsr_knn_points).
  * 19: + densification (gsr_densify_stats, gsr_densify_plan_scratch_bytes, gsr_densify_plan, gsr_densify_apply).
  * 18: + one Adam step over many tensors (GsrAdamTensor, gsr_adam_step).
  * 17: + structural similarity (gsr_ssim_scratch_bytes, gsr_ssim_forward, gsr_ssim_backward).
@@ -435,6 +437,34 @@ GSR_API int gsr_knn3_mean_dist(uint32_t n, const float* points, float* out, void
 GSR_API size_t gsr_knn_points_scratch_bytes(int64_t n1, int64_t n2, int same);
 GSR_API int gsr_knn_points(int64_t n1, const float* p1, int64_t n2, const float* p2, int K, float* dists, int64_t* idx, void* scratch,
                            size_t scratch_bytes, void* stream);
+
+/* SuGaR's density field over a neighbour list (SuGaR.get_field_values, sugar_model.py:1118-1187, and SuGaR.compute_density,
+ * :1216-1239) -- added under ABI 20.  x [n,3], idx [n,K] int64, centers [P,3], M [P,3,3] row-major (the inverse scaled rotation,
+ * get_covariance(return_full_matrix=True, return_sqrt=True, inverse_scales=True)), strengths [P], min_scaling [P] or NULL, all fp32.
+ * Per sample i and slot k with j = idx[i,k], in plain fp32, left to right, nothing contracted:
+ *   s = x_i - c_j;  w_a = (M_j[0][a] s_0 + M_j[1][a] s_1) + M_j[2][a] s_2;  q = clamp((w_0 w_0 + w_1 w_1) + w_2 w_2, 0, 1e8);
+ *   o = (density_factor strengths[j]) expf(-0.5 q);  density[i] = sum_k o;  beta[i] = (sum_k min_scaling[j]) / K   (k ascending, from 0).
+ * A slot with j outside [0, P) is skipped (gsr_knn_points writes -1 for a missing one): it adds 0 to both sums, its opacity is 0, it
+ * receives no gradient and nothing is read for it.  Outputs: density [n]; opacities [n,K] and beta [n] when not NULL.
+ * gsr_field_backward takes the same inputs and the upstream gradients g_density [n], g_opacities [n,K], g_beta [n] (each may be NULL =
+ * zeros), recomputes w, q and expf, and with G = g_density[i] + g_opacities[i,k]:
+ *   dstrength_j += (G density_factor) e;  dq = (-0.5 G) o, 0 where q lay strictly outside [0, 1e8] before the clamp;  dw_a = (2 w_a) dq;
+ *   ds_b = (M_j[b][0] dw_0 + M_j[b][1] dw_1) + M_j[b][2] dw_2;  dx_i += ds;  dc_j -= ds;  dM_j[b][a] += s_b dw_a;  dmin_scaling_j += g_beta[i] / K.
+ * dx [n,3] (may be NULL) is written whole.  The per-Gaussian sums are ADDED with float atomics into accum [P,16], which the caller
+ * zeroes: floats 0-2 of a Gaussian's line are dL/dcenters, 3-11 dL/dM row-major, 12 dL/dstrengths, 13 dL/dmin_scaling, 14-15 unused.
+ * Their last bits depend on the order the adds arrive in.
+ * scratch: gsr_field_scratch_bytes(P) bytes (64 per Gaussian), 256-byte aligned, any content, filled by each call for itself; 0 for a
+ * P outside 0 .. 2^30 - 1.  n == 0 succeeds without touching anything.  Refused (GSR_ERR_INVALID_ARG, nothing launched): K outside 1..64,
+ * a negative count, a count >= 2^30, a null required pointer, misaligned pointers (floats 4 bytes, idx 8, accum 64, scratch 256), beta or
+ * g_beta without min_scaling, too little scratch.  Both enqueue on `stream` only: no host synchronisation, no allocation. */
+GSR_API size_t gsr_field_scratch_bytes(int64_t P);
+GSR_API int gsr_field_forward(int64_t n, int K, int64_t P, const float* x, const int64_t* idx, const float* centers, const float* M,
+                              const float* strengths, const float* min_scaling, float density_factor, float* density, float* opacities,
+                              float* beta, void* scratch, size_t scratch_bytes, void* stream);
+GSR_API int gsr_field_backward(int64_t n, int K, int64_t P, const float* x, const int64_t* idx, const float* centers, const float* M,
+                               const float* strengths, const float* min_scaling, float density_factor, const float* g_density,
+                               const float* g_opacities, const float* g_beta, float* dx, float* accum, void* scratch, size_t scratch_bytes,
+                               void* stream);
 
 /* Structural similarity (the training loops' loss_utils.ssim, loss_utils.py:33-62, window 11, sigma 1.5) -- ABI 17.
  * x, y: [n,c,h,w] fp32, contiguous, device memory.  Per plane, zero-padded outside the image: mx = w*x, my = w*y, Exx = w*x^2,
