@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+from typing import Optional
 
 # PyTorch first, always: its wheel carries its own libamdhip64 / libhsa-runtime64, and the library below asks the loader for
 # "libamdhip64.so.7" by name.  Loaded after torch it binds to the runtime torch already brought in -- one HIP runtime in the
@@ -70,16 +71,6 @@ DENSIFY_MAX_TENSORS = 18
 MAX_SLABS = 8
 FORWARD_INFERENCE = 1
 
-# every symbol include/gsr.h declares
-SYMBOLS = ("gsr_forward", "gsr_mark_visible", "gsr_backward", "gsr_last_geom_offsets", "gsr_last_binning_offsets",
-           "gsr_last_image_offsets", "gsr_set_stage_timing", "gsr_get_stage_times", "gsr_last_error",
-           "gsr_abi_version", "gsr_target_arch", "gsr_set_option", "gsr_get_option", "gsr_pack_rgba8", "gsr_png_size", "gsr_png_room", "gsr_png_encode", "gsr_frame_files", "gsr_png_deflate_max_size", "gsr_png_deflate_room", "gsr_png_deflate_scratch", "gsr_png_encode_deflate", "gsr_frame_files_deflate", "gsr_resize_rgba8_bilinear", "gsr_resize_f32_nearest", "gsr_png_unfilter_scratch", "gsr_png_unfilter", "gsr_png_unfilter_batch", "gsr_exr_unpack_channel", "gsr_upload", "gsr_png_file_probe", "gsr_png_file_inflate", "gsr_exr_file_probe", "gsr_exr_file_inflate", "gsr_selftest_inflate_host", "gsr_exr_file_pack", "gsr_inflate_zlib_blocks", "gsr_last_pair_counts", "gsr_blend", "gsr_composite",
-           "gsr_radix_scratch_bytes", "gsr_radix_sort_pairs", "gsr_selftest_exp", "gsr_view_normals", "gsr_normal_maps", "gsr_forward_extra", "gsr_get_call_times",
-           "gsr_forward_begin", "gsr_forward_finish", "gsr_forward_ready", "gsr_forward_cancel", "gsr_last_slab_pairs", "gsr_plan_slabs", "gsr_selftest_lds_atomic_order", "gsr_get_backward_times", "gsr_place_object",
-           "gsr_forward_raw", "gsr_forward_raw_begin", "gsr_backward_raw", "gsr_place_object_subset", "gsr_cube_to_equirect",
-           "gsr_knn3_scratch_bytes", "gsr_knn3_mean_dist", "gsr_ssim_scratch_bytes", "gsr_ssim_forward", "gsr_ssim_backward",
-           "gsr_adam_step", "gsr_densify_stats", "gsr_densify_plan_scratch_bytes", "gsr_densify_plan", "gsr_densify_apply",
-           "gsr_knn_points_scratch_bytes", "gsr_knn_points", "gsr_field_scratch_bytes", "gsr_field_forward", "gsr_field_backward")
 OPT_TILE_CULL = 0
 OPT_SLABS = 1
 OPT_SLAB_FIRST = 2
@@ -103,6 +94,142 @@ class GsrLibraryError(ImportError):
     pass
 
 
+# ---- every function include/gsr.h declares: name -> (restype, argtypes), in the header's order ----------------------------------------
+_i, _u, _u32, _i64, _f, _sz = ctypes.c_int, ctypes.c_uint, ctypes.c_uint32, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t
+_p, _s = ctypes.c_void_p, ctypes.c_char_p    # _p: device float* / int* travel as integers (tensor.data_ptr()); _s: host bytes
+
+
+def _array(ctype, n):
+    """A host array of ``n`` values, passed with ``ctypes.byref``: ``ctype name[n]`` in the header."""
+    return ctypes.POINTER(ctype * n)
+
+
+_arenas = [ALLOC_FN, _p, ALLOC_FN, _p, ALLOC_FN, _p]   # geom_alloc geom_user binning_alloc binning_user image_alloc image_user
+_camera = [_p, _p, _p, _f, _f]                         # viewmatrix projmatrix cam_pos tan_fovx tan_fovy
+_forward = _arenas + [
+    _i, _i, _i,                                        # P D M
+    _p, _i, _i,                                        # background width height
+    _p, _p, _p, _p, _p, _f, _p, _p,                    # means3D shs colors_precomp opacities scales scale_modifier rotations cov3D_precomp
+    *_camera, _i,                                      # ... prefiltered
+    _p, _p, _p, _p]                                    # out_color out_depth out_alpha radii
+_forward_extra = _forward + [_p, _p, _u, _i, _p]       # extra_features out_extra flags debug stream
+_forward_raw = _arenas + [
+    _i, _i, _i,                                        # P D M
+    _p, _i, _i,                                        # background width height
+    ctypes.POINTER(RawParams), _f,                     # raw scale_modifier
+    *_camera, _i,                                      # ... prefiltered
+    _p, _p, _p, _p, _p, _u, _i, _p]                    # out_color out_depth out_alpha radii out_normal flags debug stream
+_png_dims = [_i, _i, _i]                               # width height channels
+_frame_files = [_p, _p, _p, _p, _f, _p, _i, _i,        # color alpha depth normal depth_scale turbo_lut width height
+                _p, _p, _p, _p, _p]                    # png_rgba png_depth_preview png_normal npy_plane work
+_field_inputs = [_i64, _i, _i64, _p, _p, _p, _p, _p, _p, _f]   # n K P x idx centers M strengths min_scaling density_factor
+_placed = [_p, _p, _p, _p, _p, _p, _p]                 # out_means3D out_scales out_rotations out_opacities out_shs out_min_axis stream
+_backward_head = [_i, _i, _i, _i, _p, _i, _i]          # P D M R background width height
+_backward_arenas = [_p, _p, _p, _p]                    # radii geom_buffer binning_buffer image_buffer
+
+SIGNATURES = {
+    # the forward pass
+    "gsr_forward": (_i, _forward + [_i, _p]),          # ... debug stream
+    "gsr_forward_extra": (_i, _forward_extra),
+    "gsr_forward_begin": (_p, _forward_extra),
+    "gsr_forward_finish": (_i, [_p]),                  # call
+    "gsr_forward_ready": (_i, [_p]),
+    "gsr_forward_cancel": (None, [_p]),
+    "gsr_forward_raw": (_i, _forward_raw),
+    "gsr_forward_raw_begin": (_p, _forward_raw),
+    "gsr_mark_visible": (_i, [_i, _p, _p, _p, _p, _p]),                # P means3D viewmatrix projmatrix present stream
+    "gsr_blend": (_i, [_p, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p]),   # geom binning image width height features background out_color out_depth out_alpha stream
+    # the compositor and the frame files
+    "gsr_composite": (_i, [_i, _i] + [_p] * 12 + [_p]),                # width height bg_c o_c o_d s_c s_d o_s_c o_gs_c o_gs_d s_f_c s_f_d s_f_c_pre out stream
+    "gsr_pack_rgba8": (_i, [_p, _p, _p, _i, _i, _p]),                  # color alpha rgba8 width height stream
+    "gsr_png_size": (_sz, _png_dims),
+    "gsr_png_room": (_sz, _png_dims),
+    "gsr_frame_files": (_i, _frame_files + [_p]),                      # ... stream
+    "gsr_png_encode": (_i, [_p, _i, _i, _i, _i, _p, _p]),              # pixels width height channels planar out stream
+    "gsr_png_deflate_max_size": (_sz, _png_dims),
+    "gsr_png_deflate_room": (_sz, _png_dims),
+    "gsr_png_deflate_scratch": (_sz, _png_dims),
+    "gsr_png_encode_deflate": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p]),   # pixels width height channels planar out scratch out_len stream
+    "gsr_frame_files_deflate": (_i, _frame_files + [_p, _p, _p]),      # ... png_scratch png_lengths stream
+    "gsr_cube_to_equirect": (_i, [ctypes.POINTER(_p), _i, _i, ctypes.POINTER(_p),   # faces face_size channels depth_faces
+                                  _p, _p, _p, _i, _i, _p, _p, _p, _p]),             # grid_u grid_v grid_ceil height width out out_u8 out_depth stream
+    "gsr_resize_rgba8_bilinear": (_i, [_p, _i, _i, _p, _i, _i, _p, _p]),   # src src_width src_height dst dst_width dst_height tmp stream
+    "gsr_resize_f32_nearest": (_i, [_p, _i, _i, _p, _i, _i, _p]),          # src src_width src_height dst dst_width dst_height stream
+    # the compositor's input files
+    "gsr_png_unfilter_scratch": (_sz, [_i, _i]),                       # width height
+    "gsr_png_unfilter": (_i, [_p, _i, _i, _i, _p, _p, _p]),            # scanlines width height channels out_rgba scratch stream
+    "gsr_png_unfilter_batch": (_i, [_i, _p, _p]),                      # count jobs stream
+    "gsr_exr_unpack_channel": (_i, [_p, _i, _i, _i, _i, _i, _p, _p]),  # blocks height bytes_per_line lines_per_block channel_at channel_bytes plane stream
+    "gsr_upload": (_i, [_p, _s, _sz, _p]),                             # device_dst host_src bytes stream
+    "gsr_png_file_probe": (_i, [_s, _sz, _p]),                         # file file_bytes info
+    "gsr_png_file_inflate": (_i, [_s, _sz, _p, _sz]),                  # file file_bytes scanlines scanline_bytes
+    "gsr_exr_file_probe": (_i, [_s, _sz, _s, _p]),                     # file file_bytes channel info
+    "gsr_exr_file_inflate": (_i, [_s, _sz, _s, _p, _sz]),              # file file_bytes channel blocks blocks_bytes
+    "gsr_exr_file_pack": (_i, [_s, _sz, _s, _p, _sz, _p, _p]),         # file file_bytes channel packed packed_room jobs packed_bytes
+    "gsr_inflate_zlib_blocks": (_i, [_p, _p, _p, _i, _p, _p, _p]),     # streams out jobs count status any_error stream
+    "gsr_selftest_inflate_host": (_i, [_s, _sz, _p, _sz]),             # zlib_stream stream_bytes out out_bytes
+    # sorting and nearest neighbours
+    "gsr_radix_scratch_bytes": (_sz, [_u32, _i]),                      # n bits
+    "gsr_radix_sort_pairs": (_i, [_u32, _i, _p, _p, _p, _p, _i, _p,    # n bits keys keys_alt vals vals_alt iota_payload scratch
+                                  _sz, ctypes.POINTER(_i), _p]),       # scratch_bytes sorted_in_alt stream
+    "gsr_knn3_scratch_bytes": (_sz, [_u32]),                           # n
+    "gsr_knn3_mean_dist": (_i, [_u32, _p, _p, _p, _sz, _p]),           # n points out scratch scratch_bytes stream
+    "gsr_knn_points_scratch_bytes": (_sz, [_i64, _i64, _i]),           # n1 n2 same
+    "gsr_knn_points": (_i, [_i64, _p, _i64, _p, _i, _p, _p, _p, _sz, _p]),   # n1 p1 n2 p2 K dists idx scratch scratch_bytes stream
+    # training: the density field, SSIM, Adam, densification
+    "gsr_field_scratch_bytes": (_sz, [_i64]),                          # P
+    "gsr_field_forward": (_i, _field_inputs + [_p, _p, _p, _p, _sz, _p]),            # ... density opacities beta scratch scratch_bytes stream
+    "gsr_field_backward": (_i, _field_inputs + [_p, _p, _p, _p, _p, _p, _sz, _p]),   # ... g_density g_opacities g_beta dx accum scratch scratch_bytes stream
+    "gsr_ssim_scratch_bytes": (_sz, [_i, _i, _i, _i]),                 # n c h w
+    "gsr_ssim_forward": (_i, [_i, _i, _i, _i, _p, _p, _p, _i, _p, _p, _p, _sz, _p]),   # n c h w x y window11 per_image out coef_or_null scratch scratch_bytes stream
+    "gsr_ssim_backward": (_i, [_i, _i, _i, _i, _p, _p, _p, _p, _i, _p, _p, _p]),       # n c h w x y coef window11 per_image grad_out grad_x stream
+    "gsr_adam_step": (_i, [ctypes.POINTER(AdamTensor), _i, _f, _f, _f, _f, _p]),       # tensors count w b2 c eps stream
+    "gsr_densify_stats": (_i, [_i64, _p, _i, _p, _p, _p, _p, _p, _p]),   # n grad grad_row_floats filter accum denom radii max_radii stream
+    "gsr_densify_plan_scratch_bytes": (_sz, [_i64]),                   # n
+    "gsr_densify_plan": (_i, [_i64, _p, _p, _p, _p, _f, _f, _f, _i, _f,   # n accum denom scaling opacity max_grad dense_bound min_opacity ws_test ws_bound
+                              _p, _p, _p, _p, _sz, _p]),                  # src_of split_idx counts scratch scratch_bytes stream
+    "gsr_densify_apply": (_i, [ctypes.POINTER(DensifyTensor), _i, ctypes.POINTER(DensifyPlan), _p]),   # tensors count plan stream
+    # render()'s elementwise work, dynamic scenes, self-tests
+    "gsr_view_normals": (_i, [_i, _p, _p, _p, _p, _p]),                # P means3D axis cam_pos colors stream
+    "gsr_normal_maps": (_i, [_i, _i, _p, _p, _p, _f, _f, _f, _f, _p, _p, _p]),   # width height normal_rgb depth c2w fx fy cx cy normal pseudo_normal stream
+    "gsr_place_object": (_i, [_i, _p, _p, _p, _p, _p, _i, _array(_f, 21)] + _placed),   # n xyz rotation_raw log_scale opacity shs M placement ...
+    "gsr_place_object_subset": (_i, [_i, _p, _p, _p, _p, _p, _p, _i, _array(_f, 21)] + _placed),   # m subset xyz rotation_raw log_scale opacity shs M placement ...
+    "gsr_selftest_exp": (_i, [_u32, _u32, _p, _p]),                    # first_bits count device_mismatches stream
+    "gsr_selftest_lds_atomic_order": (_i, [_u32, _u32, _u32, _p, _p]),   # workgroups rounds seed device_mismatches stream
+    # the backward pass
+    "gsr_backward": (_i, _backward_head + [
+        _p, _p, _p, _p, _f, _p, _p,                    # means3D shs colors_precomp scales scale_modifier rotations cov3D_precomp
+        *_camera, *_backward_arenas,
+        _p, _p, _p, _p,                                # accum_alphas dL_dpix dL_dpix_depth dL_dpix_alpha
+        _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,        # dL_dmean2D conic opacity color depth mean3D cov3D sh scale rot
+        _p, _i, _p]),                                  # accum_scratch debug stream
+    "gsr_backward_raw": (_i, _backward_head + [
+        ctypes.POINTER(RawParams), _f,                 # raw scale_modifier
+        *_camera, *_backward_arenas,
+        _p, _p, _p, _p, _p,                            # accum_alphas dL_dpix dL_dpix_depth dL_dpix_alpha dL_dpix_normal
+        _p, _p, _p, _p, _p, _p, _p,                    # dL_dmean2D xyz log_scales rotations opacity_logits features_dc features_rest
+        _p, _i, _p]),                                  # accum_scratch debug stream
+    # introspection
+    "gsr_last_geom_offsets": (_i, [_array(_sz, len(GEOM_SLOTS))]),
+    "gsr_last_binning_offsets": (_i, [_array(_sz, len(BIN_SLOTS))]),
+    "gsr_last_image_offsets": (_i, [_array(_sz, len(IMG_SLOTS))]),
+    "gsr_last_pair_counts": (_i, [_array(_u32, 2)]),
+    "gsr_last_slab_pairs": (_i, [_array(_u32, MAX_SLABS)]),
+    # options, timing, identity
+    "gsr_set_option": (_i, [_i, _i]),                  # option value
+    "gsr_plan_slabs": (_i, [_u32, _i, _i, _array(_u32, MAX_SLABS)]),   # live_pairs width height cuts
+    "gsr_get_option": (_i, [_i]),
+    "gsr_set_stage_timing": (None, [_i]),              # enable
+    "gsr_get_stage_times": (_i, [_array(_f, len(STAGES))]),
+    "gsr_get_call_times": (_i, [ctypes.POINTER(_f), _i]),   # ms capacity
+    "gsr_get_backward_times": (_i, [_array(_f, 2)]),
+    "gsr_last_error": (_s, []),
+    "gsr_abi_version": (_i, []),
+    "gsr_target_arch": (_s, []),
+}
+SYMBOLS = tuple(SIGNATURES)
+
+
 def _load() -> ctypes.CDLL:
     if not os.path.exists(LIB_PATH):
         raise GsrLibraryError(
@@ -115,192 +242,9 @@ def _load() -> ctypes.CDLL:
     missing = [s for s in SYMBOLS if not hasattr(lib, s)]
     if missing:
         raise GsrLibraryError(f"{LIB_PATH} does not export {missing}; rebuild it")
-
-    c_f = ctypes.c_void_p  # device float* / int* travel as integers (tensor.data_ptr())
-    lib.gsr_forward.restype = ctypes.c_int
-    lib.gsr_forward.argtypes = [
-        ALLOC_FN, ctypes.c_void_p, ALLOC_FN, ctypes.c_void_p, ALLOC_FN, ctypes.c_void_p,
-        ctypes.c_int, ctypes.c_int, ctypes.c_int,            # P D M
-        c_f, ctypes.c_int, ctypes.c_int,                     # background width height
-        c_f, c_f, c_f, c_f, c_f, ctypes.c_float, c_f, c_f,   # means3D shs colors opacities scales mod rotations cov3D
-        c_f, c_f, c_f, ctypes.c_float, ctypes.c_float, ctypes.c_int,  # view proj campos tanx tany prefiltered
-        c_f, c_f, c_f, c_f, ctypes.c_int, ctypes.c_void_p]   # out_color out_depth out_alpha radii debug stream
-    lib.gsr_forward_extra.restype = ctypes.c_int
-    lib.gsr_forward_extra.argtypes = lib.gsr_forward.argtypes[:-2] + [c_f, c_f, ctypes.c_uint, ctypes.c_int, ctypes.c_void_p]
-    lib.gsr_forward_begin.restype = ctypes.c_void_p
-    lib.gsr_forward_begin.argtypes = lib.gsr_forward_extra.argtypes
-    lib.gsr_forward_raw.restype = ctypes.c_int
-    lib.gsr_forward_raw.argtypes = [
-        ALLOC_FN, ctypes.c_void_p, ALLOC_FN, ctypes.c_void_p, ALLOC_FN, ctypes.c_void_p,
-        ctypes.c_int, ctypes.c_int, ctypes.c_int,            # P D M
-        c_f, ctypes.c_int, ctypes.c_int,                     # background width height
-        ctypes.POINTER(RawParams), ctypes.c_float,           # raw scale_modifier
-        c_f, c_f, c_f, ctypes.c_float, ctypes.c_float, ctypes.c_int,  # view proj campos tanx tany prefiltered
-        c_f, c_f, c_f, c_f, c_f, ctypes.c_uint, ctypes.c_int, ctypes.c_void_p]   # color depth alpha radii normal flags debug stream
-    lib.gsr_forward_raw_begin.restype = ctypes.c_void_p
-    lib.gsr_forward_raw_begin.argtypes = lib.gsr_forward_raw.argtypes
-    lib.gsr_forward_finish.restype = ctypes.c_int
-    lib.gsr_forward_finish.argtypes = [ctypes.c_void_p]
-    lib.gsr_forward_ready.restype = ctypes.c_int
-    lib.gsr_forward_ready.argtypes = [ctypes.c_void_p]
-    lib.gsr_forward_cancel.restype = None
-    lib.gsr_forward_cancel.argtypes = [ctypes.c_void_p]
-    lib.gsr_mark_visible.restype = ctypes.c_int
-    lib.gsr_mark_visible.argtypes = [ctypes.c_int, c_f, c_f, c_f, c_f, ctypes.c_void_p]
-    lib.gsr_composite.restype = ctypes.c_int
-    lib.gsr_composite.argtypes = [ctypes.c_int, ctypes.c_int] + [c_f] * 12 + [ctypes.c_void_p]
-    lib.gsr_blend.restype = ctypes.c_int
-    lib.gsr_blend.argtypes = [c_f, c_f, c_f, ctypes.c_int, ctypes.c_int] + [c_f] * 5 + [ctypes.c_void_p]
-    lib.gsr_last_slab_pairs.restype = ctypes.c_int
-    lib.gsr_plan_slabs.restype = ctypes.c_int
-    lib.gsr_plan_slabs.argtypes = [ctypes.c_uint32, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_uint32 * MAX_SLABS)]
-    lib.gsr_last_slab_pairs.argtypes = [ctypes.POINTER(ctypes.c_uint32 * MAX_SLABS)]
-    lib.gsr_last_pair_counts.restype = ctypes.c_int
-    lib.gsr_last_pair_counts.argtypes = [ctypes.POINTER(ctypes.c_uint32 * 2)]
-    lib.gsr_radix_scratch_bytes.restype = ctypes.c_size_t
-    lib.gsr_radix_scratch_bytes.argtypes = [ctypes.c_uint32, ctypes.c_int]
-    lib.gsr_radix_sort_pairs.restype = ctypes.c_int
-    lib.gsr_radix_sort_pairs.argtypes = [ctypes.c_uint32, ctypes.c_int, c_f, c_f, c_f, c_f, ctypes.c_int, c_f,
-                                         ctypes.c_size_t, ctypes.POINTER(ctypes.c_int), ctypes.c_void_p]
-    lib.gsr_view_normals.restype = ctypes.c_int
-    lib.gsr_view_normals.argtypes = [ctypes.c_int, c_f, c_f, c_f, c_f, ctypes.c_void_p]
-    lib.gsr_normal_maps.restype = ctypes.c_int
-    lib.gsr_normal_maps.argtypes = [ctypes.c_int, ctypes.c_int, c_f, c_f, c_f] + [ctypes.c_float] * 4 + [c_f, c_f, ctypes.c_void_p]
-    lib.gsr_place_object.restype = ctypes.c_int
-    lib.gsr_place_object.argtypes = [ctypes.c_int, c_f, c_f, c_f, c_f, c_f, ctypes.c_int, ctypes.POINTER(ctypes.c_float * 21),
-                                     c_f, c_f, c_f, c_f, c_f, c_f, ctypes.c_void_p]
-    lib.gsr_place_object_subset.restype = ctypes.c_int
-    lib.gsr_place_object_subset.argtypes = [ctypes.c_int, c_f, c_f, c_f, c_f, c_f, c_f, ctypes.c_int, ctypes.POINTER(ctypes.c_float * 21),
-                                            c_f, c_f, c_f, c_f, c_f, c_f, ctypes.c_void_p]
-    lib.gsr_selftest_exp.restype = ctypes.c_int
-    lib.gsr_selftest_lds_atomic_order.restype = ctypes.c_int
-    lib.gsr_selftest_lds_atomic_order.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]
-    lib.gsr_selftest_exp.argtypes = [ctypes.c_uint32, ctypes.c_uint32, c_f, ctypes.c_void_p]
-    lib.gsr_pack_rgba8.restype = ctypes.c_int
-    lib.gsr_pack_rgba8.argtypes = [c_f, c_f, c_f, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
-    lib.gsr_png_size.restype = ctypes.c_size_t
-    lib.gsr_png_size.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
-    lib.gsr_png_room.restype = ctypes.c_size_t
-    lib.gsr_png_room.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
-    lib.gsr_png_encode.restype = ctypes.c_int
-    lib.gsr_png_encode.argtypes = [c_f, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_f, ctypes.c_void_p]
-    lib.gsr_png_deflate_max_size.restype = ctypes.c_size_t
-    lib.gsr_png_deflate_max_size.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
-    lib.gsr_png_deflate_room.restype = ctypes.c_size_t
-    lib.gsr_png_deflate_room.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
-    lib.gsr_png_deflate_scratch.restype = ctypes.c_size_t
-    lib.gsr_png_deflate_scratch.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
-    lib.gsr_png_encode_deflate.restype = ctypes.c_int
-    lib.gsr_png_encode_deflate.argtypes = [c_f, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_f, c_f, c_f, ctypes.c_void_p]
-    lib.gsr_frame_files_deflate.restype = ctypes.c_int
-    lib.gsr_frame_files_deflate.argtypes = [c_f, c_f, c_f, c_f, ctypes.c_float, c_f, ctypes.c_int, ctypes.c_int, c_f, c_f, c_f, c_f, c_f, c_f, c_f, ctypes.c_void_p]
-    lib.gsr_frame_files.restype = ctypes.c_int
-    lib.gsr_frame_files.argtypes = [c_f, c_f, c_f, c_f, ctypes.c_float, c_f, ctypes.c_int, ctypes.c_int, c_f, c_f, c_f, c_f, c_f, ctypes.c_void_p]
-    lib.gsr_png_unfilter_scratch.restype = ctypes.c_size_t
-    lib.gsr_png_unfilter_scratch.argtypes = [ctypes.c_int, ctypes.c_int]
-    lib.gsr_png_unfilter.restype = ctypes.c_int
-    lib.gsr_png_unfilter.argtypes = [c_f, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_f, c_f, ctypes.c_void_p]
-    lib.gsr_png_unfilter_batch.restype = ctypes.c_int
-    lib.gsr_png_unfilter_batch.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
-    lib.gsr_exr_unpack_channel.restype = ctypes.c_int
-    lib.gsr_exr_unpack_channel.argtypes = [c_f, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_f, ctypes.c_void_p]
-    lib.gsr_png_file_probe.restype = ctypes.c_int
-    lib.gsr_png_file_probe.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_void_p]
-    lib.gsr_png_file_inflate.restype = ctypes.c_int
-    lib.gsr_png_file_inflate.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t]
-    lib.gsr_exr_file_probe.restype = ctypes.c_int
-    lib.gsr_exr_file_probe.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_void_p]
-    lib.gsr_exr_file_inflate.restype = ctypes.c_int
-    lib.gsr_exr_file_inflate.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_size_t]
-    lib.gsr_exr_file_pack.restype = ctypes.c_int
-    lib.gsr_exr_file_pack.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
-    lib.gsr_inflate_zlib_blocks.restype = ctypes.c_int
-    lib.gsr_inflate_zlib_blocks.argtypes = [c_f, c_f, c_f, ctypes.c_int, c_f, c_f, ctypes.c_void_p]
-    lib.gsr_selftest_inflate_host.restype = ctypes.c_int
-    lib.gsr_selftest_inflate_host.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t]
-    lib.gsr_upload.restype = ctypes.c_int
-    lib.gsr_upload.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_void_p]
-    lib.gsr_cube_to_equirect.restype = ctypes.c_int
-    lib.gsr_cube_to_equirect.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p),
-                                         c_f, c_f, c_f, ctypes.c_int, ctypes.c_int, c_f, c_f, c_f, ctypes.c_void_p]
-    lib.gsr_knn3_scratch_bytes.restype = ctypes.c_size_t
-    lib.gsr_knn3_scratch_bytes.argtypes = [ctypes.c_uint32]
-    lib.gsr_knn3_mean_dist.restype = ctypes.c_int
-    lib.gsr_knn3_mean_dist.argtypes = [ctypes.c_uint32, c_f, c_f, c_f, ctypes.c_size_t, ctypes.c_void_p]
-    lib.gsr_knn_points_scratch_bytes.restype = ctypes.c_size_t
-    lib.gsr_knn_points_scratch_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int]
-    lib.gsr_knn_points.restype = ctypes.c_int
-    lib.gsr_knn_points.argtypes = [ctypes.c_int64, c_f, ctypes.c_int64, c_f, ctypes.c_int, c_f, c_f, c_f, ctypes.c_size_t, ctypes.c_void_p]
-    lib.gsr_field_scratch_bytes.restype = ctypes.c_size_t
-    lib.gsr_field_scratch_bytes.argtypes = [ctypes.c_int64]
-    field_inputs = [ctypes.c_int64, ctypes.c_int, ctypes.c_int64, c_f, c_f, c_f, c_f, c_f, c_f, ctypes.c_float]   # n K P x idx centers M strengths min_scaling factor
-    lib.gsr_field_forward.restype = ctypes.c_int
-    lib.gsr_field_forward.argtypes = field_inputs + [c_f, c_f, c_f, c_f, ctypes.c_size_t, ctypes.c_void_p]   # density opacities beta scratch bytes stream
-    lib.gsr_field_backward.restype = ctypes.c_int
-    lib.gsr_field_backward.argtypes = field_inputs + [c_f, c_f, c_f, c_f, c_f, c_f, ctypes.c_size_t, ctypes.c_void_p]   # g_density g_opacities g_beta dx accum scratch bytes stream
-    c_i, c_p = ctypes.c_int, ctypes.c_void_p
-    lib.gsr_ssim_scratch_bytes.restype = ctypes.c_size_t
-    lib.gsr_ssim_scratch_bytes.argtypes = [c_i, c_i, c_i, c_i]
-    lib.gsr_ssim_forward.restype = ctypes.c_int
-    lib.gsr_ssim_forward.argtypes = [c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_p, ctypes.c_size_t, c_p]
-    lib.gsr_ssim_backward.restype = ctypes.c_int
-    lib.gsr_ssim_backward.argtypes = [c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p]
-    lib.gsr_adam_step.restype = ctypes.c_int
-    lib.gsr_adam_step.argtypes = [ctypes.POINTER(AdamTensor), c_i, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, c_p]
-    c_f32, c_i64 = ctypes.c_float, ctypes.c_int64
-    lib.gsr_densify_stats.restype = ctypes.c_int
-    lib.gsr_densify_stats.argtypes = [c_i64, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p]
-    lib.gsr_densify_plan_scratch_bytes.restype = ctypes.c_size_t
-    lib.gsr_densify_plan_scratch_bytes.argtypes = [c_i64]
-    lib.gsr_densify_plan.restype = ctypes.c_int
-    lib.gsr_densify_plan.argtypes = [c_i64, c_p, c_p, c_p, c_p, c_f32, c_f32, c_f32, c_i, c_f32, c_p, c_p, c_p, c_p, ctypes.c_size_t, c_p]
-    lib.gsr_densify_apply.restype = ctypes.c_int
-    lib.gsr_densify_apply.argtypes = [ctypes.POINTER(DensifyTensor), c_i, ctypes.POINTER(DensifyPlan), c_p]
-    lib.gsr_resize_rgba8_bilinear.restype = ctypes.c_int
-    lib.gsr_resize_rgba8_bilinear.argtypes = [c_f, ctypes.c_int, ctypes.c_int, c_f, ctypes.c_int, ctypes.c_int, c_f, ctypes.c_void_p]
-    lib.gsr_resize_f32_nearest.restype = ctypes.c_int
-    lib.gsr_resize_f32_nearest.argtypes = [c_f, ctypes.c_int, ctypes.c_int, c_f, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
-    lib.gsr_backward.restype = ctypes.c_int
-    lib.gsr_backward.argtypes = [
-        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_f, ctypes.c_int, ctypes.c_int,  # P D M R bg W H
-        c_f, c_f, c_f, c_f, ctypes.c_float, c_f, c_f,          # means3D shs colors scales mod rotations cov3D
-        c_f, c_f, c_f, ctypes.c_float, ctypes.c_float,         # view proj campos tanx tany
-        c_f, c_f, c_f, c_f,                                    # radii geom binning image
-        c_f, c_f, c_f, c_f,                                    # accum_alphas dL_dpix dL_dpix_depth dL_dpix_alpha
-        c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f,      # dL_dmean2D conic opacity color depth mean3D cov3D sh scale rot
-        c_f, ctypes.c_int, ctypes.c_void_p]                    # accum_scratch debug stream
-    lib.gsr_backward_raw.restype = ctypes.c_int
-    lib.gsr_backward_raw.argtypes = [
-        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_f, ctypes.c_int, ctypes.c_int,  # P D M R bg W H
-        ctypes.POINTER(RawParams), ctypes.c_float,             # raw scale_modifier
-        c_f, c_f, c_f, ctypes.c_float, ctypes.c_float,         # view proj campos tanx tany
-        c_f, c_f, c_f, c_f,                                    # radii geom binning image
-        c_f, c_f, c_f, c_f, c_f,                               # accum_alphas dL_dpix dL_dpix_depth dL_dpix_alpha dL_dpix_normal
-        c_f, c_f, c_f, c_f, c_f, c_f, c_f,                     # dL_dmean2D xyz log_scales rotations opacity dc rest
-        c_f, ctypes.c_int, ctypes.c_void_p]                    # accum_scratch debug stream
-    for name, n in (("gsr_last_geom_offsets", len(GEOM_SLOTS)), ("gsr_last_binning_offsets", len(BIN_SLOTS)),
-                    ("gsr_last_image_offsets", len(IMG_SLOTS))):
+    for name, (restype, argtypes) in SIGNATURES.items():
         fn = getattr(lib, name)
-        fn.restype = ctypes.c_int
-        fn.argtypes = [ctypes.POINTER(ctypes.c_size_t * n)]
-    lib.gsr_set_option.restype = ctypes.c_int
-    lib.gsr_set_option.argtypes = [ctypes.c_int, ctypes.c_int]
-    lib.gsr_get_option.restype = ctypes.c_int
-    lib.gsr_get_option.argtypes = [ctypes.c_int]
-    lib.gsr_set_stage_timing.restype = None
-    lib.gsr_set_stage_timing.argtypes = [ctypes.c_int]
-    lib.gsr_get_call_times.restype = ctypes.c_int
-    lib.gsr_get_call_times.argtypes = [ctypes.POINTER(ctypes.c_float), ctypes.c_int]
-    lib.gsr_get_backward_times.restype = ctypes.c_int
-    lib.gsr_get_backward_times.argtypes = [ctypes.POINTER(ctypes.c_float * 2)]
-    lib.gsr_get_stage_times.restype = ctypes.c_int
-    lib.gsr_get_stage_times.argtypes = [ctypes.POINTER(ctypes.c_float * len(STAGES))]
-    lib.gsr_last_error.restype = ctypes.c_char_p
-    lib.gsr_last_error.argtypes = []
-    lib.gsr_abi_version.restype = ctypes.c_int
-    lib.gsr_abi_version.argtypes = []
-    lib.gsr_target_arch.restype = ctypes.c_char_p
-    lib.gsr_target_arch.argtypes = []
+        fn.restype, fn.argtypes = restype, argtypes
     if lib.gsr_abi_version() != ABI_VERSION:
         raise GsrLibraryError(f"{LIB_PATH} has ABI {lib.gsr_abi_version()}, this binding expects {ABI_VERSION}")
     return lib
@@ -308,22 +252,61 @@ def _load() -> ctypes.CDLL:
 
 lib = _load()
 
-# A/B from the shell: GSR_RADIX_RANK=0 forces the ballot rank of the radix sort, 1 the verified LDS adds, 2 = those where the
-# per-device self-test passed, 3 = with an injected inversion (test hook); unset = the library default (2).
-if os.environ.get("GSR_RADIX_RANK", "") in ("0", "1", "2", "3"):
-    lib.gsr_set_option(5, int(os.environ["GSR_RADIX_RANK"]))
-if os.environ.get("GSR_BLEND_ORDER", "") in ("0", "1"):
-    lib.gsr_set_option(OPT_BLEND_ORDER, int(os.environ["GSR_BLEND_ORDER"]))
-if os.environ.get("GSR_DEPTH_DROP", "") in ("0", "1"):
-    lib.gsr_set_option(OPT_DEPTH_DROP, int(os.environ["GSR_DEPTH_DROP"]))
-if os.environ.get("GSR_GRAD_SLABS", "") in ("0", "1"):
-    lib.gsr_set_option(OPT_GRAD_SLABS, int(os.environ["GSR_GRAD_SLABS"]))
-if os.environ.get("GSR_BACKWARD_DETERMINISTIC", "") in ("0", "1"):   # same gradient bits on every run (include/gsr.h)
-    lib.gsr_set_option(OPT_BACKWARD_DETERMINISTIC, int(os.environ["GSR_BACKWARD_DETERMINISTIC"]))
+# A/B from the shell, (variable, option, accepted values); unset or anything else = the library default.  GSR_RADIX_RANK: 0 forces the
+# ballot rank of the radix sort, 1 the verified LDS adds, 2 (the default) = those where the per-device self-test passed, 3 = with an
+# injected inversion (test hook).  GSR_BACKWARD_DETERMINISTIC=1: the same gradient bits on every run (include/gsr.h).
+ENV_OPTIONS = (("GSR_RADIX_RANK", OPT_RADIX_RANK, ("0", "1", "2", "3")),
+               ("GSR_BLEND_ORDER", OPT_BLEND_ORDER, ("0", "1")),
+               ("GSR_DEPTH_DROP", OPT_DEPTH_DROP, ("0", "1")),
+               ("GSR_GRAD_SLABS", OPT_GRAD_SLABS, ("0", "1")),
+               ("GSR_BACKWARD_DETERMINISTIC", OPT_BACKWARD_DETERMINISTIC, ("0", "1")))
+for _var, _option, _allowed in ENV_OPTIONS:
+    if os.environ.get(_var, "") in _allowed:
+        lib.gsr_set_option(_option, int(os.environ[_var]))
 
 
 def last_error() -> str:
     return lib.gsr_last_error().decode("utf-8", "replace")
+
+
+# ---- the one call path into the library ---------------------------------------------------------------------------------------
+def stream_ptr(device) -> ctypes.c_void_p:
+    """torch's current HIP stream on ``device``, as the ``void* stream`` every launching entry point ends in."""
+    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def ptr(t: Optional[torch.Tensor]) -> Optional[int]:
+    """Device pointer of a tensor, or NULL for None and for the reference's "empty tensor means absent"."""
+    return None if t is None or t.numel() == 0 else t.data_ptr()
+
+
+def capturing() -> bool:
+    """Is the current stream capturing a graph?  Never initialises the GPU: a process that has not touched it captures nothing."""
+    return torch.cuda.is_initialized() and torch.cuda.is_current_stream_capturing()
+
+
+def failure(name: str, rc) -> RuntimeError:
+    """What every failed library call raises: the entry point, what it returned and the library's own words."""
+    return RuntimeError(f"{name} failed ({rc}): {last_error()}")
+
+
+def check(name: str, rc: int) -> None:
+    if rc != 0:
+        raise failure(name, rc)
+
+
+def call(name: str, *args, device=None) -> None:
+    """One ``int``-status entry point: looked up by name at call time, ``stream_ptr(device)`` appended when a device is given, a
+    non-zero status raised with the library's message."""
+    if device is not None:
+        args += (stream_ptr(device),)
+    check(name, getattr(lib, name)(*args))
+
+
+def scratch(name: str, *size_args, device):
+    """``(uint8 tensor, nbytes)`` of device scratch sized by the ``gsr_*_scratch_bytes`` query ``name``."""
+    nbytes = int(getattr(lib, name)(*size_args))
+    return torch.empty(nbytes, dtype=torch.uint8, device=device), nbytes
 
 
 def offsets(kind: str) -> dict:

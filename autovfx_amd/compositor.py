@@ -12,7 +12,6 @@ becomes the layer's 0.001-th percentile, computed here with numpy's "linear" rul
 """
 from __future__ import annotations
 
-import ctypes
 from typing import Optional
 
 import torch
@@ -53,10 +52,7 @@ def resize_rgba8(image: torch.Tensor, size_wh, out: Optional[torch.Tensor] = Non
         out = torch.empty((H, W, 4), dtype=torch.uint8, device=src.device)
     tmp = torch.empty((Hs, W, 4), dtype=torch.uint8, device=src.device) if (Ws != W and Hs != H) else None
     with torch.cuda.device(src.device):
-        rc = _lib.lib.gsr_resize_rgba8_bilinear(src.data_ptr(), Ws, Hs, out.data_ptr(), W, H, None if tmp is None else tmp.data_ptr(),
-                                                ctypes.c_void_p(torch.cuda.current_stream(src.device).cuda_stream))
-    if rc != 0:
-        raise RuntimeError(f"gsr_resize_rgba8_bilinear failed ({rc}): {_lib.last_error()}")
+        _lib.call("gsr_resize_rgba8_bilinear", src.data_ptr(), Ws, Hs, out.data_ptr(), W, H, _lib.ptr(tmp), device=src.device)
     return out
 
 
@@ -69,10 +65,7 @@ def resize_depth(depth: torch.Tensor, size_wh, out: Optional[torch.Tensor] = Non
     if out is None:
         out = torch.empty((H, W), dtype=torch.float32, device=src.device)
     with torch.cuda.device(src.device):
-        rc = _lib.lib.gsr_resize_f32_nearest(src.data_ptr(), int(src.shape[1]), int(src.shape[0]), out.data_ptr(), W, H,
-                                             ctypes.c_void_p(torch.cuda.current_stream(src.device).cuda_stream))
-    if rc != 0:
-        raise RuntimeError(f"gsr_resize_f32_nearest failed ({rc}): {_lib.last_error()}")
+        _lib.call("gsr_resize_f32_nearest", src.data_ptr(), int(src.shape[1]), int(src.shape[0]), out.data_ptr(), W, H, device=src.device)
     return out
 
 
@@ -102,12 +95,8 @@ def composite_frame(bg_c, o_c, o_d, s_c, s_d, o_s_c, o_gs_c=None, o_gs_d=None, s
          _layer(s_f_c_pre, torch.uint8, rgba, dev, "s_f_c_pre")]
     if out is None:
         out = torch.empty(rgba, dtype=torch.uint8, device=dev)
-    ptr = lambda t: None if t is None else t.data_ptr()
     with torch.cuda.device(dev):
-        rc = _lib.lib.gsr_composite(int(W), int(H), *[ptr(t) for t in L], out.data_ptr(),
-                                    ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc != 0:
-        raise RuntimeError(f"gsr_composite failed ({rc}): {_lib.last_error()}")
+        _lib.call("gsr_composite", int(W), int(H), *[_lib.ptr(t) for t in L], out.data_ptr(), device=dev)
     return out
 
 

@@ -114,21 +114,12 @@ def stats_kernel_takes(model, viewspace_point_tensor, update_filter, capturing: 
     return all(_dense_fp32(t, device_type, grad.device) and tuple(t.shape) == (n, 1) for t in (accum, denom)) and accum is not denom
 
 
-def _capturing() -> bool:
-    return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
-
-
 def _reference(model, name: str):
     fn = getattr(type(model), "reference_" + name, None)
     if fn is None:
         raise RuntimeError(f"autovfx_amd.densify.{name}: the kernels do not take this call and {type(model).__name__} has no "
                            f"reference_{name} to run instead (autovfx_amd.install() keeps it)")
     return fn
-
-
-def _check(rc: int, what: str) -> None:
-    if rc != 0:
-        raise RuntimeError(f"{what} failed ({rc}): {_lib.last_error()}")
 
 
 # ---------------------------------------------------------------------------------------------------------------- stats
@@ -139,16 +130,14 @@ def accumulate_stats(grad: torch.Tensor, update_filter: torch.Tensor, accum: tor
     no host synchronisation.  The caller vouches for the layout (dense fp32 / bool / int32 on one GPU)."""
     n = grad.shape[0]
     with torch.cuda.device(grad.device):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(grad.device).cuda_stream)
-        _check(_lib.lib.gsr_densify_stats(n, grad.data_ptr(), grad.shape[1], update_filter.data_ptr(), accum.data_ptr(), denom.data_ptr(),
-                                          radii.data_ptr() if radii is not None else None,
-                                          max_radii.data_ptr() if max_radii is not None else None, stream), "gsr_densify_stats")
+        _lib.call("gsr_densify_stats", n, grad.data_ptr(), grad.shape[1], update_filter.data_ptr(), accum.data_ptr(), denom.data_ptr(),
+                  _lib.ptr(radii), _lib.ptr(max_radii), device=grad.device)
     torch.autograd.graph.increment_version([accum, denom] + ([max_radii] if max_radii is not None else []))
 
 
 def add_densification_stats(self, viewspace_point_tensor, update_filter):
     """``GaussianModel.add_densification_stats`` (gaussian_model.py:415-417)."""
-    if not stats_kernel_takes(self, viewspace_point_tensor, update_filter, _capturing()):
+    if not stats_kernel_takes(self, viewspace_point_tensor, update_filter, _lib.capturing()):
         return _reference(self, "add_densification_stats")(self, viewspace_point_tensor, update_filter)
     accumulate_stats(viewspace_point_tensor.grad, update_filter, self.xyz_gradient_accum, self.denom)
 
@@ -267,19 +256,16 @@ def densify_and_prune_host(self, max_grad, min_opacity, extent, max_screen_size)
 @torch.no_grad()
 def _densify_and_prune_kernels(self, b: dict, empty_cache: bool = True) -> None:
     n, device = self._xyz.shape[0], self._xyz.device
-    L = _lib.lib
     with torch.cuda.device(device):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-        scratch_bytes = L.gsr_densify_plan_scratch_bytes(n)
-        scratch = torch.empty(scratch_bytes, dtype=torch.uint8, device=device)
+        scratch, scratch_bytes = _lib.scratch("gsr_densify_plan_scratch_bytes", n, device=device)
         src_of = torch.empty(2 * n, dtype=torch.int32, device=device)
         split_idx = torch.empty(n, dtype=torch.int32, device=device)
         counts = torch.empty(4, dtype=torch.int32, device=device)
         ws = b["ws_bound"]
-        _check(L.gsr_densify_plan(n, self.xyz_gradient_accum.data_ptr(), self.denom.data_ptr(), self._scaling.data_ptr(),
-                                  self._opacity.data_ptr(), _f32(b["max_grad"]), _f32(b["dense_bound"]), _f32(b["min_opacity"]),
-                                  0 if ws is None else 1, 0.0 if ws is None else _f32(ws), src_of.data_ptr(), split_idx.data_ptr(),
-                                  counts.data_ptr(), scratch.data_ptr(), scratch_bytes, stream), "gsr_densify_plan")
+        _lib.call("gsr_densify_plan", n, self.xyz_gradient_accum.data_ptr(), self.denom.data_ptr(), self._scaling.data_ptr(),
+                  self._opacity.data_ptr(), _f32(b["max_grad"]), _f32(b["dense_bound"]), _f32(b["min_opacity"]),
+                  0 if ws is None else 1, 0.0 if ws is None else _f32(ws), src_of.data_ptr(), split_idx.data_ptr(),
+                  counts.data_ptr(), scratch.data_ptr(), scratch_bytes, device=device)
         n_keep, n_clone, n_split, _ = counts.tolist()               # the first host synchronisation: the sizes of everything below
         new_xyz, new_scaling, child_rows = _children(self, split_idx[:n_split].to(torch.int64), b)
         child_rows = child_rows.to(torch.int32)
@@ -304,7 +290,7 @@ def _densify_and_prune_kernels(self, b: dict, empty_cache: bool = True) -> None:
         if descs:
             plan = _lib.DensifyPlan(n, n_keep, n_front, n_out, n_split, src_of.data_ptr(), child_rows.data_ptr() if child_rows.numel() else None,
                                     split_idx.data_ptr())
-            _check(L.gsr_densify_apply((_lib.DensifyTensor * len(descs))(*descs), len(descs), ctypes.byref(plan), stream), "gsr_densify_apply")
+            _lib.call("gsr_densify_apply", (_lib.DensifyTensor * len(descs))(*descs), len(descs), ctypes.byref(plan), device=device)
     _install_results(self, new)
     if empty_cache:
         torch.cuda.empty_cache()
@@ -312,6 +298,6 @@ def _densify_and_prune_kernels(self, b: dict, empty_cache: bool = True) -> None:
 
 def densify_and_prune(self, max_grad, min_opacity, extent, max_screen_size):
     """``GaussianModel.densify_and_prune`` (gaussian_model.py:399-413)."""
-    if not kernel_takes(self, max_grad, min_opacity, extent, max_screen_size, _capturing()):
+    if not kernel_takes(self, max_grad, min_opacity, extent, max_screen_size, _lib.capturing()):
         return _reference(self, "densify_and_prune")(self, max_grad, min_opacity, extent, max_screen_size)
     _densify_and_prune_kernels(self, _bounds(self, max_grad, min_opacity, extent, max_screen_size))

@@ -150,7 +150,6 @@ class DynamicScene:
         means3D, scales, rotations, opacities, shs, min_axis = self._slots[slot % len(self._slots)]
         at = self.P_base
         placements = list(placements)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         with torch.cuda.device(self.device):
             for entry in placements:
                 obj_id, center, rotation, scaling = entry[:4]
@@ -163,23 +162,21 @@ class DynamicScene:
                     raise ValueError("an untransformed placement has center = rotation = scaling = None")
                 block = None if center is None else (ctypes.c_float * 21)(*placement_block(center, rotation, scaling, o.initial_center).tolist())
                 outs = (means3D[at:].data_ptr(), scales[at:].data_ptr(), rotations[at:].data_ptr(), opacities[at:].data_ptr(),
-                        shs[at:].data_ptr(), min_axis[at:].data_ptr(), stream)
+                        shs[at:].data_ptr(), min_axis[at:].data_ptr())
                 if count == 0:
                     continue
                 if subset is None and block is not None:
-                    rc = _lib.lib.gsr_place_object(o.P, o.xyz.data_ptr(), o.rotation.data_ptr(), o.log_scale.data_ptr(), o.opacity.data_ptr(),
-                                                   o.shs.data_ptr(), self.M, ctypes.byref(block), *outs)
+                    _lib.call("gsr_place_object", o.P, o.xyz.data_ptr(), o.rotation.data_ptr(), o.log_scale.data_ptr(), o.opacity.data_ptr(),
+                              o.shs.data_ptr(), self.M, ctypes.byref(block), *outs, device=self.device)
                 else:
                     if subset is None:   # the whole object, untransformed
                         subset = torch.arange(o.P, dtype=torch.int32, device=self.device)
                     # the kernel reads the list after this call returns, on THIS stream: tell the caching allocator, so that a list
                     # built on another stream (or dropped by the caller right away) is not recycled under the pending kernel
                     subset.record_stream(torch.cuda.current_stream(self.device))
-                    rc = _lib.lib.gsr_place_object_subset(count, subset.data_ptr(), o.xyz.data_ptr(), o.rotation.data_ptr(),
-                                                          o.log_scale.data_ptr(), o.opacity.data_ptr(), o.shs.data_ptr(), self.M,
-                                                          None if block is None else ctypes.byref(block), *outs)
-                if rc != 0:
-                    raise RuntimeError(f"gsr_place_object failed ({rc}): {_lib.last_error()}")
+                    _lib.call("gsr_place_object_subset", count, subset.data_ptr(), o.xyz.data_ptr(), o.rotation.data_ptr(),
+                              o.log_scale.data_ptr(), o.opacity.data_ptr(), o.shs.data_ptr(), self.M,
+                              None if block is None else ctypes.byref(block), *outs, device=self.device)
                 at += count
         self._last_min_axis = min_axis[:at]
         degree = self.sh_degree if (not placements or self.placed_sh_degree is None) else self.placed_sh_degree

@@ -24,7 +24,6 @@ and :func:`drop_in_get_field_values` are what ``autovfx_amd.install()`` puts on 
 """
 from __future__ import annotations
 
-import ctypes
 import math
 from typing import Callable, Optional
 
@@ -71,7 +70,9 @@ def _why_not(x, idx, centers, inv_scaled_rotation, strengths, min_scaling=None, 
         return "beta needs min_scaling"
     if x.shape[0] > MAX_COUNT or P > MAX_COUNT:
         return f"{x.shape[0]} samples and {P} Gaussians: at most 2^30 - 1 each"
-    if torch.cuda.is_initialized() and torch.cuda.is_current_stream_capturing():
+    from . import _lib
+
+    if _lib.capturing():
         return "the current stream is capturing a graph (the call allocates its scratch)"
     return None
 
@@ -85,10 +86,6 @@ def field_takes(x, idx, centers, inv_scaled_rotation, strengths, min_scaling=Non
     if isinstance(density_factor, torch.Tensor) or not isinstance(density_factor, (int, float)):
         return False
     return _why_not(x, idx, centers, inv_scaled_rotation, strengths, min_scaling, want_beta) is None
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else t.data_ptr()
 
 
 class _Field(torch.autograd.Function):
@@ -110,14 +107,10 @@ class _Field(torch.autograd.Function):
                     out.zero_()
         elif N > 0:
             with torch.cuda.device(dev):
-                nbytes = int(_lib.lib.gsr_field_scratch_bytes(P))
-                scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-                stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-                rc = _lib.lib.gsr_field_forward(N, K, P, xs.data_ptr(), ix.data_ptr(), cs.data_ptr(), Ms.data_ptr(), ss.data_ptr(),
-                                                _ptr(ms), density_factor, density.data_ptr(), _ptr(opacities), _ptr(beta),
-                                                scratch.data_ptr(), nbytes, stream)
-            if rc != 0:
-                raise RuntimeError(f"gsr_field_forward failed ({rc}): {_lib.last_error()}")
+                scratch, nbytes = _lib.scratch("gsr_field_scratch_bytes", P, device=dev)
+                _lib.call("gsr_field_forward", N, K, P, xs.data_ptr(), ix.data_ptr(), cs.data_ptr(), Ms.data_ptr(), ss.data_ptr(),
+                          _lib.ptr(ms), density_factor, density.data_ptr(), _lib.ptr(opacities), _lib.ptr(beta),
+                          scratch.data_ptr(), nbytes, device=dev)
         ctx.save_for_backward(xs, ix, cs, Ms, ss, ms)     # the inputs: nothing of size [N, K] but the caller's own idx
         ctx.density_factor = density_factor
         ctx.strengths_shape = strengths.shape
@@ -137,14 +130,10 @@ class _Field(torch.autograd.Function):
         accum = torch.zeros((P, 16), dtype=torch.float32, device=dev)
         if N > 0 and P > 0:
             with torch.cuda.device(dev):
-                nbytes = int(_lib.lib.gsr_field_scratch_bytes(P))
-                scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-                stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-                rc = _lib.lib.gsr_field_backward(N, K, P, xs.data_ptr(), ix.data_ptr(), cs.data_ptr(), Ms.data_ptr(), ss.data_ptr(), _ptr(ms),
-                                                 ctx.density_factor, _ptr(gd), _ptr(go), _ptr(gb), _ptr(dx), accum.data_ptr(),
-                                                 scratch.data_ptr(), nbytes, stream)
-            if rc != 0:
-                raise RuntimeError(f"gsr_field_backward failed ({rc}): {_lib.last_error()}")
+                scratch, nbytes = _lib.scratch("gsr_field_scratch_bytes", P, device=dev)
+                _lib.call("gsr_field_backward", N, K, P, xs.data_ptr(), ix.data_ptr(), cs.data_ptr(), Ms.data_ptr(), ss.data_ptr(),
+                          _lib.ptr(ms), ctx.density_factor, _lib.ptr(gd), _lib.ptr(go), _lib.ptr(gb), _lib.ptr(dx), accum.data_ptr(),
+                          scratch.data_ptr(), nbytes, device=dev)
         elif dx is not None:
             dx.zero_()
         return (dx, None,
@@ -252,8 +241,10 @@ def field_grads_host(x, idx, centers, inv_scaled_rotation, strengths, min_scalin
 # ---- what install() puts on SuGaR ----
 def _quick_no(x) -> bool:
     """Calls that go to the reference before any input is built: not a CUDA float32 [N, 3] sample tensor, or under graph capture."""
+    from . import _lib
+
     return (not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] != 3
-            or torch.cuda.is_current_stream_capturing())
+            or _lib.capturing())
 
 
 def drop_in_compute_density(original: Callable) -> Callable:

@@ -218,7 +218,6 @@ def encode_png_gpu_deflate_queued(image: torch.Tensor, planar: bool = False):
     """``encode_png_gpu_deflate`` without the host synchronisation: ``(out, length)`` -- the buffer the file is being written into
     (``png_deflate_room`` bytes) and a device ``int64[1]`` that will hold the file's length -- for callers that copy both out behind
     the kernels and look at them once their stream has drained."""
-    import ctypes
     from . import _lib
     if not (image.is_cuda and image.dtype == torch.uint8 and image.dim() == 3):
         raise ValueError("encode_png_gpu_deflate expects a uint8 GPU tensor [H,W,C] or [C,H,W]")
@@ -231,10 +230,8 @@ def encode_png_gpu_deflate_queued(image: torch.Tensor, planar: bool = False):
     scratch = torch.empty(png_deflate_scratch(W, H, C), dtype=torch.uint8, device=img.device)
     length = torch.zeros(1, dtype=torch.int64, device=img.device)
     with torch.cuda.device(img.device):
-        rc = _lib.lib.gsr_png_encode_deflate(img.data_ptr(), W, H, C, 1 if planar else 0, out.data_ptr(), scratch.data_ptr(), length.data_ptr(),
-                                             ctypes.c_void_p(torch.cuda.current_stream(img.device).cuda_stream))
-    if rc != 0:
-        raise RuntimeError(f"gsr_png_encode_deflate failed ({rc}): {_lib.last_error()}")
+        _lib.call("gsr_png_encode_deflate", img.data_ptr(), W, H, C, 1 if planar else 0, out.data_ptr(), scratch.data_ptr(), length.data_ptr(),
+                  device=img.device)
     return out[:png_deflate_max_size(W, H, C)], length
 
 
@@ -242,7 +239,6 @@ def encode_png_gpu_deflate(image: torch.Tensor, planar: bool = False) -> torch.T
     """``encode_png_gpu`` with a compressed IDAT (``gsr_png_encode_deflate``: Paeth filter, run-length matches, one Huffman code per
     image built on the GPU).  The file's length depends on the image, so this convenience form reads it back (one host
     synchronisation); the frame writer keeps it on the device and copies it out with the file."""
-    import ctypes
     from . import _lib
     if not (image.is_cuda and image.dtype == torch.uint8 and image.dim() == 3):
         raise ValueError("encode_png_gpu_deflate expects a uint8 GPU tensor [H,W,C] or [C,H,W]")
@@ -255,10 +251,8 @@ def encode_png_gpu_deflate(image: torch.Tensor, planar: bool = False) -> torch.T
     scratch = torch.empty(png_deflate_scratch(W, H, C), dtype=torch.uint8, device=img.device)
     length = torch.zeros(1, dtype=torch.int64, device=img.device)
     with torch.cuda.device(img.device):
-        rc = _lib.lib.gsr_png_encode_deflate(img.data_ptr(), W, H, C, 1 if planar else 0, out.data_ptr(), scratch.data_ptr(), length.data_ptr(),
-                                             ctypes.c_void_p(torch.cuda.current_stream(img.device).cuda_stream))
-    if rc != 0:
-        raise RuntimeError(f"gsr_png_encode_deflate failed ({rc}): {_lib.last_error()}")
+        _lib.call("gsr_png_encode_deflate", img.data_ptr(), W, H, C, 1 if planar else 0, out.data_ptr(), scratch.data_ptr(), length.data_ptr(),
+                  device=img.device)
     n = int(length.item())
     assert 0 < n <= png_deflate_max_size(W, H, C), (n, png_deflate_max_size(W, H, C))
     return out[:n]
@@ -268,7 +262,6 @@ def encode_png_gpu(image: torch.Tensor, planar: bool = False, out: "torch.Tensor
     """uint8 GPU image -- interleaved ``[H,W,C]`` or, ``planar``, ``[C,H,W]`` (what ``pack_rgba8`` leaves); C = 3 or 4 -- to the
     bytes of its PNG file, a uint8 GPU tensor (``gsr_png_encode``).  ``out``: a 16-byte aligned uint8 buffer of at least
     ``png_room(W, H, C)`` bytes to encode into (a slice of a staging buffer); the returned tensor is its first ``png_size`` bytes."""
-    import ctypes
     from . import _lib
     if not (image.is_cuda and image.dtype == torch.uint8 and image.dim() == 3):
         raise ValueError("encode_png_gpu expects a uint8 GPU tensor [H,W,C] or [C,H,W]")
@@ -280,10 +273,7 @@ def encode_png_gpu(image: torch.Tensor, planar: bool = False, out: "torch.Tensor
     if not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() >= room and out.data_ptr() % 16 == 0):
         raise ValueError("encode_png_gpu: out must be a contiguous, 16-byte aligned uint8 GPU buffer of png_room(W, H, C) bytes")
     with torch.cuda.device(img.device):
-        rc = _lib.lib.gsr_png_encode(img.data_ptr(), W, H, C, 1 if planar else 0, out.data_ptr(),
-                                     ctypes.c_void_p(torch.cuda.current_stream(img.device).cuda_stream))
-    if rc != 0:
-        raise RuntimeError(f"gsr_png_encode failed ({rc}): {_lib.last_error()}")
+        _lib.call("gsr_png_encode", img.data_ptr(), W, H, C, 1 if planar else 0, out.data_ptr(), device=img.device)
     return out[:n]
 
 
@@ -375,20 +365,16 @@ class GpuFrameWriter:
         d, nrm = depth.reshape(H, W).contiguous(), normal.reshape(H, W, 3).contiguous()
         if not all(t.is_cuda and t.dtype == torch.float32 for t in (color, alpha, d, nrm)):
             raise ValueError("GpuFrameWriter.submit expects float32 GPU tensors (a render() result)")
-        import ctypes
         from . import _lib
         base = dev.data_ptr()
         with torch.cuda.device(dev.device):
             args = (color.data_ptr(), alpha.data_ptr(), d.data_ptr(), nrm.data_ptr(), 3.0, self._lut.data_ptr(), W, H,
                     base + off["images"][0], base + off["depth_preview"][0], base + off["normal"][0],
                     base + off["depth"][0] + self._header_len, slot["work"].data_ptr())
-            stream_ptr = ctypes.c_void_p(torch.cuda.current_stream(dev.device).cuda_stream)
             if self.deflate:
-                rc = _lib.lib.gsr_frame_files_deflate(*args, slot["scratch"].data_ptr(), base + self._lengths_at, stream_ptr)
+                _lib.call("gsr_frame_files_deflate", *args, slot["scratch"].data_ptr(), base + self._lengths_at, device=dev.device)
             else:
-                rc = _lib.lib.gsr_frame_files(*args, stream_ptr)
-            if rc != 0:
-                raise RuntimeError(f"gsr_frame_files failed ({rc}): {_lib.last_error()}")
+                _lib.call("gsr_frame_files", *args, device=dev.device)
             # (inside the device guard: the copy goes to the current stream of the FRAME's device, and the event is recorded on that
             # stream explicitly -- Event.record() without an argument would take the process's current device)
             slot["host"].copy_(dev, non_blocking=True)

@@ -48,7 +48,6 @@ def pack_rgba8(color: torch.Tensor, alpha: torch.Tensor, out: Optional[torch.Ten
     """[3,H,W] + [1,H,W] float -> [4,H,W] uint8 with save_image's rounding.  GPU tensors go through
     the library's fused kernel (one launch, 20 B per pixel); anything else through plain torch ops."""
     if color.is_cuda and color.dtype == torch.float32 and alpha.dtype == torch.float32:
-        import ctypes
         from . import _lib
         H, W = int(color.shape[-2]), int(color.shape[-1])
         if out is None:
@@ -57,10 +56,7 @@ def pack_rgba8(color: torch.Tensor, alpha: torch.Tensor, out: Optional[torch.Ten
             raise RuntimeError("pack_rgba8: out must be a contiguous uint8 tensor on the colour tensor's device")
         c, a = color.contiguous(), alpha.contiguous()
         with torch.cuda.device(color.device):
-            rc = _lib.lib.gsr_pack_rgba8(c.data_ptr(), a.data_ptr(), out.data_ptr(), W, H,
-                                         ctypes.c_void_p(torch.cuda.current_stream(color.device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError(f"gsr_pack_rgba8 failed ({rc}): {_lib.last_error()}")
+            _lib.call("gsr_pack_rgba8", c.data_ptr(), a.data_ptr(), out.data_ptr(), W, H, device=color.device)
         return out
     rgba = torch.cat((color, alpha), dim=0)
     q = rgba.mul(255.0).add_(0.5).clamp_(0.0, 255.0).to(torch.uint8)

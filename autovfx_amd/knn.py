@@ -27,7 +27,6 @@ contract in numpy by brute force, the checker of the tests and a CPU comparator.
 """
 from __future__ import annotations
 
-import ctypes
 from typing import Callable, NamedTuple, Optional
 
 import numpy as np
@@ -64,12 +63,8 @@ def mean_dist3(points: torch.Tensor) -> torch.Tensor:
     if P == 0:
         return out
     with torch.cuda.device(pts.device):
-        nbytes = int(_lib.lib.gsr_knn3_scratch_bytes(P))
-        scratch = torch.empty(nbytes, dtype=torch.uint8, device=pts.device)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(pts.device).cuda_stream)
-        rc = _lib.lib.gsr_knn3_mean_dist(P, pts.data_ptr(), out.data_ptr(), scratch.data_ptr(), nbytes, stream)
-    if rc != 0:
-        raise RuntimeError(f"gsr_knn3_mean_dist failed ({rc}): {_lib.last_error()}")
+        scratch, nbytes = _lib.scratch("gsr_knn3_scratch_bytes", P, device=pts.device)
+        _lib.call("gsr_knn3_mean_dist", P, pts.data_ptr(), out.data_ptr(), scratch.data_ptr(), nbytes, device=pts.device)
     return out
 
 
@@ -130,7 +125,9 @@ def _why_not(p1, p2, lengths1, lengths2, norm, K) -> Optional[str]:
         return f"p2 has {p2.shape[1]} points, fewer than K = {K}"
     if p1.shape[1] > MAX_POINTS or p2.shape[1] > MAX_POINTS:
         return f"{p1.shape[1]} and {p2.shape[1]} points: at most 2^30 - 1 each"
-    if torch.cuda.is_initialized() and torch.cuda.is_current_stream_capturing():
+    from . import _lib
+
+    if _lib.capturing():
         return "the current stream is capturing a graph (the call allocates its scratch)"
     return None
 
@@ -158,14 +155,10 @@ def _search(p1: torch.Tensor, p2: torch.Tensor, K: int):
     if P1 == 0:
         return dists, idx
     with torch.cuda.device(c1.device):
-        nbytes = int(_lib.lib.gsr_knn_points_scratch_bytes(P1, P2, int(same)))
-        scratch = torch.empty(nbytes, dtype=torch.uint8, device=c1.device)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(c1.device).cuda_stream)
+        scratch, nbytes = _lib.scratch("gsr_knn_points_scratch_bytes", P1, P2, int(same), device=c1.device)
         for n in range(N):   # (the batch elements share the scratch: they run one after the other on the stream)
-            rc = _lib.lib.gsr_knn_points(P1, c1[n].data_ptr(), P2, c2[n].data_ptr(), K, dists[n].data_ptr(), idx[n].data_ptr(),
-                                         scratch.data_ptr(), nbytes, stream)
-            if rc != 0:
-                raise RuntimeError(f"gsr_knn_points failed ({rc}): {_lib.last_error()}")
+            _lib.call("gsr_knn_points", P1, c1[n].data_ptr(), P2, c2[n].data_ptr(), K, dists[n].data_ptr(), idx[n].data_ptr(),
+                      scratch.data_ptr(), nbytes, device=c1.device)
     return dists, idx
 
 

@@ -38,15 +38,6 @@ except OSError:          # no shared zlib to bind: Python's module inflates, one
     _libz = None
 
 
-def _stream_ptr(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
-def _check(rc, what):
-    if rc != 0:
-        raise RuntimeError(f"{what} failed ({rc}): {_lib.last_error()}")
-
-
 class Staging:
     """Page-locked host memory handed out front to back; ``reset()`` starts over (after the stream that copies from it has drained).
     Grows by allocating a new block: earlier hand-outs stay valid until ``reset``."""
@@ -98,8 +89,8 @@ def inflate_into(dst: torch.Tensor, data: bytes) -> bool:
 
 def _upload(host: torch.Tensor, device) -> torch.Tensor:
     dst = torch.empty(host.numel(), dtype=torch.uint8, device=device)
-    _check(_lib.lib.gsr_upload(ctypes.c_void_p(dst.data_ptr()), ctypes.cast(ctypes.c_void_p(host.data_ptr()), ctypes.c_char_p), host.numel(),
-                               _stream_ptr(device)), "gsr_upload")
+    _lib.call("gsr_upload", ctypes.c_void_p(dst.data_ptr()), ctypes.cast(ctypes.c_void_p(host.data_ptr()), ctypes.c_char_p), host.numel(),
+              device=device)
     return dst
 
 
@@ -186,7 +177,6 @@ def png_scanlines(buf: bytes):
 def _unfilter_many(jobs, device):
     """``jobs``: ``[(page-locked scanline stream, w, h, c)]`` -> the RGBA8 images, by one ``gsr_png_unfilter_batch`` call (a workgroup per
     image, side by side) on the current stream."""
-    lib = _lib.lib
     if not jobs:
         return []
     table = (_lib.PngUnfilterJob * len(jobs))()
@@ -194,12 +184,12 @@ def _unfilter_many(jobs, device):
     for k, (host, w, h, c) in enumerate(jobs):
         staged = _upload(host, device)
         out = torch.empty((h, w, 4), dtype=torch.uint8, device=device)
-        scratch = torch.empty(lib.gsr_png_unfilter_scratch(w, h), dtype=torch.uint8, device=device)
+        scratch, _ = _lib.scratch("gsr_png_unfilter_scratch", w, h, device=device)
         table[k] = _lib.PngUnfilterJob(staged.data_ptr(), w, h, c, out.data_ptr(), scratch.data_ptr())
         held += [staged, scratch]         # (freed to the stream's pool after the launch below: ordered behind it)
         outs.append(out)
     with torch.cuda.device(device):
-        _check(lib.gsr_png_unfilter_batch(len(jobs), ctypes.byref(table), _stream_ptr(device)), "gsr_png_unfilter_batch")
+        _lib.call("gsr_png_unfilter_batch", len(jobs), ctypes.byref(table), device=device)
     return outs
 
 
@@ -335,8 +325,7 @@ def inflate_zlib_streams(streams, sizes, device):
     out = torch.empty(max(out_at, 1), dtype=torch.uint8, device=device)
     status = torch.full((max(n, 1),), -1, dtype=torch.int32, device=device)
     with torch.cuda.device(device):
-        _check(_lib.lib.gsr_inflate_zlib_blocks(d_packed.data_ptr(), out.data_ptr(), d_jobs.data_ptr(), n, status.data_ptr(), None, _stream_ptr(device)),
-               "gsr_inflate_zlib_blocks")
+        _lib.call("gsr_inflate_zlib_blocks", d_packed.data_ptr(), out.data_ptr(), d_jobs.data_ptr(), n, status.data_ptr(), None, device=device)
     torch.cuda.current_stream(device).synchronize()
     return out[:out_at], status[:n]
 
@@ -378,16 +367,16 @@ def _depth_blocks_on_gpu(bufs, device, staging: Staging, error_flag):
     blocks = torch.empty(out_at, dtype=torch.uint8, device=device)
     status = torch.empty(n_jobs, dtype=torch.int32, device=device)
     with torch.cuda.device(device):
-        _check(lib.gsr_inflate_zlib_blocks(staged.data_ptr() + 16 * n_jobs, blocks.data_ptr(), staged.data_ptr(), n_jobs, status.data_ptr(),
-                                           error_flag.data_ptr(), _stream_ptr(device)), "gsr_inflate_zlib_blocks")
+        _lib.call("gsr_inflate_zlib_blocks", staged.data_ptr() + 16 * n_jobs, blocks.data_ptr(), staged.data_ptr(), n_jobs, status.data_ptr(),
+                  error_flag.data_ptr(), device=device)
     return [None if sp is None else (blocks[sp[0]:sp[0] + sp[1]], info) for sp, info in zip(spans, infos)]
 
 
 def _unpack_plane(staged: torch.Tensor, L, device) -> torch.Tensor:
     plane = torch.empty((L.height, L.channel_bytes), dtype=torch.uint8, device=device)
     with torch.cuda.device(device):
-        _check(_lib.lib.gsr_exr_unpack_channel(staged.data_ptr(), L.height, L.bytes_per_line, L.lines_per_block, L.channel_at, L.channel_bytes,
-                                               plane.data_ptr(), _stream_ptr(device)), "gsr_exr_unpack_channel")
+        _lib.call("gsr_exr_unpack_channel", staged.data_ptr(), L.height, L.bytes_per_line, L.lines_per_block, L.channel_at, L.channel_bytes,
+                  plane.data_ptr(), device=device)
     return plane.view(torch.float16 if L.channel_is_half else torch.float32)
 
 

@@ -94,8 +94,7 @@ class Adam(torch.optim.Adam):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        capturing = torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
-        if not kernel_takes(self.param_groups, self.state, capturing):
+        if not kernel_takes(self.param_groups, self.state, _lib.capturing()):
             _torch_step(self)
             return loss
         with torch.no_grad():
@@ -129,13 +128,10 @@ class Adam(torch.optim.Adam):
         if device is None:
             return
         with torch.cuda.device(device):
-            stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
             for (w, b2, c, eps), descs in batches.items():
                 for i in range(0, len(descs), _lib.ADAM_MAX_TENSORS):
                     part = descs[i:i + _lib.ADAM_MAX_TENSORS]
-                    rc = _lib.lib.gsr_adam_step((_lib.AdamTensor * len(part))(*part), len(part), w, b2, c, eps, stream)
-                    if rc != 0:
-                        raise RuntimeError(f"gsr_adam_step failed ({rc}): {_lib.last_error()}")
+                    _lib.call("gsr_adam_step", (_lib.AdamTensor * len(part))(*part), len(part), w, b2, c, eps, device=device)
         torch._foreach_add_(all_steps, torch.tensor(1.0, device="cpu"), alpha=1.0)   # as torch increments CPU steps
         torch.autograd.graph.increment_version(written)
 

@@ -214,10 +214,6 @@ def _device_grid(h: int, w: int, device):
     return got
 
 
-def _stream_ptr(device) -> ctypes.c_void_p:
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
 def _face_tensors(faces, what: str, depth: bool = False):
     faces = _as_face_list(faces)
     out = []
@@ -264,11 +260,9 @@ def cube_to_equirect(faces, h: int, w: int, depth=None, out_uint8: bool = False,
     ptrs = (ctypes.c_void_p * 6)(*[f.data_ptr() for f in F])
     dptrs = (ctypes.c_void_p * 6)(*[f.data_ptr() for f in D]) if D is not None else None
     with torch.cuda.device(dev):
-        rc = _lib.lib.gsr_cube_to_equirect(ptrs, S, C, dptrs, gu.data_ptr(), gv.data_ptr(), gc.data_ptr(), h, w,
-                                           None if out_uint8 else out.data_ptr(), out.data_ptr() if out_uint8 else None,
-                                           None if D is None else out_depth.data_ptr(), _stream_ptr(dev))
-    if rc != 0:
-        raise RuntimeError(f"gsr_cube_to_equirect failed ({rc}): {_lib.last_error()}")
+        _lib.call("gsr_cube_to_equirect", ptrs, S, C, dptrs, gu.data_ptr(), gv.data_ptr(), gc.data_ptr(), h, w,
+                  None if out_uint8 else out.data_ptr(), out.data_ptr() if out_uint8 else None,
+                  None if D is None else out_depth.data_ptr(), device=dev)
     return out if D is None else (out, out_depth)
 
 
@@ -350,14 +344,11 @@ def render_panorama(gaussians, pipeline, background, center, output_dir, pano_h:
         lengths = staging[int(offsets[-1]):].view(torch.int64)
         scratch = torch.empty(max(png_deflate_scratch(w_, h_, 4) for _img, w_, h_, _p in jobs), dtype=torch.uint8, device=device)
         packed = torch.empty((4, S, S), dtype=torch.uint8, device=device)
-        stream = _stream_ptr(device)
         for j, (img, w_, h_, planar) in enumerate(jobs):
             src = pack_rgba8(img[:3], img[3:], out=packed) if planar else img
             with torch.cuda.device(device):
-                rc = _lib.lib.gsr_png_encode_deflate(src.data_ptr(), w_, h_, 4, 1 if planar else 0, staging.data_ptr() + int(offsets[j]),
-                                                     scratch.data_ptr(), lengths.data_ptr() + 8 * j, stream)
-            if rc != 0:
-                raise RuntimeError(f"gsr_png_encode_deflate failed ({rc}): {_lib.last_error()}")
+                _lib.call("gsr_png_encode_deflate", src.data_ptr(), w_, h_, 4, 1 if planar else 0, staging.data_ptr() + int(offsets[j]),
+                          scratch.data_ptr(), lengths.data_ptr() + 8 * j, device=device)
         with _PINNED_LOCK:
             host = _pinned(total)
             host.copy_(staging, non_blocking=True)

@@ -195,21 +195,13 @@ def raw_parameters(pc):
     return t
 
 
-def _stream_ptr(device):
-    import ctypes
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
 def _fused_view_normals(xyz: torch.Tensor, axis: torch.Tensor, campos: torch.Tensor) -> torch.Tensor:
     """``pc.get_normal(normalize(xyz - campos)) * 0.5 + 0.5`` in one kernel."""
     from . import _lib
     xyz_, axis_, cp_ = xyz.contiguous(), axis.contiguous().float(), campos.contiguous().float()
     out = torch.empty_like(xyz_)
     with torch.cuda.device(xyz.device):
-        rc = _lib.lib.gsr_view_normals(int(xyz_.shape[0]), xyz_.data_ptr(), axis_.data_ptr(), cp_.data_ptr(), out.data_ptr(),
-                                       _stream_ptr(xyz.device))
-    if rc != 0:
-        raise RuntimeError(f"gsr_view_normals failed ({rc}): {_lib.last_error()}")
+        _lib.call("gsr_view_normals", int(xyz_.shape[0]), xyz_.data_ptr(), axis_.data_ptr(), cp_.data_ptr(), out.data_ptr(), device=xyz.device)
     return out
 
 
@@ -221,10 +213,8 @@ def _fused_normal_maps(normal_rgb: torch.Tensor, depth: torch.Tensor, c2w: torch
     normal = torch.empty((H, W, 3), dtype=torch.float32, device=d_.device)
     pseudo = torch.empty((H, W, 3), dtype=torch.float32, device=d_.device)
     with torch.cuda.device(d_.device):
-        rc = _lib.lib.gsr_normal_maps(W, H, n_.data_ptr(), d_.data_ptr(), m_.data_ptr(), float(fx), float(fy), float(cx),
-                                      float(cy), normal.data_ptr(), pseudo.data_ptr(), _stream_ptr(d_.device))
-    if rc != 0:
-        raise RuntimeError(f"gsr_normal_maps failed ({rc}): {_lib.last_error()}")
+        _lib.call("gsr_normal_maps", W, H, n_.data_ptr(), d_.data_ptr(), m_.data_ptr(), float(fx), float(fy), float(cx),
+                  float(cy), normal.data_ptr(), pseudo.data_ptr(), device=d_.device)
     return normal, pseudo
 
 

@@ -93,11 +93,8 @@ class _FusedSSIM(torch.autograd.Function):
             coef = torch.empty(3 * x.numel(), dtype=torch.float32, device=x.device) if want_grad else None
             nbytes = int(_lib.lib.gsr_ssim_scratch_bytes(n, c, h, w))
             scratch = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=x.device)
-            stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-            rc = _lib.lib.gsr_ssim_forward(n, c, h, w, x.data_ptr(), y.data_ptr(), WINDOW11, int(per_image), out.data_ptr(),
-                                           coef.data_ptr() if want_grad else None, scratch.data_ptr(), nbytes, stream)
-        if rc != 0:
-            raise RuntimeError(f"gsr_ssim_forward failed ({rc}): {_lib.last_error()}")
+            _lib.call("gsr_ssim_forward", n, c, h, w, x.data_ptr(), y.data_ptr(), WINDOW11, int(per_image), out.data_ptr(),
+                      _lib.ptr(coef), scratch.data_ptr(), nbytes, device=x.device)
         if want_grad:
             ctx.save_for_backward(x, y, coef)
             ctx.per_image = per_image
@@ -112,11 +109,8 @@ class _FusedSSIM(torch.autograd.Function):
         g = grad_out.detach().to(torch.float32).contiguous()
         grad = torch.empty_like(x)
         with torch.cuda.device(x.device):
-            stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-            rc = _lib.lib.gsr_ssim_backward(n, c, h, w, x.data_ptr(), y.data_ptr(), coef.data_ptr(), WINDOW11, int(ctx.per_image),
-                                            g.data_ptr(), grad.data_ptr(), stream)
-        if rc != 0:
-            raise RuntimeError(f"gsr_ssim_backward failed ({rc}): {_lib.last_error()}")
+            _lib.call("gsr_ssim_backward", n, c, h, w, x.data_ptr(), y.data_ptr(), coef.data_ptr(), WINDOW11, int(ctx.per_image),
+                      g.data_ptr(), grad.data_ptr(), device=x.device)
         return grad.view(ctx.shape), None, None, None
 
 

@@ -16,7 +16,7 @@ from __future__ import annotations
 
 import ctypes
 import threading
-from typing import Optional, Tuple
+from typing import Tuple
 
 import torch
 
@@ -80,13 +80,6 @@ class _CallScratch:
         t = _new(int(nbytes), torch.uint8, self.device)
         self.buffers[which] = t
         return t.data_ptr()
-
-
-def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
-    """Device pointer of a tensor, or NULL for the reference's "empty tensor means absent"."""
-    if t is None or t.numel() == 0:
-        return None
-    return t.data_ptr()
 
 
 def _f32c(name: str, t: torch.Tensor, device: torch.device) -> torch.Tensor:
@@ -294,7 +287,7 @@ def _rasterize(begin, background, means3D, colors, opacity, scales, rotations, s
     M = int(sh.size(1)) if sh.numel() != 0 else 0
     flags = _lib.FORWARD_INFERENCE if inference else 0
     extended = begin or extra_colors is not None or bool(flags)   # (gsr_forward has no extra image and no flags)
-    symbol = (_lib.lib.gsr_forward_begin if begin else _lib.lib.gsr_forward_extra) if extended else _lib.lib.gsr_forward
+    symbol = ("gsr_forward_begin" if begin else "gsr_forward_extra") if extended else "gsr_forward"
     inputs = {"background": background, "means3D": means3D, "sh": sh, "colors": colors, "opacity": opacity, "scales": scales,
               "rotations": rotations, "cov3D_precomp": cov3D_precomp, "viewmatrix": viewmatrix, "projmatrix": projmatrix,
               "campos": campos, "extra_colors": extra_colors}
@@ -341,7 +334,7 @@ def _rasterize_raw(begin, background, xyz, log_scales, rotations, opacity_logits
                 p["projmatrix"], p["campos"], float(tan_fovx), float(tan_fovy), 1 if prefiltered else 0, *out,
                 _lib.FORWARD_INFERENCE if inference else 0)
 
-    symbol = _lib.lib.gsr_forward_raw_begin if begin else _lib.lib.gsr_forward_raw
+    symbol = "gsr_forward_raw_begin" if begin else "gsr_forward_raw"
     return _forward(symbol, begin, device, P, H, W, want_normal, inputs, args, debug)
 
 
@@ -361,7 +354,7 @@ def _outputs(device, P, H, W, third):
 def _forward(symbol, begin, device, P, H, W, third, inputs, args, debug):
     """The one forward routine behind every public forward function.  Allocates the outputs (``third``: with a third image),
     converts ``inputs`` (name -> tensor or None) to float32 device pointers ``p[name]``, installs the scratch and calls the
-    library's ``symbol`` with ``args(p, out)`` -- its arguments between the three allocator pairs and ``debug, stream``, where
+    library's entry point ``symbol`` with ``args(p, out)`` -- its arguments between the three allocator pairs and ``debug, stream``, where
     ``out`` holds the pointers of colour, depth, alpha, radii and the third image.  Returns the 9-tuple of
     ``rasterize_gaussians_extra``, or with ``begin`` a ``PendingForward``."""
     outputs = _outputs(device, P, H, W, third)
@@ -371,26 +364,26 @@ def _forward(symbol, begin, device, P, H, W, third, inputs, args, debug):
         pending = PendingForward(None, device, stream, scratch, None, outputs)
         return pending if begin else pending.finish()
     tensors = {n: None if t is None else _f32c(n, t, device) for n, t in inputs.items()}
-    p = {n: _ptr(t) for n, t in tensors.items()}
+    p = {n: _lib.ptr(t) for n, t in tensors.items()}
     out = [None if t is None else t.data_ptr() for t in outputs]
     _tls.call = scratch
     try:
         with torch.cuda.device(device):
-            rc = symbol(_GEOM_CB, None, _BINNING_CB, None, _IMAGE_CB, None, *args(p, out), 1 if debug else 0,
-                        ctypes.c_void_p(stream))
+            rc = getattr(_lib.lib, symbol)(_GEOM_CB, None, _BINNING_CB, None, _IMAGE_CB, None, *args(p, out), 1 if debug else 0,
+                                           ctypes.c_void_p(stream))
     finally:
         _tls.call = None
     if not begin:
-        return _completed(rc, symbol.__name__, scratch, outputs)
-    if not rc:
-        raise RuntimeError(f"{symbol.__name__} failed: {_lib.last_error()}")
+        return _completed(rc, symbol, scratch, outputs)
+    if not rc:   # (a begin returns its handle, NULL on failure)
+        raise _lib.failure(symbol, "NULL")
     return PendingForward(rc, device, stream, scratch, tensors, outputs)
 
 
 def _completed(rendered, what, scratch, outputs):
     """The epilogue of a full forward call, one-shot or finished: raise on failure, record the layout, build the 9-tuple."""
     if rendered < 0:
-        raise RuntimeError(f"{what} failed ({rendered}): {_lib.last_error()}")
+        raise _lib.failure(what, rendered)
     # per-thread: the library keeps these per calling thread too, and streams are driven by separate threads
     # (the pair counts are fetched by last_layout() on demand: they would cost a wait for the stream here)
     _tls.last_layout = {"geom": _lib.offsets("geom"), "binning": _lib.offsets("binning"), "image": _lib.offsets("image")}
@@ -417,7 +410,7 @@ class PendingForward:
             return True
         r = _lib.lib.gsr_forward_ready(ctypes.c_void_p(self._handle))
         if r < 0:
-            raise RuntimeError(f"gsr_forward_ready failed ({r}): {_lib.last_error()}")
+            raise _lib.failure("gsr_forward_ready", r)
         return r != 0
 
     def finish(self):
@@ -453,11 +446,8 @@ def _blend_cached(hit, background, colors, device, P, H, W):
     geom, binning, image = hit["geom"], hit["binning"], hit["image"]
     bg_, col_ = _f32c("background", background, device), _f32c("colors", colors, device)
     with torch.cuda.device(device):
-        rc = _lib.lib.gsr_blend(geom.data_ptr(), binning.data_ptr(), image.data_ptr(), W, H, col_.data_ptr(), bg_.data_ptr(),
-                                out_color.data_ptr(), out_depth.data_ptr(), out_alpha.data_ptr(),
-                                ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream))
-    if rc != 0:
-        raise RuntimeError(f"gsr_blend failed ({rc}): {_lib.last_error()}")
+        _lib.call("gsr_blend", geom.data_ptr(), binning.data_ptr(), image.data_ptr(), W, H, col_.data_ptr(), bg_.data_ptr(),
+                  out_color.data_ptr(), out_depth.data_ptr(), out_alpha.data_ptr(), device=device)
     return hit["rendered"], out_color, out_depth, out_alpha, hit["radii"].clone(), geom, binning, image, None
 
 
@@ -489,12 +479,12 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
               "rotations": rotations, "cov3D_precomp": cov3D_precomp, "viewmatrix": viewmatrix, "projmatrix": projmatrix,
               "campos": campos, "out_alpha": out_alpha, "dL_dout_color": dL_dout_color, "dL_dout_depth": dL_dout_depth,
               "dL_dout_alpha": dL_dout_alpha}
-    _backward(_lib.lib.gsr_backward, device, P, H, W, inputs, radii, lambda p: (
+    _backward("gsr_backward", device, P, H, W, inputs, radii, lambda p: (
         P, int(degree), M, int(R), p["background"], W, H, p["means3D"], p["sh"], p["colors"], p["scales"],
         float(scale_modifier), p["rotations"], p["cov3D_precomp"], p["viewmatrix"], p["projmatrix"], p["campos"],
-        float(tan_fovx), float(tan_fovy), p["radii"], _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), p["out_alpha"],
-        p["dL_dout_color"], p["dL_dout_depth"], p["dL_dout_alpha"], dL_dmeans2D.data_ptr(), _ptr(dL_dconic),
-        dL_dopacity.data_ptr(), _ptr(dL_dcolors), _ptr(dL_ddepths), dL_dmeans3D.data_ptr(), _ptr(dL_dcov3D),
+        float(tan_fovx), float(tan_fovy), p["radii"], _lib.ptr(geomBuffer), _lib.ptr(binningBuffer), _lib.ptr(imageBuffer), p["out_alpha"],
+        p["dL_dout_color"], p["dL_dout_depth"], p["dL_dout_alpha"], dL_dmeans2D.data_ptr(), _lib.ptr(dL_dconic),
+        dL_dopacity.data_ptr(), _lib.ptr(dL_dcolors), _lib.ptr(dL_ddepths), dL_dmeans3D.data_ptr(), _lib.ptr(dL_dcov3D),
         dL_dsh.data_ptr() if M else None, dL_dscales.data_ptr(), dL_drotations.data_ptr()), debug)
     return dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations
 
@@ -518,10 +508,10 @@ def rasterize_gaussians_raw_backward(background, xyz, log_scales, rotations, opa
               "viewmatrix": viewmatrix, "projmatrix": projmatrix, "campos": campos, "out_alpha": out_alpha,
               "dL_dout_color": dL_dout_color, "dL_dout_depth": dL_dout_depth, "dL_dout_alpha": dL_dout_alpha,
               "dL_dout_normal": dL_dout_normal}
-    _backward(_lib.lib.gsr_backward_raw, device, P, H, W, inputs, radii, lambda p: (
+    _backward("gsr_backward_raw", device, P, H, W, inputs, radii, lambda p: (
         P, int(degree), M, int(R), p["background"], W, H, ctypes.byref(_raw_params(p)), float(scale_modifier), p["viewmatrix"],
-        p["projmatrix"], p["campos"], float(tan_fovx), float(tan_fovy), p["radii"], _ptr(geomBuffer), _ptr(binningBuffer),
-        _ptr(imageBuffer), p["out_alpha"], p["dL_dout_color"], p["dL_dout_depth"], p["dL_dout_alpha"], p["dL_dout_normal"],
+        p["projmatrix"], p["campos"], float(tan_fovx), float(tan_fovy), p["radii"], _lib.ptr(geomBuffer), _lib.ptr(binningBuffer),
+        _lib.ptr(imageBuffer), p["out_alpha"], p["dL_dout_color"], p["dL_dout_depth"], p["dL_dout_alpha"], p["dL_dout_normal"],
         g2d.data_ptr(), gxyz.data_ptr(), gls.data_ptr(), grot.data_ptr(), gop.data_ptr(), gdc.data_ptr(),
         grest.data_ptr() if M > 1 else None), debug)
     return g2d, gxyz, gls, grot, gop, gdc, grest
@@ -529,7 +519,7 @@ def rasterize_gaussians_raw_backward(background, xyz, log_scales, rotations, opa
 
 def _backward(symbol, device, P, H, W, inputs, radii, args, debug):
     """The one backward call behind both backward functions; nothing runs for P == 0.  Converts ``inputs`` (name -> tensor or
-    None) to float32 device pointers ``p[name]``, adds ``p["radii"]`` and calls the library's ``symbol`` with ``args(p)`` -- its
+    None) to float32 device pointers ``p[name]``, adds ``p["radii"]`` and calls the library's entry point ``symbol`` with ``args(p)`` -- its
     arguments before the accumulator scratch, ``debug`` and the stream."""
     if P == 0:
         return
@@ -543,16 +533,14 @@ def _backward(symbol, device, P, H, W, inputs, radii, args, debug):
         inputs["dL_dout_depth"] = zeros(1) if inputs["dL_dout_depth"] is None else inputs["dL_dout_depth"]
         inputs["dL_dout_alpha"] = zeros(1) if inputs["dL_dout_alpha"] is None else inputs["dL_dout_alpha"]
     tensors = {n: None if t is None else _f32c(n, t, device) for n, t in inputs.items()}
-    p = {n: _ptr(t) for n, t in tensors.items()}
+    p = {n: _lib.ptr(t) for n, t in tensors.items()}
     radii_ = radii.contiguous()
     if radii_.dtype != torch.int32:
         raise RuntimeError(f"radii: expected an int32 tensor, got {radii_.dtype}")
-    p["radii"] = _ptr(radii_)
+    p["radii"] = _lib.ptr(radii_)
     accum = _new((P, 16), torch.float32, device)   # cleared by the library
     with torch.cuda.device(device):
-        rc = symbol(*args(p), accum.data_ptr(), 1 if debug else 0, ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream))
-    if rc != 0:
-        raise RuntimeError(f"{symbol.__name__} failed ({rc}): {_lib.last_error()}")
+        _lib.call(symbol, *args(p), accum.data_ptr(), 1 if debug else 0, device=device)
 
 
 def mark_visible(means3D, viewmatrix, projmatrix) -> torch.Tensor:
@@ -564,8 +552,5 @@ def mark_visible(means3D, viewmatrix, projmatrix) -> torch.Tensor:
         vm_ = _f32c("viewmatrix", viewmatrix, device)
         pm_ = _f32c("projmatrix", projmatrix, device)
         with torch.cuda.device(device):
-            rc = _lib.lib.gsr_mark_visible(P, _ptr(m3_), _ptr(vm_), _ptr(pm_), present.data_ptr(),
-                                           ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError(f"gsr_mark_visible failed ({rc}): {_lib.last_error()}")
+            _lib.call("gsr_mark_visible", P, _lib.ptr(m3_), _lib.ptr(vm_), _lib.ptr(pm_), present.data_ptr(), device=device)
     return present

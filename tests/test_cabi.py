@@ -156,3 +156,48 @@ def test_cpu_tensors_are_rejected_not_silently_handled():
         rast(c.means3D, torch.zeros_like(c.means3D), c.opacities, shs=c.shs, scales=c.scales, rotations=c.rotations)
     with pytest.raises(RuntimeError, match="no CPU fallback"):
         rast.markVisible(c.means3D)
+
+
+def declarations():
+    """name -> (return type, parameter count) of every function the header declares, comments stripped."""
+    text = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)
+    out = {}
+    for ret, name, params in re.findall(r"GSR_API\s+([\w\s\*]+?)\b(gsr_\w+)\s*\(([^)]*)\)\s*;", text):
+        params = params.strip()
+        out[name] = (re.sub(r"\s*\*", "*", " ".join(ret.split())), 0 if params == "void" else len(params.split(",")))
+    return out
+
+
+def test_signature_lengths_match_the_header():
+    from autovfx_amd import _lib
+    decl = declarations()
+    assert sorted(decl) == sorted(declared_functions()) == sorted(_lib.SIGNATURES)
+    for name, (_ret, count) in decl.items():
+        assert len(_lib.SIGNATURES[name][1]) == count, name
+        assert len(getattr(_lib.lib, name).argtypes) == count, name
+
+
+def test_return_types_match_the_header():
+    from autovfx_amd import _lib
+    ctype_of = {"size_t": ctypes.c_size_t, "const char*": ctypes.c_char_p, "void*": ctypes.c_void_p, "void": None, "int": ctypes.c_int}
+    for name, (ret, _count) in declarations().items():
+        assert _lib.SIGNATURES[name][0] is ctype_of[ret], (name, ret)
+        assert getattr(_lib.lib, name).restype is ctype_of[ret], (name, ret)
+
+
+def test_check_raises_with_the_status_and_the_library_message():
+    from autovfx_amd import _lib
+    _lib.check("gsr_x", 0)
+    assert _lib.lib.gsr_set_option(-1, 0) != 0
+    why = _lib.last_error()
+    assert why
+    with pytest.raises(RuntimeError) as e:
+        _lib.check("gsr_x", -1)
+    assert "gsr_x failed (-1)" in str(e.value) and why in str(e.value)
+
+
+def test_call_looks_the_function_up_at_call_time(monkeypatch):
+    from autovfx_amd import _lib
+    monkeypatch.setattr(_lib.lib, "gsr_adam_step", lambda *a: -1)
+    with pytest.raises(RuntimeError, match=r"gsr_adam_step failed \(-1\)"):
+        _lib.call("gsr_adam_step", None, 0, 0.0, 0.0, 0.0, 0.0, None)
