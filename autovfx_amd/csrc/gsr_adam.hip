@@ -1,4 +1,5 @@
 // gsr_adam.hip -- one Adam step over every tensor of an optimizer, in one launch (include/gsr.h: gsr_adam_step).
+// Defines the entry point gsr_adam_step.
 //
 // The update is torch.optim.Adam's default path on a GPU (torch/optim/adam.py, _multi_tensor_adam, amsgrad / maximize / weight decay
 // off), whose foreach ops run one after the other over the whole tensor list:
@@ -32,6 +33,22 @@ constexpr int kUnroll = 4;   // 16-byte accesses per lane and array per chunk
 constexpr int64_t kChunk = (int64_t)kThreads * kVec * kUnroll;
 constexpr uint32_t kMaxGrid = 2048;   // 256 CUs x 8 workgroups; more chunks are walked grid-stride
 static_assert(kChunk == 4096, "DESIGN.md §7d");
+
+struct AdamTensor {
+    float* p;
+    const float* g;
+    float* m;
+    float* v;
+    int64_t numel;
+    float a, s2;      // gsr.h: GsrAdamTensor::step_size, ::bias2_sqrt
+    int aligned16;    // p, g, m and v all 16-byte aligned
+};
+struct AdamBatch {    // passed by value (kernel arguments)
+    AdamTensor t[GSR_ADAM_MAX_TENSORS];
+    uint64_t first_chunk[GSR_ADAM_MAX_TENSORS + 1];   // prefix of adam_chunks(numel); first_chunk[count] = the total
+    int count;
+    float w, b2, c, eps;
+};
 
 // 16-byte nontemporal load (the builtin wants a native vector type).  Measured on C3 groups, same process, alternated, three
 // orders: nontemporal loads 2-10 % faster than plain ones in every order; nontemporal stores changed places with
@@ -107,9 +124,7 @@ __global__ __launch_bounds__(kThreads) void adam_step_kernel(const AdamBatch b) 
     }
 }
 
-}  // namespace
-
-uint64_t adam_chunks(int64_t numel) { return (uint64_t)((numel + kChunk - 1) / kChunk); }
+uint64_t adam_chunks(int64_t numel) { return (uint64_t)((numel + kChunk - 1) / kChunk); }   // numel >= 0
 
 hipError_t launch_adam_step(const AdamBatch& b, hipStream_t stream) {
     const uint64_t total = b.first_chunk[b.count];
@@ -118,4 +133,38 @@ hipError_t launch_adam_step(const AdamBatch& b, hipStream_t stream) {
     return hipGetLastError();
 }
 
+}  // namespace
 }  // namespace gsr
+
+using gsr::aligned4;
+using gsr::fail;
+
+extern "C" {
+
+int gsr_adam_step(const GsrAdamTensor* tensors, int count, float w, float b2, float c, float eps, void* stream_) {
+    if (count <= 0 || count > GSR_ADAM_MAX_TENSORS)
+        return fail(GSR_ERR_INVALID_ARG, "gsr_adam_step: bad count %d (1..%d)", count, GSR_ADAM_MAX_TENSORS);
+    if (!tensors) return fail(GSR_ERR_INVALID_ARG, "gsr_adam_step: null tensors");
+    if (!(w >= 0.0f && w < 0.5f)) return fail(GSR_ERR_INVALID_ARG, "gsr_adam_step: w = %g outside [0, 0.5) (ATen's small-weight lerp)", (double)w);
+    gsr::AdamBatch b{};
+    b.count = count;
+    b.w = w;
+    b.b2 = b2;
+    b.c = c;
+    b.eps = eps;
+    for (int i = 0; i < count; ++i) {
+        const GsrAdamTensor& t = tensors[i];
+        if (t.numel < 0) return fail(GSR_ERR_INVALID_ARG, "gsr_adam_step: tensor %d: numel %lld < 0", i, (long long)t.numel);
+        if (t.numel > 0 && (!t.param || !t.grad || !t.exp_avg || !t.exp_avg_sq))
+            return fail(GSR_ERR_INVALID_ARG, "gsr_adam_step: tensor %d: null pointer", i);
+        if (!aligned4(t.param) || !aligned4(t.grad) || !aligned4(t.exp_avg) || !aligned4(t.exp_avg_sq))
+            return fail(GSR_ERR_INVALID_ARG, "gsr_adam_step: tensor %d: misaligned pointer (4 bytes)", i);
+        const uintptr_t any = (uintptr_t)t.param | (uintptr_t)t.grad | (uintptr_t)t.exp_avg | (uintptr_t)t.exp_avg_sq;
+        b.t[i] = {t.param, t.grad, t.exp_avg, t.exp_avg_sq, t.numel, t.step_size, t.bias2_sqrt, (any & 15u) == 0u ? 1 : 0};
+        b.first_chunk[i + 1] = b.first_chunk[i] + gsr::adam_chunks(t.numel);   // numel == 0: no chunk, skipped
+    }
+    GSR_HIP(gsr::launch_adam_step(b, (hipStream_t)stream_));
+    return GSR_OK;
+}
+
+}  // extern "C"

@@ -1,11 +1,13 @@
-// gsr_api.hip -- the C ABI (include/gsr.h) and the host orchestration of one forward call.
+// gsr_api.hip -- the host orchestration of the rasterizer behind the C ABI (include/gsr.h): gsr_forward*, gsr_plan_slabs,
+// gsr_backward*, gsr_blend, the options, the stage timing and the gsr_last_* accessors, gsr_upload, and the error message every
+// unit's entry points set (gsr::fail, gsr_last_error).  Every other entry point is defined at the end of the unit that holds its
+// kernels; adding one touches that unit, include/gsr.h and the binding's signature table.
 //
 // Mirrors what CudaRasterizer::Rasterizer::forward does on the host
 // (DGR/cuda_rasterizer/rasterizer_impl.cu:197-339): carve scratch out of caller-provided arenas
 // (rasterizer_impl.h:22-27,66-72), run the stages, read num_rendered back once to size the binning
 // arena (:282), return it.  The stage list itself is this library's own (gsr_kernels.hip, gsr_binning.hip,
 // gsr_radix.hip, gsr_blend.hip).
-#include "../../include/gsr.h"
 #include "gsr_internal.h"
 
 #include <cstdarg>
@@ -15,6 +17,8 @@
 #include <mutex>
 #include <new>
 #include <vector>
+
+using gsr::fail;
 
 namespace {
 
@@ -72,22 +76,6 @@ bool g_bw_made = false;
 bool g_bw_done[kBackwardRing];   // the slot's three events have all been recorded
 long g_bw_begun = 0;             // timed backward calls begun since timing was (re)enabled: each reserves its own slot
 long g_bw_calls = 0;             // ... and completed
-
-int fail(gsr_status code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_error, sizeof g_error, fmt, ap);
-    va_end(ap);
-    return (int)code;
-}
-
-#define GSR_HIP(expr)                                                                          \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess)                                                                  \
-            return fail(GSR_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_),   \
-                        __FILE__, __LINE__);                                                   \
-    } while (0)
 
 // After each stage in debug mode: the CHECK_CUDA of auxiliary.h:166-173.
 #define GSR_STAGE_CHECK(name)                                                                  \
@@ -165,6 +153,14 @@ void stamp(int idx, hipStream_t s) {
 }
 
 } // namespace
+
+int gsr::fail(gsr_status code, const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_error, sizeof g_error, fmt, ap);
+    va_end(ap);
+    return (int)code;
+}
 
 extern "C" {
 
@@ -337,15 +333,6 @@ int gsr_last_image_offsets(size_t o[GSR_IMG_NUM_SLOTS]) {
     return GSR_OK;
 }
 
-int gsr_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix,
-                     uint8_t* present, void* stream_) {
-    (void)projmatrix;  // the reference passes it but only the view-space depth test is live (auxiliary.h:154)
-    if (P < 0) return fail(GSR_ERR_INVALID_ARG, "P < 0");
-    if (P == 0) return GSR_OK;
-    if (!means3D || !viewmatrix || !present) return fail(GSR_ERR_INVALID_ARG, "null pointer");
-    GSR_HIP(gsr::launch_mark_visible(P, means3D, viewmatrix, present, (hipStream_t)stream_));
-    return GSR_OK;
-}
 
 } // extern "C"
 
@@ -647,520 +634,10 @@ int gsr_blend(const char* geom_buffer, const char* binning_buffer, const char* i
     return GSR_OK;
 }
 
-int gsr_composite(int width, int height, const uint8_t* bg_c, const uint8_t* o_c, const float* o_d, const uint8_t* s_c,
-                  const float* s_d, const uint8_t* o_s_c, const uint8_t* o_gs_c, const float* o_gs_d,
-                  const uint8_t* s_f_c, const float* s_f_d, const uint8_t* s_f_c_pre, uint8_t* out, void* stream_) {
-    if (width <= 0 || height <= 0) return fail(GSR_ERR_INVALID_ARG, "bad image size %dx%d", width, height);
-    if (!bg_c || !o_c || !o_d || !s_c || !s_d || !o_s_c || !out) return fail(GSR_ERR_INVALID_ARG, "null required layer");
-    if ((o_gs_c != nullptr) != (o_gs_d != nullptr) || (s_f_c != nullptr) != (s_f_d != nullptr))
-        return fail(GSR_ERR_INVALID_ARG, "a colour layer and its depth map must be given together");
-    if (s_f_c_pre != nullptr && s_f_c == nullptr) return fail(GSR_ERR_INVALID_ARG, "fire layer without a smoke layer");
-    GSR_HIP(gsr::launch_composite(width, height, bg_c, o_c, o_d, s_c, s_d, o_s_c, o_gs_c, o_gs_d, s_f_c, s_f_d,
-                                  s_f_c_pre, out, (hipStream_t)stream_));
-    return GSR_OK;
-}
-
-size_t gsr_radix_scratch_bytes(uint32_t n, int bits) {
-    (void)bits;
-    return gsr::radix_scratch_words(n) * sizeof(uint32_t);
-}
-
-int gsr_radix_sort_pairs(uint32_t n, int bits, uint32_t* keys, uint32_t* keys_alt, uint32_t* vals, uint32_t* vals_alt,
-                         int iota_payload, void* scratch, size_t scratch_bytes, int* sorted_in_alt, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (bits < 1 || bits > 32) return fail(GSR_ERR_INVALID_ARG, "bad key width bits=%d", bits);
-    if (sorted_in_alt) *sorted_in_alt = 0;
-    if (n == 0) return GSR_OK;
-    if (!keys || !keys_alt || !vals_alt || (!vals && !iota_payload) || !scratch)
-        return fail(GSR_ERR_INVALID_ARG, "null pointer");
-    if (scratch_bytes < gsr_radix_scratch_bytes(n, bits)) return fail(GSR_ERR_INVALID_ARG, "sort scratch too small");
-    uint32_t *ks = nullptr, *vs = nullptr;
-    GSR_HIP(gsr::radix_sort_pairs((uint32_t*)scratch, n, bits, keys, keys_alt, vals, vals_alt, iota_payload != 0, true, &ks,
-                                  &vs, stream));
-    if (sorted_in_alt) *sorted_in_alt = ks == keys_alt;
-    return GSR_OK;
-}
-
-size_t gsr_knn3_scratch_bytes(uint32_t n) {
-    return n >= gsr::kKnn3MaxPoints ? 0 : gsr::knn3_layout(n).bytes;
-}
-
-int gsr_knn3_mean_dist(uint32_t n, const float* points, float* out, void* scratch, size_t scratch_bytes, void* stream_) {
-    if (n == 0) return GSR_OK;
-    if (n >= gsr::kKnn3MaxPoints) return fail(GSR_ERR_INVALID_ARG, "gsr_knn3_mean_dist: %u points (at most 2^30 - 1)", n);
-    if (!points || !out || !scratch) return fail(GSR_ERR_INVALID_ARG, "null pointer");
-    if (((uintptr_t)points & 3u) != 0u || ((uintptr_t)out & 3u) != 0u || ((uintptr_t)scratch & 255u) != 0u)
-        return fail(GSR_ERR_INVALID_ARG, "gsr_knn3_mean_dist: misaligned pointer (points / out: 4 bytes, scratch: 256 bytes)");
-    if (scratch_bytes < gsr_knn3_scratch_bytes(n))
-        return fail(GSR_ERR_INVALID_ARG, "gsr_knn3_mean_dist: scratch too small (%zu of %zu bytes)", scratch_bytes, gsr_knn3_scratch_bytes(n));
-    GSR_HIP(gsr::launch_knn3_mean_dist(n, points, out, scratch, (hipStream_t)stream_));
-    return GSR_OK;
-}
-
-size_t gsr_knn_points_scratch_bytes(int64_t n1, int64_t n2, int same) {
-    if (n1 < 0 || n2 < 0 || n1 >= (int64_t)gsr::kKnn3MaxPoints || n2 >= (int64_t)gsr::kKnn3MaxPoints) return 0;
-    return gsr::knn_points_scratch_bytes((uint32_t)n1, (uint32_t)n2, same != 0);
-}
-
-int gsr_knn_points(int64_t n1, const float* p1, int64_t n2, const float* p2, int K, float* dists, int64_t* idx, void* scratch,
-                   size_t scratch_bytes, void* stream_) {
-    if (n1 < 0 || n2 < 0) return fail(GSR_ERR_INVALID_ARG, "gsr_knn_points: negative count (n1 %lld, n2 %lld)", (long long)n1, (long long)n2);
-    if (n1 >= (int64_t)gsr::kKnn3MaxPoints || n2 >= (int64_t)gsr::kKnn3MaxPoints)
-        return fail(GSR_ERR_INVALID_ARG, "gsr_knn_points: %lld and %lld points (at most 2^30 - 1 each)", (long long)n1, (long long)n2);
-    if (K < 1 || K > gsr::kKnnPointsMaxK) return fail(GSR_ERR_INVALID_ARG, "gsr_knn_points: K = %d (1 to %d)", K, gsr::kKnnPointsMaxK);
-    if (n1 == 0) return GSR_OK;
-    if (n2 < K) return fail(GSR_ERR_INVALID_ARG, "gsr_knn_points: n2 = %lld is less than K = %d", (long long)n2, K);
-    if (!p1 || !p2 || !dists || !idx || !scratch) return fail(GSR_ERR_INVALID_ARG, "gsr_knn_points: null pointer");
-    // K = 4, 8, 16 rows are written with 16-byte stores; every other K element by element
-    const bool wide = K == 4 || K == 8 || K == 16;
-    if (((uintptr_t)p1 & 3u) != 0u || ((uintptr_t)p2 & 3u) != 0u || ((uintptr_t)dists & (wide ? 15u : 3u)) != 0u ||
-        ((uintptr_t)idx & (wide ? 15u : 7u)) != 0u || ((uintptr_t)scratch & 255u) != 0u)
-        return fail(GSR_ERR_INVALID_ARG, "gsr_knn_points: misaligned pointer (p1 / p2: 4 bytes; dists / idx: 16 bytes for K = 4, 8, 16, "
-                                         "else 4 / 8 bytes; scratch: 256 bytes)");
-    const size_t need = gsr_knn_points_scratch_bytes(n1, n2, p1 == p2 && n1 == n2);
-    if (scratch_bytes < need) return fail(GSR_ERR_INVALID_ARG, "gsr_knn_points: scratch too small (%zu of %zu bytes)", scratch_bytes, need);
-    GSR_HIP(gsr::launch_knn_points((uint32_t)n1, p1, (uint32_t)n2, p2, K, dists, reinterpret_cast<long long*>(idx), scratch,
-                                   (hipStream_t)stream_));
-    return GSR_OK;
-}
-
-size_t gsr_field_scratch_bytes(int64_t P) {
-    return (P < 0 || P >= (int64_t)gsr::kKnn3MaxPoints) ? 0 : gsr::field_scratch_bytes(P);
-}
-
-namespace {
-// What gsr_field_forward and gsr_field_backward check alike; 1: n == 0, nothing to do.
-int field_check(const char* who, const gsr::FieldInputs& in, bool wants_beta, const void* scratch, size_t scratch_bytes) {
-    if (in.K < 1 || in.K > gsr::kFieldMaxK) return fail(GSR_ERR_INVALID_ARG, "%s: K = %d (1 to %d)", who, in.K, gsr::kFieldMaxK);
-    if (in.n < 0 || in.P < 0) return fail(GSR_ERR_INVALID_ARG, "%s: negative count (n %lld, P %lld)", who, (long long)in.n, (long long)in.P);
-    if (in.n >= (int64_t)gsr::kKnn3MaxPoints || in.P >= (int64_t)gsr::kKnn3MaxPoints)
-        return fail(GSR_ERR_INVALID_ARG, "%s: %lld samples and %lld Gaussians (at most 2^30 - 1 each)", who, (long long)in.n, (long long)in.P);
-    if (in.n == 0) return 1;
-    if (!in.x || !in.idx || !scratch || (in.P > 0 && (!in.centers || !in.M || !in.strengths)))
-        return fail(GSR_ERR_INVALID_ARG, "%s: null pointer", who);
-    if (wants_beta && !in.min_scaling) return fail(GSR_ERR_INVALID_ARG, "%s: beta needs min_scaling", who);
-    if ((((uintptr_t)in.x | (uintptr_t)in.centers | (uintptr_t)in.M | (uintptr_t)in.strengths | (uintptr_t)in.min_scaling) & 3u) != 0u ||
-        ((uintptr_t)in.idx & 7u) != 0u || ((uintptr_t)scratch & 255u) != 0u)
-        return fail(GSR_ERR_INVALID_ARG, "%s: misaligned pointer (floats: 4 bytes, idx: 8, scratch: 256)", who);
-    const size_t need = gsr::field_scratch_bytes(in.P);
-    if (scratch_bytes < need) return fail(GSR_ERR_INVALID_ARG, "%s: scratch too small (%zu of %zu bytes)", who, scratch_bytes, need);
-    return GSR_OK;
-}
-}  // namespace
-
-int gsr_field_forward(int64_t n, int K, int64_t P, const float* x, const int64_t* idx, const float* centers, const float* M,
-                      const float* strengths, const float* min_scaling, float density_factor, float* density, float* opacities, float* beta,
-                      void* scratch, size_t scratch_bytes, void* stream_) {
-    const gsr::FieldInputs in{n, K, P, x, reinterpret_cast<const long long*>(idx), centers, M, strengths, min_scaling, density_factor};
-    const int rc = field_check("gsr_field_forward", in, beta != nullptr, scratch, scratch_bytes);
-    if (rc != GSR_OK) return rc == 1 ? GSR_OK : rc;
-    if (!density) return fail(GSR_ERR_INVALID_ARG, "gsr_field_forward: null pointer");
-    if ((((uintptr_t)density | (uintptr_t)opacities | (uintptr_t)beta) & 3u) != 0u)
-        return fail(GSR_ERR_INVALID_ARG, "gsr_field_forward: misaligned pointer (density / opacities / beta: 4 bytes)");
-    GSR_HIP(gsr::launch_field_forward(in, density, opacities, beta, scratch, (hipStream_t)stream_));
-    return GSR_OK;
-}
-
-int gsr_field_backward(int64_t n, int K, int64_t P, const float* x, const int64_t* idx, const float* centers, const float* M,
-                       const float* strengths, const float* min_scaling, float density_factor, const float* g_density,
-                       const float* g_opacities, const float* g_beta, float* dx, float* accum, void* scratch, size_t scratch_bytes,
-                       void* stream_) {
-    const gsr::FieldInputs in{n, K, P, x, reinterpret_cast<const long long*>(idx), centers, M, strengths, min_scaling, density_factor};
-    const int rc = field_check("gsr_field_backward", in, g_beta != nullptr, scratch, scratch_bytes);
-    if (rc != GSR_OK) return rc == 1 ? GSR_OK : rc;
-    if (!accum && P > 0) return fail(GSR_ERR_INVALID_ARG, "gsr_field_backward: null pointer");
-    if ((((uintptr_t)g_density | (uintptr_t)g_opacities | (uintptr_t)g_beta | (uintptr_t)dx) & 3u) != 0u || ((uintptr_t)accum & 63u) != 0u)
-        return fail(GSR_ERR_INVALID_ARG, "gsr_field_backward: misaligned pointer (gradients: 4 bytes, accum: 64)");
-    GSR_HIP(gsr::launch_field_backward(in, g_density, g_opacities, g_beta, dx, accum, scratch, (hipStream_t)stream_));
-    return GSR_OK;
-}
-
-namespace {
-// the sizes gsr_ssim_* accept: every dimension > 0, n c h w < 2^31
-bool ssim_size_ok(int n, int c, int h, int w) {
-    if (n <= 0 || c <= 0 || h <= 0 || w <= 0) return false;
-    const int64_t nc = (int64_t)n * c, nch = nc * h;
-    return nc < (int64_t(1) << 31) && nch < (int64_t(1) << 31) && nch * w < (int64_t(1) << 31);
-}
-bool aligned4(const void* p) { return ((uintptr_t)p & 3u) == 0u; }
-gsr::SsimWindow ssim_window(const float* window11) {
-    gsr::SsimWindow win;
-    for (int k = 0; k < gsr::kSsimTaps; ++k) win.w[k] = window11[k];
-    return win;
-}
-}  // namespace
-
-size_t gsr_ssim_scratch_bytes(int n, int c, int h, int w) {
-    return ssim_size_ok(n, c, h, w) ? (size_t)gsr::ssim_shape(n, c, h, w).blocks * sizeof(float) : 0;
-}
-
-int gsr_ssim_forward(int n, int c, int h, int w, const float* x, const float* y, const float* window11, int per_image, float* out,
-                     float* coef_or_null, void* scratch, size_t scratch_bytes, void* stream_) {
-    if (!ssim_size_ok(n, c, h, w)) return fail(GSR_ERR_INVALID_ARG, "gsr_ssim_forward: bad size %d x %d x %d x %d (each > 0, product < 2^31)", n, c, h, w);
-    if (!x || !y || !window11 || !out || !scratch) return fail(GSR_ERR_INVALID_ARG, "gsr_ssim_forward: null pointer");
-    if (!aligned4(x) || !aligned4(y) || !aligned4(out) || !aligned4(coef_or_null) || !aligned4(scratch))
-        return fail(GSR_ERR_INVALID_ARG, "gsr_ssim_forward: misaligned pointer (4 bytes)");
-    if (scratch_bytes < gsr_ssim_scratch_bytes(n, c, h, w))
-        return fail(GSR_ERR_INVALID_ARG, "gsr_ssim_forward: scratch too small (%zu of %zu bytes)", scratch_bytes, gsr_ssim_scratch_bytes(n, c, h, w));
-    GSR_HIP(gsr::launch_ssim_forward(gsr::ssim_shape(n, c, h, w), ssim_window(window11), x, y, per_image ? 1 : 0, out, coef_or_null,
-                                     (float*)scratch, (hipStream_t)stream_));
-    return GSR_OK;
-}
-
-int gsr_ssim_backward(int n, int c, int h, int w, const float* x, const float* y, const float* coef, const float* window11, int per_image,
-                      const float* grad_out, float* grad_x, void* stream_) {
-    if (!ssim_size_ok(n, c, h, w)) return fail(GSR_ERR_INVALID_ARG, "gsr_ssim_backward: bad size %d x %d x %d x %d (each > 0, product < 2^31)", n, c, h, w);
-    if (!x || !y || !coef || !window11 || !grad_out || !grad_x) return fail(GSR_ERR_INVALID_ARG, "gsr_ssim_backward: null pointer");
-    if (!aligned4(x) || !aligned4(y) || !aligned4(coef) || !aligned4(grad_out) || !aligned4(grad_x))
-        return fail(GSR_ERR_INVALID_ARG, "gsr_ssim_backward: misaligned pointer (4 bytes)");
-    GSR_HIP(gsr::launch_ssim_backward(gsr::ssim_shape(n, c, h, w), ssim_window(window11), x, y, coef, per_image ? 1 : 0, grad_out, grad_x,
-                                      (hipStream_t)stream_));
-    return GSR_OK;
-}
-
-int gsr_adam_step(const GsrAdamTensor* tensors, int count, float w, float b2, float c, float eps, void* stream_) {
-    if (count <= 0 || count > GSR_ADAM_MAX_TENSORS)
-        return fail(GSR_ERR_INVALID_ARG, "gsr_adam_step: bad count %d (1..%d)", count, GSR_ADAM_MAX_TENSORS);
-    if (!tensors) return fail(GSR_ERR_INVALID_ARG, "gsr_adam_step: null tensors");
-    if (!(w >= 0.0f && w < 0.5f)) return fail(GSR_ERR_INVALID_ARG, "gsr_adam_step: w = %g outside [0, 0.5) (ATen's small-weight lerp)", (double)w);
-    static_assert(GSR_ADAM_MAX_TENSORS == gsr::kAdamMaxTensors, "gsr.h and gsr_internal.h");
-    gsr::AdamBatch b{};
-    b.count = count;
-    b.w = w;
-    b.b2 = b2;
-    b.c = c;
-    b.eps = eps;
-    for (int i = 0; i < count; ++i) {
-        const GsrAdamTensor& t = tensors[i];
-        if (t.numel < 0) return fail(GSR_ERR_INVALID_ARG, "gsr_adam_step: tensor %d: numel %lld < 0", i, (long long)t.numel);
-        if (t.numel > 0 && (!t.param || !t.grad || !t.exp_avg || !t.exp_avg_sq))
-            return fail(GSR_ERR_INVALID_ARG, "gsr_adam_step: tensor %d: null pointer", i);
-        if (!aligned4(t.param) || !aligned4(t.grad) || !aligned4(t.exp_avg) || !aligned4(t.exp_avg_sq))
-            return fail(GSR_ERR_INVALID_ARG, "gsr_adam_step: tensor %d: misaligned pointer (4 bytes)", i);
-        const uintptr_t any = (uintptr_t)t.param | (uintptr_t)t.grad | (uintptr_t)t.exp_avg | (uintptr_t)t.exp_avg_sq;
-        b.t[i] = {t.param, t.grad, t.exp_avg, t.exp_avg_sq, t.numel, t.step_size, t.bias2_sqrt, (any & 15u) == 0u ? 1 : 0};
-        b.first_chunk[i + 1] = b.first_chunk[i] + gsr::adam_chunks(t.numel);   // numel == 0: no chunk, skipped
-    }
-    GSR_HIP(gsr::launch_adam_step(b, (hipStream_t)stream_));
-    return GSR_OK;
-}
-
-size_t gsr_densify_plan_scratch_bytes(int64_t n) {
-    return n <= 0 || n >= (int64_t(1) << 31) ? 0 : gsr::densify_plan_layout(n).bytes;
-}
-
-int gsr_densify_stats(int64_t n, const float* grad, int grad_row_floats, const uint8_t* filter, float* accum, float* denom,
-                      const int32_t* radii, float* max_radii, void* stream_) {
-    if (n < 0 || n >= (int64_t(1) << 31)) return fail(GSR_ERR_INVALID_ARG, "gsr_densify_stats: n = %lld outside [0, 2^31)", (long long)n);
-    if (grad_row_floats < 2) return fail(GSR_ERR_INVALID_ARG, "gsr_densify_stats: grad_row_floats = %d < 2", grad_row_floats);
-    if (n == 0) return GSR_OK;
-    if (!grad || !filter || !accum || !denom || (radii == nullptr) != (max_radii == nullptr))
-        return fail(GSR_ERR_INVALID_ARG, "gsr_densify_stats: null pointer (radii and max_radii go together)");
-    if (!aligned4(grad) || !aligned4(accum) || !aligned4(denom) || !aligned4(radii) || !aligned4(max_radii))
-        return fail(GSR_ERR_INVALID_ARG, "gsr_densify_stats: misaligned pointer (4 bytes)");
-    GSR_HIP(gsr::launch_densify_stats(n, grad, grad_row_floats, filter, accum, denom, radii, max_radii, (hipStream_t)stream_));
-    return GSR_OK;
-}
-
-int gsr_densify_plan(int64_t n, const float* accum, const float* denom, const float* scaling, const float* opacity, float max_grad,
-                     float dense_bound, float min_opacity, int ws_test, float ws_bound, int32_t* src_of, int32_t* split_idx,
-                     int32_t* counts, void* scratch, size_t scratch_bytes, void* stream_) {
-    if (n < 0 || n >= (int64_t(1) << 31)) return fail(GSR_ERR_INVALID_ARG, "gsr_densify_plan: n = %lld outside [0, 2^31)", (long long)n);
-    if (n == 0) return GSR_OK;
-    if (!accum || !denom || !scaling || !opacity || !src_of || !split_idx || !counts || !scratch)
-        return fail(GSR_ERR_INVALID_ARG, "gsr_densify_plan: null pointer");
-    if (!aligned4(accum) || !aligned4(denom) || !aligned4(scaling) || !aligned4(opacity) || !aligned4(src_of) || !aligned4(split_idx) ||
-        !aligned4(counts) || ((uintptr_t)scratch & 255u) != 0u)
-        return fail(GSR_ERR_INVALID_ARG, "gsr_densify_plan: misaligned pointer (arrays: 4 bytes, scratch: 256 bytes)");
-    const gsr::DensifyPlanLayout l = gsr::densify_plan_layout(n);
-    if (scratch_bytes < l.bytes) return fail(GSR_ERR_INVALID_ARG, "gsr_densify_plan: scratch too small (%zu of %zu bytes)", scratch_bytes, l.bytes);
-    char* base = (char*)scratch;
-    gsr::DensifyPlanArgs p{n, accum, denom, scaling, opacity, max_grad, dense_bound, min_opacity, ws_bound, ws_test ? 1 : 0, src_of, split_idx,
-                           counts, (uint8_t*)(base + l.flags), (uint32_t*)(base + l.block_counts), (uint32_t*)(base + l.block_offsets), l.blocks};
-    GSR_HIP(gsr::launch_densify_plan(p, (hipStream_t)stream_));
-    return GSR_OK;
-}
-
-int gsr_densify_apply(const GsrDensifyTensor* tensors, int count, const GsrDensifyPlan* plan, void* stream_) {
-    static_assert(GSR_DENSIFY_MAX_TENSORS == gsr::kDensifyMaxTensors, "gsr.h and gsr_internal.h");
-    if (count <= 0 || count > GSR_DENSIFY_MAX_TENSORS)
-        return fail(GSR_ERR_INVALID_ARG, "gsr_densify_apply: bad count %d (1..%d)", count, GSR_DENSIFY_MAX_TENSORS);
-    if (!tensors || !plan) return fail(GSR_ERR_INVALID_ARG, "gsr_densify_apply: null tensors or plan");
-    const GsrDensifyPlan& P = *plan;
-    const int64_t lim = int64_t(1) << 31;
-    if (P.n_src < 0 || P.n_src >= lim || P.n_split < 0 || P.n_split > P.n_src || P.n_keep < 0 || P.n_keep > P.n_front || P.n_front > P.n_out ||
-        P.n_out >= lim || P.n_out - P.n_front > 2 * P.n_split)
-        return fail(GSR_ERR_INVALID_ARG, "gsr_densify_apply: bad sizes (n_src %lld, n_keep %lld, n_front %lld, n_out %lld, n_split %lld)",
-                    (long long)P.n_src, (long long)P.n_keep, (long long)P.n_front, (long long)P.n_out, (long long)P.n_split);
-    if (P.n_out == 0) return GSR_OK;
-    if ((P.n_front > 0 && !P.src_of) || (P.n_out > P.n_front && (!P.child_rows || !P.split_idx)))
-        return fail(GSR_ERR_INVALID_ARG, "gsr_densify_apply: null index array");
-    if (!aligned4(P.src_of) || !aligned4(P.child_rows) || !aligned4(P.split_idx))
-        return fail(GSR_ERR_INVALID_ARG, "gsr_densify_apply: misaligned index array (4 bytes)");
-    gsr::DensifyApplyBatch b{};
-    b.count = count;
-    b.plan = {P.n_src, P.n_keep, P.n_front, P.n_out, P.n_split, P.src_of, P.child_rows, P.split_idx};
-    for (int i = 0; i < count; ++i) {
-        const GsrDensifyTensor& t = tensors[i];
-        if (t.floats_per_row < 0 || (int64_t)t.floats_per_row * P.n_out >= (int64_t(1) << 40))
-            return fail(GSR_ERR_INVALID_ARG, "gsr_densify_apply: tensor %d: floats_per_row %d", i, (int)t.floats_per_row);
-        if (t.floats_per_row > 0 && (!t.dst || (!t.src && !(t.is_moment && P.n_keep == 0) && P.n_src > 0)))
-            return fail(GSR_ERR_INVALID_ARG, "gsr_densify_apply: tensor %d: null pointer", i);
-        if (!aligned4(t.src) || !aligned4(t.dst) || !aligned4(t.side))
-            return fail(GSR_ERR_INVALID_ARG, "gsr_densify_apply: tensor %d: misaligned pointer (4 bytes)", i);
-        b.t[i] = {t.src, t.dst, t.side, t.floats_per_row, t.is_moment ? 1 : 0};
-        const int64_t floats = (int64_t)t.floats_per_row * P.n_out;
-        b.first_chunk[i + 1] = b.first_chunk[i] + (uint64_t)((floats + gsr::kDensifyApplyChunk - 1) / gsr::kDensifyApplyChunk);
-    }
-    GSR_HIP(gsr::launch_densify_apply(b, (hipStream_t)stream_));
-    return GSR_OK;
-}
-
-int gsr_view_normals(int P, const float* means3D, const float* axis, const float* cam_pos, float* colors, void* stream_) {
-    if (P < 0) return fail(GSR_ERR_INVALID_ARG, "bad size P=%d", P);
-    if (P == 0) return GSR_OK;
-    if (!means3D || !axis || !cam_pos || !colors) return fail(GSR_ERR_INVALID_ARG, "null pointer");
-    GSR_HIP(gsr::launch_view_normals(P, means3D, axis, cam_pos, colors, (hipStream_t)stream_));
-    return GSR_OK;
-}
-
-int gsr_normal_maps(int width, int height, const float* normal_rgb, const float* depth, const float* c2w, float fx,
-                    float fy, float cx, float cy, float* normal, float* pseudo_normal, void* stream_) {
-    if (width <= 0 || height <= 0) return fail(GSR_ERR_INVALID_ARG, "bad image size %dx%d", width, height);
-    if (!normal_rgb || !depth || !c2w || !normal || !pseudo_normal) return fail(GSR_ERR_INVALID_ARG, "null pointer");
-    GSR_HIP(gsr::launch_normal_maps(width, height, normal_rgb, depth, c2w, fx, fy, cx, cy, normal, pseudo_normal,
-                                    (hipStream_t)stream_));
-    return GSR_OK;
-}
-
-namespace {
-int place_impl(int n, const uint32_t* subset, const float* xyz, const float* rotation_raw, const float* log_scale, const float* opacity,
-               const float* shs, int M, const float* placement, float* out_means3D, float* out_scales, float* out_rotations,
-               float* out_opacities, float* out_shs, float* out_min_axis, void* stream_, bool placement_required) {
-    if (n < 0) return fail(GSR_ERR_INVALID_ARG, "bad size n=%d", n);
-    if (n == 0) return GSR_OK;
-    if (!xyz || !rotation_raw || !log_scale || !out_means3D || !out_scales || !out_rotations || (placement_required && !placement))
-        return fail(GSR_ERR_INVALID_ARG, "null pointer");
-    if ((out_opacities != nullptr) != (opacity != nullptr) || (out_shs != nullptr) != (shs != nullptr))
-        return fail(GSR_ERR_INVALID_ARG, "opacity / shs and their outputs must be given together");
-    if (shs != nullptr && M <= 0) return fail(GSR_ERR_INVALID_ARG, "shs given with M=%d", M);
-    gsr::ObjectPlacement pl = {};
-    static_assert(sizeof(gsr::ObjectPlacement) == 21 * sizeof(float), "the placement block is 21 floats");
-    if (placement != nullptr) memcpy(&pl, placement, sizeof pl);
-    GSR_HIP(gsr::launch_place_object(n, subset, placement != nullptr, xyz, rotation_raw, log_scale, opacity, shs, M, pl, out_means3D,
-                                     out_scales, out_rotations, out_opacities, out_shs, out_min_axis, (hipStream_t)stream_));
-    return GSR_OK;
-}
-} // namespace
-
-int gsr_place_object(int n, const float* xyz, const float* rotation_raw, const float* log_scale, const float* opacity, const float* shs,
-                     int M, const float* placement, float* out_means3D, float* out_scales, float* out_rotations, float* out_opacities,
-                     float* out_shs, float* out_min_axis, void* stream_) {
-    return place_impl(n, nullptr, xyz, rotation_raw, log_scale, opacity, shs, M, placement, out_means3D, out_scales, out_rotations,
-                      out_opacities, out_shs, out_min_axis, stream_, true);
-}
-
-int gsr_place_object_subset(int m, const uint32_t* subset, const float* xyz, const float* rotation_raw, const float* log_scale,
-                            const float* opacity, const float* shs, int M, const float* placement, float* out_means3D,
-                            float* out_scales, float* out_rotations, float* out_opacities, float* out_shs, float* out_min_axis,
-                            void* stream_) {
-    if (m > 0 && !subset) return fail(GSR_ERR_INVALID_ARG, "null subset");
-    return place_impl(m, subset, xyz, rotation_raw, log_scale, opacity, shs, M, placement, out_means3D, out_scales, out_rotations,
-                      out_opacities, out_shs, out_min_axis, stream_, false);
-}
-
-int gsr_selftest_exp(uint32_t first_bits, uint32_t count, unsigned long long* device_mismatches, void* stream_) {
-    if (!device_mismatches || count > 0x7FFFFFFFu) return fail(GSR_ERR_INVALID_ARG, "bad selftest arguments");
-    if (count == 0) return GSR_OK;
-    GSR_HIP(gsr::launch_exp_selftest(first_bits, count, device_mismatches, (hipStream_t)stream_));
-    return GSR_OK;
-}
-
-int gsr_selftest_lds_atomic_order(uint32_t workgroups, uint32_t rounds, uint32_t seed, unsigned long long* device_mismatches, void* stream_) {
-    if (!device_mismatches || workgroups == 0 || workgroups > (1u << 20)) return fail(GSR_ERR_INVALID_ARG, "bad selftest arguments");
-    GSR_HIP(gsr::launch_lds_atomic_order_selftest(workgroups, rounds, seed, device_mismatches, (hipStream_t)stream_));
-    return GSR_OK;
-}
-
-int gsr_resize_rgba8_bilinear(const uint8_t* src, int src_w, int src_h, uint8_t* dst, int dst_w, int dst_h, uint8_t* tmp, void* stream_) {
-    if (src_w <= 0 || src_h <= 0 || dst_w <= 0 || dst_h <= 0) return fail(GSR_ERR_INVALID_ARG, "bad image size %dx%d -> %dx%d", src_w, src_h, dst_w, dst_h);
-    if (!src || !dst || (!tmp && src_w != dst_w && src_h != dst_h)) return fail(GSR_ERR_INVALID_ARG, "null pointer");
-    GSR_HIP(gsr::launch_resize_rgba8_bilinear(src, src_w, src_h, dst, dst_w, dst_h, tmp, (hipStream_t)stream_));
-    return GSR_OK;
-}
-
-int gsr_resize_f32_nearest(const float* src, int src_w, int src_h, float* dst, int dst_w, int dst_h, void* stream_) {
-    if (src_w <= 0 || src_h <= 0 || dst_w <= 0 || dst_h <= 0) return fail(GSR_ERR_INVALID_ARG, "bad image size %dx%d -> %dx%d", src_w, src_h, dst_w, dst_h);
-    if (!src || !dst) return fail(GSR_ERR_INVALID_ARG, "null pointer");
-    GSR_HIP(gsr::launch_resize_f32_nearest(src, src_w, src_h, dst, dst_w, dst_h, (hipStream_t)stream_));
-    return GSR_OK;
-}
-
-int gsr_frame_files(const float* color, const float* alpha, const float* depth, const float* normal, float depth_scale, const uint8_t* turbo_lut,
-                    int width, int height, uint8_t* png_rgba, uint8_t* png_depth_preview, uint8_t* png_normal, float* npy_plane, uint8_t* work,
-                    void* stream_) {
-    if (width <= 0 || height <= 0 || gsr::png_file_bytes(width, height, 4) == 0) return fail(GSR_ERR_INVALID_ARG, "bad image size %dx%d", width, height);
-    if (!color || !alpha || !depth || !normal || !turbo_lut || !png_rgba || !png_depth_preview || !png_normal || !npy_plane || !work)
-        return fail(GSR_ERR_INVALID_ARG, "null pointer");
-    if (((reinterpret_cast<uintptr_t>(png_rgba) | reinterpret_cast<uintptr_t>(png_depth_preview) | reinterpret_cast<uintptr_t>(png_normal)) & 15u) != 0)
-        return fail(GSR_ERR_INVALID_ARG, "gsr_frame_files: the PNG buffers must be 16-byte aligned");
-    if (!(depth_scale > 0.0f)) return fail(GSR_ERR_INVALID_ARG, "gsr_frame_files: depth_scale must be positive");
-    GSR_HIP(gsr::launch_frame_files(color, alpha, depth, normal, depth_scale, turbo_lut, width, height, png_rgba, png_depth_preview, png_normal,
-                                    npy_plane, work, nullptr, nullptr, (hipStream_t)stream_));
-    return GSR_OK;
-}
-
-int gsr_frame_files_deflate(const float* color, const float* alpha, const float* depth, const float* normal, float depth_scale, const uint8_t* turbo_lut,
-                            int width, int height, uint8_t* png_rgba, uint8_t* png_depth_preview, uint8_t* png_normal, float* npy_plane, uint8_t* work,
-                            uint8_t* png_scratch, uint64_t* png_lengths, void* stream_) {
-    if (width <= 0 || height <= 0 || gsr::png_deflate_max_bytes(width, height, 4) == 0) return fail(GSR_ERR_INVALID_ARG, "bad image size %dx%d", width, height);
-    if (!color || !alpha || !depth || !normal || !turbo_lut || !png_rgba || !png_depth_preview || !png_normal || !npy_plane || !work || !png_scratch || !png_lengths)
-        return fail(GSR_ERR_INVALID_ARG, "null pointer");
-    if (((reinterpret_cast<uintptr_t>(png_rgba) | reinterpret_cast<uintptr_t>(png_depth_preview) | reinterpret_cast<uintptr_t>(png_normal) |
-          reinterpret_cast<uintptr_t>(png_scratch)) & 15u) != 0 ||
-        (reinterpret_cast<uintptr_t>(png_lengths) & 7u) != 0)
-        return fail(GSR_ERR_INVALID_ARG, "gsr_frame_files_deflate: the PNG buffers must be 16-byte aligned, the lengths 8-byte aligned");
-    if (!(depth_scale > 0.0f)) return fail(GSR_ERR_INVALID_ARG, "gsr_frame_files_deflate: depth_scale must be positive");
-    GSR_HIP(gsr::launch_frame_files(color, alpha, depth, normal, depth_scale, turbo_lut, width, height, png_rgba, png_depth_preview, png_normal,
-                                    npy_plane, work, png_scratch, reinterpret_cast<unsigned long long*>(png_lengths), (hipStream_t)stream_));
-    return GSR_OK;
-}
-
-size_t gsr_png_deflate_max_size(int width, int height, int channels) { return gsr::png_deflate_max_bytes(width, height, channels); }
-size_t gsr_png_deflate_room(int width, int height, int channels) { return gsr::png_deflate_room_bytes(width, height, channels); }
-size_t gsr_png_deflate_scratch(int width, int height, int channels) { return gsr::png_deflate_scratch_bytes(width, height, channels); }
-
-int gsr_png_encode_deflate(const uint8_t* pixels, int width, int height, int channels, int planar, uint8_t* out, uint8_t* scratch, uint64_t* out_len,
-                           void* stream_) {
-    if (gsr::png_deflate_max_bytes(width, height, channels) == 0)
-        return fail(GSR_ERR_INVALID_ARG, "gsr_png_encode_deflate: %dx%d with %d channels cannot be encoded (3 or 4 channels, < 2 GB)", width, height, channels);
-    if (!pixels || !out || !scratch || !out_len) return fail(GSR_ERR_INVALID_ARG, "null pointer");
-    if (((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(scratch)) & 15u) != 0 || (reinterpret_cast<uintptr_t>(out_len) & 7u) != 0)
-        return fail(GSR_ERR_INVALID_ARG, "gsr_png_encode_deflate: out and scratch must be 16-byte aligned, out_len 8-byte aligned");
-    GSR_HIP(gsr::launch_png_encode_deflate(pixels, width, height, channels, planar, out, scratch, reinterpret_cast<unsigned long long*>(out_len),
-                                           (hipStream_t)stream_));
-    return GSR_OK;
-}
-
-size_t gsr_png_unfilter_scratch(int width, int height) { return gsr::png_unfilter_scratch_bytes(width, height); }
-
-static_assert(sizeof(GsrPngUnfilterJob) == sizeof(gsr::PngUnfilterJob), "GsrPngUnfilterJob is passed through as it is");
-
-int gsr_png_unfilter_batch(int count, const GsrPngUnfilterJob* jobs, void* stream_) {
-    if (count < 0 || (count > 0 && !jobs)) return fail(GSR_ERR_INVALID_ARG, "gsr_png_unfilter_batch: bad job list");
-    for (int i = 0; i < count; ++i) {
-        const GsrPngUnfilterJob& j = jobs[i];
-        if (gsr::png_unfilter_scratch_bytes(j.width, j.height) == 0 || (j.channels != 3 && j.channels != 4))
-            return fail(GSR_ERR_INVALID_ARG, "gsr_png_unfilter: job %d: %dx%d with %d channels is not supported (8-bit RGB / RGBA, at most 4096 pixels wide)", i,
-                        j.width, j.height, j.channels);
-        if (!j.scanlines || !j.out_rgba || !j.scratch) return fail(GSR_ERR_INVALID_ARG, "gsr_png_unfilter: job %d: null pointer", i);
-        if (((reinterpret_cast<uintptr_t>(j.out_rgba) | reinterpret_cast<uintptr_t>(j.scratch)) & 15u) != 0)
-            return fail(GSR_ERR_INVALID_ARG, "gsr_png_unfilter: job %d: out_rgba and scratch must be 16-byte aligned", i);
-    }
-    if (count == 0) return GSR_OK;
-    GSR_HIP(gsr::launch_png_unfilter_batch(count, reinterpret_cast<const gsr::PngUnfilterJob*>(jobs), (hipStream_t)stream_));
-    return GSR_OK;
-}
-
-int gsr_png_unfilter(const uint8_t* scanlines, int width, int height, int channels, uint8_t* out_rgba, uint8_t* scratch, void* stream_) {
-    const GsrPngUnfilterJob job = {scanlines, width, height, channels, out_rgba, scratch};
-    return gsr_png_unfilter_batch(1, &job, stream_);
-}
-
-int gsr_exr_unpack_channel(const uint8_t* blocks, int height, int bytes_per_line, int lines_per_block, int channel_at, int channel_bytes, uint8_t* plane,
-                           void* stream_) {
-    if (height <= 0 || bytes_per_line <= 0 || (bytes_per_line & 1) || lines_per_block <= 0 || channel_at < 0 || channel_bytes <= 0 ||
-        channel_at + channel_bytes > bytes_per_line || (long long)bytes_per_line * lines_per_block > (1ll << 30))
-        return fail(GSR_ERR_INVALID_ARG, "gsr_exr_unpack_channel: bad layout (height %d, %d bytes per line, %d lines per block, channel at %d + %d)", height,
-                    bytes_per_line, lines_per_block, channel_at, channel_bytes);
-    if (!blocks || !plane) return fail(GSR_ERR_INVALID_ARG, "null pointer");
-    GSR_HIP(gsr::launch_exr_unpack_channel(blocks, height, bytes_per_line, lines_per_block, channel_at, channel_bytes, plane, (hipStream_t)stream_));
-    return GSR_OK;
-}
-
-static_assert(sizeof(GsrPngFileInfo) == sizeof(gsr::PngFileLayout) && sizeof(GsrExrFileInfo) == sizeof(gsr::ExrFileLayout), "file infos are passed through");
-
-int gsr_png_file_probe(const uint8_t* file, size_t file_bytes, GsrPngFileInfo* info) {
-    if (!file || !info) return fail(GSR_ERR_INVALID_ARG, "null pointer");
-    return gsr::png_file_probe(file, file_bytes, reinterpret_cast<gsr::PngFileLayout*>(info));
-}
-
-int gsr_png_file_inflate(const uint8_t* file, size_t file_bytes, uint8_t* scanlines, size_t scanline_bytes) {
-    if (!file || !scanlines) return fail(GSR_ERR_INVALID_ARG, "null pointer");
-    return gsr::png_file_inflate(file, file_bytes, scanlines, scanline_bytes);
-}
-
-int gsr_exr_file_probe(const uint8_t* file, size_t file_bytes, const char* channel, GsrExrFileInfo* info) {
-    if (!file || !info) return fail(GSR_ERR_INVALID_ARG, "null pointer");
-    return gsr::exr_file_probe(file, file_bytes, channel, reinterpret_cast<gsr::ExrFileLayout*>(info));
-}
-
-int gsr_exr_file_inflate(const uint8_t* file, size_t file_bytes, const char* channel, uint8_t* blocks, size_t blocks_bytes) {
-    if (!file || !blocks) return fail(GSR_ERR_INVALID_ARG, "null pointer");
-    return gsr::exr_file_inflate(file, file_bytes, channel, blocks, blocks_bytes);
-}
-
-static_assert(sizeof(GsrInflateJob) == sizeof(gsr::InflateJob), "GsrInflateJob is passed through as it is");
-
-int gsr_exr_file_pack(const uint8_t* file, size_t file_bytes, const char* channel, uint8_t* packed, size_t packed_room, GsrInflateJob* jobs, size_t* packed_bytes) {
-    if (!file || !packed || !jobs || !packed_bytes) return fail(GSR_ERR_INVALID_ARG, "null pointer");
-    return gsr::exr_file_pack(file, file_bytes, channel, packed, packed_room, reinterpret_cast<gsr::InflateJob*>(jobs), packed_bytes);
-}
-
-int gsr_inflate_zlib_blocks(const uint8_t* streams, uint8_t* out, const GsrInflateJob* jobs, int count, int* status, int* any_error, void* stream_) {
-    if (count < 0 || (count > 0 && (!streams || !out || !jobs || !status))) return fail(GSR_ERR_INVALID_ARG, "gsr_inflate_zlib_blocks: bad arguments");
-    if ((reinterpret_cast<uintptr_t>(streams) & 3u) != 0) return fail(GSR_ERR_INVALID_ARG, "gsr_inflate_zlib_blocks: streams must be 4-byte aligned");
-    GSR_HIP(gsr::launch_inflate_zlib_blocks(streams, out, reinterpret_cast<const gsr::InflateJob*>(jobs), count, status, any_error, (hipStream_t)stream_));
-    return GSR_OK;
-}
-
-int gsr_selftest_inflate_host(const uint8_t* zlib_stream, size_t stream_bytes, uint8_t* out, size_t out_bytes) {
-    if (!zlib_stream || (!out && out_bytes)) return fail(GSR_ERR_INVALID_ARG, "null pointer");
-    return gsr::inflate_zlib_host(zlib_stream, stream_bytes, out, out_bytes);
-}
-
 int gsr_upload(void* device_dst, const void* host_src, size_t bytes, void* stream_) {
     if (bytes == 0) return GSR_OK;
     if (!device_dst || !host_src) return fail(GSR_ERR_INVALID_ARG, "null pointer");
     GSR_HIP(hipMemcpyAsync(device_dst, host_src, bytes, hipMemcpyHostToDevice, (hipStream_t)stream_));
-    return GSR_OK;
-}
-
-size_t gsr_png_size(int width, int height, int channels) { return gsr::png_file_bytes(width, height, channels); }
-size_t gsr_png_room(int width, int height, int channels) { return gsr::png_room_bytes(width, height, channels); }
-
-int gsr_png_encode(const uint8_t* pixels, int width, int height, int channels, int planar, uint8_t* out, void* stream_) {
-    const size_t n = gsr::png_file_bytes(width, height, channels);
-    if (n == 0) return fail(GSR_ERR_INVALID_ARG, "gsr_png_encode: %dx%d with %d channels cannot be encoded (3 or 4 channels, < 2 GB)", width, height, channels);
-    if (!pixels || !out) return fail(GSR_ERR_INVALID_ARG, "null pointer");
-    if ((reinterpret_cast<uintptr_t>(out) & 15u) != 0) return fail(GSR_ERR_INVALID_ARG, "gsr_png_encode: out must be 16-byte aligned");
-    GSR_HIP(gsr::launch_png_encode(pixels, width, height, channels, planar, out, (hipStream_t)stream_));
-    return GSR_OK;
-}
-
-int gsr_cube_to_equirect(const float* const* faces, int face_size, int channels, const float* const* depth_faces, const float* grid_u,
-                         const float* grid_v, const int32_t* grid_ceil, int height, int width, float* out, uint8_t* out_u8, float* out_depth,
-                         void* stream_) {
-    if (width <= 0 || width % 8 != 0) return fail(GSR_ERR_INVALID_ARG, "gsr_cube_to_equirect: the width (%d) must be a positive multiple of 8", width);
-    if (height < 2 || height > 65535) return fail(GSR_ERR_INVALID_ARG, "gsr_cube_to_equirect: bad height %d (2 .. 65535)", height);
-    if (face_size < 2 || face_size > 32768) return fail(GSR_ERR_INVALID_ARG, "gsr_cube_to_equirect: bad face size %d (2 .. 32768)", face_size);
-    if (channels < 1 || channels > 4) return fail(GSR_ERR_INVALID_ARG, "gsr_cube_to_equirect: %d channels (1 .. 4)", channels);
-    if (!faces || !grid_u || !grid_v || !grid_ceil || (!out && !out_u8 && !out_depth) || (out_depth && !depth_faces))
-        return fail(GSR_ERR_INVALID_ARG, "null pointer");
-    gsr::CubeFacePointers f = {}, d = {};
-    for (int k = 0; k < 6; ++k) {
-        if (!(f.p[k] = faces[k])) return fail(GSR_ERR_INVALID_ARG, "gsr_cube_to_equirect: face %d is null", k);
-        if (out_depth && !(d.p[k] = depth_faces[k])) return fail(GSR_ERR_INVALID_ARG, "gsr_cube_to_equirect: depth face %d is null", k);
-    }
-    GSR_HIP(gsr::launch_cube_to_equirect(f, d, face_size, channels, grid_u, grid_v, grid_ceil, height, width, out, out_u8, out_depth,
-                                         (hipStream_t)stream_));
-    return GSR_OK;
-}
-
-int gsr_pack_rgba8(const float* color, const float* alpha, uint8_t* rgba8, int width, int height, void* stream_) {
-    if (width <= 0 || height <= 0) return fail(GSR_ERR_INVALID_ARG, "bad image size %dx%d", width, height);
-    if (!color || !alpha || !rgba8) return fail(GSR_ERR_INVALID_ARG, "null pointer");
-    GSR_HIP(gsr::launch_pack_rgba8(color, alpha, rgba8, (size_t)width * height, (hipStream_t)stream_));
     return GSR_OK;
 }
 

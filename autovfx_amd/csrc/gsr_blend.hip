@@ -28,6 +28,7 @@
 // scalar load) and, when it completes its tile, the tile in `done_rows`, which is what lets the next slab drop that
 // tile's pairs before they are expanded.  A pixel's sequence of operations is exactly that of one walk over the
 // concatenated list: same bits.
+// Defines the entry point gsr_selftest_exp.
 #include "gsr_device.h"
 
 // Profiling aid (python -m autovfx_amd.build --trace, scripts/kernel_trace.py --blend): every single-wave workgroup stamps the
@@ -321,9 +322,23 @@ hipError_t launch_blend(const Camera& cam, const BlendSegments& segs, int seg_be
     return hipGetLastError();
 }
 
-hipError_t launch_exp_selftest(uint32_t first_bits, uint32_t count, unsigned long long* mismatches, hipStream_t stream) {
+// counts the floats with bit patterns first_bits .. first_bits + count - 1 on which the blend's exp differs from expf
+static hipError_t launch_exp_selftest(uint32_t first_bits, uint32_t count, unsigned long long* mismatches, hipStream_t stream) {
     hipLaunchKernelGGL(exp_selftest_kernel, dim3(div_up((int)count, 256)), dim3(256), 0, stream, first_bits, count, mismatches);
     return hipGetLastError();
 }
 
 } // namespace gsr
+
+using gsr::fail;
+
+extern "C" {
+
+int gsr_selftest_exp(uint32_t first_bits, uint32_t count, unsigned long long* device_mismatches, void* stream_) {
+    if (!device_mismatches || count > 0x7FFFFFFFu) return fail(GSR_ERR_INVALID_ARG, "bad selftest arguments");
+    if (count == 0) return GSR_OK;
+    GSR_HIP(gsr::launch_exp_selftest(first_bits, count, device_mismatches, (hipStream_t)stream_));
+    return GSR_OK;
+}
+
+}  // extern "C"

@@ -12,6 +12,7 @@
 // Roundings are the ones PyTorch-ROCm's kernels make for the reference's expressions (gsr_device.h:183-193): torch.norm over a last
 // dimension of 2 squares each element in a lane of its own and adds the two, so sqrt(fl(x*x) + fl(y*y)); exp / sigmoid are the
 // device library's (torch_sigmoid); Python scalars arrive rounded to fp32 as a wrapped scalar is for an fp32 comparison.
+// Defines the entry points gsr_densify_plan_scratch_bytes, gsr_densify_stats, gsr_densify_plan and gsr_densify_apply.
 #include "gsr_internal.h"
 #include "gsr_device.h"
 
@@ -22,7 +23,49 @@ constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr int kRowsPerLane = 4;
 constexpr uint32_t kMaxGrid = 2048;   // 256 CUs x 8 workgroups; more work is walked grid-stride
-static_assert(kDensifyBlockRows == kThreads * kRowsPerLane, "gsr_internal.h");
+constexpr int kDensifyBlockRows = 1024;       // source rows per workgroup of the plan's classify / scatter kernels
+static_assert(kDensifyBlockRows == kThreads * kRowsPerLane, "one lane classifies kRowsPerLane rows");
+struct DensifyPlanArgs {   // gsr.h: gsr_densify_plan; passed by value
+    int64_t n;
+    const float *accum, *denom, *scaling, *opacity;
+    float max_grad, dense_bound, min_opacity, ws_bound;
+    int ws_test;
+    int32_t *src_of, *split_idx, *counts;
+    uint8_t* flags;                           // scratch: [n] class bits
+    uint32_t *block_counts, *block_offsets;   // scratch: [3][blocks] each
+    uint32_t blocks;
+};
+// Byte offsets of the regions of the plan's scratch (each 256-byte aligned); bytes = the whole.
+struct DensifyPlanLayout {
+    size_t flags, block_counts, block_offsets, bytes;
+    uint32_t blocks;
+};
+inline DensifyPlanLayout densify_plan_layout(int64_t n) {
+    DensifyPlanLayout l{};
+    l.blocks = (uint32_t)((n + kDensifyBlockRows - 1) / kDensifyBlockRows);
+    auto up = [](size_t x) { return (x + 255) & ~size_t(255); };
+    l.flags = 0;
+    l.block_counts = up((size_t)n);
+    l.block_offsets = l.block_counts + up((size_t)3 * l.blocks * sizeof(uint32_t));
+    l.bytes = l.block_offsets + up((size_t)3 * l.blocks * sizeof(uint32_t));
+    return l;
+}
+struct DensifyTensor {
+    const float* src;
+    float* dst;
+    const float* side;   // the children's rows of this tensor ([2 n_split, floats_per_row]); null: copied from the parent
+    int floats_per_row, is_moment;
+};
+struct DensifyApplyPlan {
+    int64_t n_src, n_keep, n_front, n_out, n_split;
+    const int32_t *src_of, *child_rows, *split_idx;
+};
+struct DensifyApplyBatch {   // passed by value (kernel arguments)
+    DensifyTensor t[GSR_DENSIFY_MAX_TENSORS];
+    uint64_t first_chunk[GSR_DENSIFY_MAX_TENSORS + 1];
+    DensifyApplyPlan plan;
+    int count;
+};
 
 // ---------------------------------------------------------------------------------------------------------------- stats
 __device__ __forceinline__ void stats_row(bool on, float gx, float gy, float& accum, float& denom) {
@@ -204,8 +247,7 @@ __global__ __launch_bounds__(kThreads) void densify_scatter_kernel(const Densify
 
 // ---------------------------------------------------------------------------------------------------------------- apply
 constexpr int kApplyUnroll = 8;
-constexpr int64_t kApplyChunk = (int64_t)kThreads * kApplyUnroll;
-static_assert(kApplyChunk == kDensifyApplyChunk, "gsr_internal.h");
+constexpr int64_t kApplyChunk = (int64_t)kThreads * kApplyUnroll;   // output floats per workgroup iteration of the apply kernel
 
 // The value of element (row, col) of output tensor T.  Rows [0, n_keep) are kept originals, [n_keep, n_front) clones, the rest
 // children: child_rows gives the child's row in the side tensors ([2S, ...], copy-major), its parent is split_idx[that mod S].
@@ -262,8 +304,6 @@ __global__ __launch_bounds__(kThreads) void densify_apply_kernel(const DensifyAp
     }
 }
 
-}  // namespace
-
 hipError_t launch_densify_stats(int64_t n, const float* grad, int row_floats, const uint8_t* filter, float* accum, float* denom,
                                 const int* radii, float* max_radii, hipStream_t stream) {
     const uintptr_t any = (uintptr_t)grad | (uintptr_t)accum | (uintptr_t)denom | (uintptr_t)radii | (uintptr_t)max_radii;
@@ -288,4 +328,82 @@ hipError_t launch_densify_apply(const DensifyApplyBatch& b, hipStream_t stream) 
     return hipGetLastError();
 }
 
+}  // namespace
 }  // namespace gsr
+
+using gsr::aligned4;
+using gsr::fail;
+
+extern "C" {
+
+size_t gsr_densify_plan_scratch_bytes(int64_t n) {
+    return n <= 0 || n >= (int64_t(1) << 31) ? 0 : gsr::densify_plan_layout(n).bytes;
+}
+
+int gsr_densify_stats(int64_t n, const float* grad, int grad_row_floats, const uint8_t* filter, float* accum, float* denom,
+                      const int32_t* radii, float* max_radii, void* stream_) {
+    if (n < 0 || n >= (int64_t(1) << 31)) return fail(GSR_ERR_INVALID_ARG, "gsr_densify_stats: n = %lld outside [0, 2^31)", (long long)n);
+    if (grad_row_floats < 2) return fail(GSR_ERR_INVALID_ARG, "gsr_densify_stats: grad_row_floats = %d < 2", grad_row_floats);
+    if (n == 0) return GSR_OK;
+    if (!grad || !filter || !accum || !denom || (radii == nullptr) != (max_radii == nullptr))
+        return fail(GSR_ERR_INVALID_ARG, "gsr_densify_stats: null pointer (radii and max_radii go together)");
+    if (!aligned4(grad) || !aligned4(accum) || !aligned4(denom) || !aligned4(radii) || !aligned4(max_radii))
+        return fail(GSR_ERR_INVALID_ARG, "gsr_densify_stats: misaligned pointer (4 bytes)");
+    GSR_HIP(gsr::launch_densify_stats(n, grad, grad_row_floats, filter, accum, denom, radii, max_radii, (hipStream_t)stream_));
+    return GSR_OK;
+}
+
+int gsr_densify_plan(int64_t n, const float* accum, const float* denom, const float* scaling, const float* opacity, float max_grad,
+                     float dense_bound, float min_opacity, int ws_test, float ws_bound, int32_t* src_of, int32_t* split_idx,
+                     int32_t* counts, void* scratch, size_t scratch_bytes, void* stream_) {
+    if (n < 0 || n >= (int64_t(1) << 31)) return fail(GSR_ERR_INVALID_ARG, "gsr_densify_plan: n = %lld outside [0, 2^31)", (long long)n);
+    if (n == 0) return GSR_OK;
+    if (!accum || !denom || !scaling || !opacity || !src_of || !split_idx || !counts || !scratch)
+        return fail(GSR_ERR_INVALID_ARG, "gsr_densify_plan: null pointer");
+    if (!aligned4(accum) || !aligned4(denom) || !aligned4(scaling) || !aligned4(opacity) || !aligned4(src_of) || !aligned4(split_idx) ||
+        !aligned4(counts) || ((uintptr_t)scratch & 255u) != 0u)
+        return fail(GSR_ERR_INVALID_ARG, "gsr_densify_plan: misaligned pointer (arrays: 4 bytes, scratch: 256 bytes)");
+    const gsr::DensifyPlanLayout l = gsr::densify_plan_layout(n);
+    if (scratch_bytes < l.bytes) return fail(GSR_ERR_INVALID_ARG, "gsr_densify_plan: scratch too small (%zu of %zu bytes)", scratch_bytes, l.bytes);
+    char* base = (char*)scratch;
+    gsr::DensifyPlanArgs p{n, accum, denom, scaling, opacity, max_grad, dense_bound, min_opacity, ws_bound, ws_test ? 1 : 0, src_of, split_idx,
+                           counts, (uint8_t*)(base + l.flags), (uint32_t*)(base + l.block_counts), (uint32_t*)(base + l.block_offsets), l.blocks};
+    GSR_HIP(gsr::launch_densify_plan(p, (hipStream_t)stream_));
+    return GSR_OK;
+}
+
+int gsr_densify_apply(const GsrDensifyTensor* tensors, int count, const GsrDensifyPlan* plan, void* stream_) {
+    if (count <= 0 || count > GSR_DENSIFY_MAX_TENSORS)
+        return fail(GSR_ERR_INVALID_ARG, "gsr_densify_apply: bad count %d (1..%d)", count, GSR_DENSIFY_MAX_TENSORS);
+    if (!tensors || !plan) return fail(GSR_ERR_INVALID_ARG, "gsr_densify_apply: null tensors or plan");
+    const GsrDensifyPlan& P = *plan;
+    const int64_t lim = int64_t(1) << 31;
+    if (P.n_src < 0 || P.n_src >= lim || P.n_split < 0 || P.n_split > P.n_src || P.n_keep < 0 || P.n_keep > P.n_front || P.n_front > P.n_out ||
+        P.n_out >= lim || P.n_out - P.n_front > 2 * P.n_split)
+        return fail(GSR_ERR_INVALID_ARG, "gsr_densify_apply: bad sizes (n_src %lld, n_keep %lld, n_front %lld, n_out %lld, n_split %lld)",
+                    (long long)P.n_src, (long long)P.n_keep, (long long)P.n_front, (long long)P.n_out, (long long)P.n_split);
+    if (P.n_out == 0) return GSR_OK;
+    if ((P.n_front > 0 && !P.src_of) || (P.n_out > P.n_front && (!P.child_rows || !P.split_idx)))
+        return fail(GSR_ERR_INVALID_ARG, "gsr_densify_apply: null index array");
+    if (!aligned4(P.src_of) || !aligned4(P.child_rows) || !aligned4(P.split_idx))
+        return fail(GSR_ERR_INVALID_ARG, "gsr_densify_apply: misaligned index array (4 bytes)");
+    gsr::DensifyApplyBatch b{};
+    b.count = count;
+    b.plan = {P.n_src, P.n_keep, P.n_front, P.n_out, P.n_split, P.src_of, P.child_rows, P.split_idx};
+    for (int i = 0; i < count; ++i) {
+        const GsrDensifyTensor& t = tensors[i];
+        if (t.floats_per_row < 0 || (int64_t)t.floats_per_row * P.n_out >= (int64_t(1) << 40))
+            return fail(GSR_ERR_INVALID_ARG, "gsr_densify_apply: tensor %d: floats_per_row %d", i, (int)t.floats_per_row);
+        if (t.floats_per_row > 0 && (!t.dst || (!t.src && !(t.is_moment && P.n_keep == 0) && P.n_src > 0)))
+            return fail(GSR_ERR_INVALID_ARG, "gsr_densify_apply: tensor %d: null pointer", i);
+        if (!aligned4(t.src) || !aligned4(t.dst) || !aligned4(t.side))
+            return fail(GSR_ERR_INVALID_ARG, "gsr_densify_apply: tensor %d: misaligned pointer (4 bytes)", i);
+        b.t[i] = {t.src, t.dst, t.side, t.floats_per_row, t.is_moment ? 1 : 0};
+        const int64_t floats = (int64_t)t.floats_per_row * P.n_out;
+        b.first_chunk[i + 1] = b.first_chunk[i] + (uint64_t)((floats + gsr::kApplyChunk - 1) / gsr::kApplyChunk);
+    }
+    GSR_HIP(gsr::launch_densify_apply(b, (hipStream_t)stream_));
+    return GSR_OK;
+}
+
+}  // extern "C"

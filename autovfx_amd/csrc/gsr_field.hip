@@ -26,6 +26,7 @@
 //                           add into one line (4 lines of 64 bytes per wave-instruction) instead of 64 lanes into 64 lines, which
 //                           was measured 13 x slower.  Exact zeros are not added.
 // No host synchronisation, no allocation, everything on the caller's stream.
+// Defines the entry points gsr_field_scratch_bytes, gsr_field_forward and gsr_field_backward.
 #include "gsr_internal.h"
 
 namespace gsr {
@@ -36,6 +37,16 @@ constexpr int kRound = 16;             // neighbour slots staged per round
 constexpr int kPitch = kRound + 1;     // LDS row pitch in words: lane l reads word l * 17 + kk
 constexpr int kLine = 16;              // floats per packed record and per accumulator line
 constexpr int kGrads = 14;             // of which are gradients: dc 0-2, dM 3-11, dsigma 12, dm 13
+constexpr int kFieldMaxK = 64;
+struct FieldInputs {
+    int64_t n;                   // samples, 0 < n < 2^30
+    int K;                       // neighbour slots per sample, 1 .. kFieldMaxK
+    int64_t P;                   // Gaussians, 0 <= P < 2^30
+    const float* x;              // [n,3]
+    const long long* idx;        // [n,K]; a slot outside [0, P) is skipped
+    const float *centers, *M, *strengths, *min_scaling;   // [P,3], [P,3,3], [P], [P] or null
+    float density_factor;
+};
 
 __global__ __launch_bounds__(kThreads) void field_pack_kernel(uint32_t P, const float* __restrict__ centers, const float* __restrict__ M,
                                                               const float* __restrict__ strengths, const float* __restrict__ min_scaling,
@@ -236,8 +247,7 @@ hipError_t pack(const FieldInputs& in, void* scratch, hipStream_t stream) {
     return hipGetLastError();
 }
 
-}  // namespace
-
+// scratch: field_scratch_bytes(P) bytes (one 64-byte record per Gaussian), 256-byte aligned, any content; both calls fill it themselves.
 size_t field_scratch_bytes(int64_t P) { return (size_t)(P > 0 ? P : 1) * kLine * sizeof(float); }
 
 hipError_t launch_field_forward(const FieldInputs& in, float* density, float* opacities, float* beta, void* scratch, hipStream_t stream) {
@@ -249,6 +259,8 @@ hipError_t launch_field_forward(const FieldInputs& in, float* density, float* op
     return hipGetLastError();
 }
 
+// accum [P,16], zeroed by the caller, 64-byte aligned: floats 0-2 of a line dL/dcentre, 3-11 dL/dM row-major, 12 dL/dstrength,
+// 13 dL/dmin_scaling.
 hipError_t launch_field_backward(const FieldInputs& in, const float* g_density, const float* g_opacities, const float* g_beta, float* dx,
                                  float* accum, void* scratch, hipStream_t stream) {
     hipError_t e = pack(in, scratch, stream);
@@ -259,4 +271,62 @@ hipError_t launch_field_backward(const FieldInputs& in, const float* g_density, 
     return hipGetLastError();
 }
 
+}  // namespace
 }  // namespace gsr
+
+using gsr::fail;
+
+namespace {
+// What gsr_field_forward and gsr_field_backward check alike; 1: n == 0, nothing to do.
+int field_check(const char* who, const gsr::FieldInputs& in, bool wants_beta, const void* scratch, size_t scratch_bytes) {
+    if (in.K < 1 || in.K > gsr::kFieldMaxK) return fail(GSR_ERR_INVALID_ARG, "%s: K = %d (1 to %d)", who, in.K, gsr::kFieldMaxK);
+    if (in.n < 0 || in.P < 0) return fail(GSR_ERR_INVALID_ARG, "%s: negative count (n %lld, P %lld)", who, (long long)in.n, (long long)in.P);
+    if (in.n >= (int64_t)gsr::kKnn3MaxPoints || in.P >= (int64_t)gsr::kKnn3MaxPoints)
+        return fail(GSR_ERR_INVALID_ARG, "%s: %lld samples and %lld Gaussians (at most 2^30 - 1 each)", who, (long long)in.n, (long long)in.P);
+    if (in.n == 0) return 1;
+    if (!in.x || !in.idx || !scratch || (in.P > 0 && (!in.centers || !in.M || !in.strengths)))
+        return fail(GSR_ERR_INVALID_ARG, "%s: null pointer", who);
+    if (wants_beta && !in.min_scaling) return fail(GSR_ERR_INVALID_ARG, "%s: beta needs min_scaling", who);
+    if ((((uintptr_t)in.x | (uintptr_t)in.centers | (uintptr_t)in.M | (uintptr_t)in.strengths | (uintptr_t)in.min_scaling) & 3u) != 0u ||
+        ((uintptr_t)in.idx & 7u) != 0u || ((uintptr_t)scratch & 255u) != 0u)
+        return fail(GSR_ERR_INVALID_ARG, "%s: misaligned pointer (floats: 4 bytes, idx: 8, scratch: 256)", who);
+    const size_t need = gsr::field_scratch_bytes(in.P);
+    if (scratch_bytes < need) return fail(GSR_ERR_INVALID_ARG, "%s: scratch too small (%zu of %zu bytes)", who, scratch_bytes, need);
+    return GSR_OK;
+}
+}  // namespace
+
+extern "C" {
+
+size_t gsr_field_scratch_bytes(int64_t P) {
+    return (P < 0 || P >= (int64_t)gsr::kKnn3MaxPoints) ? 0 : gsr::field_scratch_bytes(P);
+}
+
+int gsr_field_forward(int64_t n, int K, int64_t P, const float* x, const int64_t* idx, const float* centers, const float* M,
+                      const float* strengths, const float* min_scaling, float density_factor, float* density, float* opacities, float* beta,
+                      void* scratch, size_t scratch_bytes, void* stream_) {
+    const gsr::FieldInputs in{n, K, P, x, reinterpret_cast<const long long*>(idx), centers, M, strengths, min_scaling, density_factor};
+    const int rc = field_check("gsr_field_forward", in, beta != nullptr, scratch, scratch_bytes);
+    if (rc != GSR_OK) return rc == 1 ? GSR_OK : rc;
+    if (!density) return fail(GSR_ERR_INVALID_ARG, "gsr_field_forward: null pointer");
+    if ((((uintptr_t)density | (uintptr_t)opacities | (uintptr_t)beta) & 3u) != 0u)
+        return fail(GSR_ERR_INVALID_ARG, "gsr_field_forward: misaligned pointer (density / opacities / beta: 4 bytes)");
+    GSR_HIP(gsr::launch_field_forward(in, density, opacities, beta, scratch, (hipStream_t)stream_));
+    return GSR_OK;
+}
+
+int gsr_field_backward(int64_t n, int K, int64_t P, const float* x, const int64_t* idx, const float* centers, const float* M,
+                       const float* strengths, const float* min_scaling, float density_factor, const float* g_density,
+                       const float* g_opacities, const float* g_beta, float* dx, float* accum, void* scratch, size_t scratch_bytes,
+                       void* stream_) {
+    const gsr::FieldInputs in{n, K, P, x, reinterpret_cast<const long long*>(idx), centers, M, strengths, min_scaling, density_factor};
+    const int rc = field_check("gsr_field_backward", in, g_beta != nullptr, scratch, scratch_bytes);
+    if (rc != GSR_OK) return rc == 1 ? GSR_OK : rc;
+    if (!accum && P > 0) return fail(GSR_ERR_INVALID_ARG, "gsr_field_backward: null pointer");
+    if ((((uintptr_t)g_density | (uintptr_t)g_opacities | (uintptr_t)g_beta | (uintptr_t)dx) & 3u) != 0u || ((uintptr_t)accum & 63u) != 0u)
+        return fail(GSR_ERR_INVALID_ARG, "gsr_field_backward: misaligned pointer (gradients: 4 bytes, accum: 64)");
+    GSR_HIP(gsr::launch_field_backward(in, g_density, g_opacities, g_beta, dx, accum, scratch, (hipStream_t)stream_));
+    return GSR_OK;
+}
+
+}  // extern "C"

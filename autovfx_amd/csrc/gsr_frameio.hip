@@ -18,6 +18,8 @@
 //     message splits into 16-byte pieces whose raw CRCs are shifted to their place -- multiplied by x^(8 * bytes behind the
 //     piece) mod P, zlib's crc32_combine arithmetic (multmodp / x2nmodp, crc32.c) -- and XORed together in any order; the
 //     conditioning is one more term, 0xFFFFFFFF x^(8 N) ^ 0xFFFFFFFF.
+// Defines the entry points gsr_resize_rgba8_bilinear, gsr_resize_f32_nearest, gsr_frame_files(_deflate), gsr_png_size, gsr_png_room,
+// gsr_png_encode, gsr_png_deflate_max_size / _room / _scratch and gsr_png_encode_deflate.
 #include "gsr_internal.h"
 
 #include <algorithm>
@@ -1091,8 +1093,7 @@ __global__ void __launch_bounds__(256) nearest_f32_kernel(const float* __restric
     if (sx >= 0 && sy >= 0) out[(size_t)y * out_w + x] = in[(size_t)sy * in_w + sx];   // (never outside for a whole-image resize)
 }
 
-} // namespace
-
+// tmp: src_h * dst_w * 4 bytes (needed when both sizes change)
 hipError_t launch_resize_rgba8_bilinear(const uint8_t* src, int src_w, int src_h, uint8_t* dst, int dst_w, int dst_h, uint8_t* tmp,
                                         hipStream_t stream) {
     const uchar4* in = reinterpret_cast<const uchar4*>(src);
@@ -1130,7 +1131,6 @@ hipError_t launch_resize_f32_nearest(const float* src, int src_w, int src_h, flo
     return hipGetLastError();
 }
 
-namespace {
 // The two 8-bit images the reference makes with numpy / OpenCV before cv2.imwrite (scene_representation.py:429-438), one lane per
 // pixel: the turbo-coloured depth preview -- depth2img(depth, scale): uint8(clip(depth / scale, 0, 1) * 255) through the colour
 // table -- and the normal map, uint8((n + 1) / 2 * 255): the same fp32 operations in the same order, truncation.
@@ -1153,12 +1153,14 @@ __global__ void __launch_bounds__(256) frame_previews_kernel(const float* __rest
         normal_rgb[3 * i + c] = (uint8_t)(int)fminf(fmaxf(v, 0.0f), 255.0f);
     }
 }
-} // namespace
 
+size_t png_file_bytes(int W, int H, int C);
+size_t png_deflate_scratch_bytes(int W, int H, int C);
+hipError_t launch_png_encode(const uint8_t* pixels, int W, int H, int C, int planar, uint8_t* out, hipStream_t stream);
 hipError_t launch_png_encode_deflate_batch(int n, const uint8_t* const* pixels, const int* Ws, const int* Hs, const int* Cs, const int* planars,
                                            uint8_t* const* outs, uint8_t* const* scratches, unsigned long long* const* out_lens, hipStream_t stream);
 
-// One frame's four files (gsr.h: gsr_frame_files): quantise, colour, encode, copy -- ten launches queued by ONE host call.
+// One frame's four files (gsr.h: gsr_frame_files): quantise, colour, encode, copy -- ten launches queued by ONE host call.  work: 10 * W * H bytes.
 hipError_t launch_frame_files(const float* color, const float* alpha, const float* depth, const float* normal, float depth_scale,
                               const uint8_t* turbo_lut, int W, int H, uint8_t* png_rgba, uint8_t* png_depth, uint8_t* png_normal,
                               float* npy_plane, uint8_t* work, uint8_t* png_scratch, unsigned long long* png_lengths /*both null: stored PNGs; else
@@ -1189,25 +1191,25 @@ hipError_t launch_frame_files(const float* color, const float* alpha, const floa
 }
 
 // ---- deflate-compressed files: sizes and the launch sequence ----
-size_t png_deflate_max_bytes(int W, int H, int C) {
+size_t png_deflate_max_bytes(int W, int H, int C) {   // upper bound of the file's length
     PngLayout L;
     return png_layout(W, H, C, 0, &L) ? (size_t)deflate_scratch(L).file_max : 0;
 }
-size_t png_deflate_room_bytes(int W, int H, int C) {
+size_t png_deflate_room_bytes(int W, int H, int C) {   // what `out` must hold (the file's bound + what the CRC kernel may read behind it)
     PngLayout L;
     return png_layout(W, H, C, 0, &L) ? deflate_scratch(L).out_room : 0;
 }
-size_t png_deflate_scratch_bytes(int W, int H, int C) {
+size_t png_deflate_scratch_bytes(int W, int H, int C) {   // device scratch per image
     PngLayout L;
     return png_layout(W, H, C, 0, &L) ? deflate_scratch(L).total : 0;
 }
 
+// Bytes of the PNG file launch_png_encode writes for a W x H image with C (3 or 4) 8-bit channels; 0 if the size is not encodable.
 size_t png_file_bytes(int W, int H, int C) {
     PngLayout L;
     return png_layout(W, H, C, 0, &L) ? (size_t)L.file_len : 0;
 }
 
-namespace {
 struct PngScratch { size_t adler_at, crc_at, total; uint32_t enc_groups, crc_groups; };   // offsets from the start of `out`
 PngScratch png_scratch(const PngLayout& L) {
     PngScratch p;
@@ -1218,7 +1220,6 @@ PngScratch png_scratch(const PngLayout& L) {
     p.total = p.crc_at + (((size_t)p.crc_groups * 4 + 15) & ~size_t(15));
     return p;
 }
-} // namespace
 
 // Bytes `out` of launch_png_encode must hold: the file, then (from the next 16-byte boundary) the workgroups' partial checksums.
 size_t png_room_bytes(int W, int H, int C) {
@@ -1226,7 +1227,6 @@ size_t png_room_bytes(int W, int H, int C) {
     return png_layout(W, H, C, 0, &L) ? png_scratch(L).total : 0;
 }
 
-namespace {
 std::mutex g_shift_mutex;
 bool g_shift_ready[64] = {};
 hipError_t ensure_shift_tables() {   // once per device: 3 KB of constants for png_crc_kernel
@@ -1247,8 +1247,8 @@ hipError_t ensure_shift_tables() {   // once per device: 3 KB of constants for p
     if (e == hipSuccess) g_shift_ready[dev] = true;
     return e;
 }
-} // namespace
 
+// pixels: u8, interleaved [H,W,C] or (planar != 0) [C,H,W].
 // out: png_room_bytes(...) bytes, 16-byte aligned (the file image, then the kernels' partial checksums).  Three launches, no memset.
 hipError_t launch_png_encode(const uint8_t* pixels, int W, int H, int C, int planar, uint8_t* out, hipStream_t stream) {
     PngLayout L;
@@ -1307,4 +1307,84 @@ hipError_t launch_png_encode_deflate(const uint8_t* pixels, int W, int H, int C,
     return launch_png_encode_deflate_batch(1, &pixels, &W, &H, &C, &planar, &out, &scratch, &out_len, stream);
 }
 
+} // namespace
 } // namespace gsr
+
+using gsr::fail;
+
+extern "C" {
+
+int gsr_resize_rgba8_bilinear(const uint8_t* src, int src_w, int src_h, uint8_t* dst, int dst_w, int dst_h, uint8_t* tmp, void* stream_) {
+    if (src_w <= 0 || src_h <= 0 || dst_w <= 0 || dst_h <= 0) return fail(GSR_ERR_INVALID_ARG, "bad image size %dx%d -> %dx%d", src_w, src_h, dst_w, dst_h);
+    if (!src || !dst || (!tmp && src_w != dst_w && src_h != dst_h)) return fail(GSR_ERR_INVALID_ARG, "null pointer");
+    GSR_HIP(gsr::launch_resize_rgba8_bilinear(src, src_w, src_h, dst, dst_w, dst_h, tmp, (hipStream_t)stream_));
+    return GSR_OK;
+}
+
+int gsr_resize_f32_nearest(const float* src, int src_w, int src_h, float* dst, int dst_w, int dst_h, void* stream_) {
+    if (src_w <= 0 || src_h <= 0 || dst_w <= 0 || dst_h <= 0) return fail(GSR_ERR_INVALID_ARG, "bad image size %dx%d -> %dx%d", src_w, src_h, dst_w, dst_h);
+    if (!src || !dst) return fail(GSR_ERR_INVALID_ARG, "null pointer");
+    GSR_HIP(gsr::launch_resize_f32_nearest(src, src_w, src_h, dst, dst_w, dst_h, (hipStream_t)stream_));
+    return GSR_OK;
+}
+
+int gsr_frame_files(const float* color, const float* alpha, const float* depth, const float* normal, float depth_scale, const uint8_t* turbo_lut,
+                    int width, int height, uint8_t* png_rgba, uint8_t* png_depth_preview, uint8_t* png_normal, float* npy_plane, uint8_t* work,
+                    void* stream_) {
+    if (width <= 0 || height <= 0 || gsr::png_file_bytes(width, height, 4) == 0) return fail(GSR_ERR_INVALID_ARG, "bad image size %dx%d", width, height);
+    if (!color || !alpha || !depth || !normal || !turbo_lut || !png_rgba || !png_depth_preview || !png_normal || !npy_plane || !work)
+        return fail(GSR_ERR_INVALID_ARG, "null pointer");
+    if (((reinterpret_cast<uintptr_t>(png_rgba) | reinterpret_cast<uintptr_t>(png_depth_preview) | reinterpret_cast<uintptr_t>(png_normal)) & 15u) != 0)
+        return fail(GSR_ERR_INVALID_ARG, "gsr_frame_files: the PNG buffers must be 16-byte aligned");
+    if (!(depth_scale > 0.0f)) return fail(GSR_ERR_INVALID_ARG, "gsr_frame_files: depth_scale must be positive");
+    GSR_HIP(gsr::launch_frame_files(color, alpha, depth, normal, depth_scale, turbo_lut, width, height, png_rgba, png_depth_preview, png_normal,
+                                    npy_plane, work, nullptr, nullptr, (hipStream_t)stream_));
+    return GSR_OK;
+}
+
+int gsr_frame_files_deflate(const float* color, const float* alpha, const float* depth, const float* normal, float depth_scale, const uint8_t* turbo_lut,
+                            int width, int height, uint8_t* png_rgba, uint8_t* png_depth_preview, uint8_t* png_normal, float* npy_plane, uint8_t* work,
+                            uint8_t* png_scratch, uint64_t* png_lengths, void* stream_) {
+    if (width <= 0 || height <= 0 || gsr::png_deflate_max_bytes(width, height, 4) == 0) return fail(GSR_ERR_INVALID_ARG, "bad image size %dx%d", width, height);
+    if (!color || !alpha || !depth || !normal || !turbo_lut || !png_rgba || !png_depth_preview || !png_normal || !npy_plane || !work || !png_scratch || !png_lengths)
+        return fail(GSR_ERR_INVALID_ARG, "null pointer");
+    if (((reinterpret_cast<uintptr_t>(png_rgba) | reinterpret_cast<uintptr_t>(png_depth_preview) | reinterpret_cast<uintptr_t>(png_normal) |
+          reinterpret_cast<uintptr_t>(png_scratch)) & 15u) != 0 ||
+        (reinterpret_cast<uintptr_t>(png_lengths) & 7u) != 0)
+        return fail(GSR_ERR_INVALID_ARG, "gsr_frame_files_deflate: the PNG buffers must be 16-byte aligned, the lengths 8-byte aligned");
+    if (!(depth_scale > 0.0f)) return fail(GSR_ERR_INVALID_ARG, "gsr_frame_files_deflate: depth_scale must be positive");
+    GSR_HIP(gsr::launch_frame_files(color, alpha, depth, normal, depth_scale, turbo_lut, width, height, png_rgba, png_depth_preview, png_normal,
+                                    npy_plane, work, png_scratch, reinterpret_cast<unsigned long long*>(png_lengths), (hipStream_t)stream_));
+    return GSR_OK;
+}
+
+size_t gsr_png_deflate_max_size(int width, int height, int channels) { return gsr::png_deflate_max_bytes(width, height, channels); }
+size_t gsr_png_deflate_room(int width, int height, int channels) { return gsr::png_deflate_room_bytes(width, height, channels); }
+size_t gsr_png_deflate_scratch(int width, int height, int channels) { return gsr::png_deflate_scratch_bytes(width, height, channels); }
+
+int gsr_png_encode_deflate(const uint8_t* pixels, int width, int height, int channels, int planar, uint8_t* out, uint8_t* scratch, uint64_t* out_len,
+                           void* stream_) {
+    if (gsr::png_deflate_max_bytes(width, height, channels) == 0)
+        return fail(GSR_ERR_INVALID_ARG, "gsr_png_encode_deflate: %dx%d with %d channels cannot be encoded (3 or 4 channels, < 2 GB)", width, height, channels);
+    if (!pixels || !out || !scratch || !out_len) return fail(GSR_ERR_INVALID_ARG, "null pointer");
+    if (((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(scratch)) & 15u) != 0 || (reinterpret_cast<uintptr_t>(out_len) & 7u) != 0)
+        return fail(GSR_ERR_INVALID_ARG, "gsr_png_encode_deflate: out and scratch must be 16-byte aligned, out_len 8-byte aligned");
+    GSR_HIP(gsr::launch_png_encode_deflate(pixels, width, height, channels, planar, out, scratch, reinterpret_cast<unsigned long long*>(out_len),
+                                           (hipStream_t)stream_));
+    return GSR_OK;
+}
+
+size_t gsr_png_size(int width, int height, int channels) { return gsr::png_file_bytes(width, height, channels); }
+size_t gsr_png_room(int width, int height, int channels) { return gsr::png_room_bytes(width, height, channels); }
+
+int gsr_png_encode(const uint8_t* pixels, int width, int height, int channels, int planar, uint8_t* out, void* stream_) {
+    const size_t n = gsr::png_file_bytes(width, height, channels);
+    if (n == 0) return fail(GSR_ERR_INVALID_ARG, "gsr_png_encode: %dx%d with %d channels cannot be encoded (3 or 4 channels, < 2 GB)", width, height, channels);
+    if (!pixels || !out) return fail(GSR_ERR_INVALID_ARG, "null pointer");
+    if ((reinterpret_cast<uintptr_t>(out) & 15u) != 0) return fail(GSR_ERR_INVALID_ARG, "gsr_png_encode: out must be 16-byte aligned");
+    GSR_HIP(gsr::launch_png_encode(pixels, width, height, channels, planar, out, (hipStream_t)stream_));
+    return GSR_OK;
+}
+
+
+}  // extern "C"

@@ -5,7 +5,22 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "../../include/gsr.h"
+
 namespace gsr {
+
+// ---- what every unit's C entry points share (defined in gsr_api.hip, which keeps the message buffer of gsr_last_error) ----
+// Formats the calling thread's error message and returns `code`.
+int fail(gsr_status code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+inline bool aligned4(const void* p) { return ((uintptr_t)p & 3u) == 0u; }
+
+#define GSR_HIP(expr)                                                                          \
+    do {                                                                                       \
+        hipError_t e_ = (expr);                                                                \
+        if (e_ != hipSuccess)                                                                  \
+            return fail(GSR_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_),   \
+                        __FILE__, __LINE__);                                                   \
+    } while (0)
 
 constexpr int kTile = 16;                    // tile edge in pixels; part of the result
 constexpr uint32_t kCulledKey = 0xFFFFFFFFu; // depth key of a Gaussian that produces no pairs
@@ -167,8 +182,9 @@ inline int ranges_duty_blocks(int num_tiles) { return (num_tiles + 254) / 255; }
 // ---- kernels (gsr_kernels.hip: per-Gaussian and per-pixel streaming kernels) ----
 hipError_t launch_preprocess(const GaussianInputs& in, const Camera& cam, const GeometryArrays& out,
                              hipStream_t stream);
-hipError_t launch_mark_visible(int P, const float* means3D, const float* viewmatrix, uint8_t* present,
-                               hipStream_t stream);
+// RGBA8 [H,W,4] planes from the float colour and alpha images (gsr.h: gsr_pack_rgba8; gsr_frameio.hip packs a frame's files with it)
+hipError_t launch_pack_rgba8(const float* color, const float* alpha, uint8_t* out, size_t n_pixels,
+                             hipStream_t stream);
 // Sums the projection kernel's per-workgroup tallies, stores the totals at `host_totals` (pinned host memory at its
 // device-visible address; slot 0 of each array, the rest of the block must have been zeroed by the host) or, if that is
 // null, into `zero_block` itself (a D2H copy then follows), and clears the `zero_words` words at `zero_block` (frame counters,
@@ -276,8 +292,6 @@ hipError_t launch_blend(const Camera& cam, const BlendSegments& segs, int seg_be
                         int row_words, hipStream_t stream, const float* extra_features = nullptr, float* out_extra = nullptr,
                         const BlendOrder* order = nullptr);
 // counts the floats with bit patterns first_bits .. first_bits + count - 1 on which the blend's exp differs from expf
-hipError_t launch_exp_selftest(uint32_t first_bits, uint32_t count, unsigned long long* mismatches, hipStream_t stream);
-
 struct BackwardInputs {
     int P, sh_degree, M;
     const float* means3D;
@@ -322,246 +336,20 @@ hipError_t launch_det_reduce(int P, const uint32_t* seg_first, const uint32_t* s
                              const float* partial1, const uint32_t* bits2 /*nullable*/, const float* partial2 /*nullable*/, float* accum,
                              hipStream_t stream);
 hipError_t launch_preprocess_backward(const BackwardInputs& b, const Camera& cam, hipStream_t stream);
-hipError_t launch_composite(int width, int height, const void* bg_c, const void* o_c, const float* o_d,
-                            const void* s_c, const float* s_d, const void* o_s_c, const void* o_gs_c,
-                            const float* o_gs_d, const void* s_f_c, const float* s_f_d, const void* s_f_c_pre,
-                            void* out, hipStream_t stream);
-// render()'s elementwise work around the two rasterizer passes (see gsr.h: gsr_view_normals, gsr_normal_maps)
-hipError_t launch_view_normals(int P, const float* means3D, const float* axis, const float* cam_pos, float* out,
-                               hipStream_t stream);
-hipError_t launch_normal_maps(int width, int height, const float* normal_rgb, const float* depth, const float* c2w,
-                              float fx, float fy, float cx, float cy, float* normal, float* pseudo, hipStream_t stream);
-// gsr_place_object (include/gsr.h): one object of a dynamic scene, raw parameters -> activated, at its place in the scene buffers
-struct ObjectPlacement { float c[3], R[9], s, c0[3], qR[4], log_s; };
-hipError_t launch_place_object(int n, const uint32_t* subset /*nullable: output j <- input subset[j]*/, bool transform,
-                               const float* xyz, const float* rot, const float* log_scale, const float* opacity, const float* shs, int M,
-                               const ObjectPlacement& pl, float* out_xyz, float* out_scales, float* out_rot, float* out_opacity,
-                               float* out_shs, float* out_min_axis, hipStream_t stream);
-hipError_t launch_pack_rgba8(const float* color, const float* alpha, uint8_t* out, size_t n_pixels,
-                             hipStream_t stream);
-
-// ---- frame outputs / compositor inputs (gsr_frameio.hip) ----
-// Bytes of the PNG file launch_png_encode writes for a W x H image with C (3 or 4) 8-bit channels; 0 if the size is not encodable.
-size_t png_file_bytes(int W, int H, int C);
-size_t png_room_bytes(int W, int H, int C);   // what `out` must hold: the file, then the kernels' partial checksums
-// pixels: u8, interleaved [H,W,C] or (planar != 0) [C,H,W]; out: png_room_bytes bytes, 16-byte aligned.
-hipError_t launch_png_encode(const uint8_t* pixels, int W, int H, int C, int planar, uint8_t* out, hipStream_t stream);
-// The same file with a deflate-compressed IDAT (Paeth filter, run-length matches, one Huffman code per image built on the GPU).
-size_t png_deflate_max_bytes(int W, int H, int C);    // upper bound of the file's length
-size_t png_deflate_room_bytes(int W, int H, int C);   // what `out` must hold (the file's bound + what the CRC kernel may read behind it)
-size_t png_deflate_scratch_bytes(int W, int H, int C);   // device scratch per image: filtered stream, per-block histograms / offsets, checksums
-hipError_t launch_png_encode_deflate(const uint8_t* pixels, int W, int H, int C, int planar, uint8_t* out, uint8_t* scratch, unsigned long long* out_len,
-                                     hipStream_t stream);
-
-// The reference's four per-frame files from a render() result, queued by one host call (gsr.h: gsr_frame_files).  work: 10 * W * H bytes.
-hipError_t launch_frame_files(const float* color, const float* alpha, const float* depth, const float* normal, float depth_scale,
-                              const uint8_t* turbo_lut, int W, int H, uint8_t* png_rgba, uint8_t* png_depth, uint8_t* png_normal,
-                              float* npy_plane, uint8_t* work, uint8_t* png_scratch, unsigned long long* png_lengths /*both null: stored PNGs*/,
-                              hipStream_t stream);
-// PIL's Image.resize(BILINEAR) on an RGBA8 image [H,W,4] and Image.resize(NEAREST) on an fp32 image, bit for bit
-// (blend_all.py:21-28).  tmp: src_h * dst_w * 4 bytes (needed when both sizes change).
-hipError_t launch_resize_rgba8_bilinear(const uint8_t* src, int src_w, int src_h, uint8_t* dst, int dst_w, int dst_h, uint8_t* tmp,
-                                        hipStream_t stream);
-hipError_t launch_resize_f32_nearest(const float* src, int src_w, int src_h, float* dst, int dst_w, int dst_h, hipStream_t stream);
-
-// ---- panoramas (gsr_panorama.hip) ----
-// The six faces of a cube map, in the reference's dict order (front, right, back, left, up, down): planar [C,S,S] colour or [S,S] depth.
-struct CubeFacePointers { const float* p[6]; };
-// c2e(..., mode='bilinear') of the reference (gsr.h: gsr_cube_to_equirect); grid_u [W], grid_v [H], grid_ceil [W/4] as the host computes
-// them; any of out [H,W,C] / out_u8 [H,W,C] / out_depth [H,W] may be null (depth.p is read only when out_depth is set).
-hipError_t launch_cube_to_equirect(const CubeFacePointers& faces, const CubeFacePointers& depth, int S, int C, const float* grid_u,
-                                   const float* grid_v, const int* grid_ceil, int H, int W, float* out, uint8_t* out_u8, float* out_depth,
-                                   hipStream_t stream);
-
-// ---- structural similarity (gsr_ssim.hip) ----
-constexpr int kSsimTaps = 11;
-constexpr float kSsimC1 = (float)(0.01 * 0.01);   // the reference's Python constants, rounded to fp32 as its fp32 tensor ops do
-constexpr float kSsimC2 = (float)(0.03 * 0.03);
-struct SsimWindow {   // the separable window, passed by value
-    float w[kSsimTaps];
-};
-struct SsimShape {
-    int n, c, h, w;
-    int tiles_x;
-    uint32_t tiles_per_plane, blocks;   // blocks = n c tiles_per_plane (one partial sum each)
-};
-SsimShape ssim_shape(int n, int c, int h, int w);   // n c h w < 2^31
-// gsr.h: gsr_ssim_forward; partials: s.blocks floats; coef: null, or 3 n c h w floats (the maps a, b, c, one after the other)
-hipError_t launch_ssim_forward(const SsimShape& s, const SsimWindow& win, const float* x, const float* y, int per_image, float* out,
-                               float* coef, float* partials, hipStream_t stream);
-hipError_t launch_ssim_backward(const SsimShape& s, const SsimWindow& win, const float* x, const float* y, const float* coef,
-                                int per_image, const float* grad_out, float* grad_x, hipStream_t stream);
-
-// ---- one Adam step over many tensors (gsr_adam.hip) ----
-constexpr int kAdamMaxTensors = 16;   // gsr.h: GSR_ADAM_MAX_TENSORS
-struct AdamTensor {
-    float* p;
-    const float* g;
-    float* m;
-    float* v;
-    int64_t numel;
-    float a, s2;      // gsr.h: GsrAdamTensor::step_size, ::bias2_sqrt
-    int aligned16;    // p, g, m and v all 16-byte aligned
-};
-struct AdamBatch {    // passed by value (kernel arguments)
-    AdamTensor t[kAdamMaxTensors];
-    uint64_t first_chunk[kAdamMaxTensors + 1];   // prefix of adam_chunks(numel); first_chunk[count] = the total
-    int count;
-    float w, b2, c, eps;
-};
-uint64_t adam_chunks(int64_t numel);   // numel >= 0
-hipError_t launch_adam_step(const AdamBatch& b, hipStream_t stream);
-
-// ---- densification (gsr_densify.hip) ----
-constexpr int kDensifyBlockRows = 1024;       // source rows per workgroup of the plan's classify / scatter kernels
-constexpr int64_t kDensifyApplyChunk = 2048;  // output floats per workgroup iteration of the apply kernel
-constexpr int kDensifyMaxTensors = 18;        // gsr.h: GSR_DENSIFY_MAX_TENSORS (6 parameters, 12 moments)
-struct DensifyPlanArgs {   // gsr.h: gsr_densify_plan; passed by value
-    int64_t n;
-    const float *accum, *denom, *scaling, *opacity;
-    float max_grad, dense_bound, min_opacity, ws_bound;
-    int ws_test;
-    int32_t *src_of, *split_idx, *counts;
-    uint8_t* flags;                           // scratch: [n] class bits
-    uint32_t *block_counts, *block_offsets;   // scratch: [3][blocks] each
-    uint32_t blocks;
-};
-// Byte offsets of the regions of the plan's scratch (each 256-byte aligned); bytes = the whole.
-struct DensifyPlanLayout {
-    size_t flags, block_counts, block_offsets, bytes;
-    uint32_t blocks;
-};
-inline DensifyPlanLayout densify_plan_layout(int64_t n) {
-    DensifyPlanLayout l{};
-    l.blocks = (uint32_t)((n + kDensifyBlockRows - 1) / kDensifyBlockRows);
-    auto up = [](size_t x) { return (x + 255) & ~size_t(255); };
-    l.flags = 0;
-    l.block_counts = up((size_t)n);
-    l.block_offsets = l.block_counts + up((size_t)3 * l.blocks * sizeof(uint32_t));
-    l.bytes = l.block_offsets + up((size_t)3 * l.blocks * sizeof(uint32_t));
-    return l;
-}
-struct DensifyTensor {
-    const float* src;
-    float* dst;
-    const float* side;   // the children's rows of this tensor ([2 n_split, floats_per_row]); null: copied from the parent
-    int floats_per_row, is_moment;
-};
-struct DensifyApplyPlan {
-    int64_t n_src, n_keep, n_front, n_out, n_split;
-    const int32_t *src_of, *child_rows, *split_idx;
-};
-struct DensifyApplyBatch {   // passed by value (kernel arguments)
-    DensifyTensor t[kDensifyMaxTensors];
-    uint64_t first_chunk[kDensifyMaxTensors + 1];
-    DensifyApplyPlan plan;
-    int count;
-};
-hipError_t launch_densify_stats(int64_t n, const float* grad, int row_floats, const uint8_t* filter, float* accum, float* denom,
-                                const int* radii, float* max_radii, hipStream_t stream);
-hipError_t launch_densify_plan(const DensifyPlanArgs& p, hipStream_t stream);
-hipError_t launch_densify_apply(const DensifyApplyBatch& b, hipStream_t stream);
-
-// ---- three nearest neighbours (gsr_knn.hip) ----
-// Boxes over the Morton-sorted points: level 0 = leaves of 64 points, every level above = 16 boxes of the one below, up to the first
-// level of at most 16 boxes (six levels for n < 2^30).  A box is two float4 (lo, hi; w unused) at boxes[2 * (offset[level] + i)].
-constexpr int kKnnMaxLevels = 6;
-constexpr uint32_t kKnn3MaxPoints = 1u << 30;   // refused from here on (the radix sort's limit)
-struct KnnTree {
-    const float4* boxes;
-    uint32_t count[kKnnMaxLevels];
-    uint32_t offset[kKnnMaxLevels];
-    int top;
-};
-// Byte offsets of the regions of the caller's scratch (each 256-byte aligned); bytes = the whole.
-struct KnnLayout {
-    size_t keys, keys_alt, vals, vals_alt, key_hi, radix, packed, boxes, partials, bytes;
-    KnnTree tree;
-};
-KnnLayout knn3_layout(uint32_t n);
-// gsr.h: gsr_knn3_mean_dist; scratch: knn3_layout(n).bytes bytes, 256-byte aligned, any content; 0 < n < 2^30
-hipError_t launch_knn3_mean_dist(uint32_t n, const float* points, float* out, void* scratch, hipStream_t stream);
-// gsr.h: gsr_knn_points; the same tree over p2, K <= kKnnPointsMaxK slots per query.  same = (p1 == p2 && n1 == n2): the tree's own
-// leaves are the queries.  scratch: knn_points_scratch_bytes(n1, n2, same) bytes, 256-byte aligned; dists / idx 16-byte aligned for K = 4, 8, 16 (4 / 8 bytes otherwise);
-// 0 < K <= n2 < 2^30, n1 < 2^30
-constexpr int kKnnPointsMaxK = 16;
-size_t knn_points_scratch_bytes(uint32_t n1, uint32_t n2, bool same);
-hipError_t launch_knn_points(uint32_t n1, const float* p1, uint32_t n2, const float* p2, int K, float* dists, long long* idx, void* scratch,
-                             hipStream_t stream);
-
-// ---- SuGaR's density field over a neighbour list (gsr_field.hip; gsr.h: gsr_field_forward, gsr_field_backward) ----
-constexpr int kFieldMaxK = 64;
-struct FieldInputs {
-    int64_t n;                   // samples, 0 < n < 2^30
-    int K;                       // neighbour slots per sample, 1 .. kFieldMaxK
-    int64_t P;                   // Gaussians, 0 <= P < 2^30
-    const float* x;              // [n,3]
-    const long long* idx;        // [n,K]; a slot outside [0, P) is skipped
-    const float *centers, *M, *strengths, *min_scaling;   // [P,3], [P,3,3], [P], [P] or null
-    float density_factor;
-};
-// scratch: field_scratch_bytes(P) bytes (one 64-byte record per Gaussian), 256-byte aligned, any content; both calls fill it themselves.
-size_t field_scratch_bytes(int64_t P);
-hipError_t launch_field_forward(const FieldInputs& in, float* density, float* opacities, float* beta, void* scratch, hipStream_t stream);
-// accum [P,16], zeroed by the caller, 64-byte aligned: floats 0-2 of a line dL/dcentre, 3-11 dL/dM row-major, 12 dL/dstrength,
-// 13 dL/dmin_scaling.
-hipError_t launch_field_backward(const FieldInputs& in, const float* g_density, const float* g_opacities, const float* g_beta, float* dx,
-                                 float* accum, void* scratch, hipStream_t stream);
 
 // ---- the compositor's input files (gsr_layerio.hip) ----
-// The inflated IDAT stream of an 8-bit RGB / RGBA, non-interlaced PNG (device memory) -> RGBA8 [H,W,4] (alpha 255 for RGB).
-// scratch: png_unfilter_scratch_bytes(W, H) bytes, 16-byte aligned (0: the width is not supported).
+// Scratch bytes of the PNG unfilter kernels for a W x H image; 0: the width is not supported (gsr_layerfiles.hip then leaves the file
+// to a host decoder).
 size_t png_unfilter_scratch_bytes(int W, int H);
-struct PngUnfilterJob {      // (= GsrPngUnfilterJob, gsr.h)
-    const uint8_t* scanlines;
-    int width, height, channels;
-    uint8_t* out_rgba;
-    uint8_t* scratch;
-};
-hipError_t launch_png_unfilter_batch(int n, const PngUnfilterJob* jobs, hipStream_t stream);   // one workgroup per image, eight images per launch
-// The inflated, still predictor-coded scanline blocks of an OpenEXR file one after another (device memory) -> the bytes of the channel
-// that occupies [c_at, c_at + c_bytes) of every line: plane[H][c_bytes].
-hipError_t launch_exr_unpack_channel(const uint8_t* blocks, int H, int bytes_per_line, int lines_per_block, int c_at, int c_bytes, uint8_t* plane,
-                                     hipStream_t stream);
 
-// zlib streams inflated on the GPU, a single-wave workgroup each.  jobs / status / any_error: DEVICE memory; src_at multiples of 4,
-// `streams` readable up to the next multiple of 4 behind every stream.  status[i]: 0 or an inflate::Status; *any_error is OR-ed with 1.
-struct InflateJob {          // (= GsrInflateJob, gsr.h)
-    uint32_t src_at, src_bytes, dst_at, dst_bytes;
-};
-hipError_t launch_inflate_zlib_blocks(const uint8_t* streams, uint8_t* out, const InflateJob* jobs, int count, int* status, int* any_error, hipStream_t stream);
-
-// ---- the host side of the same files (gsr_layerfiles.hip: container parsing + zlib inflate, one call per file) ----
-struct PngFileLayout {       // (= GsrPngFileInfo, gsr.h)
-    int width, height, channels;
-    size_t scanline_bytes;   // height * (1 + width * channels)
-};
-struct ExrFileLayout {       // (= GsrExrFileInfo, gsr.h)
-    int width, height, bytes_per_line, lines_per_block, channel_at, channel_bytes, channel_is_half;
-    int compression, n_blocks;   // the file's compression attribute (1 RLE, 2 ZIPS, 3 ZIP); scanline blocks in the part
-    size_t blocks_bytes;     // height * bytes_per_line
-    char channel[32];
-};
-// 0: a file the kernels take; 1: not covered (another flavour, or damaged) -- a host decoder's.
-int png_file_probe(const uint8_t* file, size_t n, PngFileLayout* out);
-int png_file_inflate(const uint8_t* file, size_t n, uint8_t* scanlines, size_t scanline_bytes);
-int exr_file_probe(const uint8_t* file, size_t n, const char* want_channel, ExrFileLayout* out);
-int exr_file_inflate(const uint8_t* file, size_t n, const char* want_channel, uint8_t* blocks, size_t blocks_bytes);
-// ZIP / ZIPS files: the blocks' zlib streams copied one behind the other at 4-byte aligned offsets into `packed` (room: n + 4 * n_blocks
-// + 4 bytes), jobs[n_blocks] filled for launch_inflate_zlib_blocks; *packed_bytes: what to upload.
-int exr_file_pack(const uint8_t* file, size_t n, const char* want_channel, uint8_t* packed, size_t packed_room, InflateJob* jobs, size_t* packed_bytes);
-
-// gsr_inflate_core.h's decoder run by one host lane (tests); 0 or an inflate::Status
-int inflate_zlib_host(const uint8_t* src, size_t src_len, uint8_t* dst, size_t dst_len);
+// ---- three nearest neighbours (gsr_knn.hip) ----
+constexpr uint32_t kKnn3MaxPoints = 1u << 30;   // refused from here on (the radix sort's limit); the density field refuses the same counts
 
 // ---- hand-written radix sort (gsr_radix.hip) ----
 // Stable ascending LSD sort on the low `bits` key bits, 8 per pass (count / scan / scatter kernels, no spinning,
 // nothing to zero-fill).  scratch: radix_scratch_words(n) u32 words of any content.  iota_payload: the payload
 // is 0..n-1 and `vals` is not read.  want_sorted_keys = false skips the key stores of the last pass.
 // `extras`: RadixSortExtras below.
-// counts the returning LDS adds whose result was not (value before the instruction) + (lower lanes on the same counter)
-hipError_t launch_lds_atomic_order_selftest(uint32_t workgroups, uint32_t rounds, uint32_t seed, unsigned long long* mismatches,
-                                            hipStream_t stream);
 // The in-wave rank of the scatter kernel: request 0 = ballots, 1 = returning LDS adds verified per tile (ballot repair in place),
 // 2 = those on a device that passed the lane-order self-test (run once per device, on `stream`, by the first caller), ballots
 // elsewhere, 3 = 1 with an injected inversion (test hook).  radix_rank_mode returns what sorts on the CURRENT device use

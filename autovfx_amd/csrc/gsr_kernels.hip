@@ -14,7 +14,11 @@
 //
 // Results are the reference's: fp32 in the reference's operation order, built with
 // -ffp-contract=off so nothing is fused behind our back.
+// Defines the entry points gsr_mark_visible, gsr_composite, gsr_pack_rgba8, gsr_view_normals, gsr_normal_maps, gsr_place_object and
+// gsr_place_object_subset.
 #include "gsr_device.h"
+
+#include <cstring>
 
 // Profiling aid (python -m autovfx_amd.build --trace, scripts/kernel_trace.py): lane 0 of a workgroup stamps the
 // 100 MHz wall clock into slot `slot` of its 8-word record.  Compiled out of the normal library.
@@ -584,7 +588,7 @@ hipError_t launch_sh_colour_all(const GaussianInputs& in, const Camera& cam, con
     return hipGetLastError();
 }
 
-hipError_t launch_mark_visible(int P, const float* means3D, const float* viewmatrix, uint8_t* present,
+static hipError_t launch_mark_visible(int P, const float* means3D, const float* viewmatrix, uint8_t* present,
                                hipStream_t stream) {
     hipLaunchKernelGGL(mark_visible_kernel, dim3(div_up(P, 256)), dim3(256), 0, stream, P, means3D, viewmatrix,
                        present);
@@ -595,7 +599,7 @@ hipError_t launch_mark_visible(int P, const float* means3D, const float* viewmat
 
 
 
-hipError_t launch_composite(int width, int height, const void* bg_c, const void* o_c, const float* o_d,
+static hipError_t launch_composite(int width, int height, const void* bg_c, const void* o_c, const float* o_d,
                             const void* s_c, const float* s_d, const void* o_s_c, const void* o_gs_c,
                             const float* o_gs_d, const void* s_f_c, const float* s_f_d, const void* s_f_c_pre,
                             void* out, hipStream_t stream) {
@@ -694,6 +698,7 @@ __global__ void __launch_bounds__(256) normal_maps_kernel(NormalMapArgs a) {
 // branch of the frame loop, scene_representation.py:409-418: `orig_gaussians._xyz[mask]` ... merged as they are).
 // `transform` = 0: no rigid transform at all -- positions are copied, the raw quaternion is only normalised (that branch never
 // calls transform_gaussians, so not even the identity's roundings may be applied).
+struct ObjectPlacement { float c[3], R[9], s, c0[3], qR[4], log_s; };   // gsr.h: the 21 floats of `placement`
 __global__ void __launch_bounds__(256) place_object_kernel(int n, const uint32_t* __restrict__ subset, int transform,
                                                            const float* __restrict__ xyz, const float* __restrict__ rot,
                                                            const float* __restrict__ log_scale, const float* __restrict__ opacity,
@@ -778,7 +783,7 @@ __global__ void __launch_bounds__(256) place_object_kernel(int n, const uint32_t
     }
 }
 
-hipError_t launch_place_object(int n, const uint32_t* subset, bool transform, const float* xyz, const float* rot, const float* log_scale,
+static hipError_t launch_place_object(int n, const uint32_t* subset, bool transform, const float* xyz, const float* rot, const float* log_scale,
                                const float* opacity, const float* shs, int M, const ObjectPlacement& pl, float* out_xyz, float* out_scales,
                                float* out_rot, float* out_opacity, float* out_shs, float* out_min_axis, hipStream_t stream) {
     hipLaunchKernelGGL(place_object_kernel, dim3(div_up(n, 256)), dim3(256), 0, stream, n, subset, transform ? 1 : 0, xyz, rot, log_scale,
@@ -786,13 +791,13 @@ hipError_t launch_place_object(int n, const uint32_t* subset, bool transform, co
     return hipGetLastError();
 }
 
-hipError_t launch_view_normals(int P, const float* means3D, const float* axis, const float* cam_pos, float* out,
+static hipError_t launch_view_normals(int P, const float* means3D, const float* axis, const float* cam_pos, float* out,
                                hipStream_t stream) {
     hipLaunchKernelGGL(view_normals_kernel, dim3(div_up(P, 256)), dim3(256), 0, stream, P, means3D, axis, cam_pos, out);
     return hipGetLastError();
 }
 
-hipError_t launch_normal_maps(int width, int height, const float* normal_rgb, const float* depth, const float* c2w,
+static hipError_t launch_normal_maps(int width, int height, const float* normal_rgb, const float* depth, const float* c2w,
                               float fx, float fy, float cx, float cy, float* normal, float* pseudo, hipStream_t stream) {
     NormalMapArgs a;
     a.W = width; a.H = height; a.normal_rgb = normal_rgb; a.depth = depth;
@@ -812,5 +817,94 @@ hipError_t launch_pack_rgba8(const float* color, const float* alpha, uint8_t* ou
     return hipGetLastError();
 }
 
-
 } // namespace gsr
+
+using gsr::fail;
+
+namespace {
+int place_impl(int n, const uint32_t* subset, const float* xyz, const float* rotation_raw, const float* log_scale, const float* opacity,
+               const float* shs, int M, const float* placement, float* out_means3D, float* out_scales, float* out_rotations,
+               float* out_opacities, float* out_shs, float* out_min_axis, void* stream_, bool placement_required) {
+    if (n < 0) return fail(GSR_ERR_INVALID_ARG, "bad size n=%d", n);
+    if (n == 0) return GSR_OK;
+    if (!xyz || !rotation_raw || !log_scale || !out_means3D || !out_scales || !out_rotations || (placement_required && !placement))
+        return fail(GSR_ERR_INVALID_ARG, "null pointer");
+    if ((out_opacities != nullptr) != (opacity != nullptr) || (out_shs != nullptr) != (shs != nullptr))
+        return fail(GSR_ERR_INVALID_ARG, "opacity / shs and their outputs must be given together");
+    if (shs != nullptr && M <= 0) return fail(GSR_ERR_INVALID_ARG, "shs given with M=%d", M);
+    gsr::ObjectPlacement pl = {};
+    static_assert(sizeof(gsr::ObjectPlacement) == 21 * sizeof(float), "the placement block is 21 floats");
+    if (placement != nullptr) memcpy(&pl, placement, sizeof pl);
+    GSR_HIP(gsr::launch_place_object(n, subset, placement != nullptr, xyz, rotation_raw, log_scale, opacity, shs, M, pl, out_means3D,
+                                     out_scales, out_rotations, out_opacities, out_shs, out_min_axis, (hipStream_t)stream_));
+    return GSR_OK;
+}
+} // namespace
+
+extern "C" {
+
+int gsr_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix,
+                     uint8_t* present, void* stream_) {
+    (void)projmatrix;  // the reference passes it but only the view-space depth test is live (auxiliary.h:154)
+    if (P < 0) return fail(GSR_ERR_INVALID_ARG, "P < 0");
+    if (P == 0) return GSR_OK;
+    if (!means3D || !viewmatrix || !present) return fail(GSR_ERR_INVALID_ARG, "null pointer");
+    GSR_HIP(gsr::launch_mark_visible(P, means3D, viewmatrix, present, (hipStream_t)stream_));
+    return GSR_OK;
+}
+
+int gsr_composite(int width, int height, const uint8_t* bg_c, const uint8_t* o_c, const float* o_d, const uint8_t* s_c,
+                  const float* s_d, const uint8_t* o_s_c, const uint8_t* o_gs_c, const float* o_gs_d,
+                  const uint8_t* s_f_c, const float* s_f_d, const uint8_t* s_f_c_pre, uint8_t* out, void* stream_) {
+    if (width <= 0 || height <= 0) return fail(GSR_ERR_INVALID_ARG, "bad image size %dx%d", width, height);
+    if (!bg_c || !o_c || !o_d || !s_c || !s_d || !o_s_c || !out) return fail(GSR_ERR_INVALID_ARG, "null required layer");
+    if ((o_gs_c != nullptr) != (o_gs_d != nullptr) || (s_f_c != nullptr) != (s_f_d != nullptr))
+        return fail(GSR_ERR_INVALID_ARG, "a colour layer and its depth map must be given together");
+    if (s_f_c_pre != nullptr && s_f_c == nullptr) return fail(GSR_ERR_INVALID_ARG, "fire layer without a smoke layer");
+    GSR_HIP(gsr::launch_composite(width, height, bg_c, o_c, o_d, s_c, s_d, o_s_c, o_gs_c, o_gs_d, s_f_c, s_f_d,
+                                  s_f_c_pre, out, (hipStream_t)stream_));
+    return GSR_OK;
+}
+
+int gsr_pack_rgba8(const float* color, const float* alpha, uint8_t* rgba8, int width, int height, void* stream_) {
+    if (width <= 0 || height <= 0) return fail(GSR_ERR_INVALID_ARG, "bad image size %dx%d", width, height);
+    if (!color || !alpha || !rgba8) return fail(GSR_ERR_INVALID_ARG, "null pointer");
+    GSR_HIP(gsr::launch_pack_rgba8(color, alpha, rgba8, (size_t)width * height, (hipStream_t)stream_));
+    return GSR_OK;
+}
+
+int gsr_view_normals(int P, const float* means3D, const float* axis, const float* cam_pos, float* colors, void* stream_) {
+    if (P < 0) return fail(GSR_ERR_INVALID_ARG, "bad size P=%d", P);
+    if (P == 0) return GSR_OK;
+    if (!means3D || !axis || !cam_pos || !colors) return fail(GSR_ERR_INVALID_ARG, "null pointer");
+    GSR_HIP(gsr::launch_view_normals(P, means3D, axis, cam_pos, colors, (hipStream_t)stream_));
+    return GSR_OK;
+}
+
+int gsr_normal_maps(int width, int height, const float* normal_rgb, const float* depth, const float* c2w, float fx,
+                    float fy, float cx, float cy, float* normal, float* pseudo_normal, void* stream_) {
+    if (width <= 0 || height <= 0) return fail(GSR_ERR_INVALID_ARG, "bad image size %dx%d", width, height);
+    if (!normal_rgb || !depth || !c2w || !normal || !pseudo_normal) return fail(GSR_ERR_INVALID_ARG, "null pointer");
+    GSR_HIP(gsr::launch_normal_maps(width, height, normal_rgb, depth, c2w, fx, fy, cx, cy, normal, pseudo_normal,
+                                    (hipStream_t)stream_));
+    return GSR_OK;
+}
+
+int gsr_place_object(int n, const float* xyz, const float* rotation_raw, const float* log_scale, const float* opacity, const float* shs,
+                     int M, const float* placement, float* out_means3D, float* out_scales, float* out_rotations, float* out_opacities,
+                     float* out_shs, float* out_min_axis, void* stream_) {
+    return place_impl(n, nullptr, xyz, rotation_raw, log_scale, opacity, shs, M, placement, out_means3D, out_scales, out_rotations,
+                      out_opacities, out_shs, out_min_axis, stream_, true);
+}
+
+int gsr_place_object_subset(int m, const uint32_t* subset, const float* xyz, const float* rotation_raw, const float* log_scale,
+                            const float* opacity, const float* shs, int M, const float* placement, float* out_means3D,
+                            float* out_scales, float* out_rotations, float* out_opacities, float* out_shs, float* out_min_axis,
+                            void* stream_) {
+    if (m > 0 && !subset) return fail(GSR_ERR_INVALID_ARG, "null subset");
+    return place_impl(m, subset, xyz, rotation_raw, log_scale, opacity, shs, M, placement, out_means3D, out_scales, out_rotations,
+                      out_opacities, out_shs, out_min_axis, stream_, false);
+}
+
+
+}  // extern "C"

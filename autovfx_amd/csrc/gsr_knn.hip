@@ -25,12 +25,29 @@
 // box is skipped only when its bound is strictly greater than the lane's third slot -- no member could then enter a slot.  A
 // distance enters a slot only when it is below FLT_MAX (NaN and inf map to FLT_MAX before the branch-free insertion, whose
 // fmaxf would otherwise duplicate a slot).
+// Defines the entry points gsr_knn3_scratch_bytes, gsr_knn3_mean_dist, gsr_knn_points_scratch_bytes and gsr_knn_points.
 #include "gsr_internal.h"
 
 #include <cfloat>
 
 namespace gsr {
 namespace {
+
+// Boxes over the Morton-sorted points: level 0 = leaves of 64 points, every level above = 16 boxes of the one below, up to the first
+// level of at most 16 boxes (six levels for n < 2^30).  A box is two float4 (lo, hi; w unused) at boxes[2 * (offset[level] + i)].
+constexpr int kKnnMaxLevels = 6;
+struct KnnTree {
+    const float4* boxes;
+    uint32_t count[kKnnMaxLevels];
+    uint32_t offset[kKnnMaxLevels];
+    int top;
+};
+// Byte offsets of the regions of the caller's scratch (each 256-byte aligned); bytes = the whole.
+struct KnnLayout {
+    size_t keys, keys_alt, vals, vals_alt, key_hi, radix, packed, boxes, partials, bytes;
+    KnnTree tree;
+};
+constexpr int kKnnPointsMaxK = 16;   // slots per query of gsr_knn_points
 
 constexpr int kLeaf = 64;            // points per leaf: one wave
 constexpr int kFan = 16;             // children per box above the leaves
@@ -419,8 +436,6 @@ __global__ __launch_bounds__(256) void knn_points_search_kernel(uint32_t n1, con
 constexpr size_t kAlign = 256;
 size_t align_up(size_t v) { return (v + kAlign - 1) & ~(kAlign - 1); }
 
-}  // namespace
-
 KnnLayout knn3_layout(uint32_t n) {
     KnnLayout L = {};
     if (n == 0) return L;
@@ -446,8 +461,6 @@ KnnLayout knn3_layout(uint32_t n) {
     L.bytes = at;
     return L;
 }
-
-namespace {
 
 struct KnnRegions {
     uint32_t *keys, *keys_alt, *vals, *vals_alt, *key_hi, *radix;
@@ -500,8 +513,7 @@ void launch_points_search(bool same, uint32_t n1, const float4* queries, uint32_
         hipLaunchKernelGGL((knn_points_search_kernel<S, false>), grid, dim3(256), 0, stream, n1, queries, n2, packed, tree, K, dists, idx);
 }
 
-}  // namespace
-
+// scratch: knn3_layout(n).bytes bytes, 256-byte aligned, any content; 0 < n < 2^30
 hipError_t launch_knn3_mean_dist(uint32_t n, const float* points, float* out, void* scratch, hipStream_t stream) {
     if (n == 0) return hipSuccess;
     const KnnLayout L = knn3_layout(n);
@@ -519,6 +531,9 @@ size_t knn_points_scratch_bytes(uint32_t n1, uint32_t n2, bool same) {
     return knn3_layout(n2).bytes + (same ? 0 : knn3_layout(n1).bytes);
 }
 
+// The same tree over p2, K <= kKnnPointsMaxK slots per query.  same = (p1 == p2 && n1 == n2): the tree's own leaves are the queries.
+// scratch: knn_points_scratch_bytes(n1, n2, same) bytes, 256-byte aligned; dists / idx 16-byte aligned for K = 4, 8, 16 (4 / 8 bytes
+// otherwise); 0 < K <= n2 < 2^30, n1 < 2^30
 hipError_t launch_knn_points(uint32_t n1, const float* p1, uint32_t n2, const float* p2, int K, float* dists, long long* idx, void* scratch,
                              hipStream_t stream) {
     if (n1 == 0) return hipSuccess;
@@ -545,4 +560,55 @@ hipError_t launch_knn_points(uint32_t n1, const float* p1, uint32_t n2, const fl
     return hipGetLastError();
 }
 
+}  // namespace
 }  // namespace gsr
+
+using gsr::fail;
+
+extern "C" {
+
+size_t gsr_knn3_scratch_bytes(uint32_t n) {
+    return n >= gsr::kKnn3MaxPoints ? 0 : gsr::knn3_layout(n).bytes;
+}
+
+int gsr_knn3_mean_dist(uint32_t n, const float* points, float* out, void* scratch, size_t scratch_bytes, void* stream_) {
+    if (n == 0) return GSR_OK;
+    if (n >= gsr::kKnn3MaxPoints) return fail(GSR_ERR_INVALID_ARG, "gsr_knn3_mean_dist: %u points (at most 2^30 - 1)", n);
+    if (!points || !out || !scratch) return fail(GSR_ERR_INVALID_ARG, "null pointer");
+    if (((uintptr_t)points & 3u) != 0u || ((uintptr_t)out & 3u) != 0u || ((uintptr_t)scratch & 255u) != 0u)
+        return fail(GSR_ERR_INVALID_ARG, "gsr_knn3_mean_dist: misaligned pointer (points / out: 4 bytes, scratch: 256 bytes)");
+    if (scratch_bytes < gsr_knn3_scratch_bytes(n))
+        return fail(GSR_ERR_INVALID_ARG, "gsr_knn3_mean_dist: scratch too small (%zu of %zu bytes)", scratch_bytes, gsr_knn3_scratch_bytes(n));
+    GSR_HIP(gsr::launch_knn3_mean_dist(n, points, out, scratch, (hipStream_t)stream_));
+    return GSR_OK;
+}
+
+size_t gsr_knn_points_scratch_bytes(int64_t n1, int64_t n2, int same) {
+    if (n1 < 0 || n2 < 0 || n1 >= (int64_t)gsr::kKnn3MaxPoints || n2 >= (int64_t)gsr::kKnn3MaxPoints) return 0;
+    return gsr::knn_points_scratch_bytes((uint32_t)n1, (uint32_t)n2, same != 0);
+}
+
+int gsr_knn_points(int64_t n1, const float* p1, int64_t n2, const float* p2, int K, float* dists, int64_t* idx, void* scratch,
+                   size_t scratch_bytes, void* stream_) {
+    if (n1 < 0 || n2 < 0) return fail(GSR_ERR_INVALID_ARG, "gsr_knn_points: negative count (n1 %lld, n2 %lld)", (long long)n1, (long long)n2);
+    if (n1 >= (int64_t)gsr::kKnn3MaxPoints || n2 >= (int64_t)gsr::kKnn3MaxPoints)
+        return fail(GSR_ERR_INVALID_ARG, "gsr_knn_points: %lld and %lld points (at most 2^30 - 1 each)", (long long)n1, (long long)n2);
+    if (K < 1 || K > gsr::kKnnPointsMaxK) return fail(GSR_ERR_INVALID_ARG, "gsr_knn_points: K = %d (1 to %d)", K, gsr::kKnnPointsMaxK);
+    if (n1 == 0) return GSR_OK;
+    if (n2 < K) return fail(GSR_ERR_INVALID_ARG, "gsr_knn_points: n2 = %lld is less than K = %d", (long long)n2, K);
+    if (!p1 || !p2 || !dists || !idx || !scratch) return fail(GSR_ERR_INVALID_ARG, "gsr_knn_points: null pointer");
+    // K = 4, 8, 16 rows are written with 16-byte stores; every other K element by element
+    const bool wide = K == 4 || K == 8 || K == 16;
+    if (((uintptr_t)p1 & 3u) != 0u || ((uintptr_t)p2 & 3u) != 0u || ((uintptr_t)dists & (wide ? 15u : 3u)) != 0u ||
+        ((uintptr_t)idx & (wide ? 15u : 7u)) != 0u || ((uintptr_t)scratch & 255u) != 0u)
+        return fail(GSR_ERR_INVALID_ARG, "gsr_knn_points: misaligned pointer (p1 / p2: 4 bytes; dists / idx: 16 bytes for K = 4, 8, 16, "
+                                         "else 4 / 8 bytes; scratch: 256 bytes)");
+    const size_t need = gsr_knn_points_scratch_bytes(n1, n2, p1 == p2 && n1 == n2);
+    if (scratch_bytes < need) return fail(GSR_ERR_INVALID_ARG, "gsr_knn_points: scratch too small (%zu of %zu bytes)", scratch_bytes, need);
+    GSR_HIP(gsr::launch_knn_points((uint32_t)n1, p1, (uint32_t)n2, p2, K, dists, reinterpret_cast<long long*>(idx), scratch,
+                                   (hipStream_t)stream_));
+    return GSR_OK;
+}
+
+
+}  // extern "C"

@@ -10,6 +10,8 @@
 // Formats: PNG (ISO/IEC 15948) chunk layout + CRC, 8-bit truecolour with or without alpha, non-interlaced; OpenEXR 2 single-part
 // scanline files ("OpenEXR File Layout"), compression RLE / ZIPS / ZIP, the wanted channel HALF or FLOAT, no sub-sampling.  Anything
 // else is reported as "not covered" (the caller's host decoder reads it), never guessed at.
+// Defines the entry points gsr_png_file_probe, gsr_png_file_inflate, gsr_exr_file_probe, gsr_exr_file_inflate, gsr_exr_file_pack and
+// gsr_selftest_inflate_host.
 #include "gsr_internal.h"
 #include "gsr_inflate_core.h"
 
@@ -81,7 +83,7 @@ bool walk_png(const uint8_t* f, size_t n, PngWalk* out) {
 
 // ---- OpenEXR ---------------------------------------------------------------------------------------------------------------------
 struct ExrWalk {
-    ExrFileLayout layout = {};
+    GsrExrFileInfo layout = {};
     int compression = -1;
     int n_blocks = 0;
     size_t offsets_at = 0;
@@ -176,7 +178,7 @@ bool walk_exr(const uint8_t* f, size_t n, const char* want, ExrWalk* out) {
     }
     const long long bytes_per_line = per_pixel * W;
     if (bytes_per_line * lines_per_block > (1ll << 30) || bytes_per_line * H > (1ll << 32)) return false;
-    ExrFileLayout& L = out->layout;
+    GsrExrFileInfo& L = out->layout;
     L.width = (int)W;
     L.height = (int)H;
     L.bytes_per_line = (int)bytes_per_line;
@@ -225,8 +227,6 @@ bool exr_rle_decode(const uint8_t* in, size_t n_in, uint8_t* out, size_t n_out) 
     return o == n_out;
 }
 
-} // namespace
-
 // The wave decoder's host instantiation (one lane): what the CPU tests compare with zlib.  src need not be aligned here.
 int inflate_zlib_host(const uint8_t* src, size_t src_len, uint8_t* dst, size_t dst_len) {
     std::vector<uint32_t> aligned((src_len + 3) / 4 + 2, 0u);
@@ -236,7 +236,8 @@ int inflate_zlib_host(const uint8_t* src, size_t src_len, uint8_t* dst, size_t d
                                     *reinterpret_cast<inflate::Shared*>(shared.data()));
 }
 
-int png_file_probe(const uint8_t* file, size_t n, PngFileLayout* out) {
+// 0: a file the kernels take; 1: not covered (another flavour, or damaged) -- a host decoder's.
+int png_file_probe(const uint8_t* file, size_t n, GsrPngFileInfo* out) {
     PngWalk w;
     if (!walk_png(file, n, &w)) return 1;
     out->width = w.width;
@@ -278,7 +279,7 @@ int png_file_inflate(const uint8_t* file, size_t n, uint8_t* scanlines, size_t s
     return 0;
 }
 
-int exr_file_probe(const uint8_t* file, size_t n, const char* want_channel, ExrFileLayout* out) {
+int exr_file_probe(const uint8_t* file, size_t n, const char* want_channel, GsrExrFileInfo* out) {
     ExrWalk w;
     if (!walk_exr(file, n, want_channel, &w)) return 1;
     *out = w.layout;
@@ -288,7 +289,7 @@ int exr_file_probe(const uint8_t* file, size_t n, const char* want_channel, ExrF
 int exr_file_inflate(const uint8_t* file, size_t n, const char* want_channel, uint8_t* blocks, size_t blocks_bytes) {
     ExrWalk w;
     if (!walk_exr(file, n, want_channel, &w)) return 1;
-    const ExrFileLayout& L = w.layout;
+    const GsrExrFileInfo& L = w.layout;
     if (blocks_bytes != L.blocks_bytes) return 1;
     size_t at = 0;
     for (int k = 0; k < w.n_blocks; ++k) {
@@ -307,10 +308,12 @@ int exr_file_inflate(const uint8_t* file, size_t n, const char* want_channel, ui
     return 0;
 }
 
-int exr_file_pack(const uint8_t* file, size_t n, const char* want_channel, uint8_t* packed, size_t packed_room, InflateJob* jobs, size_t* packed_bytes) {
+// ZIP / ZIPS files: the blocks' zlib streams copied one behind the other at 4-byte aligned offsets into `packed` (room: n + 4 * n_blocks
+// + 4 bytes), jobs[n_blocks] filled for gsr_inflate_zlib_blocks; *packed_bytes: what to upload.
+int exr_file_pack(const uint8_t* file, size_t n, const char* want_channel, uint8_t* packed, size_t packed_room, GsrInflateJob* jobs, size_t* packed_bytes) {
     ExrWalk w;
     if (!walk_exr(file, n, want_channel, &w) || w.compression == 1) return 1;      // (RLE is not a zlib stream: exr_file_inflate)
-    const ExrFileLayout& L = w.layout;
+    const GsrExrFileInfo& L = w.layout;
     size_t at = 0, out_at = 0;
     for (int k = 0; k < w.n_blocks; ++k) {
         const uint64_t off = le64(file + w.offsets_at + 8 * (size_t)k);
@@ -328,4 +331,42 @@ int exr_file_pack(const uint8_t* file, size_t n, const char* want_channel, uint8
     return 0;
 }
 
+} // namespace
 } // namespace gsr
+
+using gsr::fail;
+
+extern "C" {
+
+int gsr_png_file_probe(const uint8_t* file, size_t file_bytes, GsrPngFileInfo* info) {
+    if (!file || !info) return fail(GSR_ERR_INVALID_ARG, "null pointer");
+    return gsr::png_file_probe(file, file_bytes, info);
+}
+
+int gsr_png_file_inflate(const uint8_t* file, size_t file_bytes, uint8_t* scanlines, size_t scanline_bytes) {
+    if (!file || !scanlines) return fail(GSR_ERR_INVALID_ARG, "null pointer");
+    return gsr::png_file_inflate(file, file_bytes, scanlines, scanline_bytes);
+}
+
+int gsr_exr_file_probe(const uint8_t* file, size_t file_bytes, const char* channel, GsrExrFileInfo* info) {
+    if (!file || !info) return fail(GSR_ERR_INVALID_ARG, "null pointer");
+    return gsr::exr_file_probe(file, file_bytes, channel, info);
+}
+
+int gsr_exr_file_inflate(const uint8_t* file, size_t file_bytes, const char* channel, uint8_t* blocks, size_t blocks_bytes) {
+    if (!file || !blocks) return fail(GSR_ERR_INVALID_ARG, "null pointer");
+    return gsr::exr_file_inflate(file, file_bytes, channel, blocks, blocks_bytes);
+}
+
+int gsr_exr_file_pack(const uint8_t* file, size_t file_bytes, const char* channel, uint8_t* packed, size_t packed_room, GsrInflateJob* jobs, size_t* packed_bytes) {
+    if (!file || !packed || !jobs || !packed_bytes) return fail(GSR_ERR_INVALID_ARG, "null pointer");
+    return gsr::exr_file_pack(file, file_bytes, channel, packed, packed_room, jobs, packed_bytes);
+}
+
+int gsr_selftest_inflate_host(const uint8_t* zlib_stream, size_t stream_bytes, uint8_t* out, size_t out_bytes) {
+    if (!zlib_stream || (!out && out_bytes)) return fail(GSR_ERR_INVALID_ARG, "null pointer");
+    return gsr::inflate_zlib_host(zlib_stream, stream_bytes, out, out_bytes);
+}
+
+
+}  // extern "C"

@@ -22,6 +22,7 @@
 //
 // Host-side mirror: autovfx_amd/layer_io.py (chunk / header parsing, zlib, the fall-back to Pillow / autovfx_amd.exr for files these
 // kernels do not cover).
+// Defines the entry points gsr_png_unfilter_scratch, gsr_png_unfilter(_batch), gsr_exr_unpack_channel and gsr_inflate_zlib_blocks.
 #include "gsr_internal.h"
 #include "gsr_inflate_core.h"
 
@@ -30,6 +31,9 @@
 
 namespace gsr {
 namespace {
+
+using InflateJob = GsrInflateJob;
+using PngUnfilterJob = GsrPngUnfilterJob;
 
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 typedef short i16x2 __attribute__((ext_vector_type(2)));
@@ -295,19 +299,25 @@ __global__ void __launch_bounds__(64) inflate_zlib_kernel(const uint8_t* __restr
     }
 }
 
-} // namespace
-
+// zlib streams inflated on the GPU, a single-wave workgroup each.  jobs / status / any_error: DEVICE memory; src_at multiples of 4,
+// `streams` readable up to the next multiple of 4 behind every stream.  status[i]: 0 or an inflate::Status; *any_error is OR-ed with 1.
 hipError_t launch_inflate_zlib_blocks(const uint8_t* streams, uint8_t* out, const InflateJob* jobs, int count, int* status, int* any_error, hipStream_t stream) {
     if (count > 0) hipLaunchKernelGGL(inflate_zlib_kernel, dim3(count), dim3(64), 0, stream, streams, out, jobs, status, any_error);
     return hipGetLastError();
 }
+
+} // namespace
 
 size_t png_unfilter_scratch_bytes(int W, int H) {
     if (W <= 0 || H <= 0 || W > kUnfMaxWidth) return 0;
     return (size_t)H * (size_t)(W + kUnfPad + kUnfTail) * 4;
 }
 
-hipError_t launch_png_unfilter_batch(int n, const PngUnfilterJob* jobs, hipStream_t stream) {
+namespace {
+
+// The inflated IDAT stream of an 8-bit RGB / RGBA, non-interlaced PNG (device memory) -> RGBA8 [H,W,4] (alpha 255 for RGB).
+// Every job's scratch: png_unfilter_scratch_bytes(W, H) bytes, 16-byte aligned.
+hipError_t launch_png_unfilter_batch(int n, const PngUnfilterJob* jobs, hipStream_t stream) {   // one workgroup per image, eight images per launch
     static std::once_flag once[16];
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
@@ -334,6 +344,8 @@ hipError_t launch_png_unfilter_batch(int n, const PngUnfilterJob* jobs, hipStrea
     return hipGetLastError();
 }
 
+// The inflated, still predictor-coded scanline blocks of an OpenEXR file one after another (device memory) -> the bytes of the channel
+// that occupies [c_at, c_at + c_bytes) of every line: plane[H][c_bytes].
 hipError_t launch_exr_unpack_channel(const uint8_t* blocks, int H, int bytes_per_line, int lines_per_block, int c_at, int c_bytes, uint8_t* plane,
                                      hipStream_t stream) {
     ExrPlan p = {blocks, plane, H, bytes_per_line, lines_per_block, c_at, c_bytes};
@@ -342,4 +354,53 @@ hipError_t launch_exr_unpack_channel(const uint8_t* blocks, int H, int bytes_per
     return hipGetLastError();
 }
 
+} // namespace
 } // namespace gsr
+
+using gsr::fail;
+
+extern "C" {
+
+size_t gsr_png_unfilter_scratch(int width, int height) { return gsr::png_unfilter_scratch_bytes(width, height); }
+
+int gsr_png_unfilter_batch(int count, const GsrPngUnfilterJob* jobs, void* stream_) {
+    if (count < 0 || (count > 0 && !jobs)) return fail(GSR_ERR_INVALID_ARG, "gsr_png_unfilter_batch: bad job list");
+    for (int i = 0; i < count; ++i) {
+        const GsrPngUnfilterJob& j = jobs[i];
+        if (gsr::png_unfilter_scratch_bytes(j.width, j.height) == 0 || (j.channels != 3 && j.channels != 4))
+            return fail(GSR_ERR_INVALID_ARG, "gsr_png_unfilter: job %d: %dx%d with %d channels is not supported (8-bit RGB / RGBA, at most 4096 pixels wide)", i,
+                        j.width, j.height, j.channels);
+        if (!j.scanlines || !j.out_rgba || !j.scratch) return fail(GSR_ERR_INVALID_ARG, "gsr_png_unfilter: job %d: null pointer", i);
+        if (((reinterpret_cast<uintptr_t>(j.out_rgba) | reinterpret_cast<uintptr_t>(j.scratch)) & 15u) != 0)
+            return fail(GSR_ERR_INVALID_ARG, "gsr_png_unfilter: job %d: out_rgba and scratch must be 16-byte aligned", i);
+    }
+    if (count == 0) return GSR_OK;
+    GSR_HIP(gsr::launch_png_unfilter_batch(count, jobs, (hipStream_t)stream_));
+    return GSR_OK;
+}
+
+int gsr_png_unfilter(const uint8_t* scanlines, int width, int height, int channels, uint8_t* out_rgba, uint8_t* scratch, void* stream_) {
+    const GsrPngUnfilterJob job = {scanlines, width, height, channels, out_rgba, scratch};
+    return gsr_png_unfilter_batch(1, &job, stream_);
+}
+
+int gsr_exr_unpack_channel(const uint8_t* blocks, int height, int bytes_per_line, int lines_per_block, int channel_at, int channel_bytes, uint8_t* plane,
+                           void* stream_) {
+    if (height <= 0 || bytes_per_line <= 0 || (bytes_per_line & 1) || lines_per_block <= 0 || channel_at < 0 || channel_bytes <= 0 ||
+        channel_at + channel_bytes > bytes_per_line || (long long)bytes_per_line * lines_per_block > (1ll << 30))
+        return fail(GSR_ERR_INVALID_ARG, "gsr_exr_unpack_channel: bad layout (height %d, %d bytes per line, %d lines per block, channel at %d + %d)", height,
+                    bytes_per_line, lines_per_block, channel_at, channel_bytes);
+    if (!blocks || !plane) return fail(GSR_ERR_INVALID_ARG, "null pointer");
+    GSR_HIP(gsr::launch_exr_unpack_channel(blocks, height, bytes_per_line, lines_per_block, channel_at, channel_bytes, plane, (hipStream_t)stream_));
+    return GSR_OK;
+}
+
+int gsr_inflate_zlib_blocks(const uint8_t* streams, uint8_t* out, const GsrInflateJob* jobs, int count, int* status, int* any_error, void* stream_) {
+    if (count < 0 || (count > 0 && (!streams || !out || !jobs || !status))) return fail(GSR_ERR_INVALID_ARG, "gsr_inflate_zlib_blocks: bad arguments");
+    if ((reinterpret_cast<uintptr_t>(streams) & 3u) != 0) return fail(GSR_ERR_INVALID_ARG, "gsr_inflate_zlib_blocks: streams must be 4-byte aligned");
+    GSR_HIP(gsr::launch_inflate_zlib_blocks(streams, out, jobs, count, status, any_error, (hipStream_t)stream_));
+    return GSR_OK;
+}
+
+
+}  // extern "C"

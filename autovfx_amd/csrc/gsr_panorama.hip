@@ -18,12 +18,16 @@
 // Optional outputs: the float panorama [H,W,C]; the LDR bytes the reference saves, uint8(clip(x * 255, 0, 255)) of the float
 // value (truncation, not save_image's + 0.5); and the radial-distance panorama: the same taps and weights over
 // depth * sqrt(1 + (2 cx)^2 + (2 cy)^2), evaluated at each tap's SOURCE texel ("Panoramas").
+// Defines the entry point gsr_cube_to_equirect.
 #include "gsr_internal.h"
 
 #include <cmath>
 
 namespace gsr {
 namespace {
+
+// The six faces of a cube map, in the reference's dict order (front, right, back, left, up, down): planar [C,S,S] colour or [S,S] depth.
+struct CubeFacePointers { const float* p[6]; };
 
 // the reference's dict order (cube_dict2h): 0 front, 1 right, 2 back, 3 left, 4 up, 5 down
 struct Texel { int face, row, col; };   // face < 0: a zero of the padding
@@ -130,8 +134,8 @@ __global__ void __launch_bounds__(256) cube_to_equirect_kernel(CubeFacePointers 
     }
 }
 
-}  // namespace
-
+// c2e(..., mode='bilinear') of the reference (gsr.h: gsr_cube_to_equirect); grid_u [W], grid_v [H], grid_ceil [W/4] as the host computes
+// them; any of out [H,W,C] / out_u8 [H,W,C] / out_depth [H,W] may be null (depth.p is read only when out_depth is set).
 hipError_t launch_cube_to_equirect(const CubeFacePointers& faces, const CubeFacePointers& depth, int S, int C, const float* grid_u,
                                    const float* grid_v, const int* grid_ceil, int H, int W, float* out, uint8_t* out_u8, float* out_depth,
                                    hipStream_t stream) {
@@ -140,4 +144,31 @@ hipError_t launch_cube_to_equirect(const CubeFacePointers& faces, const CubeFace
     return hipGetLastError();
 }
 
+}  // namespace
 }  // namespace gsr
+
+using gsr::fail;
+
+extern "C" {
+
+int gsr_cube_to_equirect(const float* const* faces, int face_size, int channels, const float* const* depth_faces, const float* grid_u,
+                         const float* grid_v, const int32_t* grid_ceil, int height, int width, float* out, uint8_t* out_u8, float* out_depth,
+                         void* stream_) {
+    if (width <= 0 || width % 8 != 0) return fail(GSR_ERR_INVALID_ARG, "gsr_cube_to_equirect: the width (%d) must be a positive multiple of 8", width);
+    if (height < 2 || height > 65535) return fail(GSR_ERR_INVALID_ARG, "gsr_cube_to_equirect: bad height %d (2 .. 65535)", height);
+    if (face_size < 2 || face_size > 32768) return fail(GSR_ERR_INVALID_ARG, "gsr_cube_to_equirect: bad face size %d (2 .. 32768)", face_size);
+    if (channels < 1 || channels > 4) return fail(GSR_ERR_INVALID_ARG, "gsr_cube_to_equirect: %d channels (1 .. 4)", channels);
+    if (!faces || !grid_u || !grid_v || !grid_ceil || (!out && !out_u8 && !out_depth) || (out_depth && !depth_faces))
+        return fail(GSR_ERR_INVALID_ARG, "null pointer");
+    gsr::CubeFacePointers f = {}, d = {};
+    for (int k = 0; k < 6; ++k) {
+        if (!(f.p[k] = faces[k])) return fail(GSR_ERR_INVALID_ARG, "gsr_cube_to_equirect: face %d is null", k);
+        if (out_depth && !(d.p[k] = depth_faces[k])) return fail(GSR_ERR_INVALID_ARG, "gsr_cube_to_equirect: depth face %d is null", k);
+    }
+    GSR_HIP(gsr::launch_cube_to_equirect(f, d, face_size, channels, grid_u, grid_v, grid_ceil, height, width, out, out_u8, out_depth,
+                                         (hipStream_t)stream_));
+    return GSR_OK;
+}
+
+
+}  // extern "C"

@@ -37,6 +37,7 @@
 // A sort may DROP one key value in its first pass (radix_sort_pairs' drop_key: the depth sort's culled Gaussians, a quarter
 // of C3's and most of a close-up's): the count kernel does not count those items, the scatter neither ranks nor writes them
 // and stores how many were kept; the later passes read that count (n_device) and sort the kept ones only.
+// Defines the entry points gsr_radix_scratch_bytes, gsr_radix_sort_pairs and gsr_selftest_lds_atomic_order.
 #include "gsr_internal.h"
 
 #include <mutex>
@@ -523,8 +524,9 @@ __global__ void __launch_bounds__(256) lds_atomic_order_selftest_kernel(uint32_t
 
 } // namespace
 
-hipError_t launch_lds_atomic_order_selftest(uint32_t workgroups, uint32_t rounds, uint32_t seed, unsigned long long* mismatches,
-                                            hipStream_t stream) {
+// counts the returning LDS adds whose result was not (value before the instruction) + (lower lanes on the same counter)
+static hipError_t launch_lds_atomic_order_selftest(uint32_t workgroups, uint32_t rounds, uint32_t seed, unsigned long long* mismatches,
+                                                   hipStream_t stream) {
     hipLaunchKernelGGL(lds_atomic_order_selftest_kernel, dim3(workgroups), dim3(256), 0, stream, rounds, seed, mismatches);
     return hipGetLastError();
 }
@@ -710,3 +712,37 @@ hipError_t radix_sort_pairs(uint32_t* scratch, uint32_t n, int bits, uint32_t* k
 }
 
 } // namespace gsr
+
+using gsr::fail;
+
+extern "C" {
+
+size_t gsr_radix_scratch_bytes(uint32_t n, int bits) {
+    (void)bits;
+    return gsr::radix_scratch_words(n) * sizeof(uint32_t);
+}
+
+int gsr_radix_sort_pairs(uint32_t n, int bits, uint32_t* keys, uint32_t* keys_alt, uint32_t* vals, uint32_t* vals_alt,
+                         int iota_payload, void* scratch, size_t scratch_bytes, int* sorted_in_alt, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (bits < 1 || bits > 32) return fail(GSR_ERR_INVALID_ARG, "bad key width bits=%d", bits);
+    if (sorted_in_alt) *sorted_in_alt = 0;
+    if (n == 0) return GSR_OK;
+    if (!keys || !keys_alt || !vals_alt || (!vals && !iota_payload) || !scratch)
+        return fail(GSR_ERR_INVALID_ARG, "null pointer");
+    if (scratch_bytes < gsr_radix_scratch_bytes(n, bits)) return fail(GSR_ERR_INVALID_ARG, "sort scratch too small");
+    uint32_t *ks = nullptr, *vs = nullptr;
+    GSR_HIP(gsr::radix_sort_pairs((uint32_t*)scratch, n, bits, keys, keys_alt, vals, vals_alt, iota_payload != 0, true, &ks,
+                                  &vs, stream));
+    if (sorted_in_alt) *sorted_in_alt = ks == keys_alt;
+    return GSR_OK;
+}
+
+int gsr_selftest_lds_atomic_order(uint32_t workgroups, uint32_t rounds, uint32_t seed, unsigned long long* device_mismatches, void* stream_) {
+    if (!device_mismatches || workgroups == 0 || workgroups > (1u << 20)) return fail(GSR_ERR_INVALID_ARG, "bad selftest arguments");
+    GSR_HIP(gsr::launch_lds_atomic_order_selftest(workgroups, rounds, seed, device_mismatches, (hipStream_t)stream_));
+    return GSR_OK;
+}
+
+
+}  // extern "C"

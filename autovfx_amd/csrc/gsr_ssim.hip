@@ -19,6 +19,7 @@
 // Reduction order, fixed: the workgroup's S values are summed per wave by xor-shuffles, the four wave sums in wave order, one partial
 // per workgroup in the caller's scratch; ssim_mean_kernel adds the partials of one output in fp64 over a fixed lane assignment and tree.
 // No atomics anywhere: two calls on the same inputs give the same bits, forward and backward.
+// Defines the entry points gsr_ssim_scratch_bytes, gsr_ssim_forward and gsr_ssim_backward.
 #include "gsr_internal.h"
 
 namespace gsr {
@@ -35,7 +36,17 @@ constexpr int kThreads = 256;
 constexpr uint32_t kMaxGrid = 1u << 16;           // workgroups launched; more tiles are walked grid-stride
 static_assert(kTileW * kTileH == 2 * kThreads, "the vertical pass gives every lane two outputs");
 static_assert(kRowItems <= kThreads, "one horizontal item per lane");
-static_assert(kTaps == kSsimTaps, "the window of the C ABI");
+constexpr int kSsimTaps = kTaps;                  // gsr.h: window11
+constexpr float kSsimC1 = (float)(0.01 * 0.01);   // the reference's Python constants, rounded to fp32 as its fp32 tensor ops do
+constexpr float kSsimC2 = (float)(0.03 * 0.03);
+struct SsimWindow {   // the separable window, passed by value
+    float w[kSsimTaps];
+};
+struct SsimShape {
+    int n, c, h, w;
+    int tiles_x;
+    uint32_t tiles_per_plane, blocks;   // blocks = n c tiles_per_plane (one partial sum each)
+};
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -217,9 +228,7 @@ __global__ __launch_bounds__(kThreads) void ssim_backward_kernel(SsimShape s, Ss
     }
 }
 
-}  // namespace
-
-SsimShape ssim_shape(int n, int c, int h, int w) {
+SsimShape ssim_shape(int n, int c, int h, int w) {   // n c h w < 2^31
     SsimShape s{n, c, h, w, (w + kTileW - 1) / kTileW, 0, 0};
     s.tiles_per_plane = (uint32_t)s.tiles_x * (uint32_t)((h + kTileH - 1) / kTileH);
     s.blocks = (uint32_t)n * (uint32_t)c * s.tiles_per_plane;
@@ -243,4 +252,55 @@ hipError_t launch_ssim_backward(const SsimShape& s, const SsimWindow& win, const
     return hipGetLastError();
 }
 
+}  // namespace
 }  // namespace gsr
+
+using gsr::aligned4;
+using gsr::fail;
+
+namespace {
+// the sizes gsr_ssim_* accept: every dimension > 0, n c h w < 2^31
+bool ssim_size_ok(int n, int c, int h, int w) {
+    if (n <= 0 || c <= 0 || h <= 0 || w <= 0) return false;
+    const int64_t nc = (int64_t)n * c, nch = nc * h;
+    return nc < (int64_t(1) << 31) && nch < (int64_t(1) << 31) && nch * w < (int64_t(1) << 31);
+}
+gsr::SsimWindow ssim_window(const float* window11) {
+    gsr::SsimWindow win;
+    for (int k = 0; k < gsr::kSsimTaps; ++k) win.w[k] = window11[k];
+    return win;
+}
+}  // namespace
+
+
+extern "C" {
+
+size_t gsr_ssim_scratch_bytes(int n, int c, int h, int w) {
+    return ssim_size_ok(n, c, h, w) ? (size_t)gsr::ssim_shape(n, c, h, w).blocks * sizeof(float) : 0;
+}
+
+int gsr_ssim_forward(int n, int c, int h, int w, const float* x, const float* y, const float* window11, int per_image, float* out,
+                     float* coef_or_null, void* scratch, size_t scratch_bytes, void* stream_) {
+    if (!ssim_size_ok(n, c, h, w)) return fail(GSR_ERR_INVALID_ARG, "gsr_ssim_forward: bad size %d x %d x %d x %d (each > 0, product < 2^31)", n, c, h, w);
+    if (!x || !y || !window11 || !out || !scratch) return fail(GSR_ERR_INVALID_ARG, "gsr_ssim_forward: null pointer");
+    if (!aligned4(x) || !aligned4(y) || !aligned4(out) || !aligned4(coef_or_null) || !aligned4(scratch))
+        return fail(GSR_ERR_INVALID_ARG, "gsr_ssim_forward: misaligned pointer (4 bytes)");
+    if (scratch_bytes < gsr_ssim_scratch_bytes(n, c, h, w))
+        return fail(GSR_ERR_INVALID_ARG, "gsr_ssim_forward: scratch too small (%zu of %zu bytes)", scratch_bytes, gsr_ssim_scratch_bytes(n, c, h, w));
+    GSR_HIP(gsr::launch_ssim_forward(gsr::ssim_shape(n, c, h, w), ssim_window(window11), x, y, per_image ? 1 : 0, out, coef_or_null,
+                                     (float*)scratch, (hipStream_t)stream_));
+    return GSR_OK;
+}
+
+int gsr_ssim_backward(int n, int c, int h, int w, const float* x, const float* y, const float* coef, const float* window11, int per_image,
+                      const float* grad_out, float* grad_x, void* stream_) {
+    if (!ssim_size_ok(n, c, h, w)) return fail(GSR_ERR_INVALID_ARG, "gsr_ssim_backward: bad size %d x %d x %d x %d (each > 0, product < 2^31)", n, c, h, w);
+    if (!x || !y || !coef || !window11 || !grad_out || !grad_x) return fail(GSR_ERR_INVALID_ARG, "gsr_ssim_backward: null pointer");
+    if (!aligned4(x) || !aligned4(y) || !aligned4(coef) || !aligned4(grad_out) || !aligned4(grad_x))
+        return fail(GSR_ERR_INVALID_ARG, "gsr_ssim_backward: misaligned pointer (4 bytes)");
+    GSR_HIP(gsr::launch_ssim_backward(gsr::ssim_shape(n, c, h, w), ssim_window(window11), x, y, coef, per_image ? 1 : 0, grad_out, grad_x,
+                                      (hipStream_t)stream_));
+    return GSR_OK;
+}
+
+}  // extern "C"

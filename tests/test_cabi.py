@@ -201,3 +201,85 @@ def test_call_looks_the_function_up_at_call_time(monkeypatch):
     monkeypatch.setattr(_lib.lib, "gsr_adam_step", lambda *a: -1)
     with pytest.raises(RuntimeError, match=r"gsr_adam_step failed \(-1\)"):
         _lib.call("gsr_adam_step", None, 0, 0.0, 0.0, 0.0, 0.0, None)
+
+
+def _null_faces():
+    return (ctypes.c_void_p * 6)()
+
+
+# One refusal per validation path of the entry points that live beside their kernels and have no device-free refusal test in a
+# file of their own: (id, function, arguments, status, gsr_last_error()).  Every call stops at an argument check, before any launch.
+REFUSALS = [
+    ("mark_visible-size", "gsr_mark_visible", (-1, None, None, None, None, None), -1, "P < 0"),
+    ("mark_visible-null", "gsr_mark_visible", (3, None, None, None, None, None), -1, "null pointer"),
+    ("composite-size", "gsr_composite", (0, 4) + (None,) * 13, -1, "bad image size 0x4"),
+    ("composite-null", "gsr_composite", (4, 4) + (None,) * 13, -1, "null required layer"),
+    ("pack_rgba8-size", "gsr_pack_rgba8", (None, None, None, 0, 4, None), -1, "bad image size 0x4"),
+    ("pack_rgba8-null", "gsr_pack_rgba8", (None, None, None, 4, 4, None), -1, "null pointer"),
+    ("view_normals-size", "gsr_view_normals", (-1, None, None, None, None, None), -1, "bad size P=-1"),
+    ("normal_maps-size", "gsr_normal_maps", (0, 4, None, None, None, 1.0, 1.0, 0.0, 0.0, None, None, None), -1, "bad image size 0x4"),
+    ("normal_maps-null", "gsr_normal_maps", (4, 4, None, None, None, 1.0, 1.0, 0.0, 0.0, None, None, None), -1, "null pointer"),
+    ("place_object-size", "gsr_place_object", (-1,) + (None,) * 5 + (1, None) + (None,) * 7, -1, "bad size n=-1"),
+    ("place_object-null", "gsr_place_object", (3,) + (None,) * 5 + (1, None) + (None,) * 7, -1, "null pointer"),
+    ("place_object_subset-null", "gsr_place_object_subset", (2,) + (None,) * 6 + (1, None) + (None,) * 7, -1, "null subset"),
+    ("selftest_exp", "gsr_selftest_exp", (0, 1, None, None), -1, "bad selftest arguments"),
+    ("radix_sort-bits", "gsr_radix_sort_pairs", (5, 0, None, None, None, None, 0, None, 0, None, None), -1, "bad key width bits=0"),
+    ("radix_sort-null", "gsr_radix_sort_pairs", (5, 8, None, None, None, None, 0, None, 0, None, None), -1, "null pointer"),
+    ("selftest_lds", "gsr_selftest_lds_atomic_order", (0, 1, 1, None, None), -1, "bad selftest arguments"),
+    ("resize_rgba8-size", "gsr_resize_rgba8_bilinear", (None, 0, 4, None, 4, 4, None, None), -1, "bad image size 0x4 -> 4x4"),
+    ("resize_rgba8-null", "gsr_resize_rgba8_bilinear", (None, 8, 8, None, 4, 4, None, None), -1, "null pointer"),
+    ("resize_f32-size", "gsr_resize_f32_nearest", (None, 4, 4, None, 4, -2, None), -1, "bad image size 4x4 -> 4x-2"),
+    ("frame_files-size", "gsr_frame_files", (None,) * 4 + (1.0, None, 0, 4) + (None,) * 6, -1, "bad image size 0x4"),
+    ("frame_files_deflate-null", "gsr_frame_files_deflate", (None,) * 4 + (1.0, None, 4, 4) + (None,) * 8, -1, "null pointer"),
+    ("png_encode-channels", "gsr_png_encode", (None, 4, 4, 5, 0, None, None), -1,
+     "gsr_png_encode: 4x4 with 5 channels cannot be encoded (3 or 4 channels, < 2 GB)"),
+    ("png_encode-null", "gsr_png_encode", (None, 4, 4, 3, 0, None, None), -1, "null pointer"),
+    ("png_encode_deflate-channels", "gsr_png_encode_deflate", (None, 4, 4, 2, 0, None, None, None, None), -1,
+     "gsr_png_encode_deflate: 4x4 with 2 channels cannot be encoded (3 or 4 channels, < 2 GB)"),
+    ("png_unfilter-width", "gsr_png_unfilter", (None, 5000, 4, 4, None, None, None), -1,
+     "gsr_png_unfilter: job 0: 5000x4 with 4 channels is not supported (8-bit RGB / RGBA, at most 4096 pixels wide)"),
+    ("png_unfilter-null", "gsr_png_unfilter", (None, 8, 4, 3, None, None, None), -1, "gsr_png_unfilter: job 0: null pointer"),
+    ("png_unfilter_batch-list", "gsr_png_unfilter_batch", (-1, None, None), -1, "gsr_png_unfilter_batch: bad job list"),
+    ("exr_unpack-layout", "gsr_exr_unpack_channel", (None, 0, 8, 1, 0, 2, None, None), -1,
+     "gsr_exr_unpack_channel: bad layout (height 0, 8 bytes per line, 1 lines per block, channel at 0 + 2)"),
+    ("exr_unpack-null", "gsr_exr_unpack_channel", (None, 4, 8, 1, 0, 2, None, None), -1, "null pointer"),
+    ("inflate_zlib_blocks-count", "gsr_inflate_zlib_blocks", (None, None, None, -1, None, None, None), -1,
+     "gsr_inflate_zlib_blocks: bad arguments"),
+    ("png_file_probe-null", "gsr_png_file_probe", (None, 0, None), -1, "null pointer"),
+    ("exr_file_pack-null", "gsr_exr_file_pack", (b"x", 1, None, None, 0, None, None), -1, "null pointer"),
+    ("selftest_inflate_host-null", "gsr_selftest_inflate_host", (None, 0, None, 0), -1, "null pointer"),
+    ("cube_to_equirect-width", "gsr_cube_to_equirect", (None, 8, 3, None, None, None, None, 8, 12, None, None, None, None), -1,
+     "gsr_cube_to_equirect: the width (12) must be a positive multiple of 8"),
+    ("cube_to_equirect-null", "gsr_cube_to_equirect", (None, 8, 3, None, None, None, None, 8, 16, None, None, None, None), -1,
+     "null pointer"),
+]
+
+
+@pytest.mark.parametrize("name,args,status,message", [pytest.param(*c[1:], id=c[0]) for c in REFUSALS])
+def test_refusals_keep_their_status_and_text(name, args, status, message):
+    """The texts were recorded from the library before the entry points moved out of gsr_api.hip: a refusal from any unit
+    sets the one message gsr_last_error() returns."""
+    from autovfx_amd import _lib
+    assert _lib.lib.gsr_set_option(-1, 0) == -1 and _lib.last_error() == "unknown option -1"   # a known message to overwrite
+    assert getattr(_lib.lib, name)(*args) == status
+    assert _lib.last_error() == message
+
+
+def test_a_refusal_on_another_thread_keeps_its_own_message():
+    """The message buffer is per thread and lives in one unit: a refusal from gsr_kernels.hip on a second thread is read back
+    there, and the first thread still reads the refusal it got from gsr_radix.hip."""
+    import threading
+    from autovfx_amd import _lib
+    assert _lib.lib.gsr_radix_sort_pairs(5, 0, None, None, None, None, 0, None, 0, None, None) == -1
+    seen = {}
+
+    def other():
+        seen["before"] = _lib.last_error()
+        seen["status"] = _lib.lib.gsr_pack_rgba8(None, None, None, 0, 4, None)
+        seen["after"] = _lib.last_error()
+
+    t = threading.Thread(target=other)
+    t.start()
+    t.join()
+    assert seen == {"before": "", "status": -1, "after": "bad image size 0x4"}
+    assert _lib.last_error() == "bad key width bits=0"
