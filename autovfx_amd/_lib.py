@@ -180,6 +180,8 @@ SIGNATURES = {
     "gsr_field_scratch_bytes": (_sz, [_i64]),                          # P
     "gsr_field_forward": (_i, _field_inputs + [_p, _p, _p, _p, _sz, _p]),            # ... density opacities beta scratch scratch_bytes stream
     "gsr_field_backward": (_i, _field_inputs + [_p, _p, _p, _p, _p, _p, _sz, _p]),   # ... g_density g_opacities g_beta dx accum scratch scratch_bytes stream
+    "gsr_level_surface": (_i, [_i64, _i, _i64, _i, _i, _p, _p, _p, _p, _p, _p, _p, _f,   # n K P S L origins dirs stds idx centers M strengths density_factor
+                               _p, _array(_f, 8), _p, _p, _p, _p, _p, _p, _sz, _p]),     # range levels hit t points normals densities scratch scratch_bytes stream
     "gsr_ssim_scratch_bytes": (_sz, [_i, _i, _i, _i]),                 # n c h w
     "gsr_ssim_forward": (_i, [_i, _i, _i, _i, _p, _p, _p, _i, _p, _p, _p, _sz, _p]),   # n c h w x y window11 per_image out coef_or_null scratch scratch_bytes stream
     "gsr_ssim_backward": (_i, [_i, _i, _i, _i, _p, _p, _p, _p, _i, _p, _p, _p]),       # n c h w x y coef window11 per_image grad_out grad_x stream

@@ -25,8 +25,13 @@
 //                           line of accum [P,16].  The 64 pairs of a wave are first laid out in LDS so that 16 consecutive lanes
 //                           add into one line (4 lines of 64 bytes per wave-instruction) instead of 64 lanes into 64 lines, which
 //                           was measured 13 x slower.  Exact zeros are not added.
+//   level_surface_kernel   the ray march of SuGaR's coarse mesh extraction (compute_level_surface_points_from_camera_fast,
+//                           sugar_model.py:1853-1950): one lane owns a ray and keeps the running densities of its S <= 32
+//                           samples in registers.  The neighbour loop is outermost, so a record is read once per ray instead of once
+//                           per sample and every density is still summed with k ascending; the crossings of up to 8 levels are found
+//                           in registers, and a second walk over the same K records sums the field's gradient at every crossing.
 // No host synchronisation, no allocation, everything on the caller's stream.
-// Defines the entry points gsr_field_scratch_bytes, gsr_field_forward and gsr_field_backward.
+// Defines the entry points gsr_field_scratch_bytes, gsr_field_forward, gsr_field_backward and gsr_level_surface.
 #include "gsr_internal.h"
 
 namespace gsr {
@@ -240,6 +245,154 @@ __global__ __launch_bounds__(kThreads) void field_backward_kernel(uint32_t n, in
     }
 }
 
+constexpr int kLevelMaxS = 32;         // samples per ray: the densities are a fixed register array
+constexpr int kLevelMaxL = 8;          // levels per call
+struct LevelSet {
+    float v[kLevelMaxL];
+};
+
+// Per ray i (include/gsr.h: gsr_level_surface): tau_s = range[s] stds[i], x_s = origins[i] + tau_s dirs[i], d_s = the field at x_s
+// (eval_pair's contract, k ascending, >= 1 renormalised), per level the first s with d_s > level after d_0 < level, the interpolated
+// crossing, and there -g / max(|g|, 1e-12) with g = sum_k o_k (M_k w_k).  The loops over s and over the levels are unrolled to their
+// largest counts under uniform guards, so that d[], the crossings and g[] are registers.
+__global__ __launch_bounds__(kThreads) void level_surface_kernel(uint32_t n, int K, long long P, int S, int L, const float* __restrict__ origins,
+                                                                 const float* __restrict__ dirs, const float* __restrict__ stds,
+                                                                 const long long* __restrict__ idx, const float4* __restrict__ packed,
+                                                                 float density_factor, const float* __restrict__ range, LevelSet levels,
+                                                                 unsigned char* __restrict__ hit, float* __restrict__ t_out,
+                                                                 float* __restrict__ points, float* __restrict__ normals,
+                                                                 float* __restrict__ densities) {
+    __shared__ int tile[kThreads * kPitch];
+    const uint32_t first = blockIdx.x * kThreads;
+    const uint32_t i = first + threadIdx.x;
+    const bool active = i < n;
+    float o0 = 0.0f, o1 = 0.0f, o2 = 0.0f, v0 = 0.0f, v1 = 0.0f, v2 = 0.0f, sd = 0.0f;
+    if (active) {
+        o0 = origins[(size_t)i * 3];
+        o1 = origins[(size_t)i * 3 + 1];
+        o2 = origins[(size_t)i * 3 + 2];
+        v0 = dirs[(size_t)i * 3];
+        v1 = dirs[(size_t)i * 3 + 1];
+        v2 = dirs[(size_t)i * 3 + 2];
+        sd = stds[i];
+    }
+    float tau[kLevelMaxS], d[kLevelMaxS];
+#pragma unroll
+    for (int s = 0; s < kLevelMaxS; ++s) {
+        tau[s] = s < S ? range[s] * sd : 0.0f;
+        d[s] = 0.0f;
+    }
+    const int* row = tile + threadIdx.x * kPitch;
+    for (int k0 = 0; k0 < K; k0 += kRound) {
+        const int kc = K - k0 < kRound ? K - k0 : kRound;
+        __syncthreads();
+        stage_indices(tile, idx, first, n, K, k0, kc, P);
+        __syncthreads();
+        if (!active) continue;
+        for (int kk = 0; kk < kc; ++kk) {
+            const int j = row[kk];
+            if (j < 0) continue;
+#pragma unroll
+            for (int s = 0; s < kLevelMaxS; ++s) {
+                if (s >= S) break;            // (a chain of exits, not 32 separate guards: the record's loads then dominate every sample)
+                Pair p;
+                eval_pair(packed, j, o0 + tau[s] * v0, o1 + tau[s] * v1, o2 + tau[s] * v2, p);
+                d[s] = d[s] + (density_factor * p.sigma) * p.e;
+            }
+        }
+    }
+#pragma unroll
+    for (int s = 0; s < kLevelMaxS; ++s) {
+        if (s < S) {
+            if (d[s] >= 1.0f) d[s] = d[s] / (d[s] + 1e-12f);
+            if (active && densities) densities[(size_t)i * (size_t)S + (size_t)s] = d[s];
+        }
+    }
+    float px[kLevelMaxL], py[kLevelMaxL], pz[kLevelMaxL];
+    unsigned hits = 0u;
+#pragma unroll
+    for (int l = 0; l < kLevelMaxL; ++l) {
+        px[l] = py[l] = pz[l] = 0.0f;
+        if (l < L) {
+            const float level = levels.v[l];
+            bool found = false;
+            float d_a = 0.0f, d_b = 0.0f, tau_a = 0.0f, tau_b = 0.0f;
+#pragma unroll
+            for (int s = 1; s < kLevelMaxS; ++s) {
+                if (s < S && !found && d[s] > level) {
+                    found = true;
+                    d_a = d[s];
+                    d_b = d[s - 1];
+                    tau_a = tau[s];
+                    tau_b = tau[s - 1];
+                }
+            }
+            float t = 0.0f;
+            if (found && d[0] < level) {      // (d_0 > level: the first sample above is sample 0; a NaN is neither under nor above)
+                t = (level - d_b) / (d_a - d_b) * (tau_a - tau_b) + tau_b;
+                px[l] = o0 + t * v0;
+                py[l] = o1 + t * v1;
+                pz[l] = o2 + t * v2;
+                hits |= 1u << l;
+            }
+            if (active) {
+                const size_t at = (size_t)l * (size_t)n + (size_t)i;
+                hit[at] = (unsigned char)((hits >> l) & 1u);
+                t_out[at] = t;
+                points[at * 3] = px[l];
+                points[at * 3 + 1] = py[l];
+                points[at * 3 + 2] = pz[l];
+            }
+        }
+    }
+    if (!normals) return;
+    float g0[kLevelMaxL], g1[kLevelMaxL], g2[kLevelMaxL];
+#pragma unroll
+    for (int l = 0; l < kLevelMaxL; ++l) g0[l] = g1[l] = g2[l] = 0.0f;
+    for (int k0 = 0; k0 < K; k0 += kRound) {
+        const int kc = K - k0 < kRound ? K - k0 : kRound;
+        if (K > kRound) {                     // (K <= 16: the tile still holds the one round)
+            __syncthreads();
+            stage_indices(tile, idx, first, n, K, k0, kc, P);
+            __syncthreads();
+        }
+        if (hits == 0u) continue;
+        for (int kk = 0; kk < kc; ++kk) {
+            const int j = row[kk];
+            if (j < 0) continue;
+#pragma unroll
+            for (int l = 0; l < kLevelMaxL; ++l) {
+                if (l < L && ((hits >> l) & 1u)) {
+                    Pair p;
+                    eval_pair(packed, j, px[l], py[l], pz[l], p);
+                    const float o = (density_factor * p.sigma) * p.e;
+                    g0[l] = g0[l] + o * ((p.M[0] * p.w[0] + p.M[1] * p.w[1]) + p.M[2] * p.w[2]);
+                    g1[l] = g1[l] + o * ((p.M[3] * p.w[0] + p.M[4] * p.w[1]) + p.M[5] * p.w[2]);
+                    g2[l] = g2[l] + o * ((p.M[6] * p.w[0] + p.M[7] * p.w[1]) + p.M[8] * p.w[2]);
+                }
+            }
+        }
+    }
+    if (!active) return;
+#pragma unroll
+    for (int l = 0; l < kLevelMaxL; ++l) {
+        if (l < L) {
+            float m0 = 0.0f, m1 = 0.0f, m2 = 0.0f;
+            if ((hits >> l) & 1u) {
+                const float norm = sqrtf((g0[l] * g0[l] + g1[l] * g1[l]) + g2[l] * g2[l]);
+                const float den = norm > 1e-12f ? norm : 1e-12f;
+                m0 = -(g0[l] / den);
+                m1 = -(g1[l] / den);
+                m2 = -(g2[l] / den);
+            }
+            const size_t at = ((size_t)l * (size_t)n + (size_t)i) * 3;
+            normals[at] = m0;
+            normals[at + 1] = m1;
+            normals[at + 2] = m2;
+        }
+    }
+}
+
 hipError_t pack(const FieldInputs& in, void* scratch, hipStream_t stream) {
     if (in.P == 0) return hipSuccess;
     hipLaunchKernelGGL(field_pack_kernel, dim3((uint32_t)((in.P + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream, (uint32_t)in.P,
@@ -268,6 +421,17 @@ hipError_t launch_field_backward(const FieldInputs& in, const float* g_density, 
     const dim3 grid((uint32_t)((in.n + kThreads - 1) / kThreads));
     hipLaunchKernelGGL(field_backward_kernel, grid, dim3(kThreads), 0, stream, (uint32_t)in.n, in.K, (long long)in.P, in.x, in.idx,
                        reinterpret_cast<const float4*>(scratch), in.density_factor, g_density, g_opacities, g_beta, dx, accum);
+    return hipGetLastError();
+}
+
+hipError_t launch_level_surface(const FieldInputs& in, const float* dirs, const float* stds, int S, int L, const float* range,
+                                const LevelSet& levels, unsigned char* hit, float* t, float* points, float* normals, float* densities,
+                                void* scratch, hipStream_t stream) {
+    hipError_t e = pack(in, scratch, stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(level_surface_kernel, dim3((uint32_t)((in.n + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream, (uint32_t)in.n,
+                       in.K, (long long)in.P, S, L, in.x, dirs, stds, in.idx, reinterpret_cast<const float4*>(scratch), in.density_factor,
+                       range, levels, hit, t, points, normals, densities);
     return hipGetLastError();
 }
 
@@ -326,6 +490,26 @@ int gsr_field_backward(int64_t n, int K, int64_t P, const float* x, const int64_
     if ((((uintptr_t)g_density | (uintptr_t)g_opacities | (uintptr_t)g_beta | (uintptr_t)dx) & 3u) != 0u || ((uintptr_t)accum & 63u) != 0u)
         return fail(GSR_ERR_INVALID_ARG, "gsr_field_backward: misaligned pointer (gradients: 4 bytes, accum: 64)");
     GSR_HIP(gsr::launch_field_backward(in, g_density, g_opacities, g_beta, dx, accum, scratch, (hipStream_t)stream_));
+    return GSR_OK;
+}
+
+int gsr_level_surface(int64_t n, int K, int64_t P, int S, int L, const float* origins, const float* dirs, const float* stds,
+                      const int64_t* idx, const float* centers, const float* M, const float* strengths, float density_factor,
+                      const float* range, const float* levels, uint8_t* hit, float* t, float* points, float* normals, float* densities,
+                      void* scratch, size_t scratch_bytes, void* stream_) {
+    const char* who = "gsr_level_surface";
+    if (S < 2 || S > gsr::kLevelMaxS) return fail(GSR_ERR_INVALID_ARG, "%s: S = %d (2 to %d)", who, S, gsr::kLevelMaxS);
+    if (L < 1 || L > gsr::kLevelMaxL) return fail(GSR_ERR_INVALID_ARG, "%s: L = %d (1 to %d)", who, L, gsr::kLevelMaxL);
+    const gsr::FieldInputs in{n, K, P, origins, reinterpret_cast<const long long*>(idx), centers, M, strengths, nullptr, density_factor};
+    const int rc = field_check(who, in, false, scratch, scratch_bytes);
+    if (rc != GSR_OK) return rc == 1 ? GSR_OK : rc;
+    if (!dirs || !stds || !range || !levels || !hit || !t || !points) return fail(GSR_ERR_INVALID_ARG, "%s: null pointer", who);
+    if ((((uintptr_t)dirs | (uintptr_t)stds | (uintptr_t)range | (uintptr_t)levels | (uintptr_t)t | (uintptr_t)points | (uintptr_t)normals |
+          (uintptr_t)densities) & 3u) != 0u)
+        return fail(GSR_ERR_INVALID_ARG, "%s: misaligned pointer (dirs / stds / range / levels / t / points / normals / densities: 4 bytes)", who);
+    gsr::LevelSet set{};
+    for (int l = 0; l < L; ++l) set.v[l] = levels[l];
+    GSR_HIP(gsr::launch_level_surface(in, dirs, stds, S, L, range, set, hit, t, points, normals, densities, scratch, (hipStream_t)stream_));
     return GSR_OK;
 }
 

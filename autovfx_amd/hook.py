@@ -58,7 +58,14 @@ AutoVFX reaches the rasterizer through two imports (paths under the reference tr
     follows the sum in the reference's arithmetic; ``return_sdf_grad=True``, CPU tensors and other dtypes run
     ``SuGaR.reference_<name>``.  torch and the library are imported at the first call.
 
-Items 2-11 are the rows of ``_TARGETS``, applied by ``_patch`` to every matching module, whether it was imported before
+12. the same class, when it defines ``get_covariance`` and ``compute_density``, gets ``compute_level_surface_points_from_camera_fast``
+    (``sugar_model.py:1719-1954``, once per training camera in ``sugar_extractors/coarse_mesh.py``) replaced by ``autovfx_amd.levelset``'s
+    drop-in: the depth render, the unprojection and the neighbour lists as the reference builds them, then the 21-sample ray march, the
+    crossings of every level and the normals in one HIP kernel; the flat-Gaussian variants, ``just_use_depth_as_level``, ``use_gaussian_depth``, a CPU model,
+    more than 32 samples, 8 levels or 64 neighbours run ``SuGaR.reference_compute_level_surface_points_from_camera_fast``, decided
+    before ``torch.randperm`` is consumed.  torch and the library are imported at the first call.
+
+Items 2-12 are the rows of ``_TARGETS``, applied by ``_patch`` to every matching module, whether it was imported before
 ``install()`` or after (a ``sys.meta_path`` hook).  Each replaced attribute keeps the reference's original next to it as
 ``reference_<attr>`` on the module or class (``<module>.reference_render``, ``SceneRepresentation.reference_render_from_3DGS``, ...).
 ``uninstall()`` undoes every patch in reverse.
@@ -82,7 +89,7 @@ from typing import Callable, List, NamedTuple, Optional, Tuple
 
 _REPO_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _installed: Optional["_RendererHook"] = None
-patched_modules: List[str] = []          # names of the modules patched by items 2-7, 10 and 11 (introspection / tests)
+patched_modules: List[str] = []          # names of the modules patched by items 2-7 and 10-12 (introspection / tests)
 patched_models: List[str] = []           # names of the modules whose ``GaussianModel.training_setup`` was wrapped (item 8)
 _strict = True                           # install(strict=...): may a failure to load the render path break the importing process?
 _gave_up = False                         # lenient mode: a replacement could not be loaded once; patch nothing more
@@ -175,9 +182,10 @@ def _with_hip_densify(name: str) -> Callable:
     return make
 
 
-def _with_hip_field(name: str) -> Callable:
-    """make() for ``SuGaR.compute_density`` / ``get_field_values``: ``autovfx_amd.field.drop_in_<name>(original)``, built (torch,
-    libgsr_hip.so) at the first call; it runs ``original`` itself for the calls its kernels do not take."""
+def _with_hip_sugar_method(name: str, module: str = "field", what: str = "the HIP density field") -> Callable:
+    """make() for a ``SuGaR`` method with a drop-in of its own (``compute_density`` / ``get_field_values`` in ``field``,
+    ``compute_level_surface_points_from_camera_fast`` in ``levelset``): ``autovfx_amd.<module>.drop_in_<name>(original)``, built (torch, libgsr_hip.so) at the first call; it runs ``original`` itself for
+    the calls its kernels do not take."""
     def make(original: Callable) -> Callable:
         built = []
 
@@ -187,9 +195,9 @@ def _with_hip_field(name: str) -> Callable:
                 if _gave_up:
                     return original(self, *args, **kwargs)
                 try:
-                    built.append(_load("field", "drop_in_" + name)(original))
+                    built.append(_load(module, "drop_in_" + name)(original))
                 except Exception as e:
-                    _could_not_load(f"{original.__module__}.{original.__qualname__} left as the reference's: the HIP density field", e)
+                    _could_not_load(f"{original.__module__}.{original.__qualname__} left as the reference's: {what}", e)
                     return original(self, *args, **kwargs)
             return built[0](self, *args, **kwargs)
 
@@ -236,10 +244,14 @@ _TARGETS = (
     _Target("knn", None, "knn_points", lambda original: _mark(_load("knn", "drop_in")(original)), "the HIP k-nearest-neighbour search",
             needs=("knn_points", "knn_gather"), rebind=True),
     # item 11: sugar/sugar_scene/sugar_model.py, SuGaR's density field (:1118-1187, :1216-1239)
-    _Target("sugar_model", "SuGaR", "compute_density", _with_hip_field("compute_density"), "the HIP density field",
+    _Target("sugar_model", "SuGaR", "compute_density", _with_hip_sugar_method("compute_density"), "the HIP density field",
             needs=("compute_density", "get_field_values", "get_beta", "get_covariance")),
-    _Target("sugar_model", "SuGaR", "get_field_values", _with_hip_field("get_field_values"), "the HIP density field",
+    _Target("sugar_model", "SuGaR", "get_field_values", _with_hip_sugar_method("get_field_values"), "the HIP density field",
             needs=("compute_density", "get_field_values", "get_beta", "get_covariance")),
+    # item 12: the same class's ray march of the coarse mesh extraction (:1719-1954)
+    _Target("sugar_model", "SuGaR", "compute_level_surface_points_from_camera_fast",
+            _with_hip_sugar_method("compute_level_surface_points_from_camera_fast", "levelset", "the HIP level-surface ray march"),
+            "the HIP level-surface ray march", needs=("get_covariance", "compute_density")),
 )
 
 

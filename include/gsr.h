@@ -42,7 +42,8 @@
 extern "C" {
 #endif
 
-/* Still 20: + SuGaR's density field (gsr_field_scratch_bytes, gsr_field_forward, gsr_field_backward).  They only add symbols
+/* Still 20: + the level-surface ray march of SuGaR's mesh extraction (gsr_level_surface).
+ * Still 20: + SuGaR's density field (gsr_field_scratch_bytes, gsr_field_forward, gsr_field_backward).  They only add symbols
  * behind the existing ones, so the version a binding checks did not move.
  * 20: + K nearest neighbours with indices (gsr_knn_points_scratch_bytes, gsr_knn_points).
  * 19: + densification (gsr_densify_stats, gsr_densify_plan_scratch_bytes, gsr_densify_plan, gsr_densify_apply).
@@ -465,6 +466,29 @@ GSR_API int gsr_field_backward(int64_t n, int K, int64_t P, const float* x, cons
                                const float* strengths, const float* min_scaling, float density_factor, const float* g_density,
                                const float* g_opacities, const float* g_beta, float* dx, float* accum, void* scratch, size_t scratch_bytes,
                                void* stream);
+
+/* The level-surface ray march of SuGaR's coarse mesh extraction (SuGaR.compute_level_surface_points_from_camera_fast,
+ * sugar_model.py:1853-1950, the non-flat branches) -- added under ABI 20.  origins [n,3], dirs [n,3], stds [n], idx [n,K] int64,
+ * centers [P,3], M [P,3,3], strengths [P] as for gsr_field_forward, range [S] fp32 in DEVICE memory (torch.linspace(-r, r, S)),
+ * levels [L] fp32 in HOST memory, read during the call.  Per ray i, in plain fp32, left to right, nothing contracted:
+ *   tau_s = range[s] stds[i];  x_s[b] = origins[i][b] + tau_s dirs[i][b];
+ *   d_s = sum over k ascending of (density_factor strengths[j]) expf(-0.5 q), exactly gsr_field_forward's density at x_s (slots outside
+ *   [0, P) skipped); then, if d_s >= 1, d_s = d_s / (d_s + 1e-12f)   (:1879-1880).
+ * Per level l (:1890-1908): under0 = d_0 < l, a = the smallest s with d_s > l.  The ray is empty when !under0, when no such a exists or
+ * when a == 0; a NaN compares false both ways.  Otherwise
+ *   t = (l - d_{a-1}) / (d_a - d_{a-1}) * (tau_a - tau_{a-1}) + tau_{a-1};  point[b] = origins[i][b] + t dirs[i][b].
+ * Normal at a hit (:1923-1950): with w = M_j^T s and o_k evaluated at point, g = sum over k ascending of o_k (M_j w), (M_j w)_b =
+ * (M_j[b][0] w_0 + M_j[b][1] w_1) + M_j[b][2] w_2; normal = -(g / max(sqrtf((g_0 g_0 + g_1 g_1) + g_2 g_2), 1e-12f)).
+ * Outputs, every element written: hit [L,n] uint8 (1 = a crossing), t [L,n], points [L,n,3], normals [L,n,3] (may be NULL),
+ * densities [n,S] (may be NULL; after the renormalisation).  For an empty ray hit = 0 and t, points and normals are 0.
+ * scratch: gsr_field_scratch_bytes(P) bytes, 256-byte aligned, any content, filled by the call.  n == 0 succeeds without touching
+ * anything.  Refused (GSR_ERR_INVALID_ARG, nothing launched): K outside 1..64, S outside 2..32, L outside 1..8, a negative count, a
+ * count >= 2^30, a null required pointer, misaligned pointers (floats 4 bytes, idx 8, scratch 256), too little scratch.  Enqueues on
+ * `stream` only: no host synchronisation, no allocation, no atomics. */
+GSR_API int gsr_level_surface(int64_t n, int K, int64_t P, int S, int L, const float* origins, const float* dirs, const float* stds,
+                              const int64_t* idx, const float* centers, const float* M, const float* strengths, float density_factor,
+                              const float* range, const float* levels, uint8_t* hit, float* t, float* points, float* normals,
+                              float* densities, void* scratch, size_t scratch_bytes, void* stream);
 
 /* Structural similarity (the training loops' loss_utils.ssim, loss_utils.py:33-62, window 11, sigma 1.5) -- ABI 17.
  * x, y: [n,c,h,w] fp32, contiguous, device memory.  Per plane, zero-padded outside the image: mx = w*x, my = w*y, Exx = w*x^2,
