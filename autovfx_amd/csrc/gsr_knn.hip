@@ -15,16 +15,8 @@
 //   pack    : the points gathered once in sorted order into float4 (x, y, z, index bits); one wave per leaf of 64 points reduces
 //             the leaf's box (finite members only: a leaf of non-finite points has an empty box, lo = +inf, hi = -inf);
 //   levels  : boxes of 16 children each, level over level, until at most 16 boxes are left (six levels below 2^30 points);
-//   search  : one wave per leaf, one lane per query.  The slots are seeded with the wave's own leaf; then a depth-first walk over the
-//             tree from the top, a wave-uniform stack in LDS: a node's children are kept only if some lane's lower bound is not
-//             above that lane's third slot (ballot), and pushed nearest-first by their distance to the wave's own box.  A leaf is
-//             re-tested when it is popped, streamed into LDS with one coalesced 1 KiB load and read back by all lanes at once.
-//
-// Exactness: a box's lower bound is formed with the rounded operations of d(i, j) (per axis the gap lo - q or q - hi, squared,
-// summed in the same order).  Rounding to nearest is monotone, so the bound never exceeds the computed distance of a member, and a
-// box is skipped only when its bound is strictly greater than the lane's third slot -- no member could then enter a slot.  A
-// distance enters a slot only when it is below FLT_MAX (NaN and inf map to FLT_MAX before the branch-free insertion, whose
-// fmaxf would otherwise duplicate a slot).
+//   search  : one wave per leaf, one lane per query: the slots are seeded with the wave's own leaf, then a depth-first walk over the
+//             tree from the top prunes by box bounds (walk_tree, further down: the walk, its prune rule and why it is exact).
 // Defines the entry points gsr_knn3_scratch_bytes, gsr_knn3_mean_dist, gsr_knn_points_scratch_bytes and gsr_knn_points.
 #include "gsr_internal.h"
 
@@ -86,7 +78,7 @@ __device__ __forceinline__ float sq_dist(const float4& c, float qx, float qy, fl
     return (dx * dx + dy * dy) + dz * dz;
 }
 
-// The same operations on the gap to a box: never above sq_dist of a member (see the file comment).  An empty box gives +inf.
+// The same operations on the gap to a box: never above sq_dist of a member (see walk_tree).  An empty box gives +inf.
 __device__ __forceinline__ float box_bound(const float4& lo, const float4& hi, float qx, float qy, float qz) {
     const float gx = fmaxf(fmaxf(lo.x - qx, qx - hi.x), 0.0f);
     const float gy = fmaxf(fmaxf(lo.y - qy, qy - hi.y), 0.0f);
@@ -240,79 +232,35 @@ __device__ __forceinline__ void push_children(const KnnTree& tree, int level, ui
         const float kj = lane_value(key, j);
         rank += ((keep >> j) & 1u) && (kj > key || (kj == key && j > lane)) ? 1 : 0;
     }
-    if (lane < cnt && ((keep >> lane) & 1u)) stack[top + rank] = ((uint32_t)level << 29) | (first + lane);
+    if (lane < cnt && ((keep >> lane) & 1u)) (stack + top)[rank] = ((uint32_t)level << 29) | (first + lane);   // (stack + top: where the pop read)
     top += __popc(keep);
     wave_sync();
 }
 
-__global__ __launch_bounds__(256) void knn_search_kernel(uint32_t n, const float4* __restrict__ packed, KnnTree tree, float* __restrict__ out) {
-    __shared__ float4 s_leaf[4][kLeaf];
-    __shared__ uint32_t s_stack[4][kStackDepth];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t own = blockIdx.x * 4u + (uint32_t)wave;    // this wave's leaf
-    if (own * kLeaf >= n) return;
-    float4* leaf = s_leaf[wave];
-    uint32_t* stack = s_stack[wave];
-    const uint32_t s = own * kLeaf + lane;
-    const float4 p = s < n ? packed[s] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    Query q;
-    q.active = s < n && finite3(p.x, p.y, p.z);
-    q.x = q.active ? p.x : 0.0f; q.y = q.active ? p.y : 0.0f; q.z = q.active ? p.z : 0.0f;
-    float s0 = FLT_MAX, s1 = FLT_MAX, s2 = FLT_MAX;
+// ---- a lane's slots: kernel locals in registers (slot numbers are compile-time constants, after unrolling for the K slots), handed
+// to the walk as a pack of references.  The walk asks two overloads about them: slots_kth(slots...), the lane's pruning threshold
+// (its last slot's distance), and slots_scan(leaf, cnt, q, skip, slots...): `cnt` candidates of a leaf in LDS against the slots, the
+// one at position `skip` left out (-1: none).  Not a struct that owns them: the compiler then keeps sd[S], sj[S] as 2 S scalars, not
+// as the two vector register groups it forms from kernel-local arrays, and the K = 16 search ran 2 - 6 % slower.
 
-    // seed: the own leaf, every member but the lane itself
-    const int own_cnt = (int)min((uint32_t)kLeaf, n - own * kLeaf);
-    leaf[lane] = p;
-    wave_sync();
-    for (int c = 0; c < own_cnt; ++c) {
+// gsr_knn3_mean_dist: three distances, s0 <= s1 <= s2, FLT_MAX while empty.
+__device__ __forceinline__ float slots_kth(const float&, const float&, const float& s2) { return s2; }
+__device__ __forceinline__ void slots_scan(const float4* leaf, int cnt, const Query& q, int skip, float& s0, float& s1, float& s2) {
+    for (int c = 0; c < cnt; ++c) {
         const float d = sq_dist(leaf[c], q.x, q.y, q.z);
-        insert3(c != lane ? d : FLT_MAX, s0, s1, s2);
-    }
-
-    if (__ballot(q.active) != 0ull) {
-        // the box of the wave's queries orders the walk
-        float4 wlo = make_float4(wave_min(q.active ? q.x : INFINITY), wave_min(q.active ? q.y : INFINITY),
-                                 wave_min(q.active ? q.z : INFINITY), 0.0f);
-        float4 whi = make_float4(wave_max(q.active ? q.x : -INFINITY), wave_max(q.active ? q.y : -INFINITY),
-                                 wave_max(q.active ? q.z : -INFINITY), 0.0f);
-        int top = 0;
-        push_children(tree, tree.top, 0u, (int)tree.count[tree.top], own, q, s2, wlo, whi, stack, top, lane);
-        while (top > 0) {
-            const uint32_t e = (uint32_t)__builtin_amdgcn_readfirstlane((int)stack[--top]);
-            const int level = (int)(e >> 29);
-            const uint32_t idx = e & ((1u << 29) - 1u);
-            if (level > 0) {
-                const uint32_t first = idx * kFan;
-                push_children(tree, level - 1, first, (int)min((uint32_t)kFan, tree.count[level - 1] - first), own, q, s2, wlo, whi, stack,
-                              top, lane);
-                continue;
-            }
-            const float4 lo = tree.boxes[2 * (size_t)idx], hi = tree.boxes[2 * (size_t)idx + 1];   // (leaves: level offset 0)
-            const float lb = box_bound(lo, hi, q.x, q.y, q.z);
-            if (__ballot(q.active && !(lb > s2)) == 0ull) continue;    // the slots have tightened since the push
-            const uint32_t base = idx * kLeaf;
-            const int cnt = (int)min((uint32_t)kLeaf, n - base);
-            wave_sync();
-            leaf[lane] = lane < cnt ? packed[base + lane] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            wave_sync();
-            for (int c = 0; c < cnt; ++c) insert3(sq_dist(leaf[c], q.x, q.y, q.z), s0, s1, s2);
-        }
-    }
-    if (s < n) {
-        if (!q.active) s0 = s1 = s2 = FLT_MAX;
-        out[__float_as_uint(p.w)] = ((s0 + s1) + s2) / 3.0f;
+        insert3(c != skip ? d : FLT_MAX, s0, s1, s2);
     }
 }
 
-// ---- K nearest neighbours with indices (gsr.h: gsr_knn_points) ----
-// A row is the K smallest candidates in ascending (d, j) order, j the index in p2: equal distances go by the lower index, so the
-// result is a pointwise function of the input for duplicates and lattices as well.  The self is a candidate like any other.
+// gsr_knn_points: S = 4, 8 or 16 (distance, index in p2) pairs sd[k], sj[k] in ascending (d, j) order for K <= S
+// neighbours.  Equal distances go by the lower index, so a row is a pointwise function of the input for duplicates and lattices as
+// well.  The first S - K slots hold (-inf, 0), below every candidate and never displaced, so the K-th best is always slot S - 1:
+// neither the threshold nor the early-out needs a run-time slot number.  An empty slot is (FLT_MAX, ~0).
 
 // (d, j) < (sd, sj), lexicographic
 __device__ __forceinline__ bool slot_less(float d, uint32_t j, float sd, uint32_t sj) { return d < sd || (d == sd && j < sj); }
 
-// The slots stay sorted ascending; a candidate that is not below the last slot changes nothing.  Slot numbers are compile-time
-// constants after unrolling, so the arrays live in registers.
+// The slots stay sorted ascending; a candidate that is not below the last slot changes nothing.
 template <int S>
 __device__ __forceinline__ void insert_slots(float d, uint32_t j, float (&sd)[S], uint32_t (&sj)[S]) {
     bool below = slot_less(d, j, sd[S - 1], sj[S - 1]);   // below slot k
@@ -327,14 +275,16 @@ __device__ __forceinline__ void insert_slots(float d, uint32_t j, float (&sd)[S]
     sj[0] = below ? j : sj[0];
 }
 
-// `cnt` candidates of a leaf in LDS against every lane's slots.  A distance that is not below FLT_MAX (NaN, inf) becomes the empty
-// slot's own value (FLT_MAX, ~0), which is below no slot.  Most candidates enter nobody's row: one ballot skips their insertion.
 template <int S>
-__device__ __forceinline__ void scan_leaf(const float4* leaf, int cnt, const Query& q, float (&sd)[S], uint32_t (&sj)[S]) {
+__device__ __forceinline__ float slots_kth(const float (&sd)[S], const uint32_t (&)[S]) { return sd[S - 1]; }
+// A distance that is not below FLT_MAX (NaN, inf) becomes the empty slot's own pair, which is below no slot.  Most candidates enter
+// nobody's row: one ballot skips their insertion.
+template <int S>
+__device__ __forceinline__ void slots_scan(const float4* leaf, int cnt, const Query& q, int skip, float (&sd)[S], uint32_t (&sj)[S]) {
     for (int c = 0; c < cnt; ++c) {
         const float4 cand = leaf[c];
         float d = sq_dist(cand, q.x, q.y, q.z);
-        const bool ok = d < FLT_MAX;
+        const bool ok = d < FLT_MAX && c != skip;
         d = ok ? d : FLT_MAX;
         const uint32_t j = ok ? __float_as_uint(cand.w) : ~0u;
         if (__ballot(q.active && slot_less(d, j, sd[S - 1], sj[S - 1])) == 0ull) continue;
@@ -342,13 +292,93 @@ __device__ __forceinline__ void scan_leaf(const float4* leaf, int cnt, const Que
     }
 }
 
-// One wave per 64 queries, one lane per query, S = 4, 8 or 16 slots for K <= S neighbours.  The first S - K slots hold (-inf, 0),
-// below every candidate and never displaced, so the K-th best is always slot S - 1: the prune threshold and the early-out need
-// no run-time slot number.  kSelf: the queries are the tree's own points (queries == packed, n1 == n2); a wave takes the points of
-// its leaf and seeds its slots from that leaf, which the walk then leaves out.  Otherwise `queries` is p1 in the order of its
-// Morton codes on p2's grid, and nothing is seeded.
-// Prune rule: a box is skipped only when its bound is strictly above the lane's K-th slot for every lane; at equality a member
-// with a lower index could still enter (push_children and the re-test below both say !(lb > kth)).
+// ---- the search: one wave per 64 queries, one lane per query.  Query `s` of `n`: `p` as stored (x, y, z, original index bits)
+__device__ __forceinline__ Query load_query(uint32_t n, const float4* queries, uint32_t s, float4& p) {
+    p = s < n ? queries[s] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    Query q;
+    q.active = s < n && finite3(p.x, p.y, p.z);
+    q.x = q.active ? p.x : 0.0f; q.y = q.active ? p.y : 0.0f; q.z = q.active ? p.z : 0.0f;
+    return q;
+}
+
+// the box of the wave's active queries: it orders the walk
+__device__ __forceinline__ void wave_box(const Query& q, float4& wlo, float4& whi) {
+    wlo = make_float4(wave_min(q.active ? q.x : INFINITY), wave_min(q.active ? q.y : INFINITY), wave_min(q.active ? q.z : INFINITY), 0.0f);
+    whi = make_float4(wave_max(q.active ? q.x : -INFINITY), wave_max(q.active ? q.y : -INFINITY), wave_max(q.active ? q.z : -INFINITY), 0.0f);
+}
+
+// A self query's wave holds the `cnt` points of its own leaf, `p` in lane order: they seed the slots, and the walk leaves that leaf
+// out.  `skip`: the lane itself where the own point is no candidate (by position, so a duplicate stays one), -1 where it is.
+template <class... Slots>
+__device__ __forceinline__ void seed_own_leaf(float4* leaf, const float4& p, int cnt, const Query& q, int lane, int skip, Slots&... slots) {
+    leaf[lane] = p;
+    wave_sync();
+    slots_scan(leaf, cnt, q, skip, slots...);
+}
+
+// The walk of both searches: depth first over the tree of `n` packed points from the top, on the wave-uniform `stack` in LDS;
+// `own_leaf` is left out (seeded already; ~0: none).  A node's children are kept if some lane's lower bound is not above that lane's
+// kth() (a ballot per child) and pushed nearest-first by their distance to the wave's box (push_children).  A popped leaf is tested
+// again, the slots having tightened since the push, then staged into `leaf` with one coalesced 1 KiB load and scanned by all lanes
+// at once.  The stage sits between two wave_sync(): its stores stay behind the previous scan's reads and ahead of the next one's.
+// Exactness.  A box's lower bound is formed with the rounded operations of d(i, j) (per axis the gap lo - q or q - hi, squared,
+// summed in the same order).  Rounding to nearest is monotone, so the bound never exceeds the computed distance of a member.  The
+// prune rule, here and in push_children, is !(lb > kth): a box is skipped only when its bound is strictly above kth() for every
+// lane, so that no member could enter a slot.  At equality a member of the K-slot search with a lower index still could: pruning
+// on >= would return the right distances and, on a lattice, the wrong indices.  A distance enters a slot only when it is below
+// FLT_MAX (NaN and inf map to the empty slot's value before the insertion).
+template <class... Slots>
+__device__ __forceinline__ void walk_tree(const KnnTree& tree, uint32_t n, const float4* packed, uint32_t own_leaf, const Query& q,
+                                          float4* leaf, uint32_t* stack, int lane, Slots&... slots) {
+    if (__ballot(q.active) == 0ull) return;
+    float4 wlo, whi;
+    wave_box(q, wlo, whi);
+    int top = 0;
+    push_children(tree, tree.top, 0u, (int)tree.count[tree.top], own_leaf, q, slots_kth(slots...), wlo, whi, stack, top, lane);
+    while (top > 0) {
+        const uint32_t e = (uint32_t)__builtin_amdgcn_readfirstlane((int)stack[--top]);
+        const int level = (int)(e >> 29);
+        const uint32_t node = e & ((1u << 29) - 1u);
+        if (level > 0) {
+            const uint32_t first = node * kFan;
+            push_children(tree, level - 1, first, (int)min((uint32_t)kFan, tree.count[level - 1] - first), own_leaf, q,
+                          slots_kth(slots...), wlo, whi, stack, top, lane);
+            continue;
+        }
+        const float4 lo = tree.boxes[2 * (size_t)node], hi = tree.boxes[2 * (size_t)node + 1];   // (leaves: level offset 0)
+        const float lb = box_bound(lo, hi, q.x, q.y, q.z);
+        if (__ballot(q.active && !(lb > slots_kth(slots...))) == 0ull) continue;
+        const uint32_t base = node * kLeaf;
+        const int cnt = (int)min((uint32_t)kLeaf, n - base);
+        wave_sync();
+        leaf[lane] = lane < cnt ? packed[base + lane] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        wave_sync();
+        slots_scan(leaf, cnt, q, -1, slots...);
+    }
+}
+
+// gsr_knn3_mean_dist: one wave per leaf, whose points are its queries; the own point is no candidate.
+__global__ __launch_bounds__(256) void knn_search_kernel(uint32_t n, const float4* __restrict__ packed, KnnTree tree, float* __restrict__ out) {
+    __shared__ float4 s_leaf[4][kLeaf];
+    __shared__ uint32_t s_stack[4][kStackDepth];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t own = blockIdx.x * 4u + (uint32_t)wave;    // this wave's leaf
+    if (own * kLeaf >= n) return;
+    const uint32_t s = own * kLeaf + lane;
+    float4 p;
+    const Query q = load_query(n, packed, s, p);
+    float s0 = FLT_MAX, s1 = FLT_MAX, s2 = FLT_MAX;
+    seed_own_leaf(s_leaf[wave], p, (int)min((uint32_t)kLeaf, n - own * kLeaf), q, lane, lane, s0, s1, s2);
+    walk_tree(tree, n, packed, own, q, s_leaf[wave], s_stack[wave], lane, s0, s1, s2);
+    if (s < n) {
+        if (!q.active) s0 = s1 = s2 = FLT_MAX;
+        out[__float_as_uint(p.w)] = ((s0 + s1) + s2) / 3.0f;
+    }
+}
+
+// gsr_knn_points: S slots for K <= S neighbours.  kSelf: the queries are the tree's own points (queries == packed, n1 == n2); a wave
+// takes the points of its leaf and seeds its slots from that leaf, the own point included (the self is a candidate like any other).
+// Otherwise `queries` is p1 in the order of its Morton codes on p2's grid, and nothing is seeded.
 template <int S, bool kSelf>
 __global__ __launch_bounds__(256) void knn_points_search_kernel(uint32_t n1, const float4* __restrict__ queries, uint32_t n2,
                                                                 const float4* __restrict__ packed, KnnTree tree, int K,
@@ -358,13 +388,9 @@ __global__ __launch_bounds__(256) void knn_points_search_kernel(uint32_t n1, con
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t group = blockIdx.x * 4u + (uint32_t)wave;    // this wave's 64 queries; kSelf: its leaf
     if (group * kLeaf >= n1) return;
-    float4* leaf = s_leaf[wave];
-    uint32_t* stack = s_stack[wave];
     const uint32_t s = group * kLeaf + lane;
-    const float4 p = s < n1 ? queries[s] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    Query q;
-    q.active = s < n1 && finite3(p.x, p.y, p.z);
-    q.x = q.active ? p.x : 0.0f; q.y = q.active ? p.y : 0.0f; q.z = q.active ? p.z : 0.0f;
+    float4 p;
+    const Query q = load_query(n1, queries, s, p);
     float sd[S];
     uint32_t sj[S];
 #pragma unroll
@@ -373,41 +399,8 @@ __global__ __launch_bounds__(256) void knn_points_search_kernel(uint32_t n1, con
         sd[k] = spare ? -INFINITY : FLT_MAX;
         sj[k] = spare ? 0u : ~0u;
     }
-    const uint32_t own = kSelf ? group : ~0u;   // (~0: no leaf is left out of the walk)
-    if (kSelf) {
-        leaf[lane] = p;
-        wave_sync();
-        scan_leaf<S>(leaf, (int)min((uint32_t)kLeaf, n2 - group * kLeaf), q, sd, sj);
-    }
-
-    if (__ballot(q.active) != 0ull) {
-        float4 wlo = make_float4(wave_min(q.active ? q.x : INFINITY), wave_min(q.active ? q.y : INFINITY),
-                                 wave_min(q.active ? q.z : INFINITY), 0.0f);
-        float4 whi = make_float4(wave_max(q.active ? q.x : -INFINITY), wave_max(q.active ? q.y : -INFINITY),
-                                 wave_max(q.active ? q.z : -INFINITY), 0.0f);
-        int top = 0;
-        push_children(tree, tree.top, 0u, (int)tree.count[tree.top], own, q, sd[S - 1], wlo, whi, stack, top, lane);
-        while (top > 0) {
-            const uint32_t e = (uint32_t)__builtin_amdgcn_readfirstlane((int)stack[--top]);
-            const int level = (int)(e >> 29);
-            const uint32_t node = e & ((1u << 29) - 1u);
-            if (level > 0) {
-                const uint32_t first = node * kFan;
-                push_children(tree, level - 1, first, (int)min((uint32_t)kFan, tree.count[level - 1] - first), own, q, sd[S - 1], wlo,
-                              whi, stack, top, lane);
-                continue;
-            }
-            const float4 lo = tree.boxes[2 * (size_t)node], hi = tree.boxes[2 * (size_t)node + 1];   // (leaves: level offset 0)
-            const float lb = box_bound(lo, hi, q.x, q.y, q.z);
-            if (__ballot(q.active && !(lb > sd[S - 1])) == 0ull) continue;    // the slots have tightened since the push
-            const uint32_t base = node * kLeaf;
-            const int cnt = (int)min((uint32_t)kLeaf, n2 - base);
-            wave_sync();
-            leaf[lane] = lane < cnt ? packed[base + lane] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            wave_sync();
-            scan_leaf<S>(leaf, cnt, q, sd, sj);
-        }
-    }
+    if (kSelf) seed_own_leaf(s_leaf[wave], p, (int)min((uint32_t)kLeaf, n2 - group * kLeaf), q, lane, -1, sd, sj);
+    walk_tree(tree, n2, packed, kSelf ? group : ~0u, q, s_leaf[wave], s_stack[wave], lane, sd, sj);
     if (s >= n1) return;
     // the row of the query's original index: empty slots (all of them for a non-finite query) are (+inf, -1)
     float od[S];

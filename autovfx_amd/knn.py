@@ -68,6 +68,19 @@ def mean_dist3(points: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def _sq_dists(queries: np.ndarray, candidates: np.ndarray) -> np.ndarray:
+    """``d(i, j)`` of the contract for float32 ``queries [C, 3]`` and ``candidates [P, 3]`` -> float32 ``[C, P]``: candidate minus
+    query per axis, the squares summed left to right, every operation an fp32 elementwise one (no fused multiply-add).  Overflow and
+    NaN pass through: the caller holds ``np.errstate``."""
+    dx = candidates[None, :, 0] - queries[:, 0:1]
+    d = dx * dx
+    dy = candidates[None, :, 1] - queries[:, 1:2]
+    d = d + dy * dy
+    dz = candidates[None, :, 2] - queries[:, 2:3]
+    d = d + dz * dz
+    return d
+
+
 def mean_dist3_host(points, chunk_elems: int = 1 << 23) -> np.ndarray:
     """The contract restated in numpy: every distance in fp32 elementwise operations (no fused multiply-add), the three smallest by
     partition, chunked over the queries.  ``points``: anything ``np.asarray`` takes, reshaped to ``[P, 3]`` float32."""
@@ -75,17 +88,11 @@ def mean_dist3_host(points, chunk_elems: int = 1 << 23) -> np.ndarray:
     P = pts.shape[0]
     out = np.empty(P, np.float32)
     big = np.float32(FLT_MAX)
-    xs, ys, zs = pts[:, 0], pts[:, 1], pts[:, 2]
     step = max(1, chunk_elems // max(P, 1))
     with np.errstate(over="ignore", invalid="ignore"):
         for a in range(0, P, step):
             b = min(P, a + step)
-            dx = xs[None, :] - xs[a:b, None]
-            d = dx * dx
-            dy = ys[None, :] - ys[a:b, None]
-            d = d + dy * dy
-            dz = zs[None, :] - zs[a:b, None]
-            d = d + dz * dz
+            d = _sq_dists(pts[a:b], pts)
             d[np.arange(b - a), np.arange(a, b)] = big                        # the self, by index
             d = np.where(d < big, d, big)                                     # NaN / inf never enter a slot
             d = np.concatenate([d, np.full((b - a, 3), big, np.float32)], 1)  # missing neighbours stay FLT_MAX
@@ -245,18 +252,12 @@ def knn_points_host(p1, p2, K: int, chunk_elems: int = 1 << 23):
     dists = np.full((P1, K), np.inf, np.float32)
     idx = np.full((P1, K), -1, np.int64)
     big = np.float32(FLT_MAX)
-    xs, ys, zs = a2[:, 0], a2[:, 1], a2[:, 2]
     step = max(1, chunk_elems // max(P2, 1))
     k = min(K, P2)
     with np.errstate(over="ignore", invalid="ignore"):
         for a in range(0, P1, step):
             b = min(P1, a + step)
-            dx = xs[None, :] - a1[a:b, 0:1]
-            d = dx * dx
-            dy = ys[None, :] - a1[a:b, 1:2]
-            d = d + dy * dy
-            dz = zs[None, :] - a1[a:b, 2:3]
-            d = d + dz * dz
+            d = _sq_dists(a1[a:b], a2)
             d = np.where(d < big, d, np.float32(np.inf))      # NaN / inf / FLT_MAX are no candidates
             # only what is not above the k-th smallest distance of its row can be in the row: lexsort those by (row, d, j)
             rows, cols = np.nonzero(d <= np.partition(d, k - 1, axis=1)[:, k - 1:k])

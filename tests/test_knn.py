@@ -13,7 +13,7 @@ import textwrap
 import numpy as np
 import pytest
 
-from autovfx_amd.knn import FLT_MAX, mean_dist3_host
+from autovfx_amd.knn import FLT_MAX, knn_points_host, mean_dist3_host
 from shims import reference_env
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -85,6 +85,27 @@ def test_overflowing_distances_do_not_count():
     got = mean_dist3_host(pts)
     assert np.isposinf(got[3]) and np.isposinf(got[4])   # (1 + FLT_MAX + FLT_MAX) / 3
     assert np.array_equal(got[:3], mean_dist3_host(pts[:3]))
+
+
+@pytest.mark.parametrize("kind", ["uniform", "repeated", "pairs", "lattice"])
+def test_three_slot_mean_is_the_self_query_row_without_its_first_entry(kind):
+    """The two restatements answer for each other: for finite points and P >= 4 the self query's row is [0, d1, d2, d3] (the point
+    itself, or a duplicate of it, at 0), and d1 <= d2 <= d3 are the three slots of the three-slot search.  Bit for bit."""
+    g = np.random.default_rng(21)
+    if kind == "uniform":
+        pts = g.uniform(-1, 1, (4000, 3))
+    elif kind == "repeated":     # every point four times: ties at distance 0 are the rule
+        pts = np.repeat(g.uniform(-1, 1, (1000, 3)), 4, axis=0)[g.permutation(4000)]
+    elif kind == "pairs":        # every point twice: one tie at 0 and a sum that is not 0
+        pts = np.repeat(g.uniform(-1, 1, (2000, 3)), 2, axis=0)[g.permutation(4000)]
+    else:                        # 13^3 lattice points: equal distances in every row
+        pts = np.stack(np.meshgrid(*[np.arange(13)] * 3, indexing="ij"), -1).reshape(-1, 3) * 0.25
+    pts = pts.astype(F)
+    d = knn_points_host(pts, pts, 4)[0]
+    assert np.all(d[:, 0] == 0)
+    want = ((d[:, 1] + d[:, 2]) + d[:, 3]) / F(3.0)
+    got = mean_dist3_host(pts)
+    assert got.dtype == want.dtype == F and np.array_equal(got.view(np.uint32), want.view(np.uint32))
 
 
 def test_cabi_refusals_need_no_device():

@@ -118,6 +118,20 @@ def test_millions_on_sampled_queries(P, kind):
     assert _same_bits(got[q], want), q[np.flatnonzero(got[q].view(np.uint32) != want.view(np.uint32))[:10]]
 
 
+@pytest.mark.parametrize("repeats", [1, 4])
+def test_three_slot_search_equals_the_four_slot_self_query(repeats):
+    """The two searches answer for each other, not for a restatement: the self query's row is
+    [0, d1, d2, d3], so mean_dist3 is ((d1 + d2) + d3) / 3 bit for bit.  20 000 clustered points are 313 leaves under 20 boxes under
+    2: the descent, the prune and the re-test of a popped leaf all run.  repeats = 4: every point four times, ties at 0 the rule."""
+    pts = np.repeat(_points("clusters", 20_000, seed=13), repeats, axis=0)
+    dev = torch.from_numpy(pts).to(DEV)
+    d = knn.knn_points(dev[None], dev[None], K=4).dists[0].cpu().numpy()
+    got = mean_dist3(dev).cpu().numpy()
+    assert d.shape == (len(pts), 4) and np.all(d[:, 0] == 0)
+    want = ((d[:, 1] + d[:, 2]) + d[:, 3]) / F(3.0)   # (numpy float32: an IEEE division, as the kernel's)
+    assert _same_bits(got, want), np.flatnonzero(got.view(np.uint32) != want.view(np.uint32))[:10]
+
+
 def test_permuting_the_input_permutes_the_output():
     pts = _points("clusters", 200_000, seed=4)
     perm = np.random.default_rng(9).permutation(len(pts))
