@@ -1,31 +1,38 @@
-// gsr_frameio.hip -- the frame loop's outputs and the compositor's inputs on the GPU.
+// gsr_frameio.hip -- the frame loop's output files, built on the GPU.
 //
-//   png_encode_kernel / png_crc_kernel / png_finish_kernel : an 8-bit RGB / RGBA image that lives on the GPU -> the bytes of its PNG FILE, also on
-//       the GPU, so that one device-to-host copy and one write() put a frame on disk.  Replaces, for the reference's per-frame
-//       files (scene_representation.py:425-438: torchvision.utils.save_image, cv2.imwrite x 2), the host-side zlib pass that made
-//       the unchanged trajectory job I/O-bound 28x (round 4: 6.8 ms per 960x540 frame through a 32-thread pool, 0.24 ms to
-//       render and composite it).
-//   resize kernels                         : PIL's Image.resize(BILINEAR) on RGBA8 and Image.resize(NEAREST) on fp32 depth,
-//       bit for bit (blender/blend_all.py:21-28 downsample_image, called at :217-234).
+// An 8-bit RGB / RGBA image that lives on the GPU -> the bytes of its PNG FILE, also on the GPU, so that one device-to-host copy and
+// one write() put a frame on disk.  Replaces, for the reference's per-frame files (scene_representation.py:425-438:
+// torchvision.utils.save_image, cv2.imwrite x 2), the host-side zlib pass that made the unchanged trajectory job I/O-bound 28x
+// (round 4: 6.8 ms per 960x540 frame through a 32-thread pool, 0.24 ms to render and composite it).
 //
-// PNG as written here: signature, IHDR, ONE IDAT chunk, IEND.  The IDAT payload is a zlib stream of STORED deflate blocks
-// (RFC 1951 section 3.2.4: BTYPE = 00, up to 65535 bytes each, no compression): filter-0 scanlines copied through.  Every PNG
-// reader inflates it to the same pixels as the reference's compressed files; the file is as large as the raw image
-// (960x540 RGBA: 2.07 MB).  The two checksums a reader verifies are computed here:
-//   * Adler-32 of the scanline stream (RFC 1950): s1 = 1 + sum b_r, s2 = N + sum (N - r) b_r, both mod 65521 -- two integer sums,
-//     accumulated in 64 bits with integer atomics (order-free) and reduced at the end;
+// PNG as written here: signature, IHDR, ONE IDAT chunk, IEND.  The IDAT payload is a zlib stream in one of two forms:
+//   * STORED deflate blocks (RFC 1951 section 3.2.4: BTYPE = 00, up to 65535 bytes each, no compression) of filter-0 scanlines copied
+//     through -- png_encode_kernel, png_crc_kernel, png_finish_kernel, three launches per image.  The file is as large as the raw image
+//     (960x540 RGBA: 2.07 MB) and its layout is known on the host (PngLayout);
+//   * DYNAMIC-HUFFMAN deflate blocks of Paeth-filtered scanlines ("Compressed PNGs" below) -- png_filter_kernel, png_hist_kernel,
+//     png_table_kernel, png_size_kernel, png_deflate_kernel, png_crc_dynamic_kernel, png_finish_dynamic_kernel, each launched once for
+//     up to three images.  The file's length is known on the device only (PngDynamic).
+// Every PNG reader inflates either form to the same pixels as the reference's files.  The two checksums a reader verifies are computed
+// the same way for both, each step written once and called by both encoders' kernels:
+//   * Adler-32 of the scanline stream (RFC 1950): s1 = 1 + sum b_r, s2 = N + sum (N - r) b_r, both mod 65521 -- two integer sums in
+//     64 bits.  The kernel the scanline bytes pass through anyway stores one pair of partial sums per workgroup (adler_workgroup_sums);
 //   * CRC-32 of "IDAT" + payload (PNG section 5.5): the CRC without its pre / post conditioning is LINEAR over GF(2), so the
-//     message splits into 16-byte pieces whose raw CRCs are shifted to their place -- multiplied by x^(8 * bytes behind the
+//     message splits into 64-byte pieces whose raw CRCs are shifted to their place -- multiplied by x^(8 * bytes behind the
 //     piece) mod P, zlib's crc32_combine arithmetic (multmodp / x2nmodp, crc32.c) -- and XORed together in any order; the
-//     conditioning is one more term, 0xFFFFFFFF x^(8 N) ^ 0xFFFFFFFF.
-// Defines the entry points gsr_resize_rgba8_bilinear, gsr_resize_f32_nearest, gsr_frame_files(_deflate), gsr_png_size, gsr_png_room,
-// gsr_png_encode, gsr_png_deflate_max_size / _room / _scratch and gsr_png_encode_deflate.
+//     conditioning is one more term, 0xFFFFFFFF x^(8 N) ^ 0xFFFFFFFF.  The CRC kernel stores one partial XOR per workgroup
+//     (crc_tables_to_lds, crc_chunk_term, crc_workgroup_xor);
+//   * the finish kernel, one wave per image, folds both sets of partials and writes the two checksums (png_write_checksums).
+// Every partial is written by one plain store and every entry is written: no atomics on global memory, no memset.
+//
+// frame_previews_kernel / launch_frame_files: a frame's four files (three PNGs in either form, the depth plane of the .npy) queued
+// by one host call.
+// Defines the entry points gsr_frame_files(_deflate), gsr_png_size, gsr_png_room, gsr_png_encode, gsr_png_deflate_max_size / _room /
+// _scratch and gsr_png_encode_deflate.
 #include "gsr_internal.h"
 
 #include <algorithm>
-#include <cmath>
+#include <initializer_list>
 #include <mutex>
-#include <vector>
 
 namespace gsr {
 namespace {
@@ -77,12 +84,31 @@ struct PngLayout {
     uint8_t tail[16];            // the 12 bytes after the IDAT CRC: IEND chunk
 };
 
+// Adler-32's two sums over a 256-lane workgroup: wave sums -> workgroup sums -> ONE plain store per workgroup; the finish kernel adds the
+// workgroups up.  (Same-address atomics are served one per ~12 ns on this GPU: two per wave made png_encode_kernel 50 us for a 2 MB
+// image, a memset in front of it included.)  a1 is kept whole; a2, whose terms carry the weight N - r, is reduced mod 65521 once per
+// wave and once per workgroup.
+__device__ __forceinline__ void adler_workgroup_sums(unsigned long long a1, unsigned long long a2,
+                                                     unsigned long long* __restrict__ partials /*[workgroups][2], every entry written*/) {
+    __shared__ unsigned long long s_sum[4][2];
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        a1 += __shfl_xor(a1, d);
+        a2 += __shfl_xor(a2, d);
+    }
+    if ((threadIdx.x & 63) == 0) { s_sum[threadIdx.x >> 6][0] = a1; s_sum[threadIdx.x >> 6][1] = a2 % 65521ull; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        partials[2 * (size_t)blockIdx.x + 0] = s_sum[0][0] + s_sum[1][0] + s_sum[2][0] + s_sum[3][0];
+        partials[2 * (size_t)blockIdx.x + 1] = (s_sum[0][1] + s_sum[1][1] + s_sum[2][1] + s_sum[3][1]) % 65521ull;
+    }
+}
+
 // One lane = 16 consecutive, 16-byte aligned bytes of the FILE: where each byte comes from is worked out once per lane (two 64-bit
 // divisions) and stepped from byte to byte; the CRC is a kernel of its own (below).  Adler-32's two sums are taken here, where the
 // scanline bytes pass through registers anyway.
 __global__ void __launch_bounds__(256) png_encode_kernel(PngLayout L, const uint8_t* __restrict__ pixels, uint8_t* __restrict__ out,
                                                         unsigned long long* __restrict__ adler_partials /*[workgroups][2], every entry written*/) {
-    __shared__ unsigned long long s_sum[4][2];
     const unsigned long long first = ((unsigned long long)blockIdx.x * 256ull + threadIdx.x) * 16ull;
     unsigned long long a1 = 0ull, a2 = 0ull;
     if (first < L.file_len) {
@@ -156,55 +182,46 @@ __global__ void __launch_bounds__(256) png_encode_kernel(PngLayout L, const uint
             for (unsigned long long f = first; f < L.file_len; ++f) out[f] = (uint8_t)(words[(f - first) >> 2] >> (8 * ((f - first) & 3)));
         }
     }
-    // wave sums -> workgroup sums -> ONE plain store per workgroup; png_finish_kernel adds the workgroups up.  (Same-address atomics
-    // are served one per ~12 ns on this GPU: two per wave made this kernel 50 us for a 2 MB image, a memset in front of it included.)
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        a1 += __shfl_xor(a1, d);
-        a2 += __shfl_xor(a2, d);
-    }
-    if ((threadIdx.x & 63) == 0) { s_sum[threadIdx.x >> 6][0] = a1; s_sum[threadIdx.x >> 6][1] = a2 % 65521ull; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        adler_partials[2 * (size_t)blockIdx.x + 0] = s_sum[0][0] + s_sum[1][0] + s_sum[2][0] + s_sum[3][0];
-        adler_partials[2 * (size_t)blockIdx.x + 1] = (s_sum[0][1] + s_sum[1][1] + s_sum[2][1] + s_sum[3][1]) % 65521ull;
-    }
+    adler_workgroup_sums(a1, a2, adler_partials);
 }
 
 // x^(8 * 64 * m) mod P for m = i, 256 i, 65536 i (i = 0 .. 255): a CRC piece's shift by 64 m bytes is a product of three table entries.
 __device__ uint32_t g_crc_shift64[3][256];
 
-// CRC-32 of the IDAT chunk's type + payload, read back from the file image png_encode_kernel just wrote (L2-resident).  One lane =
+// CRC-32 of the IDAT chunk's type + payload, read back from the file image the encoder just wrote (L2-resident).  One lane =
 // kCrcChunk consecutive file bytes, loaded up front: their raw CRC four bytes at a time (slicing-by-4: four table lookups per word
 // instead of a chain of four), then ONE shift to the lane's place in the message -- x^(8 * bytes behind it) mod P -- and an XOR into
-// the total.
+// the total.  The three steps below are the whole of png_crc_kernel and png_crc_dynamic_kernel (256 lanes each).
 constexpr uint32_t kCrcChunk = 64u;
-__global__ void __launch_bounds__(256) png_crc_kernel(PngLayout L, PngTables T, const uint8_t* __restrict__ file,
-                                                     uint32_t* __restrict__ crc_partials /*[workgroups], every entry written*/) {
-    __shared__ uint32_t s_t[4][256];
-    __shared__ uint32_t s_shift[3][256];
-    __shared__ uint32_t s_crc[4];
-    {
-        const int i = threadIdx.x;
-        const uint32_t t0 = T.byte[i];
-        const uint32_t t1 = (t0 >> 8) ^ T.byte[t0 & 0xFFu];
-        const uint32_t t2 = (t1 >> 8) ^ T.byte[t1 & 0xFFu];
-        s_t[0][i] = t0; s_t[1][i] = t1; s_t[2][i] = t2; s_t[3][i] = (t2 >> 8) ^ T.byte[t2 & 0xFFu];
-        s_shift[0][i] = g_crc_shift64[0][i]; s_shift[1][i] = g_crc_shift64[1][i]; s_shift[2][i] = g_crc_shift64[2][i];
-    }
+
+// The slicing-by-4 tables and the shift tables into LDS, one entry of each per lane; the barrier behind them.
+__device__ __forceinline__ void crc_tables_to_lds(const PngTables& T, uint32_t (*s_t)[256], uint32_t (*s_shift)[256]) {
+    const int i = threadIdx.x;
+    const uint32_t t0 = T.byte[i];
+    const uint32_t t1 = (t0 >> 8) ^ T.byte[t0 & 0xFFu];
+    const uint32_t t2 = (t1 >> 8) ^ T.byte[t1 & 0xFFu];
+    s_t[0][i] = t0; s_t[1][i] = t1; s_t[2][i] = t2; s_t[3][i] = (t2 >> 8) ^ T.byte[t2 & 0xFFu];
+    s_shift[0][i] = g_crc_shift64[0][i]; s_shift[1][i] = g_crc_shift64[1][i]; s_shift[2][i] = g_crc_shift64[2][i];
     __syncthreads();
-    const unsigned long long crc_from = L.data_at - 4ull, crc_end = L.data_at + L.data_len;   // "IDAT" ... Adler-32 (still zeros) inclusive
-    const unsigned long long lo0 = ((unsigned long long)blockIdx.x * 256ull + threadIdx.x) * kCrcChunk;
+}
+
+// One lane's term of the CRC: the raw CRC of the file bytes [lo0, lo0 + kCrcChunk) that lie inside [crc_from, body_end), shifted to its
+// place in the message [crc_from, crc_end).  The message ends with the four Adler-32 bytes, which the finish kernel writes and whose
+// term it adds: the raw CRC being linear, they count here as zeros, read (body_end = crc_end, where the file holds zeros there) or
+// left out (body_end = crc_end - 4) -- the same term either way.  tail_shift: x^(8 * (crc_end mod 64)) mod P.
+__device__ __forceinline__ uint32_t crc_chunk_term(const uint8_t* __restrict__ file, unsigned long long lo0, unsigned long long crc_from,
+                                                   unsigned long long body_end, unsigned long long crc_end, uint32_t tail_shift,
+                                                   const uint32_t (*s_t)[256], const uint32_t (*s_shift)[256], const uint32_t* x2n) {
     uint32_t crc = 0u;
-    if (lo0 < crc_end && lo0 + kCrcChunk > crc_from) {
-        // the lane's 64 bytes in four 16-byte loads, all issued before the first is used (the file image ends with 32 bytes of
-        // scratch behind a 16-byte boundary: reading the whole chunk is always inside the buffer)
+    if (lo0 < body_end && lo0 + kCrcChunk > crc_from) {
+        // the lane's 64 bytes in four 16-byte loads, all issued before the first is used (behind the file image lie 32 bytes or more
+        // of the same buffer, from a 16-byte boundary: reading the whole chunk is always inside the buffer)
         uint4 v[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k)   // (a 16-byte piece that starts inside the message ends inside the file)
-            v[k] = lo0 + 16u * k < crc_end ? *reinterpret_cast<const uint4*>(file + lo0 + 16u * k) : make_uint4(0u, 0u, 0u, 0u);
+            v[k] = lo0 + 16u * k < body_end ? *reinterpret_cast<const uint4*>(file + lo0 + 16u * k) : make_uint4(0u, 0u, 0u, 0u);
         const uint32_t w[16] = {v[0].x, v[0].y, v[0].z, v[0].w, v[1].x, v[1].y, v[1].z, v[1].w, v[2].x, v[2].y, v[2].z, v[2].w, v[3].x, v[3].y, v[3].z, v[3].w};
-        const unsigned long long lo = lo0 < crc_from ? crc_from : lo0, hi = lo0 + kCrcChunk < crc_end ? lo0 + kCrcChunk : crc_end;
+        const unsigned long long lo = lo0 < crc_from ? crc_from : lo0, hi = lo0 + kCrcChunk < body_end ? lo0 + kCrcChunk : body_end;
         if (lo == lo0 && hi == lo0 + kCrcChunk) {
 #pragma unroll
             for (int k = 0; k < 16; ++k) {
@@ -217,27 +234,54 @@ __global__ void __launch_bounds__(256) png_crc_kernel(PngLayout L, PngTables T, 
                 crc = s_t[0][(crc ^ b) & 0xFFu] ^ (crc >> 8);
             }
         }
-        if (crc != 0u && hi < crc_end) {
-            // shift to its place: crc_end - hi = 64 m + (crc_end mod 64) bytes lie behind this piece (hi is a multiple of 64 here);
-            // x^(8 * 64 m) from the three tables, x^(8 * (crc_end mod 64)) host-computed -- four modular products instead of the
-            // twenty of an exponentiation (38 -> 12 us for a 2 MB image)
-            const unsigned long long m = (crc_end - hi) >> 6;
-            crc = crc_multmodp(L.crc_tail_shift, crc);
-            if (m & 0xFFull) crc = crc_multmodp(s_shift[0][m & 0xFFull], crc);
-            if ((m >> 8) & 0xFFull) crc = crc_multmodp(s_shift[1][(m >> 8) & 0xFFull], crc);
-            if (m >> 16) crc = crc_multmodp(s_shift[2][(m >> 16) & 0xFFull], crc);
+        const unsigned long long behind = crc_end - hi;   // bytes of the message behind this piece
+        if (crc != 0u && behind != 0ull) {
+            if ((hi & 63ull) == 0ull) {
+                // hi is a chunk end: behind = 64 m + (crc_end mod 64).  x^(8 * 64 m) from the three tables, x^(8 * (crc_end mod 64)) computed
+                // once per image -- four modular products instead of the twenty of an exponentiation (38 -> 12 us for a 2 MB image)
+                const unsigned long long m = behind >> 6;
+                crc = crc_multmodp(tail_shift, crc);
+                if (m & 0xFFull) crc = crc_multmodp(s_shift[0][m & 0xFFull], crc);
+                if ((m >> 8) & 0xFFull) crc = crc_multmodp(s_shift[1][(m >> 8) & 0xFFull], crc);
+                if (m >> 16) crc = crc_multmodp(s_shift[2][(m >> 16) & 0xFFull], crc);
+            } else {   // the one piece that ends with the body, off a chunk boundary: any number of bytes behind it
+                crc = crc_multmodp(crc_x2nmodp(x2n, behind, 3u), crc);
+            }
         }
     }
+    return crc;
+}
+
+// The workgroup's XOR of its lanes' terms, one plain store.  (XOR: any order, same result)
+__device__ __forceinline__ void crc_workgroup_xor(uint32_t crc, uint32_t* __restrict__ crc_partials /*[workgroups], every entry written*/) {
+    __shared__ uint32_t s_crc[4];
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) crc ^= (uint32_t)__shfl_xor((int)crc, d);
     if ((threadIdx.x & 63) == 0) s_crc[threadIdx.x >> 6] = crc;
     __syncthreads();
-    if (threadIdx.x == 0) crc_partials[blockIdx.x] = s_crc[0] ^ s_crc[1] ^ s_crc[2] ^ s_crc[3];   // (XOR: any order, same result)
+    if (threadIdx.x == 0) crc_partials[blockIdx.x] = s_crc[0] ^ s_crc[1] ^ s_crc[2] ^ s_crc[3];
 }
 
-// One wave: adds up the workgroups' Adler sums and XORs their CRC terms, writes the two checksums into the file image.
-__global__ void __launch_bounds__(64) png_finish_kernel(PngLayout L, uint8_t* __restrict__ out, const unsigned long long* __restrict__ adler_partials,
-                                                       uint32_t adler_groups, const uint32_t* __restrict__ crc_partials, uint32_t crc_groups) {
+__global__ void __launch_bounds__(256) png_crc_kernel(PngLayout L, PngTables T, const uint8_t* __restrict__ file,
+                                                     uint32_t* __restrict__ crc_partials /*[workgroups], every entry written*/) {
+    __shared__ uint32_t s_t[4][256];
+    __shared__ uint32_t s_shift[3][256];
+    crc_tables_to_lds(T, s_t, s_shift);
+    // "IDAT" ... Adler-32 (still the zeros png_encode_kernel wrote) inclusive: the last piece then has nothing behind it and needs no shift.
+    // (Ending the body 4 bytes earlier, as the compressed file must, puts an exponentiation on one lane at the kernel's tail: 31 -> 35 us
+    // for a 960x540 RGBA file.)
+    const unsigned long long crc_from = L.data_at - 4ull, crc_end = L.data_at + L.data_len;
+    const unsigned long long lo0 = ((unsigned long long)blockIdx.x * 256ull + threadIdx.x) * kCrcChunk;
+    crc_workgroup_xor(crc_chunk_term(file, lo0, crc_from, crc_end, crc_end, L.crc_tail_shift, s_t, s_shift, T.x2n), crc_partials);
+}
+
+// One wave: adds up the workgroups' Adler sums and XORs their CRC terms, writes the two checksums into the file image behind the
+// deflate stream.  N: bytes of the scanline stream; init_term (lane 0's counts): the CRC's pre-conditioning as one more linear term,
+// 0xFFFFFFFF x^(8 * (4 + data_len)) mod P.
+__device__ __forceinline__ void png_write_checksums(uint8_t* __restrict__ out, unsigned long long N, unsigned long long data_at,
+                                                    unsigned long long data_len, uint32_t init_term,
+                                                    const unsigned long long* __restrict__ adler_partials, uint32_t adler_groups,
+                                                    const uint32_t* __restrict__ crc_partials, uint32_t crc_groups) {
     unsigned long long a1 = 0ull, a2 = 0ull;
     uint32_t crc_sum = 0u;
     for (uint32_t i = threadIdx.x; i < adler_groups; i += 64u) { a1 += adler_partials[2 * (size_t)i]; a2 += adler_partials[2 * (size_t)i + 1]; }
@@ -250,9 +294,9 @@ __global__ void __launch_bounds__(64) png_finish_kernel(PngLayout L, uint8_t* __
     }
     if (threadIdx.x != 0) return;
     const uint32_t s1 = (uint32_t)((1ull + a1) % 65521ull);
-    const uint32_t s2 = (uint32_t)((L.N % 65521ull + a2) % 65521ull);
+    const uint32_t s2 = (uint32_t)((N % 65521ull + a2) % 65521ull);
     const uint32_t adler = (s2 << 16) | s1;
-    const unsigned long long adler_at = L.data_at + L.data_len - 4ull;
+    const unsigned long long adler_at = data_at + data_len - 4ull;
     uint32_t crc_a = 0u;   // raw CRC of the four Adler bytes: the last bytes of the message, nothing behind them
     for (int k = 0; k < 4; ++k) {
         const uint32_t b = (adler >> (24 - 8 * k)) & 0xFFu;   // big-endian
@@ -260,8 +304,13 @@ __global__ void __launch_bounds__(64) png_finish_kernel(PngLayout L, uint8_t* __
         crc_a ^= b;
         for (int i = 0; i < 8; ++i) crc_a = (crc_a & 1u) ? (crc_a >> 1) ^ kCrcPoly : crc_a >> 1;
     }
-    const uint32_t crc = (crc_sum ^ crc_a ^ L.crc_init_term) ^ 0xFFFFFFFFu;
+    const uint32_t crc = (crc_sum ^ crc_a ^ init_term) ^ 0xFFFFFFFFu;
     for (int k = 0; k < 4; ++k) out[adler_at + 4 + k] = (uint8_t)(crc >> (24 - 8 * k));
+}
+
+__global__ void __launch_bounds__(64) png_finish_kernel(PngLayout L, uint8_t* __restrict__ out, const unsigned long long* __restrict__ adler_partials,
+                                                       uint32_t adler_groups, const uint32_t* __restrict__ crc_partials, uint32_t crc_groups) {
+    png_write_checksums(out, L.N, L.data_at, L.data_len, L.crc_init_term, adler_partials, adler_groups, crc_partials, crc_groups);
 }
 
 const PngTables& png_tables() {
@@ -425,7 +474,6 @@ __global__ void __launch_bounds__(256) png_filter_kernel(PngBatch B) {
     const PngJob& J = B.job[blockIdx.y];
     if (blockIdx.x >= J.filter_groups) return;
     const PngLayout& L = J.L;
-    __shared__ unsigned long long s_sum[4][2];
     const unsigned long long base = (unsigned long long)blockIdx.x * kFilterBytes;
     unsigned long long a1 = 0ull, a2 = 0ull;
 #pragma unroll 4
@@ -439,14 +487,7 @@ __global__ void __launch_bounds__(256) png_filter_kernel(PngBatch B) {
             a2 += (L.N - r) * v;
         }
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { a1 += __shfl_xor(a1, d); a2 += __shfl_xor(a2, d); }
-    if ((threadIdx.x & 63) == 0) { s_sum[threadIdx.x >> 6][0] = a1; s_sum[threadIdx.x >> 6][1] = a2 % 65521ull; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        J.adler[2 * (size_t)blockIdx.x + 0] = s_sum[0][0] + s_sum[1][0] + s_sum[2][0] + s_sum[3][0];
-        J.adler[2 * (size_t)blockIdx.x + 1] = (s_sum[0][1] + s_sum[1][1] + s_sum[2][1] + s_sum[3][1]) % 65521ull;
-    }
+    adler_workgroup_sums(a1, a2, J.adler);
 }
 
 // A workgroup's 16 KB block of the filtered stream into LDS, consecutive lanes loading consecutive 16-byte pieces (piece p of the block
@@ -841,353 +882,40 @@ __global__ void __launch_bounds__(256) png_deflate_kernel(PngBatch B, PngTables 
     }
 }
 
-// CRC-32 and the last bytes of a deflate-compressed file: as png_crc_kernel / png_finish_kernel, with the lengths read from the device
+// CRC-32 and the last bytes of a deflate-compressed file: the steps of png_crc_kernel / png_finish_kernel, with the lengths read from the device
 __global__ void __launch_bounds__(256) png_crc_dynamic_kernel(PngBatch B, PngTables T) {
     if ((int)blockIdx.y >= B.n) return;
     const PngJob& J = B.job[blockIdx.y];
     if (blockIdx.x >= J.crc_groups) return;
-    const PngLayout& L = J.L;
-    const uint8_t* __restrict__ file = J.out;
     __shared__ uint32_t s_t[4][256];
     __shared__ uint32_t s_shift[3][256];
-    __shared__ uint32_t s_crc[4];
-    {
-        const int i = threadIdx.x;
-        const uint32_t t0 = T.byte[i];
-        const uint32_t t1 = (t0 >> 8) ^ T.byte[t0 & 0xFFu];
-        const uint32_t t2 = (t1 >> 8) ^ T.byte[t1 & 0xFFu];
-        s_t[0][i] = t0; s_t[1][i] = t1; s_t[2][i] = t2; s_t[3][i] = (t2 >> 8) ^ T.byte[t2 & 0xFFu];
-        s_shift[0][i] = g_crc_shift64[0][i]; s_shift[1][i] = g_crc_shift64[1][i]; s_shift[2][i] = g_crc_shift64[2][i];
-    }
-    __syncthreads();
-    const unsigned long long data_len = J.dyn->data_len;
-    const uint32_t tail_shift = J.dyn->crc_tail_shift;
-    // "IDAT" ... the last deflate byte; the four Adler bytes that end the message are folded in by the finish kernel, which writes them
-    const unsigned long long crc_from = L.data_at - 4ull, crc_end = L.data_at + data_len, body_end = crc_end - 4ull;
+    crc_tables_to_lds(T, s_t, s_shift);
+    // "IDAT" ... Adler-32 inclusive; the body ends in front of the Adler-32: nothing has written those four bytes yet
+    const unsigned long long crc_from = J.L.data_at - 4ull, crc_end = J.L.data_at + J.dyn->data_len;
     const unsigned long long lo0 = ((unsigned long long)blockIdx.x * 256ull + threadIdx.x) * kCrcChunk;
-    uint32_t crc = 0u;
-    if (lo0 < body_end && lo0 + kCrcChunk > crc_from) {
-        uint4 v[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] = lo0 + 16u * k < body_end ? *reinterpret_cast<const uint4*>(file + lo0 + 16u * k) : make_uint4(0u, 0u, 0u, 0u);
-        const uint32_t w[16] = {v[0].x, v[0].y, v[0].z, v[0].w, v[1].x, v[1].y, v[1].z, v[1].w, v[2].x, v[2].y, v[2].z, v[2].w, v[3].x, v[3].y, v[3].z, v[3].w};
-        const unsigned long long lo = lo0 < crc_from ? crc_from : lo0, hi = lo0 + kCrcChunk < body_end ? lo0 + kCrcChunk : body_end;
-        if (lo == lo0 && hi == lo0 + kCrcChunk) {
-#pragma unroll
-            for (int k = 0; k < 16; ++k) {
-                const uint32_t x = crc ^ w[k];
-                crc = s_t[3][x & 0xFFu] ^ s_t[2][(x >> 8) & 0xFFu] ^ s_t[1][(x >> 16) & 0xFFu] ^ s_t[0][x >> 24];
-            }
-        } else {
-            for (unsigned long long f = lo; f < hi; ++f) {
-                const uint32_t b = (w[(f - lo0) >> 2] >> (8 * ((f - lo0) & 3ull))) & 0xFFu;
-                crc = s_t[0][(crc ^ b) & 0xFFu] ^ (crc >> 8);
-            }
-        }
-        if (crc != 0u) {   // crc_end - hi bytes lie behind this piece: a multiple of 64 plus (crc_end mod 64) when hi is a chunk end, anything for the last piece
-            const unsigned long long behind = crc_end - hi;
-            if ((hi & 63ull) == 0ull) {
-                const unsigned long long m = behind >> 6;
-                crc = crc_multmodp(tail_shift, crc);
-                if (m & 0xFFull) crc = crc_multmodp(s_shift[0][m & 0xFFull], crc);
-                if ((m >> 8) & 0xFFull) crc = crc_multmodp(s_shift[1][(m >> 8) & 0xFFull], crc);
-                if (m >> 16) crc = crc_multmodp(s_shift[2][(m >> 16) & 0xFFull], crc);
-            } else {
-                crc = crc_multmodp(crc_x2nmodp(T.x2n, behind, 3u), crc);
-            }
-        }
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) crc ^= (uint32_t)__shfl_xor((int)crc, d);
-    if ((threadIdx.x & 63) == 0) s_crc[threadIdx.x >> 6] = crc;
-    __syncthreads();
-    if (threadIdx.x == 0) J.crc_partials[blockIdx.x] = s_crc[0] ^ s_crc[1] ^ s_crc[2] ^ s_crc[3];
+    crc_workgroup_xor(crc_chunk_term(J.out, lo0, crc_from, crc_end - 4ull, crc_end, J.dyn->crc_tail_shift, s_t, s_shift, T.x2n), J.crc_partials);
 }
 
 __global__ void __launch_bounds__(64) png_finish_dynamic_kernel(PngBatch B, PngTables T) {
     if ((int)blockIdx.x >= B.n) return;
     const PngJob& J = B.job[blockIdx.x];
     const PngLayout& L = J.L;
-    uint8_t* __restrict__ out = J.out;
+    const unsigned long long data_len = J.dyn->data_len;
     // the CRC's pre-conditioning as one more linear term: 0xFFFFFFFF x^(8 n) mod P, n = 4 + data_len = 64 m + r.  x^(8 64 m) is a product of
     // three entries of the shift tables the CRC kernel uses, x^(8 r) six squarings' worth at most: nine modular products on one lane
     // (twenty in a row cost 35 us where this first lived; a product tree over the wave was no faster: every lane runs the worst case)
     uint32_t init_term = 0u;
     if (threadIdx.x == 0) {
-        const unsigned long long n = 4ull + J.dyn->data_len, m = n >> 6;
+        const unsigned long long n = 4ull + data_len, m = n >> 6;
         uint32_t f = crc_x2nmodp(T.x2n, n & 63ull, 3u);
         if (m & 0xFFull) f = crc_multmodp(g_crc_shift64[0][m & 0xFFull], f);
         if ((m >> 8) & 0xFFull) f = crc_multmodp(g_crc_shift64[1][(m >> 8) & 0xFFull], f);
         if ((m >> 16) & 0xFFull) f = crc_multmodp(g_crc_shift64[2][(m >> 16) & 0xFFull], f);
         init_term = crc_multmodp(f, 0xFFFFFFFFu);
     }
-    unsigned long long a1 = 0ull, a2 = 0ull;
-    uint32_t crc_sum = 0u;
-    for (uint32_t i = threadIdx.x; i < J.filter_groups; i += 64u) { a1 += J.adler[2 * (size_t)i]; a2 += J.adler[2 * (size_t)i + 1]; }
-    for (uint32_t i = threadIdx.x; i < J.crc_groups; i += 64u) crc_sum ^= J.crc_partials[i];
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        a1 += __shfl_xor(a1, d);
-        a2 += __shfl_xor(a2, d);
-        crc_sum ^= (uint32_t)__shfl_xor((int)crc_sum, d);
-    }
-    if (threadIdx.x != 0) return;
-    const uint32_t s1 = (uint32_t)((1ull + a1) % 65521ull);
-    const uint32_t s2 = (uint32_t)((L.N % 65521ull + a2) % 65521ull);
-    const uint32_t adler = (s2 << 16) | s1;
-    const unsigned long long adler_at = L.data_at + J.dyn->data_len - 4ull;
-    uint32_t crc_a = 0u;
-    for (int k = 0; k < 4; ++k) {
-        const uint32_t b = (adler >> (24 - 8 * k)) & 0xFFu;
-        out[adler_at + k] = (uint8_t)b;
-        crc_a ^= b;
-        for (int i = 0; i < 8; ++i) crc_a = (crc_a & 1u) ? (crc_a >> 1) ^ kCrcPoly : crc_a >> 1;
-    }
-    const uint32_t crc = (crc_sum ^ crc_a ^ init_term) ^ 0xFFFFFFFFu;
-    for (int k = 0; k < 4; ++k) out[adler_at + 4 + k] = (uint8_t)(crc >> (24 - 8 * k));
-    for (int k = 0; k < 12; ++k) out[adler_at + 8 + k] = L.tail[k];
-}
-
-// ================================================================================================
-// PIL's Image.resize, bit for bit (blender/blend_all.py:21-28: downsample_image = Image.fromarray(a).resize(new_size, BILINEAR) for
-// the RGBA8 layers, resize(new_size, NEAREST) for the float depth maps; called on every Blender layer of every frame, :217-234).
-//
-// BILINEAR on an RGBA image is three steps in Pillow (src/PIL/Image.py resize; src/libImaging/Convert.c, Resample.c):
-//   1. RGBA -> RGBa: colour channels premultiplied, MULDIV255(c, a) = (t = c a + 128, ((t >> 8) + t) >> 8);
-//   2. a separable resample in 8-bit fixed point, horizontal pass first, each pass rounding to 8 bits: the triangle filter's
-//      support is stretched by the down-scale factor (an area-weighted average, not a 2 x 2 lookup), the weights of an output
-//      pixel are normalised to sum 1 in double and converted to integers with 22 fraction bits ((int)(0.5 + w 2^22)), a pixel is
-//      clip8((2^21 + sum k_i p_i) >> 22);
-//   3. RGBa -> RGBA: c = min(255, 255 c / a) (integer division) unless a is 0 or 255.
-// An image that already has the target size is copied (no premultiply round trip); a pass whose size does not change is skipped.
-// The weight tables depend only on (input size, output size): computed on the host in the doubles Pillow uses, cached per device.
-//
-// NEAREST on a mode "F" image is an affine scale with the source coordinate ACCUMULATED in double (Geometry.c
-// ImagingScaleAffine: xo = a / 2, then xo += a per output pixel, index = (int)xo): the index tables are built on the host the same way.
-// ================================================================================================
-constexpr int kResampleBits = 32 - 8 - 2;
-
-struct ResampleTable {
-    int dev, in, out, kind;   // kind 0: bilinear weights, 1: nearest indices
-    int ksize;
-    int* bounds;              // [out][2] (first input index, count); nearest: [out] indices
-    int* coef;                // [out][ksize]
-};
-std::mutex g_table_mutex;
-std::vector<ResampleTable> g_tables;
-
-double triangle(double x) {
-    if (x < 0.0) x = -x;
-    return x < 1.0 ? 1.0 - x : 0.0;
-}
-
-// Resample.c: precompute_coeffs + normalize_coeffs_8bpc for the bilinear filter (support 1.0) over the whole input (box = image)
-void bilinear_weights(int in_size, int out_size, std::vector<int>* bounds, std::vector<int>* coef, int* ksize_out) {
-    double scale = (double)in_size / out_size, filterscale = scale;
-    if (filterscale < 1.0) filterscale = 1.0;
-    const double support = 1.0 * filterscale;
-    const int ksize = (int)std::ceil(support) * 2 + 1;
-    bounds->assign((size_t)out_size * 2, 0);
-    coef->assign((size_t)out_size * ksize, 0);
-    std::vector<double> k((size_t)ksize);
-    for (int xx = 0; xx < out_size; ++xx) {
-        const double center = 0.0 + (xx + 0.5) * scale;
-        const double ss = 1.0 / filterscale;
-        double ww = 0.0;
-        int xmin = (int)(center - support + 0.5);
-        if (xmin < 0) xmin = 0;
-        int xmax = (int)(center + support + 0.5);
-        if (xmax > in_size) xmax = in_size;
-        xmax -= xmin;
-        for (int x = 0; x < xmax; ++x) {
-            const double w = triangle((x + xmin - center + 0.5) * ss);
-            k[x] = w;
-            ww += w;
-        }
-        for (int x = 0; x < xmax; ++x) {
-            if (ww != 0.0) k[x] /= ww;
-            (*coef)[(size_t)xx * ksize + x] = k[x] < 0 ? (int)(-0.5 + k[x] * (1 << kResampleBits)) : (int)(0.5 + k[x] * (1 << kResampleBits));
-        }
-        (*bounds)[2 * (size_t)xx] = xmin;
-        (*bounds)[2 * (size_t)xx + 1] = xmax;
-    }
-    *ksize_out = ksize;
-}
-
-// Geometry.c ImagingScaleAffine, nearest: the source index of every output pixel (-1: outside)
-void nearest_indices(int in_size, int out_size, std::vector<int>* index) {
-    const double a = (double)in_size / out_size;
-    double xo = a * 0.5;
-    index->assign((size_t)out_size, -1);
-    for (int x = 0; x < out_size; ++x) {
-        const int xin = xo < 0.0 ? -1 : (int)xo;
-        (*index)[x] = (xin >= 0 && xin < in_size) ? xin : -1;
-        xo += a;
-    }
-}
-
-hipError_t resample_table(int in_size, int out_size, int kind, ResampleTable* out) {
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    std::lock_guard<std::mutex> lock(g_table_mutex);
-    for (const ResampleTable& t : g_tables)
-        if (t.dev == dev && t.in == in_size && t.out == out_size && t.kind == kind) { *out = t; return hipSuccess; }
-    std::vector<int> bounds, coef;
-    ResampleTable t = {dev, in_size, out_size, kind, 0, nullptr, nullptr};
-    if (kind == 0) bilinear_weights(in_size, out_size, &bounds, &coef, &t.ksize);
-    else nearest_indices(in_size, out_size, &bounds);
-    if ((e = hipMalloc((void**)&t.bounds, bounds.size() * sizeof(int))) != hipSuccess) return e;
-    if ((e = hipMemcpy(t.bounds, bounds.data(), bounds.size() * sizeof(int), hipMemcpyHostToDevice)) != hipSuccess) return e;
-    if (!coef.empty()) {
-        if ((e = hipMalloc((void**)&t.coef, coef.size() * sizeof(int))) != hipSuccess) return e;
-        if ((e = hipMemcpy(t.coef, coef.data(), coef.size() * sizeof(int), hipMemcpyHostToDevice)) != hipSuccess) return e;
-    }
-    g_tables.push_back(t);   // (a handful of sizes per process; never freed)
-    *out = t;
-    return hipSuccess;
-}
-
-__device__ __forceinline__ uint32_t muldiv255(uint32_t c, uint32_t a) {
-    const uint32_t t = c * a + 128u;
-    return ((t >> 8) + t) >> 8;
-}
-__device__ __forceinline__ int clip8(int v) {
-    v >>= kResampleBits;   // arithmetic shift: floor, as the reference's lookup table is indexed
-    return v < 0 ? 0 : v > 255 ? 255 : v;
-}
-
-// One lane = one output pixel of one pass.  kHorizontal: out[row][xx] from in[row][xmin .. xmin + n); else out[yy][x] from
-// in[ymin .. ymin + n)[x].  kPremultiply: the input is straight RGBA (the first pass of a call); kUnpremultiply: the output is
-// converted back (the last pass).
-template <bool kHorizontal, bool kPremultiply, bool kUnpremultiply>
-__global__ void __launch_bounds__(256) resample_rgba8_kernel(const uchar4* __restrict__ in, int in_w, uchar4* __restrict__ out, int out_w, int out_h,
-                                                            const int* __restrict__ bounds, const int* __restrict__ coef, int ksize) {
-    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
-    if (x >= out_w || y >= out_h) return;
-    const int o = kHorizontal ? x : y;
-    const int first = bounds[2 * o], n = bounds[2 * o + 1];
-    const int* k = coef + (size_t)o * ksize;
-    int s0 = 1 << (kResampleBits - 1), s1 = s0, s2 = s0, s3 = s0;
-    for (int i = 0; i < n; ++i) {
-        const uchar4 p = kHorizontal ? in[(size_t)y * in_w + first + i] : in[(size_t)(first + i) * in_w + x];
-        uint32_t r = p.x, g = p.y, b = p.z;
-        const uint32_t a = p.w;
-        if (kPremultiply) { r = muldiv255(r, a); g = muldiv255(g, a); b = muldiv255(b, a); }
-        const int w = k[i];
-        s0 += (int)r * w; s1 += (int)g * w; s2 += (int)b * w; s3 += (int)a * w;
-    }
-    int r = clip8(s0), g = clip8(s1), b = clip8(s2);
-    const int a = clip8(s3);
-    if (kUnpremultiply && a != 255 && a != 0) {
-        r = min(255, 255 * r / a); g = min(255, 255 * g / a); b = min(255, 255 * b / a);
-    }
-    out[(size_t)y * out_w + x] = make_uchar4((unsigned char)r, (unsigned char)g, (unsigned char)b, (unsigned char)a);
-}
-
-__global__ void __launch_bounds__(256) nearest_f32_kernel(const float* __restrict__ in, int in_w, float* __restrict__ out, int out_w, int out_h,
-                                                         const int* __restrict__ xi, const int* __restrict__ yi) {
-    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
-    if (x >= out_w || y >= out_h) return;
-    const int sx = xi[x], sy = yi[y];
-    if (sx >= 0 && sy >= 0) out[(size_t)y * out_w + x] = in[(size_t)sy * in_w + sx];   // (never outside for a whole-image resize)
-}
-
-// tmp: src_h * dst_w * 4 bytes (needed when both sizes change)
-hipError_t launch_resize_rgba8_bilinear(const uint8_t* src, int src_w, int src_h, uint8_t* dst, int dst_w, int dst_h, uint8_t* tmp,
-                                        hipStream_t stream) {
-    const uchar4* in = reinterpret_cast<const uchar4*>(src);
-    uchar4* out = reinterpret_cast<uchar4*>(dst);
-    if (src_w == dst_w && src_h == dst_h)   // Image.resize returns a copy: no premultiply round trip
-        return hipMemcpyAsync(dst, src, (size_t)src_w * src_h * 4, hipMemcpyDeviceToDevice, stream);
-    const bool horizontal = src_w != dst_w, vertical = src_h != dst_h;
-    ResampleTable tx = {}, ty = {};
-    hipError_t e;
-    if (horizontal && (e = resample_table(src_w, dst_w, 0, &tx)) != hipSuccess) return e;
-    if (vertical && (e = resample_table(src_h, dst_h, 0, &ty)) != hipSuccess) return e;
-    if (horizontal && vertical) {
-        uchar4* mid = reinterpret_cast<uchar4*>(tmp);   // [src_h, dst_w]
-        hipLaunchKernelGGL((resample_rgba8_kernel<true, true, false>), dim3((dst_w + 255) / 256, src_h), dim3(256), 0, stream, in, src_w, mid, dst_w,
-                           src_h, tx.bounds, tx.coef, tx.ksize);
-        hipLaunchKernelGGL((resample_rgba8_kernel<false, false, true>), dim3((dst_w + 255) / 256, dst_h), dim3(256), 0, stream, mid, dst_w, out, dst_w,
-                           dst_h, ty.bounds, ty.coef, ty.ksize);
-    } else if (horizontal) {
-        hipLaunchKernelGGL((resample_rgba8_kernel<true, true, true>), dim3((dst_w + 255) / 256, src_h), dim3(256), 0, stream, in, src_w, out, dst_w,
-                           src_h, tx.bounds, tx.coef, tx.ksize);
-    } else {
-        hipLaunchKernelGGL((resample_rgba8_kernel<false, true, true>), dim3((dst_w + 255) / 256, dst_h), dim3(256), 0, stream, in, src_w, out, dst_w,
-                           dst_h, ty.bounds, ty.coef, ty.ksize);
-    }
-    return hipGetLastError();
-}
-
-hipError_t launch_resize_f32_nearest(const float* src, int src_w, int src_h, float* dst, int dst_w, int dst_h, hipStream_t stream) {
-    if (src_w == dst_w && src_h == dst_h) return hipMemcpyAsync(dst, src, (size_t)src_w * src_h * 4, hipMemcpyDeviceToDevice, stream);
-    ResampleTable tx = {}, ty = {};
-    hipError_t e;
-    if ((e = resample_table(src_w, dst_w, 1, &tx)) != hipSuccess) return e;
-    if ((e = resample_table(src_h, dst_h, 1, &ty)) != hipSuccess) return e;
-    hipLaunchKernelGGL(nearest_f32_kernel, dim3((dst_w + 255) / 256, dst_h), dim3(256), 0, stream, src, src_w, dst, dst_w, dst_h, tx.bounds, ty.bounds);
-    return hipGetLastError();
-}
-
-// The two 8-bit images the reference makes with numpy / OpenCV before cv2.imwrite (scene_representation.py:429-438), one lane per
-// pixel: the turbo-coloured depth preview -- depth2img(depth, scale): uint8(clip(depth / scale, 0, 1) * 255) through the colour
-// table -- and the normal map, uint8((n + 1) / 2 * 255): the same fp32 operations in the same order, truncation.
-__global__ void __launch_bounds__(256) frame_previews_kernel(const float* __restrict__ depth, const float* __restrict__ normal /*[H,W,3]*/,
-                                                            float depth_scale, const uint8_t* __restrict__ lut /*[256,3]*/, size_t n_pixels,
-                                                            uint8_t* __restrict__ depth_rgb, uint8_t* __restrict__ normal_rgb,
-                                                            float* __restrict__ depth_copy /*the .npy plane: the depth map as it is*/) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n_pixels) return;
-    const float depth_i = depth[i];
-    depth_copy[i] = depth_i;
-    const float d = fminf(fmaxf(depth_i / depth_scale, 0.0f), 1.0f) * 255.0f;
-    const uint32_t idx = (uint32_t)(int)d & 255u;
-    depth_rgb[3 * i + 0] = lut[3 * idx + 0];
-    depth_rgb[3 * i + 1] = lut[3 * idx + 1];
-    depth_rgb[3 * i + 2] = lut[3 * idx + 2];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float v = (normal[3 * i + c] + 1.0f) / 2.0f * 255.0f;
-        normal_rgb[3 * i + c] = (uint8_t)(int)fminf(fmaxf(v, 0.0f), 255.0f);
-    }
-}
-
-size_t png_file_bytes(int W, int H, int C);
-size_t png_deflate_scratch_bytes(int W, int H, int C);
-hipError_t launch_png_encode(const uint8_t* pixels, int W, int H, int C, int planar, uint8_t* out, hipStream_t stream);
-hipError_t launch_png_encode_deflate_batch(int n, const uint8_t* const* pixels, const int* Ws, const int* Hs, const int* Cs, const int* planars,
-                                           uint8_t* const* outs, uint8_t* const* scratches, unsigned long long* const* out_lens, hipStream_t stream);
-
-// One frame's four files (gsr.h: gsr_frame_files): quantise, colour, encode, copy -- ten launches queued by ONE host call.  work: 10 * W * H bytes.
-hipError_t launch_frame_files(const float* color, const float* alpha, const float* depth, const float* normal, float depth_scale,
-                              const uint8_t* turbo_lut, int W, int H, uint8_t* png_rgba, uint8_t* png_depth, uint8_t* png_normal,
-                              float* npy_plane, uint8_t* work, uint8_t* png_scratch, unsigned long long* png_lengths /*both null: stored PNGs; else
-                              scratch for the three compressed files and [3] lengths, device*/, hipStream_t stream) {
-    const size_t n = (size_t)W * H;
-    uint8_t* rgba8 = work;                 // planar [4,H,W]
-    uint8_t* depth_rgb = work + 4 * n;     // [H,W,3]
-    uint8_t* normal_rgb = work + 7 * n;    // [H,W,3]
-    hipError_t e = launch_pack_rgba8(color, alpha, rgba8, n, stream);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(frame_previews_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, depth, normal, depth_scale, turbo_lut, n,
-                       depth_rgb, normal_rgb, npy_plane);
-    const size_t sizes[3] = {png_file_bytes(W, H, 4), png_file_bytes(W, H, 3), png_file_bytes(W, H, 3)};
-    uint8_t* outs[3] = {png_rgba, png_depth, png_normal};
-    const uint8_t* srcs[3] = {rgba8, depth_rgb, normal_rgb};
-    for (int k = 0; k < 3; ++k)
-        if (sizes[k] == 0) return hipErrorInvalidValue;
-    if (png_lengths) {
-        const int Ws[3] = {W, W, W}, Hs[3] = {H, H, H}, Cs[3] = {4, 3, 3}, planars[3] = {1, 0, 0};
-        unsigned long long* lens[3] = {png_lengths, png_lengths + 1, png_lengths + 2};
-        const size_t s4 = png_deflate_scratch_bytes(W, H, 4), s3 = png_deflate_scratch_bytes(W, H, 3);
-        uint8_t* scratches[3] = {png_scratch, png_scratch + s4, png_scratch + s4 + s3};
-        return launch_png_encode_deflate_batch(3, srcs, Ws, Hs, Cs, planars, outs, scratches, lens, stream);
-    }
-    for (int k = 0; k < 3; ++k)
-        if ((e = launch_png_encode(srcs[k], W, H, k == 0 ? 4 : 3, k == 0 ? 1 : 0, outs[k], stream)) != hipSuccess) return e;
-    return hipSuccess;
+    png_write_checksums(J.out, L.N, L.data_at, data_len, init_term, J.adler, J.filter_groups, J.crc_partials, J.crc_groups);
+    if (threadIdx.x == 0)   // IEND (the stored encoder's first kernel writes it: there the file's length is known up front)
+        for (int k = 0; k < 12; ++k) J.out[L.data_at + data_len + 4ull + k] = L.tail[k];
 }
 
 // ---- deflate-compressed files: sizes and the launch sequence ----
@@ -1266,7 +994,7 @@ hipError_t launch_png_encode(const uint8_t* pixels, int W, int H, int C, int pla
 
 // A batch of up to three images (a frame's three PNGs), every kernel launched once for all of them.  outs[i]: png_deflate_room_bytes(...)
 // bytes (the file), scratches[i]: png_deflate_scratch_bytes(...) bytes, both 16-byte aligned; the files' lengths go to out_lens[i] (device
-// memory; entries may be null).  Six launches per batch, no memset, no global atomics.
+// memory; entries may be null).  Seven launches per batch, no memset, no global atomics.
 hipError_t launch_png_encode_deflate_batch(int n, const uint8_t* const* pixels, const int* Ws, const int* Hs, const int* Cs, const int* planars,
                                            uint8_t* const* outs, uint8_t* const* scratches, unsigned long long* const* out_lens, hipStream_t stream) {
     if (n < 1 || n > kMaxBatch) return hipErrorInvalidValue;
@@ -1307,36 +1035,87 @@ hipError_t launch_png_encode_deflate(const uint8_t* pixels, int W, int H, int C,
     return launch_png_encode_deflate_batch(1, &pixels, &W, &H, &C, &planar, &out, &scratch, &out_len, stream);
 }
 
+// The two 8-bit images the reference makes with numpy / OpenCV before cv2.imwrite (scene_representation.py:429-438), one lane per
+// pixel: the turbo-coloured depth preview -- depth2img(depth, scale): uint8(clip(depth / scale, 0, 1) * 255) through the colour
+// table -- and the normal map, uint8((n + 1) / 2 * 255): the same fp32 operations in the same order, truncation.
+__global__ void __launch_bounds__(256) frame_previews_kernel(const float* __restrict__ depth, const float* __restrict__ normal /*[H,W,3]*/,
+                                                            float depth_scale, const uint8_t* __restrict__ lut /*[256,3]*/, size_t n_pixels,
+                                                            uint8_t* __restrict__ depth_rgb, uint8_t* __restrict__ normal_rgb,
+                                                            float* __restrict__ depth_copy /*the .npy plane: the depth map as it is*/) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_pixels) return;
+    const float depth_i = depth[i];
+    depth_copy[i] = depth_i;
+    const float d = fminf(fmaxf(depth_i / depth_scale, 0.0f), 1.0f) * 255.0f;
+    const uint32_t idx = (uint32_t)(int)d & 255u;
+    depth_rgb[3 * i + 0] = lut[3 * idx + 0];
+    depth_rgb[3 * i + 1] = lut[3 * idx + 1];
+    depth_rgb[3 * i + 2] = lut[3 * idx + 2];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float v = (normal[3 * i + c] + 1.0f) / 2.0f * 255.0f;
+        normal_rgb[3 * i + c] = (uint8_t)(int)fminf(fmaxf(v, 0.0f), 255.0f);
+    }
+}
+
+// One frame's four files (gsr.h: gsr_frame_files): quantise, colour, encode, copy -- ten launches queued by ONE host call.  work: 10 * W * H bytes.
+hipError_t launch_frame_files(const float* color, const float* alpha, const float* depth, const float* normal, float depth_scale,
+                              const uint8_t* turbo_lut, int W, int H, uint8_t* png_rgba, uint8_t* png_depth, uint8_t* png_normal,
+                              float* npy_plane, uint8_t* work, uint8_t* png_scratch, unsigned long long* png_lengths /*both null: stored PNGs; else
+                              scratch for the three compressed files and [3] lengths, device*/, hipStream_t stream) {
+    const size_t n = (size_t)W * H;
+    uint8_t* rgba8 = work;                 // planar [4,H,W]
+    uint8_t* depth_rgb = work + 4 * n;     // [H,W,3]
+    uint8_t* normal_rgb = work + 7 * n;    // [H,W,3]
+    hipError_t e = launch_pack_rgba8(color, alpha, rgba8, n, stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(frame_previews_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, depth, normal, depth_scale, turbo_lut, n,
+                       depth_rgb, normal_rgb, npy_plane);
+    const size_t sizes[3] = {png_file_bytes(W, H, 4), png_file_bytes(W, H, 3), png_file_bytes(W, H, 3)};
+    uint8_t* outs[3] = {png_rgba, png_depth, png_normal};
+    const uint8_t* srcs[3] = {rgba8, depth_rgb, normal_rgb};
+    for (int k = 0; k < 3; ++k)
+        if (sizes[k] == 0) return hipErrorInvalidValue;
+    if (png_lengths) {
+        const int Ws[3] = {W, W, W}, Hs[3] = {H, H, H}, Cs[3] = {4, 3, 3}, planars[3] = {1, 0, 0};
+        unsigned long long* lens[3] = {png_lengths, png_lengths + 1, png_lengths + 2};
+        const size_t s4 = png_deflate_scratch_bytes(W, H, 4), s3 = png_deflate_scratch_bytes(W, H, 3);
+        uint8_t* scratches[3] = {png_scratch, png_scratch + s4, png_scratch + s4 + s3};
+        return launch_png_encode_deflate_batch(3, srcs, Ws, Hs, Cs, planars, outs, scratches, lens, stream);
+    }
+    for (int k = 0; k < 3; ++k)
+        if ((e = launch_png_encode(srcs[k], W, H, k == 0 ? 4 : 3, k == 0 ? 1 : 0, outs[k], stream)) != hipSuccess) return e;
+    return hipSuccess;
+}
+
 } // namespace
 } // namespace gsr
 
 using gsr::fail;
 
+namespace {
+// What gsr_frame_files and gsr_frame_files_deflate check alike: the size, `required` (every pointer argument), the alignments and depth_scale.
+int frame_files_check(const char* who, int width, int height, float depth_scale, std::initializer_list<const void*> required,
+                             uintptr_t aligned16, uintptr_t aligned8, const char* alignment_rule) {
+    if (width <= 0 || height <= 0 || gsr::png_file_bytes(width, height, 4) == 0) return fail(GSR_ERR_INVALID_ARG, "bad image size %dx%d", width, height);
+    for (const void* p : required)
+        if (!p) return fail(GSR_ERR_INVALID_ARG, "null pointer");
+    if ((aligned16 & 15u) != 0 || (aligned8 & 7u) != 0) return fail(GSR_ERR_INVALID_ARG, "%s: %s", who, alignment_rule);
+    if (!(depth_scale > 0.0f)) return fail(GSR_ERR_INVALID_ARG, "%s: depth_scale must be positive", who);
+    return GSR_OK;
+}
+}  // namespace
+
 extern "C" {
-
-int gsr_resize_rgba8_bilinear(const uint8_t* src, int src_w, int src_h, uint8_t* dst, int dst_w, int dst_h, uint8_t* tmp, void* stream_) {
-    if (src_w <= 0 || src_h <= 0 || dst_w <= 0 || dst_h <= 0) return fail(GSR_ERR_INVALID_ARG, "bad image size %dx%d -> %dx%d", src_w, src_h, dst_w, dst_h);
-    if (!src || !dst || (!tmp && src_w != dst_w && src_h != dst_h)) return fail(GSR_ERR_INVALID_ARG, "null pointer");
-    GSR_HIP(gsr::launch_resize_rgba8_bilinear(src, src_w, src_h, dst, dst_w, dst_h, tmp, (hipStream_t)stream_));
-    return GSR_OK;
-}
-
-int gsr_resize_f32_nearest(const float* src, int src_w, int src_h, float* dst, int dst_w, int dst_h, void* stream_) {
-    if (src_w <= 0 || src_h <= 0 || dst_w <= 0 || dst_h <= 0) return fail(GSR_ERR_INVALID_ARG, "bad image size %dx%d -> %dx%d", src_w, src_h, dst_w, dst_h);
-    if (!src || !dst) return fail(GSR_ERR_INVALID_ARG, "null pointer");
-    GSR_HIP(gsr::launch_resize_f32_nearest(src, src_w, src_h, dst, dst_w, dst_h, (hipStream_t)stream_));
-    return GSR_OK;
-}
 
 int gsr_frame_files(const float* color, const float* alpha, const float* depth, const float* normal, float depth_scale, const uint8_t* turbo_lut,
                     int width, int height, uint8_t* png_rgba, uint8_t* png_depth_preview, uint8_t* png_normal, float* npy_plane, uint8_t* work,
                     void* stream_) {
-    if (width <= 0 || height <= 0 || gsr::png_file_bytes(width, height, 4) == 0) return fail(GSR_ERR_INVALID_ARG, "bad image size %dx%d", width, height);
-    if (!color || !alpha || !depth || !normal || !turbo_lut || !png_rgba || !png_depth_preview || !png_normal || !npy_plane || !work)
-        return fail(GSR_ERR_INVALID_ARG, "null pointer");
-    if (((reinterpret_cast<uintptr_t>(png_rgba) | reinterpret_cast<uintptr_t>(png_depth_preview) | reinterpret_cast<uintptr_t>(png_normal)) & 15u) != 0)
-        return fail(GSR_ERR_INVALID_ARG, "gsr_frame_files: the PNG buffers must be 16-byte aligned");
-    if (!(depth_scale > 0.0f)) return fail(GSR_ERR_INVALID_ARG, "gsr_frame_files: depth_scale must be positive");
+    const int rc = frame_files_check("gsr_frame_files", width, height, depth_scale,
+                                     {color, alpha, depth, normal, turbo_lut, png_rgba, png_depth_preview, png_normal, npy_plane, work},
+                                     reinterpret_cast<uintptr_t>(png_rgba) | reinterpret_cast<uintptr_t>(png_depth_preview) | reinterpret_cast<uintptr_t>(png_normal),
+                                     0, "the PNG buffers must be 16-byte aligned");
+    if (rc != GSR_OK) return rc;
     GSR_HIP(gsr::launch_frame_files(color, alpha, depth, normal, depth_scale, turbo_lut, width, height, png_rgba, png_depth_preview, png_normal,
                                     npy_plane, work, nullptr, nullptr, (hipStream_t)stream_));
     return GSR_OK;
@@ -1345,14 +1124,12 @@ int gsr_frame_files(const float* color, const float* alpha, const float* depth, 
 int gsr_frame_files_deflate(const float* color, const float* alpha, const float* depth, const float* normal, float depth_scale, const uint8_t* turbo_lut,
                             int width, int height, uint8_t* png_rgba, uint8_t* png_depth_preview, uint8_t* png_normal, float* npy_plane, uint8_t* work,
                             uint8_t* png_scratch, uint64_t* png_lengths, void* stream_) {
-    if (width <= 0 || height <= 0 || gsr::png_deflate_max_bytes(width, height, 4) == 0) return fail(GSR_ERR_INVALID_ARG, "bad image size %dx%d", width, height);
-    if (!color || !alpha || !depth || !normal || !turbo_lut || !png_rgba || !png_depth_preview || !png_normal || !npy_plane || !work || !png_scratch || !png_lengths)
-        return fail(GSR_ERR_INVALID_ARG, "null pointer");
-    if (((reinterpret_cast<uintptr_t>(png_rgba) | reinterpret_cast<uintptr_t>(png_depth_preview) | reinterpret_cast<uintptr_t>(png_normal) |
-          reinterpret_cast<uintptr_t>(png_scratch)) & 15u) != 0 ||
-        (reinterpret_cast<uintptr_t>(png_lengths) & 7u) != 0)
-        return fail(GSR_ERR_INVALID_ARG, "gsr_frame_files_deflate: the PNG buffers must be 16-byte aligned, the lengths 8-byte aligned");
-    if (!(depth_scale > 0.0f)) return fail(GSR_ERR_INVALID_ARG, "gsr_frame_files_deflate: depth_scale must be positive");
+    const int rc = frame_files_check("gsr_frame_files_deflate", width, height, depth_scale,
+                                     {color, alpha, depth, normal, turbo_lut, png_rgba, png_depth_preview, png_normal, npy_plane, work, png_scratch, png_lengths},
+                                     reinterpret_cast<uintptr_t>(png_rgba) | reinterpret_cast<uintptr_t>(png_depth_preview) | reinterpret_cast<uintptr_t>(png_normal) |
+                                         reinterpret_cast<uintptr_t>(png_scratch),
+                                     reinterpret_cast<uintptr_t>(png_lengths), "the PNG buffers must be 16-byte aligned, the lengths 8-byte aligned");
+    if (rc != GSR_OK) return rc;
     GSR_HIP(gsr::launch_frame_files(color, alpha, depth, normal, depth_scale, turbo_lut, width, height, png_rgba, png_depth_preview, png_normal,
                                     npy_plane, work, png_scratch, reinterpret_cast<unsigned long long*>(png_lengths), (hipStream_t)stream_));
     return GSR_OK;
@@ -1385,6 +1162,5 @@ int gsr_png_encode(const uint8_t* pixels, int width, int height, int channels, i
     GSR_HIP(gsr::launch_png_encode(pixels, width, height, channels, planar, out, (hipStream_t)stream_));
     return GSR_OK;
 }
-
 
 }  // extern "C"

@@ -214,15 +214,21 @@ def png_deflate_scratch(width: int, height: int, channels: int) -> int:
     return int(_lib.lib.gsr_png_deflate_scratch(int(width), int(height), int(channels)))
 
 
+def _gpu_image(who: str, image: torch.Tensor, planar: bool):
+    """The encoders' source check: ``(img, C, H, W)`` of a contiguous uint8 GPU image, interleaved or ``planar``."""
+    if not (image.is_cuda and image.dtype == torch.uint8 and image.dim() == 3):
+        raise ValueError(f"{who} expects a uint8 GPU tensor [H,W,C] or [C,H,W]")
+    img = image.contiguous()
+    C, H, W = (int(v) for v in (img.shape if planar else (img.shape[2], img.shape[0], img.shape[1])))
+    return img, C, H, W
+
+
 def encode_png_gpu_deflate_queued(image: torch.Tensor, planar: bool = False):
     """``encode_png_gpu_deflate`` without the host synchronisation: ``(out, length)`` -- the buffer the file is being written into
     (``png_deflate_room`` bytes) and a device ``int64[1]`` that will hold the file's length -- for callers that copy both out behind
     the kernels and look at them once their stream has drained."""
     from . import _lib
-    if not (image.is_cuda and image.dtype == torch.uint8 and image.dim() == 3):
-        raise ValueError("encode_png_gpu_deflate expects a uint8 GPU tensor [H,W,C] or [C,H,W]")
-    img = image.contiguous()
-    C, H, W = (int(v) for v in (img.shape if planar else (img.shape[2], img.shape[0], img.shape[1])))
+    img, C, H, W = _gpu_image("encode_png_gpu_deflate", image, planar)
     room = png_deflate_room(W, H, C)
     if room == 0:
         raise ValueError(f"a {W}x{H} image with {C} channels cannot be encoded")
@@ -239,22 +245,9 @@ def encode_png_gpu_deflate(image: torch.Tensor, planar: bool = False) -> torch.T
     """``encode_png_gpu`` with a compressed IDAT (``gsr_png_encode_deflate``: Paeth filter, run-length matches, one Huffman code per
     image built on the GPU).  The file's length depends on the image, so this convenience form reads it back (one host
     synchronisation); the frame writer keeps it on the device and copies it out with the file."""
-    from . import _lib
-    if not (image.is_cuda and image.dtype == torch.uint8 and image.dim() == 3):
-        raise ValueError("encode_png_gpu_deflate expects a uint8 GPU tensor [H,W,C] or [C,H,W]")
-    img = image.contiguous()
-    C, H, W = (int(v) for v in (img.shape if planar else (img.shape[2], img.shape[0], img.shape[1])))
-    room = png_deflate_room(W, H, C)
-    if room == 0:
-        raise ValueError(f"a {W}x{H} image with {C} channels cannot be encoded")
-    out = torch.empty(room, dtype=torch.uint8, device=img.device)
-    scratch = torch.empty(png_deflate_scratch(W, H, C), dtype=torch.uint8, device=img.device)
-    length = torch.zeros(1, dtype=torch.int64, device=img.device)
-    with torch.cuda.device(img.device):
-        _lib.call("gsr_png_encode_deflate", img.data_ptr(), W, H, C, 1 if planar else 0, out.data_ptr(), scratch.data_ptr(), length.data_ptr(),
-                  device=img.device)
+    out, length = encode_png_gpu_deflate_queued(image, planar)
     n = int(length.item())
-    assert 0 < n <= png_deflate_max_size(W, H, C), (n, png_deflate_max_size(W, H, C))
+    assert 0 < n <= out.numel(), (n, out.numel())   # (out: png_deflate_max_size bytes)
     return out[:n]
 
 
@@ -263,10 +256,7 @@ def encode_png_gpu(image: torch.Tensor, planar: bool = False, out: "torch.Tensor
     bytes of its PNG file, a uint8 GPU tensor (``gsr_png_encode``).  ``out``: a 16-byte aligned uint8 buffer of at least
     ``png_room(W, H, C)`` bytes to encode into (a slice of a staging buffer); the returned tensor is its first ``png_size`` bytes."""
     from . import _lib
-    if not (image.is_cuda and image.dtype == torch.uint8 and image.dim() == 3):
-        raise ValueError("encode_png_gpu expects a uint8 GPU tensor [H,W,C] or [C,H,W]")
-    img = image.contiguous()
-    C, H, W = (int(v) for v in (img.shape if planar else (img.shape[2], img.shape[0], img.shape[1])))
+    img, C, H, W = _gpu_image("encode_png_gpu", image, planar)
     n, room = png_size(W, H, C), png_room(W, H, C)
     if out is None:
         out = torch.empty(room, dtype=torch.uint8, device=img.device)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""The frame-file and compositor-input kernels on their own (gsr_frameio.hip): gsr_frame_files (three PNG encodes + previews + depth
+"""The frame-file and compositor-input kernels on their own (gsr_frameio.hip, gsr_resample.hip): gsr_frame_files (three PNG encodes + previews + depth
 copy), one gsr_png_encode, the two resizes and the composite from 2x layers, each timed with HIP events over many launches and priced
 against its algorithmic bytes.  Run under rocprofv3 --kernel-trace --stats for the per-kernel table (profiles/r05_frameio_kernel_stats.csv)."""
 import json
@@ -44,7 +44,7 @@ rgba = torch.stack([0.5 + 0.4 * torch.sin(xx * (0.011 + 0.003 * k) + yy * (0.007
 rgba = rgba.clamp(0, 1)
 u8 = pack_rgba8(rgba[:3], rgba[3:4])
 out = torch.empty(frame_io.png_room(W, H, 4), dtype=torch.uint8, device=dev)
-row("gsr_png_encode RGBA (memset + png_encode_kernel + png_finish_kernel)", timed(lambda: frame_io.encode_png_gpu(u8, planar=True, out=out)),
+row("gsr_png_encode RGBA (png_encode_kernel + png_crc_kernel + png_finish_kernel)", timed(lambda: frame_io.encode_png_gpu(u8, planar=True, out=out)),
     4 * W * H + frame_io.png_size(W, H, 4), "4 B/pixel in, the file (4 B/pixel + 1 B/row + 5 B/65535) out")
 result = {"render": rgba, "depth": torch.rand(H, W, device=dev, generator=g) * 5, "normal": torch.nn.functional.normalize(torch.randn(H, W, 3, device=dev, generator=g), dim=-1)}
 import tempfile

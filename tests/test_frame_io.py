@@ -310,6 +310,33 @@ def test_gpu_deflate_png_files_are_valid_and_decode_to_the_image(shape, planar):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("deflate", [False, True])
+def test_gpu_png_checksums_wherever_the_idat_ends_within_a_64_byte_chunk(deflate):
+    """The CRC kernels take the file in 64-byte chunks and shift the one ragged last piece by its own rule; the finish kernels add the
+    Adler-32's bytes behind it.  One-row RGB images of 1 .. 64 pixels: the stored IDAT's payload ends at file offset 52 + (1 + 3 W) (the
+    chunk, with its CRC, 4 bytes later), and 3 is invertible mod 64, so the end takes every residue mod 64 -- on a chunk boundary
+    (W = 25: 128), one byte behind one (W = 4: 65), one byte short of one (W = 46: 191), and for W <= 3 the whole message lies inside
+    the file's first chunk.  The compressed encoder sends noise this small as one stored block; where its IDATs ended is read from
+    the files and must cover the residues too."""
+    import struct
+    encode = frame_io.encode_png_gpu_deflate if deflate else frame_io.encode_png_gpu
+    residues = set()
+    for w in range(1, 65):
+        img = np.random.default_rng(131 + w + 3).integers(0, 256, (1, w, 3)).astype(np.uint8)
+        data = encode(torch.from_numpy(img).cuda()).cpu().numpy().tobytes()
+        try:
+            _check_png_file(data, img, paeth=deflate)
+        except Exception as e:
+            raise AssertionError(f"W = {w}, deflate = {deflate}: {e!r}") from e
+        (n,) = struct.unpack(">I", data[33:37])
+        assert data[37:41] == b"IDAT"
+        if not deflate:
+            assert 41 + n == 52 + (1 + 3 * w) and len(data) == 41 + n + 4 + 12
+        residues.add((41 + n) % 64)
+    assert residues == set(range(64))
+
+
+@pytest.mark.gpu
 def test_gpu_deflate_png_constant_images_and_size_against_pil():
     PIL = pytest.importorskip("PIL.Image")
     for value in (0, 255):
