@@ -182,6 +182,11 @@ SIGNATURES = {
     "gsr_field_backward": (_i, _field_inputs + [_p, _p, _p, _p, _p, _p, _sz, _p]),   # ... g_density g_opacities g_beta dx accum scratch scratch_bytes stream
     "gsr_level_surface": (_i, [_i64, _i, _i64, _i, _i, _p, _p, _p, _p, _p, _p, _p, _f,   # n K P S L origins dirs stds idx centers M strengths density_factor
                                _p, _array(_f, 8), _p, _p, _p, _p, _p, _p, _sz, _p]),     # range levels hit t points normals densities scratch scratch_bytes stream
+    "gsr_mesh_raster_plan_bytes": (_sz, [_i64, _i64, _i, _i]),         # F N H W
+    "gsr_mesh_raster_pair_bytes": (_sz, [_i64]),                       # pairs
+    "gsr_mesh_raster_count": (_i, [_i64, _i64, _p, _p, _p, _i, _i, _i, _p, _sz, ctypes.POINTER(_i64), _p]),   # F N face_verts first num H W cull plan plan_bytes pair_total stream
+    "gsr_mesh_raster": (_i, [_i64, _i64, _p, _p, _p, _p, _i, _i, _f, _i, _i, _i, _i,   # F N face_verts first num neighbour H W blur_radius K perspective clip cull
+                             _p, _sz, _i64, _p, _sz, _p, _p, _p, _p, _p]),             # plan plan_bytes pair_total pairs pair_bytes pix_to_face zbuf bary_coords dists stream
     "gsr_ssim_scratch_bytes": (_sz, [_i, _i, _i, _i]),                 # n c h w
     "gsr_ssim_forward": (_i, [_i, _i, _i, _i, _p, _p, _p, _i, _p, _p, _p, _sz, _p]),   # n c h w x y window11 per_image out coef_or_null scratch scratch_bytes stream
     "gsr_ssim_backward": (_i, [_i, _i, _i, _i, _p, _p, _p, _p, _i, _p, _p, _p]),       # n c h w x y coef window11 per_image grad_out grad_x stream

@@ -65,7 +65,17 @@ AutoVFX reaches the rasterizer through two imports (paths under the reference tr
     more than 32 samples, 8 levels or 64 neighbours run ``SuGaR.reference_compute_level_surface_points_from_camera_fast``, decided
     before ``torch.randperm`` is consumed.  torch and the library are imported at the first call.
 
-Items 2-12 are the rows of ``_TARGETS``, applied by ``_patch`` to every matching module, whether it was imported before
+13. a module named ``..._C`` that defines both ``rasterize_meshes`` and ``rasterize_meshes_backward`` (``pytorch3d._C``; this repository
+    ships no ``pytorch3d``, and its own ``diff_gaussian_rasterization._C`` and ``simple_knn._C`` define neither) gets its
+    ``rasterize_meshes`` replaced by ``autovfx_amd.meshraster.drop_in(<the original>)``: the HIP z-buffer for CUDA float32 faces at
+    ``blur_radius == 0`` with up to 16 faces per pixel that need no gradient (the ``MeshRasterizer`` of SuGaR's mesh extraction,
+    ``sugar_extractors/coarse_mesh.py:216-227``, ``sugar_model.py:1341``, ``:1568``, ``:1798``, ``:2541-2598``, ``metrics.py:283-290``), the
+    original for every other call.  pytorch3d's Python looks the operator up on ``_C`` at every call, so nothing is rebound, and its
+    ``clip_faces``, bin heuristics and ``convert_clipped_rasterization_to_original_faces`` run as they are.  The leaf name makes
+    the hook's loader wrapper pass every ``*._C`` imported after ``install()`` through (``torch._C`` among them): it delegates to the real
+    loader and the ``needs`` keep the patch off (tests/test_meshraster.py loads ``torch._C`` that way; other packages' ``_C`` are not tested).
+
+Items 2-13 are the rows of ``_TARGETS``, applied by ``_patch`` to every matching module, whether it was imported before
 ``install()`` or after (a ``sys.meta_path`` hook).  Each replaced attribute keeps the reference's original next to it as
 ``reference_<attr>`` on the module or class (``<module>.reference_render``, ``SceneRepresentation.reference_render_from_3DGS``, ...).
 ``uninstall()`` undoes every patch in reverse.
@@ -89,7 +99,7 @@ from typing import Callable, List, NamedTuple, Optional, Tuple
 
 _REPO_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _installed: Optional["_RendererHook"] = None
-patched_modules: List[str] = []          # names of the modules patched by items 2-7 and 10-12 (introspection / tests)
+patched_modules: List[str] = []          # names of the modules patched by items 2-7 and 10-13 (introspection / tests)
 patched_models: List[str] = []           # names of the modules whose ``GaussianModel.training_setup`` was wrapped (item 8)
 _strict = True                           # install(strict=...): may a failure to load the render path break the importing process?
 _gave_up = False                         # lenient mode: a replacement could not be loaded once; patch nothing more
@@ -252,6 +262,9 @@ _TARGETS = (
     _Target("sugar_model", "SuGaR", "compute_level_surface_points_from_camera_fast",
             _with_hip_sugar_method("compute_level_surface_points_from_camera_fast", "levelset", "the HIP level-surface ray march"),
             "the HIP level-surface ray march", needs=("get_covariance", "compute_density")),
+    # item 13: pytorch3d/_C, rasterize_meshes() under every MeshRasterizer (sugar_extractors/coarse_mesh.py:216-227); looked up at call time
+    _Target("_C", None, "rasterize_meshes", lambda original: _mark(_load("meshraster", "drop_in")(original)), "the HIP mesh rasterizer",
+            needs=("rasterize_meshes", "rasterize_meshes_backward")),
 )
 
 

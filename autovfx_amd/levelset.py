@@ -216,7 +216,8 @@ def _quaternion_apply(q, point):
 
 def drop_in_compute_level_surface_points_from_camera_fast(original: Callable) -> Callable:
     """``SuGaR.compute_level_surface_points_from_camera_fast``: ``:1742-1851`` as the reference performs them, through ``self`` and the
-    objects the caller handed in (the texture image, the splatted mesh, the caller's rasterizer, the depth fill, ``unproject_points``,
+    objects the caller handed in (the texture image, the splatted mesh, the caller's rasterizer -- pytorch3d's ``MeshRasterizer``, whose
+    ``_C.rasterize_meshes`` is ``autovfx_amd.meshraster``'s under ``install()`` --, the depth fill, ``unproject_points``,
     ``knn_idx``, the per-Gaussian standard deviation; the two pixel tables as ``torch.arange`` expressions of the same fp32 values),
     then one :func:`level_surface` call in place of ``:1853-1950`` and the reference's compaction by boolean indexing: the same nested
     dict, dtypes, order and keys.  Whether the call is the kernel's is decided before anything is consumed -- ``torch.randperm`` in

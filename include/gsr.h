@@ -42,7 +42,9 @@
 extern "C" {
 #endif
 
-/* Still 20: + the level-surface ray march of SuGaR's mesh extraction (gsr_level_surface).
+/* Still 20: + the triangle-mesh z-buffer of SuGaR's mesh extraction (gsr_mesh_raster_plan_bytes, gsr_mesh_raster_pair_bytes,
+ * gsr_mesh_raster_count, gsr_mesh_raster).
+ * Still 20: + the level-surface ray march of SuGaR's mesh extraction (gsr_level_surface).
  * Still 20: + SuGaR's density field (gsr_field_scratch_bytes, gsr_field_forward, gsr_field_backward).  They only add symbols
  * behind the existing ones, so the version a binding checks did not move.
  * 20: + K nearest neighbours with indices (gsr_knn_points_scratch_bytes, gsr_knn_points).
@@ -489,6 +491,40 @@ GSR_API int gsr_level_surface(int64_t n, int K, int64_t P, int S, int L, const f
                               const int64_t* idx, const float* centers, const float* M, const float* strengths, float density_factor,
                               const float* range, const float* levels, uint8_t* hit, float* t, float* points, float* normals,
                               float* densities, void* scratch, size_t scratch_bytes, void* stream);
+
+/* A z-buffer over triangle meshes: the forward of pytorch3d's rasterize_meshes at blur_radius == 0, as SuGaR's MeshRasterizer calls it
+ * (sugar_extractors/coarse_mesh.py:216-227, sugar_model.py:1341, :1568, :1798, :2541-2598, metrics.py:283-290) -- added under ABI 20.
+ * face_verts [F,3,3] fp32 (x, y in NDC with +x left and +y up, z the view depth; finite), mesh_to_face_first_idx [N], num_faces_per_mesh [N]
+ * and clipped_faces_neighbor_idx [F] int64; a face belongs to the lowest mesh n with first[n] <= f < first[n] + num[n] and lands only in
+ * image n.  Outputs, every element written: pix_to_face [N,H,W,K] int64 (the packed face index), zbuf [N,H,W,K], bary_coords [N,H,W,K,3],
+ * dists [N,H,W,K] fp32; an empty slot holds -1 in all four.  The arithmetic, in fp32 and in a fixed operation order, is the contract in
+ * the module docstring of autovfx_amd/meshraster.py: per pixel the K kept faces smallest in (pz, face index) order,
+ * whatever order the faces are visited in; no face is ever dropped for the length of a tile's list (pytorch3d's bin_size and
+ * max_faces_per_bin have no counterpart here).
+ * Two steps, because the lists' total length is only known on the device:
+ *   gsr_mesh_raster_count  culls, bins every face's bounding box into 16x16 tiles and sums the tiles' list lengths.  It blocks the host
+ *                          once, to hand *pair_total (HOST memory) back: the only host read of a call.  plan: gsr_mesh_raster_plan_bytes
+ *                          bytes of device memory, 256-byte aligned, any content; the count leaves the binning in it.
+ *   gsr_mesh_raster        fills the lists and blends.  It takes the same sizes, inputs, cull_backfaces and stream as the count that wrote
+ *                          `plan`, that count's pair_total, and pairs: gsr_mesh_raster_pair_bytes(pair_total) bytes, 256-byte aligned, any
+ *                          content.  No host synchronisation, no allocation; integer atomics only (list lengths and cursors).  It
+ *                          leaves `plan` as it found it: one count serves any number of raster calls (another K, other flags but
+ *                          cull_backfaces), one after the other on the stream.
+ * F == 0 needs no count: gsr_mesh_raster then writes -1 everywhere and reads no input, plan or pairs (all may be NULL); N == 0 returns 0
+ * and touches nothing.  The sizing functions return 0 for sizes the calls refuse.  Refused (GSR_ERR_INVALID_ARG, nothing launched, no
+ * device needed): K outside 1..16, blur_radius != 0, H or W outside 1..16384, a negative count, F >= 2^31 - 1, N times the tiles of an
+ * image >= 2^31 - 1, pair_total >= 2^31, a null pointer, misaligned pointers (floats 4 bytes, int64 8, plan and pairs 256), too little
+ * scratch. */
+GSR_API size_t gsr_mesh_raster_plan_bytes(int64_t F, int64_t N, int H, int W);
+GSR_API size_t gsr_mesh_raster_pair_bytes(int64_t pairs);
+GSR_API int gsr_mesh_raster_count(int64_t F, int64_t N, const float* face_verts, const int64_t* mesh_to_face_first_idx,
+                                  const int64_t* num_faces_per_mesh, int H, int W, int cull_backfaces, void* plan, size_t plan_bytes,
+                                  int64_t* pair_total, void* stream);
+GSR_API int gsr_mesh_raster(int64_t F, int64_t N, const float* face_verts, const int64_t* mesh_to_face_first_idx,
+                            const int64_t* num_faces_per_mesh, const int64_t* clipped_faces_neighbor_idx, int H, int W, float blur_radius,
+                            int K, int perspective_correct, int clip_barycentric_coords, int cull_backfaces, void* plan,
+                            size_t plan_bytes, int64_t pair_total, void* pairs, size_t pair_bytes, int64_t* pix_to_face, float* zbuf,
+                            float* bary_coords, float* dists, void* stream);
 
 /* Structural similarity (the training loops' loss_utils.ssim, loss_utils.py:33-62, window 11, sigma 1.5) -- ABI 17.
  * x, y: [n,c,h,w] fp32, contiguous, device memory.  Per plane, zero-padded outside the image: mx = w*x, my = w*y, Exx = w*x^2,
