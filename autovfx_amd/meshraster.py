@@ -36,6 +36,15 @@ Otherwise ``w = (edge(p, v1, v2), edge(p, v2, v0), edge(p, v0, v1))``, each divi
 ``q = a + min(max(t, 0), 1) * u`` and it is ``|p - q|^2`` (``|e|^2 = e.x * e.x + e.y * e.y``).  With ``blur_radius == 0`` only ``inside`` pixels
 are kept; they carry ``zbuf = pz``, ``bary_coords = b``, ``dists = -dist``.
 
+**Overflow.**  Every finite input is admitted, and huge finite coordinates overflow the intermediates to infinities and, through
+``inf - inf`` and ``inf / inf``, to NaN.  Every ``min`` and ``max`` above is C's ``fminf`` / ``fmaxf`` (numpy's ``fmin`` / ``fmax``, not its
+``minimum`` / ``maximum``): of a NaN and a number the number is returned, a NaN operand loses, so ``max(NaN, eps) = eps``,
+``max(0, min(1, NaN)) = 1`` and ``min(max(NaN, 0), 1) = 0``.  Every comparison with a NaN is false: a NaN ``w`` is not inside, a NaN ``pz`` is
+not ``< 0`` (the face counts as kept for a neighbour that names it) but orders before nothing, so such a face is never listed; a kept face
+with ``pz = +inf`` is listed behind every finite depth, the lower index first.  A face with a NaN or infinite coordinate is outside the
+contract: what that face itself receives, and whether it is listed, is unspecified; the code only promises that it finishes and that the
+finite faces of every pixel come out among each other as if it were not there, as far as the K slots it may occupy leave room.
+
 **Per pixel.**  The K kept faces smallest in ``(pz, packed face index)`` order, compared lexicographically, ascending: the result does not
 depend on the order the faces are visited in.  pytorch3d leaves equal depths in whatever order its bins produced; here the lower face
 index comes first (difference 1).  The neighbour rule: a kept face f with ``g = clipped_faces_neighbor_idx[f] >= 0``, g another face of the
@@ -222,7 +231,7 @@ def _segment_dist2(px, py, ax, ay, bx, by):
     ex, ey = px - bx, py - by
     at_end = ex * ex + ey * ey
     t = (dx * (px - ax) + dy * (py - ay)) / l2
-    tt = np.minimum(np.maximum(t, _F(0.0)), _F(1.0))
+    tt = np.fmin(np.fmax(t, _F(0.0)), _F(1.0))
     qx, qy = ax + tt * dx, ay + tt * dy
     ex, ey = px - qx, py - qy
     return np.where(l2 <= EPS, at_end, ex * ex + ey * ey)
@@ -253,7 +262,7 @@ def rasterize_face_verts_host(face_verts, mesh_to_face_first_idx, num_faces_per_
     x0, y0, z0, x1, y1, z1, x2, y2, z2 = (fv[:, i, j] for i in range(3) for j in range(3))
     with np.errstate(all="ignore"):
         area = _edge(x0, y0, x1, y1, x2, y2)
-        culled = (np.maximum(z0, np.maximum(z1, z2)) < EPS) | (np.abs(area) <= EPS)
+        culled = (np.fmax(z0, np.fmax(z1, z2)) < EPS) | (np.abs(area) <= EPS)
         if cull_backfaces:
             culled |= area < _F(0.0)
     mesh_of = np.full(F, -1, np.int64)
@@ -271,8 +280,8 @@ def rasterize_face_verts_host(face_verts, mesh_to_face_first_idx, num_faces_per_
         ax, ay, az, bx, by, bz, cx, cy, cz = (v[idx][None, :] for v in (x0, y0, z0, x1, y1, z1, x2, y2, z2))
         with np.errstate(all="ignore"):
             denom = _edge(cx, cy, ax, ay, bx, by) + EPS
-        xmin, xmax = np.minimum(ax, np.minimum(bx, cx)), np.maximum(ax, np.maximum(bx, cx))
-        ymin, ymax = np.minimum(ay, np.minimum(by, cy)), np.maximum(ay, np.maximum(by, cy))
+        xmin, xmax = np.fmin(ax, np.fmin(bx, cx)), np.fmax(ax, np.fmax(bx, cx))
+        ymin, ymax = np.fmin(ay, np.fmin(by, cy)), np.fmax(ay, np.fmax(by, cy))
         # the neighbour of every listed face as a column of this mesh's list (-1: none, culled, itself or in another mesh)
         column_of = np.full(F, -1, np.int64)
         column_of[idx] = np.arange(idx.size)
@@ -293,22 +302,22 @@ def rasterize_face_verts_host(face_verts, mesh_to_face_first_idx, num_faces_per_
                 b0, b1, b2 = w0, w1, w2
                 if perspective_correct:
                     t0, t1, t2 = (w0 * bz) * cz, (az * w1) * cz, (az * bz) * w2
-                    d = np.maximum((t0 + t1) + t2, EPS)
+                    d = np.fmax((t0 + t1) + t2, EPS)
                     b0, b1, b2 = t0 / d, t1 / d, t2 / d
                 if clip_barycentric_coords:
-                    c0, c1, c2 = (np.maximum(_F(0.0), np.minimum(_F(1.0), v)) for v in (b0, b1, b2))
-                    d = np.maximum((c0 + c1) + c2, BARY_CLIP_EPS)
+                    c0, c1, c2 = (np.fmax(_F(0.0), np.fmin(_F(1.0), v)) for v in (b0, b1, b2))
+                    d = np.fmax((c0 + c1) + c2, BARY_CLIP_EPS)
                     b0, b1, b2 = c0 / d, c1 / d, c2 / d
                 pz = (b0 * az + b1 * bz) + b2 * cz
                 kept = ~outside & inside & ~(pz < _F(0.0))
-                dist = np.minimum(_segment_dist2(px, py, ax, ay, bx, by),
-                                  np.minimum(_segment_dist2(px, py, ax, ay, cx, cy), _segment_dist2(px, py, bx, by, cx, cy)))
-            final = kept.copy()
+                dist = np.fmin(_segment_dist2(px, py, ax, ay, bx, by),
+                               np.fmin(_segment_dist2(px, py, ax, ay, cx, cy), _segment_dist2(px, py, bx, by, cx, cy)))
+            final = kept & ~np.isnan(pz)                             # a NaN depth is nearer than nothing: never listed (a neighbour still sees it kept)
             if has_g.size:                                           # the neighbour rule, on the faces that name a listed one
                 theirs, mine = dist[:, g_col[has_g]], dist[:, has_g]
                 gives_way = kept[:, g_col[has_g]] & ((theirs < mine) | ((theirs == mine) & (idx[g_col[has_g]] < idx[has_g])[None, :]))
                 final[:, has_g] &= ~gives_way
-            key = np.where(final, pz, _F(np.inf))
+            key = np.where(final, pz, _F(np.nan))                    # numpy sorts NaN behind +inf: a listed face of infinite depth comes before the unlisted
             order = np.argsort(key, axis=1, kind="stable")[:, :K]   # the faces are in index order: equal depths go by the lower index
             k = order.shape[1]
             found = np.take_along_axis(final, order, axis=1)

@@ -5,6 +5,7 @@ from __future__ import annotations
 
 import ctypes
 import importlib
+import os
 import subprocess
 import sys
 import types
@@ -38,6 +39,90 @@ def test_host_restatement_against_truth(index, perspective):
     assert ez <= cases.BAR_Z and eb <= cases.BAR_BARY and ed <= cases.BAR_DIST
     listed = (want[0] >= 0).sum(-1)
     assert listed.mean() > 3 and listed.max() >= 9                  # the scenes are deep enough to exercise the K slots
+
+
+@pytest.mark.parametrize("index", range(len(cases.NEAR_PLANE)))
+def test_near_plane_restatement_against_truth(index):
+    """Depths at and behind the camera plane, with the flags off and with ``perspective_correct`` and ``clip_barycentric_coords``: the
+    truth's faces on every decided pixel and 4 x the restatement's own measured error, as on the scenes.  With ``perspective_correct`` and
+    no clip only ``pix_to_face`` is compared: the corrected barycentrics are a quotient by a denominator that passes through zero inside
+    such a face, and where it is tiny the fp32 quotient is far from the float64 one (z differs by up to 87, the barycentrics by 1061, on
+    these two scenes) -- no bar would say anything there; the clip bounds the barycentrics again."""
+    H, W, _n, _seed = cases.NEAR_PLANE[index]
+    for flags in ((False, False), (True, True)):
+        fv, want = cases.near_plane_truth(index, *flags)
+        got = rasterize_face_verts_host(fv, *one_mesh(fv), (H, W), 0.0, 10, perspective_correct=flags[0], clip_barycentric_coords=flags[1])
+        ez, eb, ed = cases.against_truth(got, want, f"near plane {index}, perspective and clip {flags}")
+        assert ez <= cases.NEAR_BAR_Z and eb <= cases.NEAR_BAR_BARY and ed <= cases.NEAR_BAR_DIST
+        assert (got[1][got[0] >= 0] < 0.05).any()
+    plain = rasterize_face_verts_host(fv, *one_mesh(fv), (H, W), 0.0, 10)
+    fv, want = cases.near_plane_truth(index, True, False)
+    got = rasterize_face_verts_host(fv, *one_mesh(fv), (H, W), 0.0, 10, perspective_correct=True)
+    decided = ~want[4]
+    assert want[4].mean() <= cases.MAX_UNDECIDED and np.array_equal(got[0][decided], want[0][decided])
+    assert (got[0] >= 0).sum() < (plain[0] >= 0).sum()               # depths that only the correction turns negative
+
+
+def test_huge_depths_are_pinned():
+    """Finite depths times 1e19 overflow ``(w0 * z1) * z2``: the sum of the three is ``inf`` or NaN, ``max(NaN, eps)`` must be ``eps`` and
+    ``max(0, min(1, NaN))`` must be 1, as C's ``fmaxf`` / ``fminf`` give them (with numpy's ``maximum`` / ``minimum`` the NaN spreads and all
+    four outputs differ).  The fixture is what the kernels give on an MI355X."""
+    golden = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "meshraster", "huge_z_37x53.npz"))
+    H, W, n_faces, seed = cases.SCENES[0]
+    fv = cases.scaled_scene(n_faces, seed, z_scale=1e19)
+    assert np.array_equal(fv, golden["face_verts"]) and np.isfinite(fv).all()
+    got = rasterize_face_verts_host(fv, *one_mesh(fv), (H, W), 0.0, 10, perspective_correct=True, clip_barycentric_coords=True)
+    assert (got[0] >= 0).sum() > 5000 and not np.isnan(got[1]).any()
+    for name, g in zip(("pix_to_face", "zbuf", "bary_coords", "dists"), got):
+        w = golden[name].astype(g.dtype)
+        assert g.shape == w.shape and np.array_equal(g.view(np.int32) if g.dtype == F else g, w.view(np.int32) if w.dtype == F else w), name
+
+
+def test_nan_loses_every_min_and_max_and_orders_before_nothing():
+    """By hand, on one pixel (4 x 4, pixel (1, 1) at (0.25, 0.25)): three faces around it whose perspective products overflow."""
+    big = np.float32(3e38)
+    t = tri_around(0.25, 0.25, r=0.3)
+    over, near = t.copy(), t.copy()
+    over[:, 2] = big                                                  # (w * z) * z = inf for every w: inf / inf = NaN in all three
+    near[:, 2] = 1.0
+    # perspective_correct alone: b is NaN, pz is NaN, which is not < 0 and not less than anything: never listed
+    face, z, _b, _d = _host([over, near], (4, 4), K=2, perspective_correct=True)
+    assert list(face[0, 1, 1]) == [1, -1] and list(z[0, 1, 1]) == [1.0, -1.0]
+    # with the clip: max(0, min(1, NaN)) = 1 three times, b = 1 / 3 each, pz = 3e38 or its neighbour
+    face, z, b, _d = _host([over, near], (4, 4), K=2, perspective_correct=True, clip_barycentric_coords=True)
+    third = np.float32(1.0) / np.float32(3.0)
+    assert list(face[0, 1, 1]) == [1, 0] and np.array_equal(b[0, 1, 1, 1], [third] * 3)
+    assert z[0, 1, 1, 1] == (third * big + third * big) + third * big
+
+
+def test_an_infinite_depth_is_listed_last():
+    """Depths at the largest finite float32: ``(b0 * z0 + b1 * z1) + b2 * z2`` rounds to ``inf`` on some pixels.  Such a face is kept: it comes
+    behind every finite depth, the lower index first, and before the empty slots."""
+    H, W, n_faces, seed = cases.SCENES[0]
+    fv = cases.scaled_scene(n_faces, seed, z_scale=1e38)
+    assert np.isfinite(fv).all() and (fv[:, :, 2] == np.finfo(F).max).any()
+    face, z, _b, _d = rasterize_face_verts_host(fv, *one_mesh(fv), (H, W), 0.0, 10)
+    listed = face >= 0
+    assert np.isinf(z[listed]).sum() > 100 and (~np.isinf(z[listed])).sum() > 100 and not np.isnan(z).any()
+    assert (listed[..., :-1] >= listed[..., 1:]).all()                                    # no empty slot before a filled one
+    pair = listed[..., 1:]
+    assert (z[..., :-1][pair] <= z[..., 1:][pair]).all()
+    assert (face[..., :-1][pair] < face[..., 1:][pair])[z[..., :-1][pair] == z[..., 1:][pair]].all()
+    assert (np.isinf(z[..., :-1]) & pair & ~np.isinf(z[..., 1:])).sum() == 0
+
+
+@pytest.mark.parametrize("K", [4, 16])
+def test_non_finite_vertices_leave_the_finite_faces_alone(K):
+    """Outside the contract (what such a face receives is unspecified), but the finite faces of a pixel keep their order and their values."""
+    H, W, n_faces, seed = cases.SCENES[0]
+    broken, finite_only, is_broken = cases.non_finite_scene(n_faces, seed)
+    assert 40 <= is_broken.sum() and all(np.isnan(broken[..., i]).any() and np.isinf(broken[..., i]).any() for i in range(3))
+    held = 0
+    for flags in ((False, False, False), (True, False, False), (True, True, False)):
+        got = rasterize_face_verts_host(broken, *one_mesh(broken), (H, W), 0.0, K, None, None, *flags)
+        want = rasterize_face_verts_host(finite_only, *one_mesh(finite_only), (H, W), 0.0, K, None, None, *flags)
+        held += cases.finite_faces_are_a_prefix(got, want, is_broken, f"K={K}, flags={flags}")
+    assert held > 0                                                  # an infinite depth is listed last, where slots are to spare
 
 
 def test_host_restatement_is_chunk_independent():
