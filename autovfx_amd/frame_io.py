@@ -7,7 +7,8 @@
 
 * ``depth/<name>.png``   the turbo-coloured preview of the depth map the reference's depth video is made of
   (``depth2img(depth, scale=3.0)``, ``sugar/gaussian_splatting/render.py:45-49``: ``uint8(clip(depth / 3, 0, 1) * 255)``
-  through ``cv2.COLORMAP_TURBO``).
+  through ``cv2.COLORMAP_TURBO``).  A NaN depth is outside what numpy defines (``uint8(NaN)``); the GPU writer's kernel clips it
+  to 0 (``fmaxf(NaN, 0)``), so it takes table entry 0, the colour of depth 0 (pinned in ``tests/test_png_deflate_gpu.py``).
 
 Two ways to the files.  ``FrameWriter`` / ``write_frame_outputs``: the frame crosses to the host as pixels and a pool of host
 threads deflates it (zlib level 3) -- small files, 6.8 ms of host time per 960x540 frame even on 32 threads.  ``GpuFrameWriter``:

@@ -149,18 +149,7 @@ def test_render_trajectory_script_with_moving_objects(tmp_path):
 
 # ---- file images built on the GPU (gsr_png_encode, GpuFrameWriter) -----------------------------------------------------
 
-def _paeth_stream(img: np.ndarray) -> np.ndarray:
-    """The scanline stream of ``img`` with every row Paeth-filtered (PNG filter type 4), [H, 1 + W*C] uint8."""
-    H, W, C = img.shape
-    raw = img.reshape(H, W * C).astype(np.int16)
-    left, up, ul = np.zeros_like(raw), np.zeros_like(raw), np.zeros_like(raw)
-    left[:, C:] = raw[:, :-C]
-    up[1:] = raw[:-1]
-    ul[1:, C:] = raw[:-1, :-C]
-    p = left + up - ul
-    pa, pb, pc = np.abs(p - left), np.abs(p - up), np.abs(p - ul)
-    pred = np.where((pa <= pb) & (pa <= pc), left, np.where(pb <= pc, up, ul))
-    return np.concatenate((np.full((H, 1), 4, np.uint8), ((raw - pred) & 255).astype(np.uint8)), axis=1)
+from png_deflate_cases import paeth_stream as _paeth_stream   # (the host restatement of the deflate encoder owns it)
 
 
 def _check_png_file(data: bytes, img: np.ndarray, paeth: bool = False):
@@ -424,3 +413,11 @@ def test_gpu_deflate_png_length_limits_a_skewed_code():
     data = frame_io.encode_png_gpu_deflate(torch.from_numpy(img).cuda()).cpu().numpy().tobytes()
     _check_png_file(data, img, paeth=True)
     assert len(data) < img.size                                                     # (about two bits per byte)
+    # that the limit was needed and the blocks were dynamic, from the host restatement of the encoder (the shuffle leaves runs of the
+    # frequent values, so matches hold a share of the histogram: what the code was is the restatement's to say), and the file is its file
+    import png_deflate_cases
+    want, trace = png_deflate_cases.encode(img)
+    types = [b["type"] for b in trace["blocks"]]
+    assert types == ["dynamic"] * 16 + ["stored"]              # (the 17th block is the stream's last 62 bytes: less than a header)
+    assert max(trace["depths"]) > 15 and trace["limit_picks"] and int(trace["lengths"].max()) == 15
+    assert png_deflate_cases.first_difference(data, want) is None, png_deflate_cases.first_difference(data, want)
