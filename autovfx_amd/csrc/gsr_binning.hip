@@ -27,7 +27,8 @@
 //                         the expansion walks the compacted list, not the depth order).
 //   expand_kernel       : one workgroup per kPairTile = 2048 PAIRS (fewer when few are left), 8 consecutive pairs per lane: every workgroup
 //                         does the same work whatever the splat sizes, and writes one contiguous 16 KB slice of the
-//                         two pair arrays with 16-byte stores.
+//                         two pair arrays with 16-byte stores.  The offsets and records of the splats that own the pairs
+//                         are staged in LDS with coalesced loads, 768 items at a time; the walk reads LDS only.
 //   tile_ranges_kernel  : one binary search per tile over the sorted tile keys (a list ends where the next tile's begins).
 // Every pair count past the first host read-back lives in device memory (SlabInfo::pairs): launches are sized for an
 // upper bound and surplus workgroups leave at once.
@@ -55,8 +56,7 @@ static_assert(kDupTile == 1024, "256 lanes x 4 consecutive positions");
 
 // Sum over the workgroup's 256 lanes, returned to every lane; scratch is 4 words of LDS.
 __device__ __forceinline__ uint32_t block_sum_256(uint32_t v, uint32_t* scratch) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d);
+    v = wave_sum(v);
     if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
     __syncthreads();
     const uint32_t total = scratch[0] + scratch[1] + scratch[2] + scratch[3];
@@ -67,12 +67,7 @@ __device__ __forceinline__ uint32_t block_sum_256(uint32_t v, uint32_t* scratch)
 // Inclusive scan of one value per lane over the 256 lanes; returns the exclusive prefix, *total = sum of all.
 __device__ __forceinline__ uint32_t block_exclusive_256(uint32_t mine, uint32_t* s_wave, uint32_t* total) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t incl = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = (uint32_t)__shfl_up((int)incl, d);
-        if (lane >= d) incl += o;
-    }
+    const uint32_t incl = wave_inclusive_scan(mine);
     if (lane == 63) s_wave[wave] = incl;
     __syncthreads();
     uint32_t before = incl - mine, all = 0;
@@ -293,13 +288,8 @@ __global__ void __launch_bounds__(256, 7) bin_gather_kernel(BinningArrays a) {
                 }
             }
             const uint32_t rows = walk ? h : 0u;
-            uint32_t rincl = rows;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t o = (uint32_t)__shfl_up((int)rincl, d);
-                if (lane >= d) rincl += o;
-            }
-            const uint32_t total = (uint32_t)__shfl((int)rincl, 63);
+            const uint32_t rincl = wave_inclusive_scan(rows);
+            const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)rincl, 63);
             if (total != 0u) {   // wave-uniform
                 if (walk) {
                     const float4* rr = reinterpret_cast<const float4*>(a.raster + gid[j]);
@@ -519,13 +509,8 @@ __global__ void __launch_bounds__(256, 7) slab_recount_kernel(BinningArrays a, i
         for (int j = 0; j < 4; ++j) {
             const bool large = k0 + j < end && rec[j].y != 0u && !rec_is_masked(rec[j].y);
             const uint32_t rows = large ? rec[j].y >> 16 : 0u;
-            uint32_t rincl = rows;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t o = (uint32_t)__shfl_up((int)rincl, d);
-                if (lane >= d) rincl += o;
-            }
-            const uint32_t total = (uint32_t)__shfl((int)rincl, 63);
+            const uint32_t rincl = wave_inclusive_scan(rows);
+            const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)rincl, 63);
             if (total == 0u) continue;   // wave-uniform
             s_geo[wave][lane] = rec[j];
             s_rows[wave][lane] = rincl;
@@ -641,11 +626,19 @@ __global__ void __launch_bounds__(256) slab_compact_kernel(BinningArrays a, int 
 // ascending inclusive pair offsets: for slab 0 the positions of the depth order themselves (global POINT_OFFSETS); for
 // a later slab the compacted list of the positions that still have a live pair (slab_compact_kernel).
 // ------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) expand_kernel(BinningArrays a, int slab, uint32_t* __restrict__ tile_keys,
+__global__ void __launch_bounds__(256, 7) expand_kernel(BinningArrays a, int slab, uint32_t* __restrict__ tile_keys,
                                                      uint32_t* __restrict__ point_list, uint32_t* __restrict__ first_counts,
                                                      uint32_t count_stride, uint32_t digit_mask) {
-    constexpr int kBatch = 2048;            // items whose offsets are parked in LDS at a time
-    __shared__ uint32_t s_incl[kBatch + 1]; // s_incl[0] = pairs before the batch's first item
+    // Items are staged in LDS a chunk at a time: their offsets and, fetched in the same cooperative pass with coalesced
+    // loads, their records (the 16 bytes of sorted_bins and the Gaussian id), so that the walk below never waits for global
+    // memory -- with per-lane loads of the record at the first owner and again at every change of owner, two or three
+    // dependent round trips per lane were two thirds of a workgroup's life.  18.4 KB: with the finished-tile rows of a
+    // later slab (1 KB at 1920 x 1080) seven workgroups still share a CU, which keeps every workgroup of a C3 launch resident.
+    constexpr int kChunk = 768;
+    constexpr int kChunkLoads = kChunk / 256;           // items per lane
+    __shared__ uint32_t s_incl[kChunk + 1]; // s_incl[i] = pairs before the chunk's item i (= inclusive offset of the item before it)
+    __shared__ uint4 s_rec[kChunk];         // the items' records ...
+    __shared__ uint32_t s_gid[kChunk];      // ... and Gaussians: staged for the items that start before this workgroup's last pair
     __shared__ uint32_t s_scratch[4];
     extern __shared__ uint32_t s_done[];   // grid_y * row_words words (sized at the launch; none for the first slab's expansion)
     const int tid = threadIdx.x;
@@ -681,7 +674,12 @@ __global__ void __launch_bounds__(256) expand_kernel(BinningArrays a, int slab, 
     // tiles first (their last offsets), then inside the tile that straddles p_begin
     const int tiles = (V + kDupTile - 1) / kDupTile;
     uint32_t n_le = 0;
-    for (int t = tid; t < tiles; t += 256) n_le += offsets[min((t + 1) * kDupTile, V) - 1] <= p_begin ? 1u : 0u;
+    // (slab 0: the offsets at the ends of whole tiles are also a contiguous array, left by bin_offsets_kernel)
+    const uint32_t* __restrict__ tile_ends = (!compacted && first == 0u) ? a.tile_totals + a.tiles_p : nullptr;
+    for (int t = tid; t < tiles; t += 256) {
+        const uint32_t tile_end = (tile_ends != nullptr && (t + 1) * kDupTile <= V) ? tile_ends[t] : offsets[min((t + 1) * kDupTile, V) - 1];
+        n_le += tile_end <= p_begin ? 1u : 0u;
+    }
     const int tile0 = (int)block_sum_256(n_le, s_scratch);  // tiles that end at or before p_begin
     n_le = 0;
     {
@@ -691,43 +689,56 @@ __global__ void __launch_bounds__(256) expand_kernel(BinningArrays a, int slab, 
             if (k0 + j < V) n_le += offsets[k0 + j] <= p_begin ? 1u : 0u;
     }
     int s0 = tile0 * kDupTile + (int)block_sum_256(n_le, s_scratch);
-    auto position_of = [&](int item) -> uint32_t { return compacted ? cpos[item] : (uint32_t)item; };
     GSR_BTRACE(16384 + 8192 * slab + blockIdx.x, 2);
 
     const uint32_t my_begin = p_begin + per_lane * (uint32_t)tid;
     const uint32_t my_end = min(p_end, my_begin + per_lane);
     uint32_t keys[kPairsPerLane], ids[kPairsPerLane];
     while (s0 < V) {  // workgroup-uniform
-        for (int i = tid; i <= kBatch; i += 256) {
-            const int k = s0 - 1 + i;
-            s_incl[i] = k < 0 ? 0u : offsets[min(k, V - 1)];
+        uint32_t before[kChunkLoads], pos[kChunkLoads];
+#pragma unroll
+        for (int j = 0; j < kChunkLoads; ++j) {   // independent loads first
+            const int i = tid + 256 * j, k = s0 - 1 + i;
+            before[j] = k < 0 ? 0u : offsets[min(k, V - 1)];
+            pos[j] = (uint32_t)(s0 + i);          // item s0 + i <-> position first + (compacted ? cpos[item] : item)
+            if (compacted && s0 + i < V) pos[j] = cpos[s0 + i];
+        }
+        if (tid == 0) s_incl[kChunk] = offsets[min(s0 - 1 + kChunk, V - 1)];
+#pragma unroll
+        for (int j = 0; j < kChunkLoads; ++j) {
+            const int i = tid + 256 * j;
+            s_incl[i] = before[j];
+            if (s0 + i < V && before[j] < p_end) {   // the item starts before this workgroup's last pair
+                s_rec[i] = sorted_bins[pos[j]];
+                s_gid[i] = order[pos[j]];
+            }
         }
         __syncthreads();
         const uint32_t lo_pair = max(my_begin, s_incl[0]);
-        const uint32_t hi_pair = min(my_end, s_incl[kBatch]);
+        const uint32_t hi_pair = min(my_end, s_incl[kChunk]);
         if (lo_pair < hi_pair) {
-            int lo = 1, hi = kBatch;  // smallest i with s_incl[i] > lo_pair: the owner of this lane's first pair
+            int lo = 1, hi = kChunk;  // smallest i with s_incl[i] > lo_pair: the owner of this lane's first pair
 #pragma unroll
-            for (int step = 0; step < 11; ++step) {
+            for (int step = 0; step < 10; ++step) {   // (2^10 >= kChunk; once lo == hi nothing moves: s_incl[lo] > lo_pair)
                 const int mid = (lo + hi) >> 1;
                 if (s_incl[mid] > lo_pair) hi = mid; else lo = mid + 1;
             }
             int owner = lo;
             uint32_t owner_end = s_incl[owner];
             TileWalker w;
-            uint32_t pos = position_of(s0 + owner - 1);
-            w.start(sorted_bins[pos], lo_pair - s_incl[owner - 1], a.run_pool, a.run_incl, done, a.row_words);
-            uint32_t gid = order[pos];
+            w.start(s_rec[owner - 1], lo_pair - s_incl[owner - 1], a.run_pool, a.run_incl, done, a.row_words);
+            uint32_t gid = s_gid[owner - 1];
             if (a.listed != nullptr) a.listed[gid] = (uint8_t)(slab + 1);  // (several lanes may say so: same value)
+            uint32_t p0 = my_begin;
+            asm("" : "+v"(p0));   // (keeps my_begin + q from being held in a register each across the chunk loop: seven waves per SIMD need <= 72)
 #pragma unroll
             for (int q = 0; q < kPairsPerLane; ++q) {
-                const uint32_t p = my_begin + (uint32_t)q;
+                const uint32_t p = p0 + (uint32_t)q;
                 if (p >= lo_pair && p < hi_pair) {
                     if (p >= owner_end) {
                         do { owner_end = s_incl[++owner]; } while (p >= owner_end);  // splats without live tiles
-                        pos = position_of(s0 + owner - 1);
-                        w.start(sorted_bins[pos], 0u, a.run_pool, a.run_incl, done, a.row_words);
-                        gid = order[pos];
+                        w.start(s_rec[owner - 1], 0u, a.run_pool, a.run_incl, done, a.row_words);
+                        gid = s_gid[owner - 1];
                         if (a.listed != nullptr) a.listed[gid] = (uint8_t)(slab + 1);
                     }
                     keys[q] = w.next(grid_x);
@@ -735,17 +746,17 @@ __global__ void __launch_bounds__(256) expand_kernel(BinningArrays a, int slab, 
                 }
             }
         }
-        const bool finished = s_incl[kBatch] >= p_end;
+        const bool finished = s_incl[kChunk] >= p_end;
         __syncthreads();
         if (finished) break;
-        s0 += kBatch;
+        s0 += kChunk;
     }
     GSR_BTRACE(16384 + 8192 * slab + blockIdx.x, 3);
     if (first_counts != nullptr) {
         // The tile sort's first pass would read these keys back only to count their low digits per 4096-pair tile: the
         // workgroup that made them counts them itself (one launch less per slab), and the sort's first scan folds the two or
         // four workgroups of a tile.  Every one of the 256 digit rows is written (zeros above the mask): the scan reads all.
-        uint32_t* s_hist = s_incl;   // 4 x 256 words of the offsets' parking place (every lane is past its last read of it)
+        uint32_t* s_hist = reinterpret_cast<uint32_t*>(s_rec);   // 4 x 256 words of the records' parking place (every lane is past its last read of it)
         __syncthreads();
         for (int i = tid; i < 4 * 256; i += 256) s_hist[i] = 0u;
         __syncthreads();

@@ -50,19 +50,27 @@ __global__ void __launch_bounds__(256) preprocess_kernel(GaussianInputs in, Came
     const float* __restrict__ vm = cam.viewmatrix;
     const float* __restrict__ pm = cam.projmatrix;
 
+    // What crosses the divergent region below is what the wave-cooperative phases and the final stores consume, and
+    // nothing else: every other per-lane result (the mask's full-rectangle bits, the pair bound, the rows of a large
+    // splat) is a function of the tight rectangle in `bin` and is worked out once, after the region, by every lane.
     int radius_out = 0;
     uint32_t rect_area = 0;     // the reference's rectangle: what num_rendered counts
-    uint32_t live_bound = 0;    // upper bound of the pairs this splat will emit (exact for masked splats)
-    uint32_t big_rows = 0;      // tile rows of a splat too large for a mask
     bool violation = false;     // culled although the caller said nothing would be (prefiltered)
-    SplatBin bin = {0u, 0u, 0u, 0u};
+    uint32_t bin_xy0 = 0u, bin_wh = 0u;   // the tight rectangle of a splat that emits pairs (SplatBin::xy0, wh), else zeros
     uint32_t key = kCulledKey;
-    // what the tile-mask phase needs of a candidate (a visible splat whose tight rectangle has <= kMaskTiles tiles and
-    // at least 2 x 2 of them)
-    bool mask_candidate = false;
+    // rows of a mask candidate: a visible splat whose tight rectangle has <= kMaskTiles tiles and at least 2 x 2 of them.
+    // The rest of what the tile-mask phase needs of a candidate goes to LDS where it is known; the slots of the other
+    // lanes are never read (no (splat, row) item belongs to a splat without rows).
     uint32_t cand_rows = 0;
-    LiveRegion cand_region = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0};
-    float2 cand_centre = make_float2(0.f, 0.f);
+    // (Each of these lives in ONE register from here to its use: a constant that meets a computed value where branches
+    // join is otherwise materialised again on every way out of the four nested culling tests, a move per value and exit.)
+    asm("" : "+v"(radius_out), "+v"(rect_area), "+v"(bin_xy0), "+v"(bin_wh), "+v"(key), "+v"(cand_rows));
+    __shared__ float4 s_reg0[4][64];    // conic A, B, C, beta
+    __shared__ float4 s_reg1[4][64];    // half extents u, v, centre x, y
+    __shared__ uint2 s_place[4][64];    // first tile x | y << 16, rectangle width
+    __shared__ uint32_t s_incl[4][64];
+    __shared__ uint32_t s_mask[4][64][2];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 
     if (in_range) {
     if (out.ids != nullptr) out.ids[i] = (uint32_t)i;
@@ -175,27 +183,18 @@ __global__ void __launch_bounds__(256) preprocess_kernel(GaussianInputs in, Came
                 // one-tile rectangle: counted in num_rendered by the reference's scan, never emitted -- its slot in the
                 // reference's key array keeps whatever the allocation held.  Here it emits nothing.)
                 if (tarea != 0u && irad > 0) {
-                    bin.xy0 = (uint32_t)tr.x0 | ((uint32_t)tr.y0 << 16);
-                    bin.wh = tw | (th << 16);
-                    if (tarea <= kMaskTiles) {
-                        // part 2: one bit per tile, computed below by the whole wave (or all ones when culling is off)
-                        const unsigned long long all = tarea == 64u ? ~0ull : (1ull << tarea) - 1ull;
-                        bin.lo = (uint32_t)all; bin.hi = (uint32_t)(all >> 32);
-                        live_bound = tarea;
-                        // A tight rectangle one tile wide (or high) has no dead tile: it is the bounding box of the ellipse
-                        // {q <= beta}, so every tile row it spans contains the ellipse's extreme point of that side, and
-                        // with a single column that point lies in the row's only tile.  Only rectangles of at least
-                        // 2 x 2 tiles have corners to test (a third of C3's splats).
-                        if (in.tile_cull && tw >= 2u && th >= 2u && region.kind == 1) {   // (kind 0: nothing can be bounded)
-                            mask_candidate = true;
-                            cand_rows = th;
-                            cand_region = region;
-                            cand_centre = make_float2(px, py);
-                        }
-                    } else {  // too large for a mask: one run of live columns per tile row, worked out at gather time
-                        bin.lo = bin.hi = 0xFFFFFFFFu;
-                        live_bound = tarea;
-                        big_rows = th;
+                    bin_xy0 = (uint32_t)tr.x0 | ((uint32_t)tr.y0 << 16);
+                    bin_wh = tw | (th << 16);
+                    // A mask (tarea <= kMaskTiles) starts as all ones and is cut down below by the whole wave.
+                    // A tight rectangle one tile wide (or high) has no dead tile: it is the bounding box of the ellipse
+                    // {q <= beta}, so every tile row it spans contains the ellipse's extreme point of that side, and
+                    // with a single column that point lies in the row's only tile.  Only rectangles of at least
+                    // 2 x 2 tiles have corners to test (a third of C3's splats).
+                    if (in.tile_cull && tarea <= kMaskTiles && tw >= 2u && th >= 2u && region.kind == 1) {   // (kind 0: nothing can be bounded)
+                        cand_rows = th;
+                        s_reg0[wave][lane] = make_float4(region.A, region.B, region.C, region.beta);
+                        s_reg1[wave][lane] = make_float4(region.u_ext, region.v_ext, px, py);
+                        s_place[wave][lane] = make_uint2(bin_xy0, tw);
                     }
                     key = __float_as_uint(vz);
                     if (key == kCulledKey) key = kCulledKey - 1u;  // a NaN depth with an all-ones payload must not look culled
@@ -215,24 +214,17 @@ __global__ void __launch_bounds__(256) preprocess_kernel(GaussianInputs in, Came
     // whose inclusive row count first exceeds t (binary search over the counts parked in LDS), every lane computes one
     // run per iteration and ORs its bits into the splat's mask in LDS.  Iterations = rows of the wave's candidates / 64:
     // one, as a rule.
+    // every lane, once: the rest of the record and of the tallies from the tight rectangle
+    const uint32_t tiles = (bin_wh & 0xFFFFu) * (bin_wh >> 16);                // 0: emits nothing
+    const bool big = tiles > (uint32_t)kMaskTiles;                              // too large for a mask: one run of live columns per tile row, worked out at gather time
+    const uint32_t big_rows = big ? bin_wh >> 16 : 0u;
+    // a mask starts as all ones over the rectangle (and stays so when culling is off or the splat is no candidate)
+    unsigned long long payload = big ? ~0ull : tiles == 64u ? ~0ull : (1ull << tiles) - 1ull;
+    uint32_t live_bound = tiles;   // upper bound of the pairs this splat will emit (exact for masked splats)
     {
-        __shared__ float4 s_reg0[4][64];    // conic A, B, C, beta
-        __shared__ float4 s_reg1[4][64];    // half extents u, v, centre x, y
-        __shared__ uint2 s_place[4][64];    // first tile x | y << 16, rectangle width
-        __shared__ uint32_t s_incl[4][64];
-        __shared__ uint32_t s_mask[4][64][2];
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        uint32_t incl = cand_rows;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t o = (uint32_t)__shfl_up((int)incl, d);
-            if (lane >= d) incl += o;
-        }
-        const uint32_t total = (uint32_t)__shfl((int)incl, 63);
+        const uint32_t incl = wave_inclusive_scan(cand_rows);
+        const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
         if (total != 0u) {  // wave-uniform
-            s_reg0[wave][lane] = make_float4(cand_region.A, cand_region.B, cand_region.C, cand_region.beta);
-            s_reg1[wave][lane] = make_float4(cand_region.u_ext, cand_region.v_ext, cand_centre.x, cand_centre.y);
-            s_place[wave][lane] = make_uint2(bin.xy0, bin.wh & 0xFFFFu);
             s_incl[wave][lane] = incl;
             s_mask[wave][lane][0] = 0u;
             s_mask[wave][lane][1] = 0u;
@@ -265,13 +257,11 @@ __global__ void __launch_bounds__(256) preprocess_kernel(GaussianInputs in, Came
             }
             GSR_WAIT_LDS();
             __builtin_amdgcn_wave_barrier();
-            if (mask_candidate) {
-                const unsigned long long mask = ((unsigned long long)s_mask[wave][lane][0] | ((unsigned long long)s_mask[wave][lane][1] << 32)) &
-                                                ((unsigned long long)bin.lo | ((unsigned long long)bin.hi << 32));   // (inside the rectangle)
-                bin.lo = (uint32_t)mask; bin.hi = (uint32_t)(mask >> 32);
-                live_bound = (uint32_t)__popcll(mask);
-                if (mask == 0ull) {  // every tile is dead: the splat is listed nowhere (radii and num_rendered still count it)
-                    bin.wh = 0u;
+            if (cand_rows != 0u) {
+                payload &= (unsigned long long)s_mask[wave][lane][0] | ((unsigned long long)s_mask[wave][lane][1] << 32);   // (inside the rectangle)
+                live_bound = (uint32_t)__popcll(payload);
+                if (payload == 0ull) {  // every tile is dead: the splat is listed nowhere (radii and num_rendered still count it)
+                    bin_wh = 0u;
                     key = kCulledKey;
                 }
             }
@@ -291,35 +281,26 @@ __global__ void __launch_bounds__(256) preprocess_kernel(GaussianInputs in, Came
     // (about 12 ns each on this part: a third of that kernel on a cloud of large splats).
     __shared__ unsigned long long s_tot[4];
     __shared__ uint32_t s_vis[4], s_big[4];
-    unsigned long long wave_tot = ((unsigned long long)rect_area << 32) | (unsigned long long)live_bound;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) wave_tot += __shfl_xor(wave_tot, d);
+    // (Each word summed on its own.  That equals the 64-bit sum unless the low words carry, i.e. unless ONE wave's splats
+    // bound more than 2^32 live pairs -- more than the 32-bit pair offsets of the binning arena can address for a frame.)
+    const unsigned long long wave_tot = ((unsigned long long)wave_sum(rect_area) << 32) | (unsigned long long)wave_sum(live_bound);
     const unsigned long long emitting = __ballot(key != kCulledKey);
-    const unsigned long long any_big = __ballot(big_rows != 0u);
-    uint32_t big_incl = big_rows;
-    if (any_big != 0ull) {   // wave-uniform
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t o = (uint32_t)__shfl_up((int)big_incl, d);
-            if ((int)(threadIdx.x & 63) >= d) big_incl += o;
-        }
-    }
+    const uint32_t big_incl = wave_inclusive_scan(big_rows);
     const unsigned long long any_violation = __ballot(violation);
-    if ((threadIdx.x & 63) == 63) {
-        const int w = threadIdx.x >> 6;
-        s_tot[w] = wave_tot;
-        s_vis[w] = (uint32_t)__popcll(emitting);
-        s_big[w] = big_incl | (any_violation != 0ull ? 0x80000000u : 0u);
+    if (lane == 63) {
+        s_tot[wave] = wave_tot;
+        s_vis[wave] = (uint32_t)__popcll(emitting);
+        s_big[wave] = big_incl | (any_violation != 0ull ? 0x80000000u : 0u);
     }
     __syncthreads();
     if (big_rows != 0u) {
         uint32_t before = big_incl - big_rows;
-        for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) before += s_big[w] & 0x7FFFFFFFu;
-        bin.lo = before;   // (hi stays all ones)
+        for (int w = 0; w < wave; ++w) before += s_big[w] & 0x7FFFFFFFu;
+        payload = 0xFFFFFFFF00000000ull | before;   // (SplatBin::hi stays all ones)
     }
     if (in_range) {
         out.radii[i] = radius_out;
-        *reinterpret_cast<uint4*>(out.bins + i) = make_uint4(bin.xy0, bin.wh, bin.lo, bin.hi);
+        *reinterpret_cast<uint4*>(out.bins + i) = make_uint4(bin_xy0, bin_wh, (uint32_t)payload, (uint32_t)(payload >> 32));
         out.depth_keys[i] = key;
         if (out.listed != nullptr) out.listed[i] = 0u;   // (a 3 MB memset queued beside other frames' blends took ~100 us)
     }
@@ -376,13 +357,8 @@ __global__ void __launch_bounds__(256) sh_colour_listed_kernel(GaussianInputs in
         mine[j] = ((marks >> (8 * j)) & 0xFFu) == (uint32_t)tag;
         cnt += mine[j] ? 1u : 0u;
     }
-    uint32_t incl = cnt;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = (uint32_t)__shfl_up((int)incl, d);
-        if (lane >= d) incl += o;
-    }
-    const uint32_t n = (uint32_t)__shfl((int)incl, 63);
+    const uint32_t incl = wave_inclusive_scan(cnt);
+    const uint32_t n = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
     uint32_t at = incl - cnt;
 #pragma unroll
     for (int j = 0; j < 4; ++j)
