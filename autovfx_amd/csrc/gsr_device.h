@@ -162,11 +162,11 @@ constexpr float kSH3_0 = -0.5900435899266435f, kSH3_1 = 2.890611442640554f, kSH3
                 kSH3_3 = 0.3731763325901154f, kSH3_4 = -0.4570457994644658f, kSH3_5 = 1.445305721320277f,
                 kSH3_6 = -0.5900435899266435f;
 
-__device__ __forceinline__ F3 ld3(const float* p) { return *reinterpret_cast<const F3*>(p); }
-__device__ __forceinline__ F3 axpy(F3 acc, float s, F3 v) {  // acc + s * v, unfused
+__host__ __device__ __forceinline__ F3 ld3(const float* p) { return *reinterpret_cast<const F3*>(p); }
+__host__ __device__ __forceinline__ F3 axpy(F3 acc, float s, F3 v) {  // acc + s * v, unfused
     return F3{acc.x + s * v.x, acc.y + s * v.y, acc.z + s * v.z};
 }
-__device__ __forceinline__ F3 axmy(F3 acc, float s, F3 v) {  // acc - s * v, unfused
+__host__ __device__ __forceinline__ F3 axmy(F3 acc, float s, F3 v) {  // acc - s * v, unfused
     return F3{acc.x - s * v.x, acc.y - s * v.y, acc.z - s * v.z};
 }
 
@@ -174,7 +174,7 @@ __device__ __forceinline__ F3 axmy(F3 acc, float s, F3 v) {  // acc - s * v, unf
 // direction; coefficient 0 sits at `sh0`, coefficient k >= 1 at `shr + 3 k`; deg already clamped to what M holds.
 // One [M,3] block (the reference's `shs`): sh0 = shr = the block.  A model's two tensors (gsr_forward_raw): sh0 = its
 // _features_dc row, shr = its _features_rest row - 3 -- what torch.cat((dc, rest), dim=1) would have laid out, unread.
-__device__ __forceinline__ F3 sh_unclamped(int deg, float x, float y, float z, const float* sh0, const float* shr) {
+__host__ __device__ __forceinline__ F3 sh_unclamped(int deg, float x, float y, float z, const float* sh0, const float* shr) {
     F3 c = ld3(sh0);
     F3 v = F3{kSH0 * c.x, kSH0 * c.y, kSH0 * c.z};
     if (deg > 0) {
@@ -202,18 +202,98 @@ __device__ __forceinline__ F3 sh_unclamped(int deg, float x, float y, float z, c
     v.x += 0.5f; v.y += 0.5f; v.z += 0.5f;
     return v;
 }
-__device__ __forceinline__ F3 sh_unclamped(int deg, float x, float y, float z, const float* sh) {
+__host__ __device__ __forceinline__ F3 sh_unclamped(int deg, float x, float y, float z, const float* sh) {
     return sh_unclamped(deg, x, y, z, sh, sh);
 }
 
-__device__ __forceinline__ F3 sh_to_rgb(int deg, F3 pos, F3 cam, const float* sh0, const float* shr) {
+// One whole degree-3 record ([16,3] floats, 192 bytes, 16-byte aligned) as the twelve 16-byte pieces it is made of.  The
+// deferred colour kernels fetch these back to back, with the position, before any arithmetic: one trip to memory per
+// Gaussian.  (sh_unclamped's loads sit behind its run-time `deg` tests and so cannot be hoisted: four dependent trips.)
+struct ShRecord {
+    float4 q[12];
+    __host__ __device__ __forceinline__ float at(int f) const {   // float f of the 48; f is a constant wherever this is called
+        const float4& v = q[f >> 2];
+        return (f & 3) == 0 ? v.x : (f & 3) == 1 ? v.y : (f & 3) == 2 ? v.z : v.w;
+    }
+    __host__ __device__ __forceinline__ F3 coeff(int k) const { return F3{at(3 * k), at(3 * k + 1), at(3 * k + 2)}; }
+};
+__host__ __device__ __forceinline__ ShRecord ld_sh_record(const float* sh) {
+    ShRecord r;
+    const float4* p = reinterpret_cast<const float4*>(sh);
+#pragma unroll
+    for (int k = 0; k < 12; ++k) r.q[k] = p[k];
+    return r;
+}
+
+// acc + t and acc - t with the accumulator as the FIRST source operand of the instruction.  Where both are NaN the hardware
+// returns the first (the second's sign flipped by a subtraction does not matter then), and the compiler is free to commute a
+// plain `+`: it did in one of the two colour kernels, and the colour of a Gaussian AT the camera position (a direction of
+// 0 / 0) came out as the in-line evaluation's NaN with the other sign.  Same instruction, same rounding; only the order is pinned.
+__host__ __device__ __forceinline__ float add_acc_first(float acc, float t) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    float d;
+    asm("v_add_f32_e32 %0, %1, %2" : "=v"(d) : "v"(acc), "v"(t));
+    return d;
+#else
+    return acc + t;
+#endif
+}
+__host__ __device__ __forceinline__ float sub_acc_first(float acc, float t) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    float d;
+    asm("v_sub_f32_e32 %0, %1, %2" : "=v"(d) : "v"(acc), "v"(t));
+    return d;
+#else
+    return acc - t;
+#endif
+}
+__host__ __device__ __forceinline__ F3 axpy_acc_first(F3 acc, float s, F3 v) {
+    return F3{add_acc_first(acc.x, s * v.x), add_acc_first(acc.y, s * v.y), add_acc_first(acc.z, s * v.z)};
+}
+__host__ __device__ __forceinline__ F3 axmy_acc_first(F3 acc, float s, F3 v) {
+    return F3{sub_acc_first(acc.x, s * v.x), sub_acc_first(acc.y, s * v.y), sub_acc_first(acc.z, s * v.z)};
+}
+
+// sh_unclamped(3, x, y, z, sh) from a record already in registers: the same operations in the same order.
+__host__ __device__ __forceinline__ F3 sh_unclamped_record(float x, float y, float z, const ShRecord& r) {
+    const F3 c = r.coeff(0);
+    F3 v = F3{kSH0 * c.x, kSH0 * c.y, kSH0 * c.z};
+    v = axmy_acc_first(v, kSH1 * y, r.coeff(1));
+    v = axpy_acc_first(v, kSH1 * z, r.coeff(2));
+    v = axmy_acc_first(v, kSH1 * x, r.coeff(3));
+    const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
+    v = axpy_acc_first(v, kSH2_0 * xy, r.coeff(4));
+    v = axpy_acc_first(v, kSH2_1 * yz, r.coeff(5));
+    v = axpy_acc_first(v, kSH2_2 * (2.0f * zz - xx - yy), r.coeff(6));
+    v = axpy_acc_first(v, kSH2_3 * xz, r.coeff(7));
+    v = axpy_acc_first(v, kSH2_4 * (xx - yy), r.coeff(8));
+    v = axpy_acc_first(v, kSH3_0 * y * (3.0f * xx - yy), r.coeff(9));
+    v = axpy_acc_first(v, kSH3_1 * xy * z, r.coeff(10));
+    v = axpy_acc_first(v, kSH3_2 * y * (4.0f * zz - xx - yy), r.coeff(11));
+    v = axpy_acc_first(v, kSH3_3 * z * (2.0f * zz - 3.0f * xx - 3.0f * yy), r.coeff(12));
+    v = axpy_acc_first(v, kSH3_4 * x * (4.0f * zz - xx - yy), r.coeff(13));
+    v = axpy_acc_first(v, kSH3_5 * z * (xx - yy), r.coeff(14));
+    v = axpy_acc_first(v, kSH3_6 * x * (xx - 3.0f * yy), r.coeff(15));
+    v.x += 0.5f; v.y += 0.5f; v.z += 0.5f;
+    return v;
+}
+
+// sh_to_rgb(3, pos, cam, sh) with the record and the position in registers.
+__host__ __device__ __forceinline__ F3 sh_to_rgb_record(F3 pos, F3 cam, const ShRecord& r) {
+    float dx = pos.x - cam.x, dy = pos.y - cam.y, dz = pos.z - cam.z;
+    const float len = sqrtf(dx * dx + dy * dy + dz * dz);
+    const F3 v = sh_unclamped_record(dx / len, dy / len, dz / len, r);
+    return F3{v.x < 0.0f ? 0.0f : v.x, v.y < 0.0f ? 0.0f : v.y, v.z < 0.0f ? 0.0f : v.z};
+}
+
+__host__ __device__ __forceinline__ F3 sh_to_rgb(int deg, F3 pos, F3 cam, const float* sh0, const float* shr) {
     float dx = pos.x - cam.x, dy = pos.y - cam.y, dz = pos.z - cam.z;
     const float len = sqrtf(dx * dx + dy * dy + dz * dz);
     const F3 v = sh_unclamped(deg, dx / len, dy / len, dz / len, sh0, shr);
     // glm::max(result, 0.0f) (forward.cu:70) is `(x < y) ? y : x`: a NaN colour stays a NaN (fmaxf would turn it into 0)
     return F3{v.x < 0.0f ? 0.0f : v.x, v.y < 0.0f ? 0.0f : v.y, v.z < 0.0f ? 0.0f : v.z};
 }
-__device__ __forceinline__ F3 sh_to_rgb(int deg, F3 pos, F3 cam, const float* sh) { return sh_to_rgb(deg, pos, cam, sh, sh); }
+__host__ __device__ __forceinline__ F3 sh_to_rgb(int deg, F3 pos, F3 cam, const float* sh) { return sh_to_rgb(deg, pos, cam, sh, sh); }
 
 // ------------------------------------------------------------------------------------------------
 // The reference's per-frame PyTorch preparation, restated per Gaussian (gsr_forward_raw, gsr_place_object,

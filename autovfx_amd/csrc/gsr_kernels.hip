@@ -324,7 +324,21 @@ __global__ void __launch_bounds__(256) preprocess_kernel(GaussianInputs in, Came
 // addresses, neighbouring lanes sharing lines -- rather than gathered in depth order (measured: the gather moved 495 MB
 // per C3 frame for 163 MB of records, every 128-byte line fetched about three times).  Same arithmetic as the in-line
 // evaluation (sh_to_rgb), so rgb[] holds the same bits wherever it is read.
+//
+// A whole record is fetched in ONE trip: the position and the twelve aligned 16-byte pieces of the 192-byte record are
+// issued back to back, the view direction (square root, three divisions) is computed while they are in flight and the
+// evaluation runs from registers (sh_to_rgb_record; 64 registers, still 8 waves per SIMD, no scratch).  sh_to_rgb's loads sit
+// behind its run-time degree tests, which made four dependent trips per Gaussian (position + coefficient 0, 1-3, 4-8, 9-15),
+// the last with a 16-byte load across a line boundary in every record.  MI355X, C3, one stream, per launch: slab 0
+// 73.6 -> 69.6 us (median of 147 calls; the parent's fastest call 71.1), slab 1 28.9 -> 25.1 us; profiles/r08_sh_record_ab.txt.
 // ------------------------------------------------------------------------------------------------
+// The record-first path (gsr_device.h: ShRecord) applies to a call whose records are whole and aligned: degree 3 of one
+// [P,16,3] block on a 16-byte boundary.  Lower degrees, fewer coefficients, a base that is only 4-byte aligned (a view
+// into a larger tensor) and the raw call's two tensors keep the coefficient-by-coefficient path.
+__device__ __forceinline__ bool sh_record_path(const GaussianInputs& in, int deg) {
+    return deg == 3 && in.M == 16 && !in.raw && (reinterpret_cast<uintptr_t>(in.shs) & 15u) == 0u;
+}
+
 __global__ void __launch_bounds__(256) sh_colour_listed_kernel(GaussianInputs in, const float* __restrict__ cam_pos,
                                                                const uint8_t* __restrict__ listed, int tag,
                                                                const SlabInfo* __restrict__ slab, float* __restrict__ rgb,
@@ -372,6 +386,17 @@ __global__ void __launch_bounds__(256) sh_colour_listed_kernel(GaussianInputs in
     if (deg > 1 && in.M < 9) deg = 1;
     if (deg > 0 && in.M < 4) deg = 0;
     const F3 cp = ld3(cam_pos);
+    if (sh_record_path(in, deg)) {   // wave-uniform: kernel arguments only
+        for (uint32_t t = (uint32_t)lane; t < n; t += 64u) {
+            const uint32_t i = s_list[wave][t];
+            const F3 p = ld3(in.means3D + 3 * (size_t)i);
+            const ShRecord rec = ld_sh_record(in.shs + 48 * (size_t)i);
+            __builtin_amdgcn_sched_barrier(0);   // all thirteen loads are issued before the first instruction that waits for one
+            *reinterpret_cast<F3*>(rgb + 3 * (size_t)i) = sh_to_rgb_record(p, cp, rec);
+        }
+        GSR_KTRACE(16384 + 8192 * (tag - 1) + blockIdx.x, 3);
+        return;
+    }
     for (uint32_t t = (uint32_t)lane; t < n; t += 64u) {
         const uint32_t i = s_list[wave][t];
         const F3 p = ld3(in.means3D + 3 * (size_t)i);
@@ -399,6 +424,13 @@ __global__ void __launch_bounds__(256) sh_colour_all_kernel(GaussianInputs in, c
     if (deg > 2 && in.M < 16) deg = 2;
     if (deg > 1 && in.M < 9) deg = 1;
     if (deg > 0 && in.M < 4) deg = 0;
+    if (sh_record_path(in, deg)) {   // uniform over the launch
+        const F3 p = ld3(in.means3D + 3 * (size_t)i);
+        const ShRecord rec = ld_sh_record(in.shs + 48 * (size_t)i);
+        __builtin_amdgcn_sched_barrier(0);   // (as in sh_colour_listed_kernel)
+        *reinterpret_cast<F3*>(rgb + 3 * (size_t)i) = sh_to_rgb_record(p, ld3(cam_pos), rec);
+        return;
+    }
     const F3 p = ld3(in.means3D + 3 * (size_t)i);
     const float* sh0 = in.raw ? in.shs + 3 * (size_t)i : in.shs + 3 * (size_t)in.M * i;
     const float* shr = (in.raw && in.M > 1) ? in.shs_rest + 3 * (size_t)(in.M - 1) * i - 3 : sh0;
