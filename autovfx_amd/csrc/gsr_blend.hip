@@ -11,7 +11,10 @@
 //   * while staging a batch of 64 list entries each lane runs the conservative reach test of its entry against the
 //     quadrant (gsr_device.h: splat_reaches_rect); the wave then walks only the set bits of the ballot, so entries
 //     that cannot touch the quadrant cost no LDS read and no per-pixel work at all;
-//   * entries are parked in LDS as one 48-byte record (one address register, three broadcast reads);
+//   * the entries that reach are parked in LDS slots in list order, each with the terms of `power` that depend only on
+//     the pixel's column or only on its row (gsr_device.h: blend_power_terms), computed by the entry's own lane while it
+//     stages: the walk reads its column's pair and its row's pair and is left with an add, a multiply and a subtract
+//     per (entry, pixel); slots are addressed by the reads' immediate offsets in a body unrolled over kWalkUnroll slots;
 //   * which pixels have stopped is a wave-uniform 64-bit mask in scalar registers, combined only in uniform control
 //     flow, so "any pixel live?" / "all done?" cost no vector instructions and the accumulate block is gated through
 //     the exec mask (inverse_ballot);
@@ -115,16 +118,39 @@ __device__ __forceinline__ void mark_quadrant_done(const BlendArgs& a, int item)
     }
 }
 
+// The LDS of one single-wave workgroup: kCount slots of kStride bytes, then one tail word (or, with the second feature set,
+// one 16-byte tail record) per slot.
+//   slot  +0    eight column pairs ((mh_cxx dx) dx, cxy dx)     one 8-byte read per lane, address by lane & 7
+//         +64   eight row pairs    ((mh_cyy dy) dy, dy)         one 8-byte read per lane, address by lane >> 3
+//         +128  skip_below, opacity                             broadcast, every processed entry
+//         +136  r, g   +144  b, z                               broadcast, contributing entries only
+//   tail  the entry's index in its batch of 64 (with the second set: ex, ey, ez, index)
+// 32 workgroups share a CU's 160 KiB at eight waves per SIMD: 5 120 bytes each.  kStride = 152 bytes = 38 dwords, and
+// 38 mod 32 = 6 = 2 * 3: the 8-byte stores of 16 consecutive slots (one store group) fall on 16 different bank pairs, and the
+// walk's reads are 8 neighbouring pairs or one address.  152 is not a multiple of 16, so (r, g, b, z) is read as two 8-byte halves.
+template <bool kExtra>
+struct BlendSlots {
+    static constexpr int kCount = kExtra ? 30 : 32;
+    static constexpr int kStride = 152;
+    static constexpr int kCol = 0, kRow = 64, kGate = 128, kRG = 136, kBZ = 144;
+    static constexpr int kTail = kCount * kStride;
+    static constexpr int kTailStride = kExtra ? 16 : 4;
+    static constexpr int kBytes = kTail + kCount * kTailStride;
+    static_assert(kStride % 8 == 0 && (kStride / 4) % 4 == 2 && kTail % 16 == 0, "8-byte slots on distinct bank pairs; aligned tail");
+    static_assert(32 * kBytes <= 160 * 1024 && kCount <= 64, "32 single-wave workgroups per CU");
+};
+constexpr int kWalkUnroll = 8;
+
 // kExtra: a second per-Gaussian feature triple (extra_features[P,3] -> out_extra[3,H,W]) is composited in the
 // same walk with the same alpha and transmittance -- what the reference's render() obtains from a second full
 // rasterizer pass for its normal map (gaussian_renderer/__init__.py:176-184): identical arithmetic per channel,
 // one list walk instead of two.
 template <bool kExtra>
 __global__ void __launch_bounds__(64, 8) blend_quadrant_kernel(BlendArgs a) {
-    __shared__ BlendEntry s_entry[64];
-    __shared__ float4 s_extra[kExtra ? 64 : 1];
+    using Slots = BlendSlots<kExtra>;
+    __shared__ __attribute__((aligned(16))) char s_slots[Slots::kBytes];
 
-    constexpr int kQ = kTile / 2;
+    constexpr int kQ = kQuad;
     const int W = a.W, H = a.H;
     // the 4 quadrants of a tile share an XCD; large images: longest lists first inside the XCD's band (BlendOrder)
     const int item = a.order.counts == nullptr ? xcd_band_tile(blockIdx.x, 4 * a.num_tiles) : ordered_item(a.order, blockIdx.x);
@@ -137,7 +163,6 @@ __global__ void __launch_bounds__(64, 8) blend_quadrant_kernel(BlendArgs a) {
     const int qx0 = (tile % a.grid_x) * kTile + kQ * (quad & 1);
     const int qy0 = (tile / a.grid_x) * kTile + kQ * (quad >> 1);
     const int px = qx0 + (lane & 7), py = qy0 + (lane >> 3);
-    const float fx = (float)px, fy = (float)py;
     const bool inside = px < W && py < H;
     const size_t plane = (size_t)W * (size_t)H;
     const size_t pid = (size_t)W * (size_t)py + (size_t)px;
@@ -169,6 +194,16 @@ __global__ void __launch_bounds__(64, 8) blend_quadrant_kernel(BlendArgs a) {
         }
         done_mask |= __ballot(stopped);
     }
+
+    // The pixel coordinates of the quadrant's eight columns and eight rows, wave-uniform, in scalar registers for the staging
+    // lanes; the two lane-constant LDS offsets of the walk (this lane's column pair and row pair inside a slot).
+    float qfx[kQ], qfy[kQ];
+#pragma unroll
+    for (int i = 0; i < kQ; ++i) {
+        qfx[i] = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint((float)(qx0 + i))));
+        qfy[i] = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint((float)(qy0 + i))));
+    }
+    const uint32_t lane_col = Slots::kCol + 8u * ((uint32_t)lane & 7u), lane_row = Slots::kRow + 8u * ((uint32_t)lane >> 3);
 
     uint32_t seg_base = 0u;  // list positions of earlier segments (n_contrib counts through the concatenation)
     for (int seg = 0; seg < a.seg_begin; ++seg) {  // ... also of the segments earlier launches walked
@@ -202,67 +237,117 @@ __global__ void __launch_bounds__(64, 8) blend_quadrant_kernel(BlendArgs a) {
 
         for (uint32_t first = 0; first < count; first += 64) {
             const bool mine = first + (uint32_t)lane < count;
-            unsigned long long todo = __ballot(mine && splat_reaches_rect(g_co, g_skip, g_xy, qx0, qy0, kQ, kQ));
-            if (todo != 0ull) {
-                __syncthreads();  // single-wave workgroup: orders this wave's LDS reads / writes only
-                float4* rec = reinterpret_cast<float4*>(&s_entry[lane]);
-                // The conic's diagonal is parked already multiplied by -0.5: scaling by a power of two commutes with every
-                // rounding of -0.5 * (cxx*dx*dx + cyy*dy*dy), so the walk below gets the same bits with one multiply less
-                // per (entry, pixel).
-                rec[0] = make_float4(g_xy.x, g_xy.y, -0.5f * g_co.x, g_co.y);
-                rec[1] = make_float4(-0.5f * g_co.z, g_skip, g_co.w, 0.f);
-                rec[2] = make_float4(g_rgb.x, g_rgb.y, g_rgb.z, g_z);
-                if (kExtra) s_extra[lane] = make_float4(g_ext.x, g_ext.y, g_ext.z, 0.f);
-                __syncthreads();
-            }
-            if (first + 64 < count) gather(first + 64);
-
-            while (todo != 0ull) {
-                const int j = __builtin_ctzll(todo);
-                todo &= todo - 1ull;
-                // The entry's LDS offset is wave-uniform; parked in ONE vector register (opaque to the compiler, which
-                // would otherwise re-create it from the scalar before each of the three reads of the record).
-                uint32_t entry_offset;
-                asm("v_mov_b32 %0, %1" : "=v"(entry_offset) : "s"(j * (int)sizeof(BlendEntry)));
-                const float4* rec = reinterpret_cast<const float4*>(reinterpret_cast<const char*>(s_entry) + entry_offset);
-                const float4 ra = rec[0], rb = rec[1];
-                struct { float x, y, mh_cxx, cxy; } ea = {ra.x, ra.y, ra.z, ra.w};   // mh_ = times minus one half
-                struct { float mh_cyy, skip_below, opacity; } eb = {rb.x, rb.y, rb.z};
-                // One list entry against this lane's pixel: forward.cu:331-364, same bits as
-                // -0.5f * (cxx * dx * dx + cyy * dy * dy) - cxy * dx * dy.
-                const float dx = ea.x - fx, dy = ea.y - fy;
-                const float power = (ea.mh_cxx * dx * dx + eb.mh_cyy * dy * dy) - ea.cxy * dx * dy;
-                // (one ballot per comparison: the ballot of a conjunction goes through a vector register and back)
-                const unsigned long long live = __ballot(!(power > 0.0f)) & __ballot(!(power < eb.skip_below)) & ~done_mask;
-                if (live == 0ull) continue;
-                // From here every lane computes (a vector instruction costs the same with 1 or 64 lanes enabled);
-                // the outcome of a lane that is not live is masked out below.  All masks stay wave-uniform scalars
-                // because they are only combined in uniform control flow.
-                const float alpha = fminf(0.99f, eb.opacity * exp_nonpositive(power));
-                const unsigned long long blends = live & __ballot(!(alpha < 1.0f / 255.0f));
-                if (blends == 0ull) continue;
-                const float test_T = T * (1.f - alpha);
-                const unsigned long long stops = blends & __ballot(test_T < 0.0001f);
-                done_mask |= stops;
-                const unsigned long long adds = blends & ~stops;
-                if (adds != 0ull && __builtin_amdgcn_inverse_ballot_w64(adds)) {
-                    const float4 c = rec[2];  // r g b z
-                    Crg = composite2(Crg, (v2f){c.x, c.y}, alpha, T);
-                    Cbz = composite2(Cbz, (v2f){c.z, c.w}, alpha, T);
-                    if (kExtra) {
-                        const float4 e = s_extra[j];
-                        Erg = composite2(Erg, (v2f){e.x, e.y}, alpha, T);
-                        Eb = composite(Eb, e.z, alpha, T);
+            bool reach = mine && splat_reaches_rect(g_co, g_skip, g_xy, qx0, qy0, kQ, kQ);
+            unsigned long long todo = __ballot(reach);
+            // The reaching entries are walked in rounds of at most Slots::kCount (C3: about 22 of a batch's 64 reach, so nearly
+            // always one round); a later round builds its slots from the same g_* registers, which is why the next batch is
+            // prefetched into them only once the batch's LAST round is built.
+            for (;;) {
+                uint32_t n = 0u;
+                if (todo != 0ull) {
+                    // lane = entry: a reaching entry takes the slot of its rank among the reaching ones, so slots are in list order
+                    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(todo >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)todo, 0u));
+                    const bool staged = reach && rank < (uint32_t)Slots::kCount;
+                    __syncthreads();  // single-wave workgroup: orders this wave's LDS reads / writes only
+                    if (staged) {
+                        char* slot = s_slots + rank * (uint32_t)Slots::kStride;
+                        // The conic's diagonal goes in already multiplied by -0.5: scaling by a power of two commutes with every
+                        // rounding of -0.5 * (cxx*dx*dx + cyy*dy*dy), so the terms give the same bits with one multiply less.
+                        blend_power_terms(g_xy.x, g_xy.y, -0.5f * g_co.x, g_co.y, -0.5f * g_co.z, qfx, qfy,
+                                          reinterpret_cast<float2*>(slot + Slots::kCol), reinterpret_cast<float2*>(slot + Slots::kRow));
+                        *reinterpret_cast<float2*>(slot + Slots::kGate) = make_float2(g_skip, g_co.w);
+                        *reinterpret_cast<float2*>(slot + Slots::kRG) = make_float2(g_rgb.x, g_rgb.y);
+                        *reinterpret_cast<float2*>(slot + Slots::kBZ) = make_float2(g_rgb.z, g_z);
+                        char* tail = s_slots + Slots::kTail + rank * (uint32_t)Slots::kTailStride;
+                        if (kExtra) *reinterpret_cast<float4*>(tail) = make_float4(g_ext.x, g_ext.y, g_ext.z, __uint_as_float((uint32_t)lane));
+                        else *reinterpret_cast<uint32_t*>(tail) = (uint32_t)lane;
                     }
-                    T = test_T;
-                    last = seg_base + first + (uint32_t)j + 1u;
+                    __syncthreads();
+                    const unsigned long long taken = __ballot(staged);
+                    n = (uint32_t)__popcll(taken);
+                    todo &= ~taken;
+                    reach = reach && !staged;
                 }
-                if (done_mask == ~0ull) break;
+                if (todo == 0ull && first + 64 < count) gather(first + 64);
+
+                for (uint32_t s = 0u; s < n; s += kWalkUnroll) {
+                    // The addresses of slot s for this lane, parked in vector registers the compiler cannot see through: the
+                    // kWalkUnroll slots of the body below differ only in the immediate offsets of their reads.
+                    uint32_t col_a = lane_col + s * (uint32_t)Slots::kStride, row_a = lane_row + s * (uint32_t)Slots::kStride;
+                    uint32_t slot_a = s * (uint32_t)Slots::kStride, tail_a = (uint32_t)Slots::kTail + s * (uint32_t)Slots::kTailStride;
+                    asm("" : "+v"(col_a), "+v"(row_a), "+v"(slot_a), "+v"(tail_a));
+#pragma unroll
+                    for (int u = 0; u < kWalkUnroll; ++u) {
+                        if (s + (uint32_t)u >= n) break;
+                        const char* slot_u = s_slots + u * Slots::kStride;
+                        const char* tail_u = s_slots + u * Slots::kTailStride + tail_a;
+                        // The LDS unit is this kernel's second limiter after vector issue (profiles/r09_blend_terms.md): every
+                        // read of an entry is issued here, in one round trip, each as ONE 8-byte read of two LDS cycles.  The
+                        // empty asm statements keep it so: the compiler would read skip_below and opacity as two halves (the
+                        // second behind the first early exit: a second round trip), pair neighbouring 8-byte reads into one
+                        // 8-cycle ds_read2_b64, and sink the colour reads behind the last early exit (a third round trip).
+                        const float2 cp = *reinterpret_cast<const float2*>(slot_u + col_a);
+                        const float2 rp = *reinterpret_cast<const float2*>(slot_u + row_a);
+                        unsigned long long gate_bits = *reinterpret_cast<const unsigned long long*>(slot_u + Slots::kGate + slot_a);
+                        asm("" : "+v"(gate_bits));
+                        const float skip_below = __uint_as_float((uint32_t)gate_bits), opacity = __uint_as_float((uint32_t)(gate_bits >> 32));
+                        // (with the second feature set there are no registers to hold an entry's colours across its early
+                        // exits at eight waves per SIMD: that kernel reads them where it accumulates)
+                        float2 rg = make_float2(0.f, 0.f), bz = rg;
+                        uint32_t j = 0u;  // the entry's index in its batch of 64
+                        if (!kExtra) {
+                            asm volatile("" ::: "memory");
+                            rg = *reinterpret_cast<const float2*>(slot_u + Slots::kRG + slot_a);
+                            asm volatile("" ::: "memory");
+                            bz = *reinterpret_cast<const float2*>(slot_u + Slots::kBZ + slot_a);
+                            j = *reinterpret_cast<const uint32_t*>(tail_u);
+                        }
+                        // One list entry against this lane's pixel: forward.cu:331-364, same bits as
+                        // -0.5f * (cxx * dx * dx + cyy * dy * dy) - cxy * dx * dy.
+                        const float power = blend_power(cp, rp);
+                        if (!kExtra) asm("" : "+v"(rg.x), "+v"(rg.y), "+v"(bz.x), "+v"(bz.y), "+v"(j));
+                        // (one ballot per comparison: the ballot of a conjunction goes through a vector register and back)
+                        const unsigned long long live = __ballot(!(power > 0.0f)) & __ballot(!(power < skip_below)) & ~done_mask;
+                        if (live == 0ull) continue;
+                        // From here every lane computes (a vector instruction costs the same with 1 or 64 lanes enabled);
+                        // the outcome of a lane that is not live is masked out below.  All masks stay wave-uniform scalars
+                        // because they are only combined in uniform control flow.
+                        const float alpha = fminf(0.99f, opacity * exp_nonpositive(power));
+                        const unsigned long long blends = live & __ballot(!(alpha < 1.0f / 255.0f));
+                        if (blends == 0ull) continue;
+                        const float test_T = T * (1.f - alpha);
+                        const unsigned long long stops = blends & __ballot(test_T < 0.0001f);
+                        done_mask |= stops;
+                        const unsigned long long adds = blends & ~stops;
+                        if (adds != 0ull && __builtin_amdgcn_inverse_ballot_w64(adds)) {
+                            if (kExtra) {
+                                rg = *reinterpret_cast<const float2*>(slot_u + Slots::kRG + slot_a);
+                                asm volatile("" ::: "memory");
+                                bz = *reinterpret_cast<const float2*>(slot_u + Slots::kBZ + slot_a);
+                                const float4 e = *reinterpret_cast<const float4*>(tail_u);
+                                Erg = composite2(Erg, (v2f){e.x, e.y}, alpha, T);
+                                Eb = composite(Eb, e.z, alpha, T);
+                                j = __float_as_uint(e.w);
+                            }
+                            Crg = composite2(Crg, (v2f){rg.x, rg.y}, alpha, T);
+                            Cbz = composite2(Cbz, (v2f){bz.x, bz.y}, alpha, T);
+                            T = test_T;
+                            last = (seg_base + first + 1u) + j;
+                        }
+                        // Every pixel of the quadrant has stopped: the walk ends at the next slot's bound, which keeps it a loop
+                        // with ONE way out (opaque, or the compiler threads the jump and pays a second exit with a state
+                        // variable after every entry).
+                        n = done_mask == ~0ull ? 0u : n;
+                        asm("" : "+s"(n));
+                    }
+                }
+                if (done_mask == ~0ull) goto walked;
+                if (todo == 0ull) break;
             }
-            if (done_mask == ~0ull) break;
         }
         seg_base += count;
     }
+walked:
 
     const bool all_done = done_mask == ~0ull;
     if (final || all_done) {

@@ -495,6 +495,44 @@ struct BlendEntry {
     float r, g, b, z;                   // contributing entries only
 };
 
+// The quadrant blend's `power` with its per-column and per-row terms taken out of the per-pixel walk.  A lane's pixel is
+// (column lane & 7, row lane >> 3) of an 8x8 quadrant, and in
+//     dx = x - fx;  dy = y - fy;  power = (mh_cxx * dx * dx + mh_cyy * dy * dy) - cxy * dx * dy
+// dx, (mh_cxx * dx) * dx and cxy * dx take one value per column, dy and (mh_cyy * dy) * dy one per row.  blend_power_terms
+// computes them once per (entry, column) and once per (entry, row) -- the same operations on the same operands, unfused, so
+// the same bits -- and blend_power finishes a pixel with one add, one multiply and one subtract, the first operand of
+// the add and of the subtract pinned (add_acc_first above: which NaN comes back when both are).
+//   col[c] = ((mh_cxx * dx_c) * dx_c, cxy * dx_c)   dx_c = x - fx[c]     fx[c] = (float)(column c's pixel x)
+//   row[r] = ((mh_cyy * dy_r) * dy_r, dy_r)         dy_r = y - fy[r]
+constexpr int kQuad = kTile / 2;
+__host__ __device__ __forceinline__ void blend_power_terms(float x, float y, float mh_cxx, float cxy, float mh_cyy, const float* fx,
+                                                           const float* fy, float2* col, float2* row) {
+#pragma unroll
+    for (int c = 0; c < kQuad; ++c) {
+        const float dx = x - fx[c];
+        col[c] = make_float2(mh_cxx * dx * dx, cxy * dx);
+    }
+#pragma unroll
+    for (int r = 0; r < kQuad; ++r) {
+        const float dy = y - fy[r];
+        row[r] = make_float2(mh_cyy * dy * dy, dy);
+    }
+}
+// ... from the quadrant's origin (qx0, qy0): pixel (qx0 + c, qy0 + r)
+__host__ __device__ __forceinline__ void blend_power_terms(float x, float y, float mh_cxx, float cxy, float mh_cyy, int qx0, int qy0,
+                                                           float2* col, float2* row) {
+    float fx[kQuad], fy[kQuad];
+#pragma unroll
+    for (int i = 0; i < kQuad; ++i) {
+        fx[i] = (float)(qx0 + i);
+        fy[i] = (float)(qy0 + i);
+    }
+    blend_power_terms(x, y, mh_cxx, cxy, mh_cyy, fx, fy, col, row);
+}
+__host__ __device__ __forceinline__ float blend_power(float2 col, float2 row) {
+    return sub_acc_first(add_acc_first(col.x, row.x), col.y * row.y);
+}
+
 __device__ __forceinline__ int xcd_band_tile(int b, int T) {
     // Blocks are dealt round-robin to the 8 XCDs (block b -> XCD b % 8).  Give each XCD a contiguous
     // band of tile rows so neighbouring tiles, which share splats, hit the same L2.  Bijective for

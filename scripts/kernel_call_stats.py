@@ -1,6 +1,6 @@
 """Per-call kernel times from a rocprofv3 kernel trace: calls, mean, min, median and max per kernel, over the calls that
-follow the warm-up (the first third of a kernel's calls is dropped).  `expand_kernel` and `sh_colour_listed_kernel` run once per
-depth slab, so their calls are split into [even] (slab 0) and [odd] (slab 1) for a two-slab frame.
+follow the warm-up (the first third of a kernel's calls is dropped).  `expand_kernel`, `sh_colour_listed_kernel` and
+`blend_quadrant_kernel` run once per depth slab, so their calls are split into [even] (slab 0) and [odd] (slab 1) for a two-slab frame.
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o r -- python bench.py --profile-run --streams 1
     python scripts/kernel_call_stats.py DIR/.../r_kernel_trace.csv out.csv
 What profiles/r07_trim_*_kernel_calls.csv were made with (220 calls per launch, the last 147 kept)."""
@@ -19,7 +19,7 @@ for n, v in per.items():
     v.sort()
     d = [x[1] for x in v]
     groups = {'': d}
-    if n.startswith('gsr::expand_kernel') or n.startswith('gsr::sh_colour_listed_kernel'):
+    if n.startswith(('gsr::expand_kernel', 'gsr::sh_colour_listed_kernel', 'gsr::blend_quadrant_kernel')):
         groups = {'[even]': d[0::2], '[odd]': d[1::2]}
     for g, dd in groups.items():
         dd = dd[len(dd) // 3:]   # drop the warm-up calls
