@@ -1,6 +1,7 @@
 """The HIP densification without a GPU: ``plan_host`` and the Python surgery against the reference's own ``GaussianModel`` (where
-its tree is mounted) and against recorded runs of it (tests/golden/densify/ref_*.npz, always), the hook rows, ``kernel_takes`` rule by
-rule, the C ABI's refusals."""
+its tree is mounted) and against recorded runs of it (tests/golden/densify/ref_*.npz, always), the restated method of the GPU tests
+against the host path on non-finite rows and on rows of chosen classes (with the non-finite rules spelled out on ``plan_host``'s
+masks), the hook rows, ``kernel_takes`` rule by rule, the C ABI's refusals."""
 from __future__ import annotations
 
 import glob
@@ -170,6 +171,107 @@ def test_restated_model_of_the_tests_equals_the_host_path():
         D.densify_and_prune_host(b, THR, MIN_OP, 5.0, mss)
         C.assert_same(C.snapshot(a), C.snapshot(b))
         assert torch.equal(rng, torch.get_rng_state())
+
+
+# --- non-finite rows and runs of one class: the truth of the GPU tests holds on them ---
+
+def both_on_the_cpu(base, mss, extent=5.0):
+    a, b = C.twin(base), C.twin(base)
+    torch.manual_seed(1)
+    a.reference_densify_and_prune(THR, MIN_OP, extent, mss)
+    rng = torch.get_rng_state()
+    torch.manual_seed(1)
+    assert D.kernel_takes(b, THR, MIN_OP, extent, mss, device_type="cpu")
+    D.densify_and_prune_host(b, THR, MIN_OP, extent, mss)
+    got = C.snapshot(b)
+    C.assert_same(C.snapshot(a), got)
+    assert torch.equal(rng, torch.get_rng_state())
+    return got
+
+
+@pytest.mark.parametrize("n, degree, steps", [(128, 3, 1), (3000, 3, 1), (5000, 0, 0)])
+def test_non_finite_rows_restated_method_equals_the_host_path(n, degree, steps):
+    base, _ = C.non_finite_model(n, degree, steps)
+    for mss, extent in ((None, 5.0), (20, 5.0), (20, 100.0)):             # extent 100: the clone bound is exp(0)
+        got = both_on_the_cpu(base, mss, extent)
+        assert any(bool(v.isnan().any()) for v in got.values()) and got["xyz"].shape[0] != n
+
+
+@pytest.mark.parametrize("n", [3000, 5000])
+def test_non_finite_rows_are_classified_by_the_rules(n):
+    """What gaussian_model.py:399-411 does with a NaN or an infinity, said once more, row kind by row kind, about plan_host's masks."""
+    m, rows = C.non_finite_model(n, 0, 0)
+    injected = torch.cat(list(rows.values()))
+    assert injected.unique().numel() == injected.numel() and {0, 63, 64, 1023, 1024} <= set(injected.tolist())
+    scaling, opacity = m._scaling.detach(), m._opacity.detach()
+    big = torch.exp(scaling).max(dim=1).values
+    small, large = big <= 0.05, big > 0.05
+    dim = (torch.sigmoid(opacity) < MIN_OP).reshape(-1)
+    hot = (m.xyz_gradient_accum >= THR).reshape(-1)
+    for ws in (None, 0.5):
+        plan = D.plan_host(m.xyz_gradient_accum, m.denom, scaling, opacity, THR, 0.05, MIN_OP, ws)
+        keep, clone, split = plan["keep"], plan["clone"], plan["split"]
+        wide = big > ws if ws else torch.zeros(n, dtype=torch.bool)
+        at = lambda *kinds: torch.cat([rows[k] for k in kinds])
+        # any NaN in a scale: the largest scale is NaN, every comparison with it is false
+        r = at("scaling.nan.0", "scaling.nan.1", "scaling.nan.2", "scaling.nan0.+inf2")
+        assert hot[r].any() and not hot[r].all() and scaling[r].isnan().any(dim=1).all()
+        assert not clone[r].any() and not split[r].any() and torch.equal(keep[r], ~dim[r]) and not dim[r].all()
+        # g = NaN is g = 0
+        r = at("accum.nan", "denom.0.accum0", "denom.nan", "denom.+inf.accum+inf")
+        assert (m.xyz_gradient_accum[r] / m.denom[r]).isnan().all() and not clone[r].any() and not split[r].any()
+        assert torch.equal(keep[r], ~dim[r] & ~wide[r])
+        # a negative gradient: its norm clones a small row, the gradient itself splits nothing
+        r = at("accum.negative", "accum.-inf")
+        assert small[r].any() and large[r].any() and not split[r].any()
+        assert torch.equal(clone[r], small[r] & ~dim[r]) and clone[r].any() and torch.equal(keep[r], ~dim[r] & ~wide[r])
+        # an infinite gradient is hot
+        r = at("accum.+inf", "denom.0.accum+")
+        assert torch.equal(split[r], large[r]) and torch.equal(clone[r], small[r] & ~dim[r]) and split[r].any() and clone[r].any()
+        # an infinite scale is large, a zero scale (exp(-inf)) leaves the other two to decide
+        r = at("scaling.+inf.0", "scaling.+inf.1", "scaling.+inf.2")
+        assert torch.equal(split[r], hot[r]) and not clone[r].any() and torch.equal(keep[r], ~hot[r] & ~dim[r] & ~wide[r])
+        assert wide[r].all() if ws else not wide[r].any()
+        r = at("scaling.-inf.0", "scaling.-inf.1", "scaling.-inf.2")
+        assert torch.equal(split[r], hot[r] & large[r]) and torch.equal(clone[r], hot[r] & small[r] & ~dim[r]) and split[r].any()
+        # sigmoid(NaN) < min_opacity is false; sigmoid(-inf) = 0, sigmoid(+inf) = 1
+        r = at("opacity.nan", "opacity.+inf")
+        assert not dim[r].any() and (keep[r] | split[r] | wide[r]).all()
+        r = rows["opacity.-inf"]
+        assert dim[r].all() and not keep[r].any() and not clone[r].any() and torch.equal(split[r], hot[r] & large[r])
+        for mask in (keep, clone, split, ~keep & ~split):
+            assert mask[injected].any()
+    # exp(0) on the clone bound (percent_dense * extent = 1): `<=` clones, nothing splits
+    r = rows["scaling.exp0"]
+    plan = D.plan_host(m.xyz_gradient_accum, m.denom, scaling, opacity, THR, 0.01 * 100.0, MIN_OP, 0.1 * 100.0)
+    assert bool((big[r] == 1.0).all()) and torch.equal(plan["clone"][r], hot[r] & ~dim[r]) and plan["clone"][r].any() and not plan["split"][r].any()
+
+
+LAYOUT_N = 4096 + 37
+LAYOUTS = ([(name, 3 if name == "mod7" else 0, LAYOUT_N) for name in C.run_layouts(8)]
+           + [(f"seam{k}", degree, 0) for k in (1047, 1048, 1049) for degree in (2, 1)] + [("only_children", 2, 0), ("no_child", 1, 0), ("scanA", 0, 262_145 + 1024)])
+
+
+def layout(name, n):
+    """The class list of a named layout (the GPU tests build theirs here too)."""
+    if name.startswith("seam"):
+        return C.seam_layout(int(name[4:]), seed=int(name[4:]))
+    if name in ("only_children", "no_child"):
+        return torch.full((300,), C.SPLIT if name == "only_children" else C.SPLIT_PRUNED)
+    if name.startswith("scan"):
+        return C.scan_layouts(n)[name[4:]]
+    return C.run_layouts(n)[name]
+
+
+@pytest.mark.parametrize("name, degree, n", LAYOUTS, ids=[f"{name}-d{d}" for name, d, _ in LAYOUTS])
+def test_rows_of_chosen_classes_restated_method_equals_the_host_path(name, degree, n):
+    cls = layout(name, n)
+    base = C.rows_of_classes(cls, degree, seed=3, steps=1 if degree else 0)   # asserts plan_host's three masks are these classes
+    for mss in (None, 20):
+        got = both_on_the_cpu(base, mss)
+        assert got["xyz"].shape[0] == C.rows_left(cls, mss)
+    if name.startswith("seam"):
+        assert got["xyz"].shape[0] == int(name[4:]) + 1000
 
 
 # --- the hook rows ---

@@ -11,21 +11,21 @@ from autovfx_amd import densify as D
 from autovfx_amd import optim as O
 
 import densify_cases as C
-from test_densify import FIXTURES, fixture_call, inject_samples, model_from_fixture
+from test_densify import FIXTURES, fixture_call, inject_samples, layout, model_from_fixture
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 THR, MIN_OP, EXTENT = 0.0002, 0.005, 5.0
 
 
-def run_both(base, mss, thr=THR):
+def run_both(base, mss, thr=THR, extent=EXTENT):
     a, b = C.twin(base), C.twin(base)
     torch.manual_seed(1)
-    a.reference_densify_and_prune(thr, MIN_OP, EXTENT, mss)
+    a.reference_densify_and_prune(thr, MIN_OP, extent, mss)
     rng = torch.cuda.get_rng_state()
     torch.manual_seed(1)
-    assert D.kernel_takes(b, thr, MIN_OP, EXTENT, mss) == (base._xyz.shape[0] >= 2)
-    D.densify_and_prune(b, thr, MIN_OP, EXTENT, mss)
+    assert D.kernel_takes(b, thr, MIN_OP, extent, mss) == (base._xyz.shape[0] >= 2)
+    D.densify_and_prune(b, thr, MIN_OP, extent, mss)
     assert torch.equal(rng, torch.cuda.get_rng_state())
     want, got = C.snapshot(a), C.snapshot(b)
     C.assert_same(want, got)
@@ -84,7 +84,8 @@ def test_no_clones_no_splits_nothing_left():
 def test_recorded_reference_runs_on_the_gpu(path, monkeypatch):
     """Rows, order and every copied field bit-equal to the reference's CPU run; the two computed fields (children's xyz, scaling)
     cross from glibc's exp / log to the device's: both are compared with an fp64 evaluation, and the drop-in's largest error may be
-    at most twice the fixture's own plus one ulp of the value."""
+    at most twice the fixture's own plus one ulp of the value, wherever the truth is finite; where it is not (ref_d: a scale of
+    exp(-inf) = 0 has the children's log(0 / 1.6) = -inf), the fixture and the drop-in hold the same NaN or the same infinity."""
     z = np.load(path)
     host = model_from_fixture(z)
     inject_samples(monkeypatch, z)
@@ -105,9 +106,9 @@ def test_recorded_reference_runs_on_the_gpu(path, monkeypatch):
         assert want[key].shape == got[key].shape, key
         if key in ("xyz", "scaling"):
             front = want[key].shape[0] - n_children
-            assert torch.equal(want[key][:front], got[key][:front]), key
+            C.assert_same_tensor(want[key][:front], got[key][:front], key)
         else:
-            assert torch.equal(want[key], got[key]), key
+            C.assert_same_tensor(want[key], got[key], key)
     # fp64 truth of the children from the fixture's inputs and samples
     src = {k: torch.from_numpy(z["in." + k]).double() for k in ("xyz", "scaling", "rotation", "accum", "denom")}
     rots = D._build_rotation(src["rotation"][sidx]).repeat(2, 1, 1)
@@ -117,10 +118,15 @@ def test_recorded_reference_runs_on_the_gpu(path, monkeypatch):
     for key in ("xyz", "scaling"):
         t = truth[key]
         ulp = torch.abs(torch.nextafter(t.float(), torch.full_like(t.float(), float("inf"))) - t.float()).double()
-        err_fixture = (want[key][-n_children:].double() - t).abs()
-        err_ours = (got[key][-n_children:].double() - t).abs()
-        print(f"{path.split('_')[-1]} {key}: largest error fixture {err_fixture.max():.3e} drop-in {err_ours.max():.3e}")
-        assert bool((err_ours <= 2 * err_fixture.max() + ulp).all()), key
+        finite = t.isfinite()
+        for name, kids in (("fixture", want[key][-n_children:].double()), ("drop-in", got[key][-n_children:].double())):
+            assert torch.equal(kids.isnan(), t.isnan()) and torch.equal(kids[~finite & ~t.isnan()], t[~finite & ~t.isnan()]), (key, name)
+        err_fixture = (want[key][-n_children:].double() - t).abs()[finite]
+        err_ours = (got[key][-n_children:].double() - t).abs()[finite]
+        print(f"{path.split('_')[-1]} {key}: largest error fixture {err_fixture.max():.3e} drop-in {err_ours.max():.3e}, {int((~finite).sum())} non-finite")
+        assert bool((err_ours <= 2 * err_fixture.max() + ulp[finite]).all()), key
+    if path.endswith("ref_d.npz"):
+        assert not truth["scaling"].isfinite().all() and got["scaling"].isnan().any() and got["opacity"].isnan().any()
 
 
 def stats_inputs(n, share, seed=0, cols=3):
@@ -201,26 +207,33 @@ def test_apply_writes_every_element():
         C.assert_same(C.snapshot(a), C.snapshot(b))
 
 
+def plan_kernel_against_plan_host(base, ws, thr=THR, dense=0.01 * EXTENT):
+    """One gsr_densify_plan call on the model's tensors: counts, both index lists, and nothing written behind them."""
+    n = base._xyz.shape[0]
+    want = D.plan_host(base.xyz_gradient_accum, base.denom, base._scaling.detach(), base._opacity.detach(), thr, dense, MIN_OP, ws)
+    L = _lib.lib
+    room = L.gsr_densify_plan_scratch_bytes(n)
+    scratch = torch.empty(room, dtype=torch.uint8, device=DEV)
+    src_of = torch.full((2 * n,), -7, dtype=torch.int32, device=DEV)
+    split_idx = torch.full((n,), -7, dtype=torch.int32, device=DEV)
+    counts = torch.full((4,), -7, dtype=torch.int32, device=DEV)
+    rc = L.gsr_densify_plan(n, base.xyz_gradient_accum.data_ptr(), base.denom.data_ptr(), base._scaling.data_ptr(), base._opacity.data_ptr(),
+                            O._f32(thr), O._f32(dense), O._f32(MIN_OP), 0 if ws is None else 1, O._f32(ws or 0.0), src_of.data_ptr(),
+                            split_idx.data_ptr(), counts.data_ptr(), scratch.data_ptr(), room, torch.cuda.current_stream().cuda_stream)
+    assert rc == 0, _lib.last_error()
+    k, c, s, z = counts.tolist()
+    assert [k, c, s, z] == want["counts"].tolist()
+    assert torch.equal(src_of[:k + c].cpu(), want["src_of"].cpu()) and torch.equal(split_idx[:s].cpu(), want["split_idx"].cpu())
+    assert bool((src_of[k + c:] == -7).all()) and bool((split_idx[s:] == -7).all())
+    return want
+
+
 def test_plan_kernel_equals_plan_host():
     for n in (2, 1023, 1024, 1025, 262_145 + 77):
         base = C.Model(C.random_tensors(n, 0, n % 50, DEV))
         C.fill_stats(base)
         for ws in (None, 0.1 * EXTENT):
-            want = D.plan_host(base.xyz_gradient_accum, base.denom, base._scaling.detach(), base._opacity.detach(), THR, 0.01 * EXTENT, MIN_OP, ws)
-            L = _lib.lib
-            room = L.gsr_densify_plan_scratch_bytes(n)
-            scratch = torch.empty(room, dtype=torch.uint8, device=DEV)
-            src_of = torch.full((2 * n,), -7, dtype=torch.int32, device=DEV)
-            split_idx = torch.full((n,), -7, dtype=torch.int32, device=DEV)
-            counts = torch.full((4,), -7, dtype=torch.int32, device=DEV)
-            rc = L.gsr_densify_plan(n, base.xyz_gradient_accum.data_ptr(), base.denom.data_ptr(), base._scaling.data_ptr(), base._opacity.data_ptr(),
-                                    O._f32(THR), O._f32(0.01 * EXTENT), O._f32(MIN_OP), 0 if ws is None else 1, O._f32(ws or 0.0), src_of.data_ptr(),
-                                    split_idx.data_ptr(), counts.data_ptr(), scratch.data_ptr(), room, torch.cuda.current_stream().cuda_stream)
-            assert rc == 0, _lib.last_error()
-            k, c, s, z = counts.tolist()
-            assert [k, c, s, z] == want["counts"].tolist()
-            assert torch.equal(src_of[:k + c].cpu(), want["src_of"].cpu()) and torch.equal(split_idx[:s].cpu(), want["split_idx"].cpu())
-            assert bool((src_of[k + c:] == -7).all()) and bool((split_idx[s:] == -7).all())
+            plan_kernel_against_plan_host(base, ws)
 
 
 @pytest.mark.parametrize("opt_cls", [torch.optim.Adam, O.Adam], ids=["torch_adam", "gsr_adam"])
@@ -243,3 +256,117 @@ def test_thirty_iterations_with_densification_match_the_restated_loop(opt_cls):
         runs.append((C.snapshot(m), torch.cuda.get_rng_state()))
     C.assert_same(runs[0][0], runs[1][0])
     assert torch.equal(runs[0][1], runs[1][1]) and runs[1][0]["xyz"].shape[0] > 20_000
+
+
+# --- non-finite rows, runs of one class, the seams of the scan, apply and stats kernels ---
+
+@pytest.mark.parametrize("mss", [None, 20])
+@pytest.mark.parametrize("opt_cls", [torch.optim.Adam, O.Adam], ids=["torch_adam", "gsr_adam"])
+def test_non_finite_rows_equal_the_restated_method(opt_cls, mss):
+    """NaN and both infinities in the statistics, the scales and the opacities (densify_cases.inject_non_finite), moments present.
+    At extent 100 the clone bound is exp(0), which the ``scaling.exp0`` rows sit on."""
+    base, _ = C.non_finite_model(5000, 3, 1, device=DEV, opt_cls=opt_cls)
+    for extent in (EXTENT, 100.0):
+        got = run_both(base, mss, extent=extent)
+        assert got["scaling"].isnan().any() and got["opacity"].isnan().any() and got["xyz"].shape[0] != 5000
+
+
+def test_non_finite_rows_plan_kernel_equals_plan_host():
+    """The plan kernel alone on the same rows.  With a threshold of 0, which ``kernel_takes`` never lets through to the kernels, g = 0
+    passes the gradient tests and g = NaN would not: the one setting at which ``grads[grads.isnan()] = 0.0`` is visible in the plan."""
+    base, rows = C.non_finite_model(5000, 3, 1, device=DEV)
+    for thr, extent, ws in ((THR, EXTENT, False), (THR, EXTENT, True), (THR, 100.0, True), (0.0, EXTENT, False), (0.0, EXTENT, True)):
+        want = plan_kernel_against_plan_host(base, 0.1 * extent if ws else None, thr, 0.01 * extent)
+        assert all(c > 0 for c in want["counts"].tolist()[:3])
+    r = torch.cat([rows[k] for k in ("accum.nan", "denom.0.accum0", "denom.nan", "denom.+inf.accum+inf")]).to(DEV)
+    assert bool((want["clone"][r] | want["split"][r] | ~want["keep"][r]).all())   # at threshold 0 these rows are hot
+
+
+RUN_N = 5000 + 37
+
+
+@pytest.mark.parametrize("name", list(C.run_layouts(8)))
+def test_runs_of_one_class_equal_the_restated_method(name):
+    """Waves, quarter workgroups and whole workgroups of one class; all rows of one class; a class on the last wave or the two end rows
+    only: ballots of all zeros and all ones, per-wave counts of 0 and 64, workgroup counts of 0 and 1024."""
+    cls = layout(name, RUN_N)
+    degree = 3 if name == "mod7" else 0
+    base = C.rows_of_classes(cls, degree, seed=4, device=DEV, steps=1 if degree else 0)
+    for mss in (None, 20):
+        plan_kernel_against_plan_host(base, 0.1 * EXTENT if mss else None)
+        assert run_both(base, mss)["xyz"].shape[0] == C.rows_left(cls, mss)
+
+
+@pytest.mark.parametrize("name", ["scanA", "scanB", "scanC"])
+def test_scan_carry_across_its_step_of_256_workgroups(name):
+    n = 262_144 + 1024 + 5                                                  # 258 workgroups: two steps of the scan kernel
+    cls = layout(name, n)
+    base = C.rows_of_classes(cls, 0, seed=5, device=DEV)
+    for mss in (None, 20):
+        plan_kernel_against_plan_host(base, 0.1 * EXTENT if mss else None)
+        assert run_both(base, mss)["xyz"].shape[0] == C.rows_left(cls, mss)
+
+
+def run_poisoned(base, mss):
+    """run_both with every fp32 output pre-filled with 0xFF bytes (as test_apply_writes_every_element does)."""
+    real_empty = torch.empty
+
+    def poisoned(*a, **k):
+        t = real_empty(*a, **k)
+        if t.is_cuda and t.dtype == torch.float32:
+            t.view(torch.uint8).fill_(0xFF)
+        return t
+
+    a, b = C.twin(base), C.twin(base)
+    torch.manual_seed(2)
+    a.reference_densify_and_prune(THR, MIN_OP, EXTENT, mss)
+    torch.manual_seed(2)
+    torch.empty = poisoned
+    try:
+        D.densify_and_prune(b, THR, MIN_OP, EXTENT, mss)
+    finally:
+        torch.empty = real_empty
+    C.assert_same(C.snapshot(a), C.snapshot(b))
+
+
+@pytest.mark.parametrize("degree", [2, 1])
+@pytest.mark.parametrize("name, rows", [("seam1047", 2047), ("seam1048", 2048), ("seam1049", 2049), ("only_children", 600), ("no_child", 0)])
+def test_apply_at_chunk_ends_and_generic_row_widths(name, rows, degree):
+    """f_rest of 24 and 9 floats (the apply kernel's generic width) with moments; results of 2047, 2048 and 2049 rows: at 2048 every
+    tensor of every width ends on a chunk of 2048 floats; a result of children only (n_keep = 0) and one of no rows at all."""
+    cls = layout(name, 0)
+    base = C.rows_of_classes(cls, degree, seed=6, device=DEV, steps=1)
+    assert base._features_rest[0].numel() == {2: 24, 1: 9}[degree]
+    for mss in (None, 20):
+        assert run_both(base, mss)["xyz"].shape[0] == rows == C.rows_left(cls, mss)
+        run_poisoned(base, mss)
+
+
+@pytest.mark.parametrize("radii, off", [(True, 0), (False, 0), (True, 1)], ids=["radii", "no_radii", "radii_offset_by_one"])
+def test_stats_grid_stride_walk(radii, off):
+    """More rows than one pass of the stats kernel's largest grid covers (2048 * 4 workgroups * 256 lanes * 4 rows = 8 388 608), against
+    torch's boolean-index lines on the device; ``off`` = 1 starts every array one element in, which takes the scalar path."""
+    n = 8_388_608 + 4099
+    g = torch.Generator(device=DEV).manual_seed(9)
+    grad = (torch.randn(n + 1, 3, device=DEV, generator=g) * 1e-3)[off:off + n]
+    f = (torch.rand(n + 1, device=DEV, generator=g) < 0.3)[off:off + n]
+    a = torch.rand(n + 1, 1, device=DEV, generator=g)[off:off + n]
+    d = torch.randint(0, 5, (n + 1, 1), device=DEV, generator=g).float()[off:off + n]
+    r = torch.randint(0, 90, (n + 1,), device=DEV, generator=g, dtype=torch.int32)[off:off + n]
+    mr = (torch.rand(n + 1, device=DEV, generator=g) * 60)[off:off + n]
+    assert all(t.is_contiguous() and (t.data_ptr() % 16 != 0) == bool(off) for t in (grad, a, d, r, mr)) and f.data_ptr() % 4 == off
+    assert bool(f[8_388_608:].any()) and not bool(f[8_388_608:].all())
+    wa, wd, wm = a.clone(), d.clone(), mr.clone()
+    if not radii:
+        r = mr = None
+    wa[f] += torch.norm(grad[f, :2], dim=-1, keepdim=True)
+    wd[f] += 1
+    if radii:
+        wm[f] = torch.max(wm[f], r[f].float())
+    torch.cuda.synchronize()
+    torch.cuda.set_sync_debug_mode("error")
+    try:
+        D.accumulate_stats(grad, f, a, d, r, mr)
+    finally:
+        torch.cuda.set_sync_debug_mode("default")
+    assert torch.equal(wa, a) and torch.equal(wd, d) and (mr is None or torch.equal(wm, mr))
