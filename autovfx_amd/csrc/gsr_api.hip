@@ -1,7 +1,9 @@
 // gsr_api.hip -- the host orchestration of the rasterizer behind the C ABI (include/gsr.h): gsr_forward*, gsr_plan_slabs,
 // gsr_backward*, gsr_blend, the options, the stage timing and the gsr_last_* accessors, gsr_upload, and the error message every
 // unit's entry points set (gsr::fail, gsr_last_error).  Every other entry point is defined at the end of the unit that holds its
-// kernels; adding one touches that unit, include/gsr.h and the binding's signature table.
+// kernels; adding one touches that unit, include/gsr.h and the binding's signature table.  What a forward call leaves for
+// gsr_backward and gsr_blend goes through one pair of functions: scratch_headers writes the three arena headers, open_scratch
+// reads and validates them into a ScratchView; a call's own state (timing slot, pinned slot, camera) lives on its ForwardCall.
 //
 // Mirrors what CudaRasterizer::Rasterizer::forward does on the host
 // (DGR/cuda_rasterizer/rasterizer_impl.cu:197-339): carve scratch out of caller-provided arenas
@@ -35,14 +37,48 @@ struct PinnedSlot {
     hipEvent_t copied = nullptr;  // freed: freeing at thread exit can race HIP runtime teardown
     hipEvent_t finished = nullptr;
 };
-thread_local std::vector<PinnedSlot> g_pinned_free;
-thread_local std::vector<PinnedSlot> g_pinned_draining;  // retired slots whose last copy / `finished` event may still be pending
-thread_local PinnedSlot g_last_slot;           // holds the slab table of the call that finished last on this thread
-thread_local uint32_t g_last_num_rendered = 0; // ... its reference pair count
-thread_local int g_last_slabs = 0;             // ... and how many slabs it used (0: nothing to wait for)
 constexpr size_t kCounterBytes = gsr::kCounterCopyBytes;          // what travels back to the host in the middle of a call
 constexpr size_t kSlabTableAt = (kCounterBytes + 63) & ~size_t(63);  // byte offset of the slab table in a pinned slot
 constexpr size_t kPinnedBytes = kSlabTableAt + sizeof(gsr::SlabInfo) * gsr::kMaxSlabs;
+// The slots of one calling thread: every forward call acquires one, and gives it back one of two ways.
+struct PinnedPool {
+    std::vector<PinnedSlot> free;
+    std::vector<PinnedSlot> draining;  // retired slots whose last copy / `finished` event may still be pending
+    PinnedSlot last;                   // holds the slab table of the call that finished last on this thread
+    // A retired slot goes back to the free list only once its `finished` event has completed: its slab-table copy may still
+    // be in flight on ANOTHER stream (several streams fed by one thread), and a new call on this stream must neither
+    // share that host buffer nor re-record that event.
+    int acquire(PinnedSlot& slot) {
+        for (size_t i = 0; i < draining.size();) {
+            if (hipEventQuery(draining[i].finished) != hipSuccess) { ++i; continue; }   // (an error is not "complete": the slot stays parked)
+            free.push_back(draining[i]);
+            draining[i] = draining.back();
+            draining.pop_back();
+        }
+        if (!free.empty()) { slot = free.back(); free.pop_back(); return GSR_OK; }
+        GSR_HIP(hipHostMalloc((void**)&slot.host, kPinnedBytes, hipHostMallocPortable | hipHostMallocMapped));
+        if (hipHostGetDevicePointer(&slot.dev, slot.host, 0) != hipSuccess) { (void)hipGetLastError(); slot.dev = nullptr; }
+        GSR_HIP(hipEventCreateWithFlags(&slot.copied, hipEventDisableTiming));
+        GSR_HIP(hipEventCreateWithFlags(&slot.finished, hipEventDisableTiming));
+        return GSR_OK;
+    }
+    // The slot of a call that did not complete (cancelled, or failed part way).  Kernels already queued on the stream
+    // (`in_flight`) may still store into it (the totals; the slab table written by bin_offsets / slab_compact): it goes back to
+    // the free list only after an event behind everything queued so far has completed -- no host wait.
+    void retire_behind_event(const PinnedSlot& slot, bool in_flight, hipStream_t stream) {
+        if (!in_flight) free.push_back(slot);
+        else if (hipEventRecord(slot.finished, stream) == hipSuccess) draining.push_back(slot);
+        // (an event that cannot be recorded means the device is gone: the few KB of pinned memory are abandoned)
+    }
+    // The slot of a call that finished, its `finished` event recorded: what gsr_last_slab_pairs reads until the next call finishes.
+    void adopt_as_last(PinnedSlot& slot) {
+        if (last.host) draining.push_back(last);  // (its copy may still be pending on another stream)
+        last = slot; slot = PinnedSlot();
+    }
+};
+thread_local PinnedPool g_pinned;
+thread_local uint32_t g_last_num_rendered = 0; // the reference pair count of the call that finished last on this thread
+thread_local int g_last_slabs = 0;             // ... and how many slabs it used (0: nothing to wait for)
 
 // Stage timing: a ring of event sets so a whole timed region can be averaged afterwards without
 // synchronising between calls.  Events of one call: start, after projection, after the depth sort, after the host
@@ -65,8 +101,6 @@ thread_local bool g_ev_made = false;
 thread_local long g_timed_calls = 0;   // completed timed calls since timing was (re)enabled
 thread_local long g_begun_calls = 0;   // timed calls begun since then: several may be in flight (split calls), each owns a slot
 thread_local int g_inflight = 0;       // timed calls begun and not yet finished / cancelled
-thread_local bool g_stamp = false;     // whether the call being queued records events
-thread_local int g_slot = 0;           // ring slot of the call being queued
 
 // Backward timing: process-wide (autograd calls gsr_backward from its own thread), guarded by a mutex.
 constexpr int kBackwardRing = 64;
@@ -76,6 +110,7 @@ bool g_bw_made = false;
 bool g_bw_done[kBackwardRing];   // the slot's three events have all been recorded
 long g_bw_begun = 0;             // timed backward calls begun since timing was (re)enabled: each reserves its own slot
 long g_bw_calls = 0;             // ... and completed
+void trim_det_pools();           // (the deterministic backward's memory pools, below)
 
 // After each stage in debug mode: the CHECK_CUDA of auxiliary.h:166-173.
 #define GSR_STAGE_CHECK(name)                                                                  \
@@ -146,10 +181,18 @@ int tile_key_bits(uint32_t num_tiles) {
     return b;  // bit_length(T) >= bit_length(T - 1): every tile id fits
 }
 
-
-void stamp(int idx, hipStream_t s) {
-    if (!g_stamp) return;
-    (void)hipEventRecord(g_ev[g_slot][idx], s);
+// rasterizer_impl.cu:223-224 (forward), :390-391 (backward); gsr_blend and gsr_plan_slabs read the sizes alone and bring no matrices
+gsr::Camera make_camera(int width, int height, float tan_fovx, float tan_fovy, const float* viewmatrix, const float* projmatrix,
+                        const float* cam_pos) {
+    gsr::Camera cam;
+    cam.viewmatrix = viewmatrix; cam.projmatrix = projmatrix; cam.cam_pos = cam_pos;
+    cam.tan_fovx = tan_fovx; cam.tan_fovy = tan_fovy;
+    cam.focal_y = height / (2.0f * tan_fovy);
+    cam.focal_x = width / (2.0f * tan_fovx);
+    cam.width = width; cam.height = height;
+    cam.grid_x = (width + gsr::kTile - 1) / gsr::kTile;
+    cam.grid_y = (height + gsr::kTile - 1) / gsr::kTile;
+    return cam;
 }
 
 } // namespace
@@ -168,7 +211,6 @@ const char* gsr_last_error(void) { return g_error; }
 int gsr_abi_version(void) { return GSR_ABI_VERSION; }
 const char* gsr_target_arch(void) { return "gfx950"; }
 
-static void trim_det_pools();
 int gsr_set_option(int option, int value) {
     if (option < 0 || option >= GSR_OPT_NUM) return fail(GSR_ERR_INVALID_ARG, "unknown option %d", option);
     if (option == GSR_OPT_RADIX_RANK_ACTIVE) return fail(GSR_ERR_INVALID_ARG, "GSR_OPT_RADIX_RANK_ACTIVE is read-only");
@@ -313,8 +355,8 @@ int gsr_last_slab_pairs(uint32_t pairs[GSR_MAX_SLABS]) {
     if (!g_have_offsets) return fail(GSR_ERR_INVALID_ARG, "no gsr_forward call on this thread");
     for (int i = 0; i < GSR_MAX_SLABS; ++i) pairs[i] = 0u;
     if (g_last_slabs == 0) return 0;
-    GSR_HIP(hipEventSynchronize(g_last_slot.finished));  // the call's last copy has landed
-    const gsr::SlabInfo* t = reinterpret_cast<const gsr::SlabInfo*>(reinterpret_cast<const char*>(g_last_slot.host) + kSlabTableAt);
+    GSR_HIP(hipEventSynchronize(g_pinned.last.finished));  // the call's last copy has landed
+    const gsr::SlabInfo* t = reinterpret_cast<const gsr::SlabInfo*>(reinterpret_cast<const char*>(g_pinned.last.host) + kSlabTableAt);
     for (int i = 0; i < g_last_slabs; ++i) pairs[i] = t[i].pairs;
     return g_last_slabs;
 }
@@ -333,7 +375,6 @@ int gsr_last_image_offsets(size_t o[GSR_IMG_NUM_SLOTS]) {
     return GSR_OK;
 }
 
-
 } // extern "C"
 
 namespace {
@@ -346,17 +387,15 @@ std::mutex g_det_pool_mutex;
 hipMemPool_t g_det_pool[kMaxPoolDevices] = {};
 bool g_det_pool_tried[kMaxPoolDevices] = {};
 
-} // namespace
 // Switching GSR_OPT_BACKWARD_DETERMINISTIC off releases what its pools hold (after one call at C3 the library kept
 // 1.4 GB per device outside the host framework's allocator for the life of the process).  While the option is on the pools keep
 // their memory between calls -- that is what they are for.
-static void trim_det_pools() {
+void trim_det_pools() {
     std::lock_guard<std::mutex> lock(g_det_pool_mutex);
     for (int d = 0; d < kMaxPoolDevices; ++d)
         if (g_det_pool[d] != nullptr) (void)hipMemPoolTrimTo(g_det_pool[d], 0);
     (void)hipGetLastError();
 }
-namespace {
 
 hipError_t det_alloc(void** ptr, size_t bytes, hipStream_t stream) {
     int dev = 0;
@@ -387,6 +426,75 @@ hipError_t det_alloc(void** ptr, size_t bytes, hipStream_t stream) {
     }
     return hipMallocAsync(ptr, bytes, stream);   // (a runtime without pools of one's own: the device's default pool)
 }
+struct DetAllocation {   // gives the call's buffers back to the pool on every path, behind what the call queued
+    char* raw = nullptr; hipStream_t stream = nullptr;
+    ~DetAllocation() { if (raw != nullptr) (void)hipFreeAsync(raw, stream); }
+};
+
+// What gsr_backward and gsr_blend know about the three arenas of a forward call: read out of the arenas' headers by
+// open_scratch, which stands next to the function that writes them (scratch_headers, below).
+struct ScratchView {
+    const char* base[3];             // geometry, binning, image: the aligned bases
+    uint32_t P, R, W, H;             // Gaussians, the reference's pair count, image size
+    int S; bool inference;           // depth slabs; whether the call was a GSR_FORWARD_INFERENCE one
+    const gsr::SplatRaster* raster;
+    const float *rgb, *view_normals; // view_normals null: the call composited none
+    const int* radii;                // the internal radii
+    const gsr::SlabInfo* slabs;      // the slab table on the device
+    uint32_t* n_contrib;
+    gsr::BlendSegments segs;         // the lists and tile ranges of the S slabs
+    uint32_t list_room;              // room of slab 0's list (>= its pairs)
+};
+int open_scratch(ScratchView& v, const char* geom, const char* binning, const char* image, hipStream_t stream, bool force_device_read);
+
+// GSR_OPT_BACKWARD_DETERMINISTIC: per-Gaussian sums in a fixed order (gsr_backward.hip: kDet).  The per-pixel passes store one
+// record per (list position, quadrant), the point list is sorted by Gaussian id (stable: a Gaussian's positions ascend) and one
+// lane per Gaussian adds its records in that order (one list per tile: S = 1).  Buffers come from the library's pool for the call.
+int accumulate_deterministic(const ScratchView& v, const gsr::Camera& cam, const float* background, const float* colors,
+                             const float* accum_alphas, const float* dL_dpix, const float* dL_dpix_depth, const float* dL_dpix_alpha,
+                             const float* dL_dpix_normal, float* accum_scratch, hipStream_t stream) {
+    const int P = (int)v.P;
+    const uint32_t bound = v.list_room;
+    const uint32_t* n_device = &v.slabs->pairs;
+    const int passes = dL_dpix_normal != nullptr ? 2 : 1;
+    int id_bits = 1;
+    while (id_bits < 32 && (1ull << id_bits) < (unsigned long long)P) ++id_bits;
+    Carver dc;
+    const size_t bit_words = ((size_t)bound + 7) / 8;
+    const size_t off_first = dc.take<uint32_t>((size_t)P), off_end = dc.take<uint32_t>((size_t)P);
+    const size_t off_bits = dc.take<uint32_t>(bit_words * passes);
+    const size_t zero_bytes = (dc.off + 255) & ~size_t(255);   // everything up to here must be zero
+    const size_t off_keys = dc.take<uint32_t>(bound), off_keys_alt = dc.take<uint32_t>(bound);
+    const size_t off_pos = dc.take<uint32_t>(bound), off_pos_alt = dc.take<uint32_t>(bound);
+    const size_t off_tmp = dc.take<uint32_t>(gsr::radix_scratch_words(bound));
+    const size_t off_part = dc.take<float>((size_t)bound * 40 * passes);
+    DetAllocation mem{nullptr, stream};
+    GSR_HIP(det_alloc((void**)&mem.raw, dc.total() + 256, stream));
+    char* const dbase = align_base(mem.raw);
+    GSR_HIP(hipMemsetAsync(dbase, 0, zero_bytes, stream));
+    uint32_t* bits1 = (uint32_t*)(dbase + off_bits);
+    float* part1 = (float*)(dbase + off_part);
+    uint32_t* bits2 = passes == 2 ? bits1 + bit_words : nullptr;
+    float* part2 = passes == 2 ? part1 + (size_t)bound * 40 : nullptr;
+    GSR_HIP(gsr::launch_render_backward(cam, v.segs, v.S, background, v.raster, colors, accum_alphas, v.n_contrib, dL_dpix,
+                                        dL_dpix_depth, dL_dpix_alpha, accum_scratch, stream, 0, part1, bits1));
+    if (passes == 2)
+        GSR_HIP(gsr::launch_render_backward(cam, v.segs, v.S, background, v.raster, v.view_normals, accum_alphas, v.n_contrib,
+                                            dL_dpix_normal, nullptr, nullptr, accum_scratch, stream, 10, part2, bits2));
+    uint32_t *ids_sorted = nullptr, *pos_sorted = nullptr;
+    if (bound > 0u) {
+        GSR_HIP(hipMemcpyAsync(dbase + off_keys, v.segs.point_list[0], (size_t)bound * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
+        gsr::RadixSortExtras ex;
+        ex.n_device = n_device;
+        GSR_HIP(gsr::radix_sort_pairs((uint32_t*)(dbase + off_tmp), bound, id_bits, (uint32_t*)(dbase + off_keys),
+                                      (uint32_t*)(dbase + off_keys_alt), (uint32_t*)(dbase + off_pos), (uint32_t*)(dbase + off_pos_alt),
+                                      /*iota_payload=*/true, /*want_sorted_keys=*/true, &ids_sorted, &pos_sorted, stream, ex));
+        GSR_HIP(gsr::launch_det_segments(n_device, ids_sorted, bound, (uint32_t*)(dbase + off_first), (uint32_t*)(dbase + off_end), stream));
+    }
+    GSR_HIP(gsr::launch_det_reduce(P, (const uint32_t*)(dbase + off_first), (const uint32_t*)(dbase + off_end), pos_sorted, bits1, part1,
+                                   bits2, part2, accum_scratch, stream));
+    return GSR_OK;
+}
 
 // gsr_backward and gsr_backward_raw: `raw` != nullptr -> the parameter pointers are the model's raw tensors (raw->xyz in
 // means3D's place, and so on), dL_dsh_rest / dL_dpix_normal belong to that form.
@@ -414,52 +522,24 @@ int backward_impl(int P, int D, int M, int R, const float* background, int width
     if (raw != nullptr && (!shs || !scales || !raw->opacity_logits || (M > 1 && (!raw->features_rest || !dL_dsh_rest))))
         return fail(GSR_ERR_INVALID_ARG, "raw parameters: all six tensors and dL_dfeatures_rest (M > 1) are required");
 
-    const char* bases[3] = {align_base(const_cast<char*>(geom_buffer)), align_base(const_cast<char*>(binning_buffer)),
-                            align_base(const_cast<char*>(image_buffer))};
-    gsr::ArenaHeader h[3];
-    if (debug || !recall_headers(bases, h)) {  // not a forward call this process remembers (or debug): read and validate
-        for (int i = 0; i < 3; ++i) GSR_HIP(hipMemcpyAsync(&h[i], bases[i], sizeof h[i], hipMemcpyDeviceToHost, stream));
-        GSR_HIP(hipStreamSynchronize(stream));
-    }
-    for (int i = 0; i < 3; ++i)
-        if (h[i].magic != gsr::kArenaMagic || h[i].kind != (uint32_t)i)
-            return fail(GSR_ERR_INVALID_ARG, "scratch buffer %d was not produced by gsr_forward", i);
+    ScratchView v;
+    if (const int rc = open_scratch(v, geom_buffer, binning_buffer, image_buffer, stream, /*force_device_read=*/debug != 0)) return rc;
     // The forward call may have been cut into depth slabs (GSR_FORWARD_INFERENCE: what the binding also makes in grad mode under
     // GSR_OPT_GRAD_SLABS): the per-pixel pass walks the slabs' list segments back to front.  Pairs a later slab dropped belong to
     // tiles whose 256 pixels had all stopped: no pixel's last contributor lies behind them, the backward never wanted them.
-    const int S = (int)h[0].count[2];
-    if (S < 1 || S > gsr::kMaxSlabs || h[2].count[3] != (uint32_t)S)
-        return fail(GSR_ERR_INVALID_ARG, "scratch buffers describe %d depth slabs (image arena: %u)", S, h[2].count[3]);
-    if (S > 1 && g_options[GSR_OPT_BACKWARD_DETERMINISTIC] != 0)
+    const bool deterministic = g_options[GSR_OPT_BACKWARD_DETERMINISTIC] != 0;
+    if (v.S > 1 && deterministic)
         return fail(GSR_ERR_INVALID_ARG, "GSR_OPT_BACKWARD_DETERMINISTIC needs the scratch of a forward call with ONE list per tile (this one "
-                                         "has %d depth slabs): set the option before the forward call, or make a full call", S);
-    if (h[0].count[0] != (uint32_t)P || h[0].count[1] != (uint32_t)R || h[2].count[0] != (uint32_t)width ||
-        h[2].count[1] != (uint32_t)height)
+                                         "has %d depth slabs): set the option before the forward call, or make a full call", v.S);
+    if (v.P != (uint32_t)P || v.R != (uint32_t)R || v.W != (uint32_t)width || v.H != (uint32_t)height)
         return fail(GSR_ERR_INVALID_ARG, "scratch buffers belong to a different call (P %u/%d, R %u/%d, %ux%u/%dx%d)",
-                    h[0].count[0], P, h[0].count[1], R, h[2].count[0], h[2].count[1], width, height);
-    if (dL_dpix_normal != nullptr && (raw == nullptr || h[0].off[1] == 0))
+                    v.P, P, v.R, R, v.W, v.H, width, height);
+    if (dL_dpix_normal != nullptr && (raw == nullptr || v.view_normals == nullptr))
         return fail(GSR_ERR_INVALID_ARG, "dL_dpix_normal needs the scratch of a gsr_forward_raw call that composited the normal image");
 
-    gsr::Camera cam;
-    cam.viewmatrix = viewmatrix; cam.projmatrix = projmatrix; cam.cam_pos = cam_pos;
-    cam.tan_fovx = tan_fovx; cam.tan_fovy = tan_fovy;
-    cam.focal_y = height / (2.0f * tan_fovy);  // rasterizer_impl.cu:390-391
-    cam.focal_x = width / (2.0f * tan_fovx);
-    cam.width = width; cam.height = height;
-    cam.grid_x = (width + gsr::kTile - 1) / gsr::kTile;
-    cam.grid_y = (height + gsr::kTile - 1) / gsr::kTile;
-
-    const gsr::SplatRaster* raster = (const gsr::SplatRaster*)(bases[0] + h[0].off[0]);
-    const float* rgb = (const float*)(bases[0] + h[0].off[3]);
-    if (radii == nullptr) radii = (const int*)(bases[0] + h[0].off[4]);
-    gsr::BlendSegments segs = {};
-    for (int k = 0; k < S; ++k) {
-        segs.point_list[k] = (const uint32_t*)(bases[1] + h[1].slab_off[k]);
-        segs.ranges[k] = (const uint2*)(bases[2] + h[2].slab_off[k]);
-    }
-    const uint32_t* point_list = segs.point_list[0];   // (the deterministic mode's id sort: one segment)
-    const uint32_t* n_contrib = (const uint32_t*)(bases[2] + h[2].off[1]);
-    const float* colors = colors_precomp != nullptr ? colors_precomp : rgb;  // rasterizer_impl.cu:399
+    const gsr::Camera cam = make_camera(width, height, tan_fovx, tan_fovy, viewmatrix, projmatrix, cam_pos);
+    if (radii == nullptr) radii = v.radii;
+    const float* colors = colors_precomp != nullptr ? colors_precomp : v.rgb;  // rasterizer_impl.cu:399
 
     int bw_slot = -1;
     if (g_timing) {
@@ -473,70 +553,17 @@ int backward_impl(int P, int D, int M, int R, const float* background, int width
         g_bw_done[bw_slot] = false;
         GSR_HIP(hipEventRecord(g_bw_ev[bw_slot][0], stream));
     }
-    const float* normal_colours = dL_dpix_normal != nullptr ? (const float*)(bases[0] + h[0].off[1]) : nullptr;
-    if (g_options[GSR_OPT_BACKWARD_DETERMINISTIC] != 0) {
-        // Per-Gaussian sums in a fixed order (gsr_backward.hip: kDet): the per-pixel passes store one record per (list position,
-        // quadrant), the point list is sorted by Gaussian id (stable: a Gaussian's positions ascend) and one lane per Gaussian
-        // adds its records in that order.  Buffers come from the stream's pool for the duration of the call.
-        const uint32_t bound = h[1].count[1];
-        const uint32_t* n_device = &reinterpret_cast<const gsr::SlabInfo*>(bases[0] + h[0].off[5])->pairs;
-        const int passes = dL_dpix_normal != nullptr ? 2 : 1;
-        int id_bits = 1;
-        while (id_bits < 32 && (1ull << id_bits) < (unsigned long long)P) ++id_bits;
-        Carver dc;
-        const size_t bit_words = ((size_t)bound + 7) / 8;
-        const size_t off_first = dc.take<uint32_t>((size_t)P), off_end = dc.take<uint32_t>((size_t)P);
-        const size_t off_bits = dc.take<uint32_t>(bit_words * passes);
-        const size_t zero_bytes = (dc.off + 255) & ~size_t(255);   // everything up to here must be zero
-        const size_t off_keys = dc.take<uint32_t>(bound), off_keys_alt = dc.take<uint32_t>(bound);
-        const size_t off_pos = dc.take<uint32_t>(bound), off_pos_alt = dc.take<uint32_t>(bound);
-        const size_t off_tmp = dc.take<uint32_t>(gsr::radix_scratch_words(bound));
-        const size_t off_part = dc.take<float>((size_t)bound * 40 * passes);
-        char* draw = nullptr;
-        GSR_HIP(det_alloc((void**)&draw, dc.total() + 256, stream));
-        char* dbase = align_base(draw);
-        int rc = GSR_OK;
-        do {
-#define GSR_DET(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) { (void)hipGetLastError(); \
-            rc = fail(GSR_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); } } while (0)
-            GSR_DET(hipMemsetAsync(dbase, 0, zero_bytes, stream));
-            if (rc != GSR_OK) break;
-            uint32_t* bits1 = (uint32_t*)(dbase + off_bits);
-            float* part1 = (float*)(dbase + off_part);
-            uint32_t* bits2 = passes == 2 ? bits1 + bit_words : nullptr;
-            float* part2 = passes == 2 ? part1 + (size_t)bound * 40 : nullptr;
-            GSR_DET(gsr::launch_render_backward(cam, segs, S, background, raster, colors, accum_alphas, n_contrib, dL_dpix,
-                                                dL_dpix_depth, dL_dpix_alpha, accum_scratch, stream, 0, part1, bits1));
-            if (rc == GSR_OK && passes == 2)
-                GSR_DET(gsr::launch_render_backward(cam, segs, S, background, raster, normal_colours, accum_alphas, n_contrib,
-                                                    dL_dpix_normal, nullptr, nullptr, accum_scratch, stream, 10, part2, bits2));
-            if (rc != GSR_OK) break;
-            uint32_t *ids_sorted = nullptr, *pos_sorted = nullptr;
-            if (bound > 0u) {
-                GSR_DET(hipMemcpyAsync(dbase + off_keys, point_list, (size_t)bound * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
-                gsr::RadixSortExtras ex;
-                ex.n_device = n_device;
-                if (rc == GSR_OK)
-                    GSR_DET(gsr::radix_sort_pairs((uint32_t*)(dbase + off_tmp), bound, id_bits, (uint32_t*)(dbase + off_keys),
-                                                  (uint32_t*)(dbase + off_keys_alt), (uint32_t*)(dbase + off_pos), (uint32_t*)(dbase + off_pos_alt),
-                                                  /*iota_payload=*/true, /*want_sorted_keys=*/true, &ids_sorted, &pos_sorted, stream, ex));
-                if (rc == GSR_OK)
-                    GSR_DET(gsr::launch_det_segments(n_device, ids_sorted, bound, (uint32_t*)(dbase + off_first), (uint32_t*)(dbase + off_end), stream));
-            }
-            if (rc == GSR_OK)
-                GSR_DET(gsr::launch_det_reduce(P, (const uint32_t*)(dbase + off_first), (const uint32_t*)(dbase + off_end), pos_sorted, bits1, part1,
-                                               bits2, part2, accum_scratch, stream));
-#undef GSR_DET
-        } while (0);
-        (void)hipFreeAsync(draw, stream);
-        if (rc != GSR_OK) return rc;
+    if (deterministic) {
+        if (const int rc = accumulate_deterministic(v, cam, background, colors, accum_alphas, dL_dpix, dL_dpix_depth, dL_dpix_alpha,
+                                                    dL_dpix_normal, accum_scratch, stream))
+            return rc;
     } else {
-    GSR_HIP(hipMemsetAsync(accum_scratch, 0, (size_t)P * 16 * sizeof(float), stream));
-    GSR_HIP(gsr::launch_render_backward(cam, segs, S, background, raster, colors, accum_alphas, n_contrib,
-                                        dL_dpix, dL_dpix_depth, dL_dpix_alpha, accum_scratch, stream));
-    if (dL_dpix_normal != nullptr)   // the second feature set's pass: colour sums to slots 10 - 12, geometry sums add to 4 - 9
-        GSR_HIP(gsr::launch_render_backward(cam, segs, S, background, raster, normal_colours,
-                                            accum_alphas, n_contrib, dL_dpix_normal, nullptr, nullptr, accum_scratch, stream, 10));
+        GSR_HIP(hipMemsetAsync(accum_scratch, 0, (size_t)P * 16 * sizeof(float), stream));
+        GSR_HIP(gsr::launch_render_backward(cam, v.segs, v.S, background, v.raster, colors, accum_alphas, v.n_contrib,
+                                            dL_dpix, dL_dpix_depth, dL_dpix_alpha, accum_scratch, stream));
+        if (dL_dpix_normal != nullptr)   // the second feature set's pass: colour sums to slots 10 - 12, geometry sums add to 4 - 9
+            GSR_HIP(gsr::launch_render_backward(cam, v.segs, v.S, background, v.raster, v.view_normals,
+                                                accum_alphas, v.n_contrib, dL_dpix_normal, nullptr, nullptr, accum_scratch, stream, 10));
     }
     GSR_STAGE_CHECK("render_backward");
     if (bw_slot >= 0) GSR_HIP(hipEventRecord(g_bw_ev[bw_slot][1], stream));
@@ -603,34 +630,15 @@ int gsr_blend(const char* geom_buffer, const char* binning_buffer, const char* i
     if (width <= 0 || height <= 0) return fail(GSR_ERR_INVALID_ARG, "bad image size %dx%d", width, height);
     if (!geom_buffer || !binning_buffer || !image_buffer || !features || !background || !out_color || !out_depth || !out_alpha)
         return fail(GSR_ERR_INVALID_ARG, "null pointer");
-    const char* bases[3] = {align_base(const_cast<char*>(geom_buffer)), align_base(const_cast<char*>(binning_buffer)),
-                            align_base(const_cast<char*>(image_buffer))};
-    gsr::ArenaHeader h[3];
-    if (!recall_headers(bases, h)) {
-        for (int i = 0; i < 3; ++i) GSR_HIP(hipMemcpyAsync(&h[i], bases[i], sizeof h[i], hipMemcpyDeviceToHost, stream));
-        GSR_HIP(hipStreamSynchronize(stream));
-    }
-    for (int i = 0; i < 3; ++i)
-        if (h[i].magic != gsr::kArenaMagic || h[i].kind != (uint32_t)i)
-            return fail(GSR_ERR_INVALID_ARG, "scratch buffer %d was not produced by gsr_forward", i);
-    if (h[2].count[0] != (uint32_t)width || h[2].count[1] != (uint32_t)height)
-        return fail(GSR_ERR_INVALID_ARG, "scratch buffers belong to a %ux%u frame, not %dx%d", h[2].count[0], h[2].count[1], width, height);
-    const int slabs = (int)h[0].count[2];
-    if (slabs < 1 || slabs > gsr::kMaxSlabs) return fail(GSR_ERR_INVALID_ARG, "bad slab count %d in the geometry header", slabs);
-    gsr::Camera cam = {};
-    cam.width = width; cam.height = height;
-    cam.grid_x = (width + gsr::kTile - 1) / gsr::kTile;
-    cam.grid_y = (height + gsr::kTile - 1) / gsr::kTile;
-    gsr::BlendSegments segs = {};
-    for (int k = 0; k < slabs; ++k) {
-        segs.ranges[k] = (const uint2*)(bases[2] + h[2].slab_off[k]);
-        segs.point_list[k] = (const uint32_t*)(bases[1] + h[1].slab_off[k]);
-    }
+    ScratchView v;
+    if (const int rc = open_scratch(v, geom_buffer, binning_buffer, image_buffer, stream, /*force_device_read=*/false)) return rc;
+    if (v.W != (uint32_t)width || v.H != (uint32_t)height)
+        return fail(GSR_ERR_INVALID_ARG, "scratch buffers belong to a %ux%u frame, not %dx%d", v.W, v.H, width, height);
+    const gsr::Camera cam = make_camera(width, height, 1.0f, 1.0f, nullptr, nullptr, nullptr);
     // one launch over every segment of the tile's list; the per-pixel last-contributor positions are only rewritten
     // for a single-slab call (they are the same values: same lists, same geometry)
-    uint32_t* n_contrib = slabs == 1 ? (uint32_t*)(bases[2] + h[2].off[1]) : nullptr;
-    GSR_HIP(gsr::launch_blend(cam, segs, 0, slabs, /*fresh=*/true, /*final=*/true, (const gsr::SplatRaster*)(bases[0] + h[0].off[0]),
-                              features, background, out_color, out_depth, out_alpha, n_contrib, nullptr, nullptr, 0, stream));
+    GSR_HIP(gsr::launch_blend(cam, v.segs, 0, v.S, /*fresh=*/true, /*final=*/true, v.raster, features, background, out_color, out_depth,
+                              out_alpha, v.S == 1 ? v.n_contrib : nullptr, nullptr, nullptr, 0, stream));
     return GSR_OK;
 }
 
@@ -678,15 +686,14 @@ struct ForwardCall {
 
     ~ForwardCall() {
         if (timed && g_inflight > 0) --g_inflight;  // (a call that never finished leaves g_ev_slabs[slot] == 0: readers skip it)
-        if (!pinned.host) return;
-        // Only reached with a slot when the call did not complete (cancelled, or failed part way).  Kernels already queued
-        // on the stream may still store into the slot (the totals; the slab table written by bin_offsets / slab_compact):
-        // it goes back to the free list only after an event behind everything queued so far has completed -- no host wait.
-        if ((queued || device_work) && hipEventRecord(pinned.finished, stream) == hipSuccess) g_pinned_draining.push_back(pinned);
-        else if (!(queued || device_work)) g_pinned_free.push_back(pinned);
-        // (an event that cannot be recorded means the device is gone: the few KB of pinned memory are abandoned)
+        if (pinned.host) g_pinned.retire_behind_event(pinned, queued || device_work, stream);  // (a call that finished has handed its slot on)
     }
 };
+
+// Stage timing of one call: event `idx` of its ring slot.
+void stamp(const ForwardCall& fc, int idx) {
+    if (fc.timed) (void)hipEventRecord(g_ev[fc.slot][idx], fc.stream);
+}
 
 // Depth slabs of an inference call.  Slab s takes the splats whose inclusive pair offset (over the depth order) lies in
 // (cut[s-1], cut[s]]: the first slab holds ~`first` pairs per tile -- enough to finish most tiles of a scene with an
@@ -754,18 +761,7 @@ int forward_begin(ForwardCall& fc, gsr_alloc_fn geom_alloc, void* geom_user, gsr
     if (fc.raw_normals && (!fc.raw || out_extra == nullptr || extra_features != nullptr))
         return fail(GSR_ERR_INVALID_ARG, "view normals need a raw-parameter call and an output image");
 
-    gsr::Camera& cam = fc.cam;
-    cam.viewmatrix = viewmatrix;
-    cam.projmatrix = projmatrix;
-    cam.cam_pos = cam_pos;
-    cam.tan_fovx = tan_fovx;
-    cam.tan_fovy = tan_fovy;
-    cam.focal_y = height / (2.0f * tan_fovy);  // rasterizer_impl.cu:223-224
-    cam.focal_x = width / (2.0f * tan_fovx);
-    cam.width = width;
-    cam.height = height;
-    cam.grid_x = (width + gsr::kTile - 1) / gsr::kTile;
-    cam.grid_y = (height + gsr::kTile - 1) / gsr::kTile;
+    gsr::Camera& cam = fc.cam = make_camera(width, height, tan_fovx, tan_fovy, viewmatrix, projmatrix, cam_pos);
     if (cam.grid_x > 65535 || cam.grid_y > 65535) return fail(GSR_ERR_INVALID_ARG, "image too large");
     const int T = cam.grid_x * cam.grid_y;
     const size_t n = (size_t)P;
@@ -786,30 +782,10 @@ int forward_begin(ForwardCall& fc, gsr_alloc_fn geom_alloc, void* geom_user, gsr
         g_epoch_seen = g_timing_epoch.load();
         g_timed_calls = 0; g_begun_calls = 0; g_inflight = 0;
     }
-    g_slot = fc.slot = (int)(g_begun_calls % kTimingRing);  // one slot per call in flight (ring of 256: more than any driver keeps)
-    g_stamp = fc.timed = g_timing;
+    fc.slot = (int)(g_begun_calls % kTimingRing);  // one slot per call in flight (ring of 256: more than any driver keeps)
+    fc.timed = g_timing;
     if (fc.timed) { ++g_begun_calls; ++g_inflight; g_ev_slabs[fc.slot] = 0; }
-    // A retired slot goes back to the free list only once its `finished` event has completed: its slab-table copy may still
-    // be in flight on ANOTHER stream (several streams fed by one thread), and a new call on this stream must neither
-    // share that host buffer nor re-record that event.
-    for (size_t i = 0; i < g_pinned_draining.size();) {
-        if (hipEventQuery(g_pinned_draining[i].finished) == hipSuccess) {   // (an error is not "complete": the slot stays parked)
-            g_pinned_free.push_back(g_pinned_draining[i]);
-            g_pinned_draining[i] = g_pinned_draining.back();
-            g_pinned_draining.pop_back();
-        } else {
-            ++i;
-        }
-    }
-    if (!g_pinned_free.empty()) {
-        fc.pinned = g_pinned_free.back();
-        g_pinned_free.pop_back();
-    } else {
-        GSR_HIP(hipHostMalloc((void**)&fc.pinned.host, kPinnedBytes, hipHostMallocPortable | hipHostMallocMapped));
-        if (hipHostGetDevicePointer(&fc.pinned.dev, fc.pinned.host, 0) != hipSuccess) { (void)hipGetLastError(); fc.pinned.dev = nullptr; }
-        GSR_HIP(hipEventCreateWithFlags(&fc.pinned.copied, hipEventDisableTiming));
-        GSR_HIP(hipEventCreateWithFlags(&fc.pinned.finished, hipEventDisableTiming));
-    }
+    if (const int rc = g_pinned.acquire(fc.pinned)) return rc;
 
     // ---- geometry arena ----
     const size_t dup_blocks = (n + gsr::kDupTile - 1) / gsr::kDupTile;
@@ -894,10 +870,10 @@ int forward_begin(ForwardCall& fc, gsr_alloc_fn geom_alloc, void* geom_user, gsr
     fc.slab_tile_totals = (uint32_t*)(gbase + off_slab_totals);
     fc.sorted_bins = (uint4*)(gbase + off_sorted_bins);
 
-    stamp(0, stream);
+    stamp(fc, 0);
     GSR_HIP(gsr::launch_preprocess(in, cam, ga, stream));
     GSR_STAGE_CHECK("preprocess");
-    stamp(1, stream);
+    stamp(fc, 1);
 
     // The one host round trip of the call (rasterizer_impl.cu:282 reads num_rendered back to size the binning arena).  Here
     // the totals are summed by one extra workgroup of the depth sort's first kernel, which stores them straight into the call's
@@ -925,10 +901,61 @@ int forward_begin(ForwardCall& fc, gsr_alloc_fn geom_alloc, void* geom_user, gsr
         GSR_HIP(hipEventRecord(fc.pinned.copied, stream));
     }
     GSR_STAGE_CHECK("depth_sort");
-    stamp(2, stream);
+    stamp(fc, 2);
     geom_off[GSR_GEOM_DEPTH_ORDER] = (size_t)((char*)fc.order - gbase);
     geom_off[GSR_GEOM_LISTED] = fc.defer_colour ? fc.off_listed : 0;
     return 0;
+}
+
+// ---- the arena headers: written by scratch_headers, read by open_scratch, their count[] and off[] indexed nowhere else (what each
+// slot holds: gsr_internal.h, ArenaHeader).  The slab_off entries are filled in by forward_finish's slab loop as each list is settled.
+void scratch_headers(const ForwardCall& fc, uint32_t num_rendered, int S, uint32_t list_room, gsr::ArenaHeader h[3]) {
+    gsr::ArenaHeader &hg = h[0], &hb = h[1], &hi = h[2];
+    hg = hb = hi = gsr::ArenaHeader{};
+    hg.magic = hb.magic = hi.magic = gsr::kArenaMagic; hg.kind = 0; hb.kind = 1; hi.kind = 2;
+    hg.count[0] = (uint32_t)fc.P; hg.count[1] = num_rendered; hg.count[2] = (uint32_t)S; hg.count[3] = fc.inference ? 1u : 0u;
+    hg.off[0] = (uint64_t)((char*)fc.ga.raster - fc.gbase);
+    hg.off[1] = (uint64_t)(fc.raw_normals ? fc.geom_off[GSR_GEOM_VIEW_NORMALS] : 0);   // 0 = the call composited no view normals
+    hg.off[3] = (uint64_t)((char*)fc.ga.rgb - fc.gbase);
+    hg.off[4] = (uint64_t)fc.geom_off[GSR_GEOM_INTERNAL_RADII];
+    hg.off[5] = (uint64_t)fc.off_slabs; hg.off[6] = (uint64_t)fc.off_quad; hg.off[7] = (uint64_t)fc.off_rows;
+    hb.count[0] = (uint32_t)S; hb.count[1] = list_room;
+    hi.count[0] = (uint32_t)fc.width; hi.count[1] = (uint32_t)fc.height; hi.count[2] = (uint32_t)fc.T; hi.count[3] = (uint32_t)S;
+    hi.off[1] = (uint64_t)(fc.iraw + fc.img_off[GSR_IMG_N_CONTRIB] - fc.ibase);
+}
+
+// The headers of a forward call this process remembers cost no host wait; anything else (or `force_device_read`: debug) is read
+// from the device and waited for.  Either way the checked fields are validated before a pointer is formed.
+int open_scratch(ScratchView& v, const char* geom, const char* binning, const char* image, hipStream_t stream, bool force_device_read) {
+    const char* const base[3] = {align_base(const_cast<char*>(geom)), align_base(const_cast<char*>(binning)),
+                                 align_base(const_cast<char*>(image))};
+    gsr::ArenaHeader h[3];
+    if (force_device_read || !recall_headers(base, h)) {
+        for (int i = 0; i < 3; ++i) GSR_HIP(hipMemcpyAsync(&h[i], base[i], sizeof h[i], hipMemcpyDeviceToHost, stream));
+        GSR_HIP(hipStreamSynchronize(stream));
+    }
+    for (int i = 0; i < 3; ++i)
+        if (h[i].magic != gsr::kArenaMagic || h[i].kind != (uint32_t)i)
+            return fail(GSR_ERR_INVALID_ARG, "scratch buffer %d was not produced by gsr_forward", i);
+    const gsr::ArenaHeader &hg = h[0], &hb = h[1], &hi = h[2];
+    const int S = (int)hg.count[2];
+    if (S < 1 || S > gsr::kMaxSlabs || hi.count[3] != (uint32_t)S)
+        return fail(GSR_ERR_INVALID_ARG, "scratch buffers describe %d depth slabs (image arena: %u)", S, hi.count[3]);
+    for (int i = 0; i < 3; ++i) v.base[i] = base[i];
+    v.P = hg.count[0]; v.R = hg.count[1]; v.S = S; v.inference = hg.count[3] != 0u; v.W = hi.count[0]; v.H = hi.count[1];
+    v.raster = (const gsr::SplatRaster*)(base[0] + hg.off[0]);
+    v.view_normals = hg.off[1] != 0 ? (const float*)(base[0] + hg.off[1]) : nullptr;
+    v.rgb = (const float*)(base[0] + hg.off[3]);
+    v.radii = (const int*)(base[0] + hg.off[4]);
+    v.slabs = (const gsr::SlabInfo*)(base[0] + hg.off[5]);
+    v.n_contrib = (uint32_t*)const_cast<char*>(base[2] + hi.off[1]);
+    v.list_room = hb.count[1];
+    v.segs = {};
+    for (int k = 0; k < S; ++k) {
+        v.segs.point_list[k] = (const uint32_t*)(base[1] + hb.slab_off[k]);
+        v.segs.ranges[k] = (const uint2*)(base[2] + hi.slab_off[k]);
+    }
+    return GSR_OK;
 }
 
 int forward_finish(ForwardCall& fc) {
@@ -938,8 +965,6 @@ int forward_finish(ForwardCall& fc) {
     const gsr::Camera& cam = fc.cam;
     const gsr::GeometryArrays& ga = fc.ga;
     char* const gbase = fc.gbase;
-    g_slot = fc.slot;
-    g_stamp = fc.timed;
 
     GSR_HIP(hipEventSynchronize(fc.pinned.copied));
     fc.queued = false;
@@ -964,7 +989,7 @@ int forward_finish(ForwardCall& fc) {
     const uint32_t live_bound = (uint32_t)live_total;    // upper bound of the pairs that will be expanded (exact without large splats)
     const uint32_t num_rendered = (uint32_t)rect_total;  // the reference's count
     if (!fc.in.tile_cull) pool_rows = 0;                 // (every row of a large splat is its full width)
-    stamp(3, stream);
+    stamp(fc, 3);
 
     // ---- depth slabs and the binning arena ----
     const SlabPlan plan = plan_slabs(fc.inference, live_bound, T, cam.grid_y * fc.row_words);
@@ -1027,25 +1052,12 @@ int forward_finish(ForwardCall& fc) {
 
     uint32_t* n_contrib = (uint32_t*)(fc.iraw + fc.img_off[GSR_IMG_N_CONTRIB]);
     gsr::BlendSegments segs = {};
-    uint32_t* list_of[gsr::kMaxSlabs] = {};
     uint32_t* tile_keys_sorted = nullptr;
 
-    // self-describing arenas (gsr_backward, gsr_blend): stamped by the last ranges launch
-    gsr::ArenaHeader hg = {}, hb = {}, hi = {};
-    hg.magic = hb.magic = hi.magic = gsr::kArenaMagic;
-    hg.kind = 0; hb.kind = 1; hi.kind = 2;
-    hg.count[0] = (uint32_t)P; hg.count[1] = num_rendered; hg.count[2] = (uint32_t)S; hg.count[3] = fc.inference ? 1u : 0u;
-    hg.off[0] = (uint64_t)((char*)ga.raster - gbase);
-    hg.off[1] = (uint64_t)(fc.raw_normals ? fc.geom_off[GSR_GEOM_VIEW_NORMALS] : 0);   // 0 = the call composited no view normals
-    hg.off[3] = (uint64_t)((char*)ga.rgb - gbase);
-    hg.off[4] = (uint64_t)fc.geom_off[GSR_GEOM_INTERNAL_RADII];
-    hg.off[5] = (uint64_t)fc.off_slabs;
-    hg.off[6] = (uint64_t)fc.off_quad;
-    hg.off[7] = (uint64_t)fc.off_rows;
-    hb.count[0] = (uint32_t)S;
-    hb.count[1] = plan.bound[0];   // room of slab 0's list (>= its pairs): sizes the deterministic backward's buffers
-    hi.count[0] = (uint32_t)fc.width; hi.count[1] = (uint32_t)fc.height; hi.count[2] = (uint32_t)T; hi.count[3] = (uint32_t)S;
-    hi.off[1] = (uint64_t)((char*)n_contrib - fc.ibase);
+    // self-describing arenas (gsr_backward, gsr_blend): stamped by the last ranges launch, each slab's entries filled in below
+    gsr::ArenaHeader headers[3];
+    scratch_headers(fc, num_rendered, S, plan.bound[0], headers);
+    char* const bases[3] = {gbase, bbase, fc.ibase};
 
     GSR_HIP(gsr::launch_bin_scan(ba, cam, S, plan.cut, stream));
     GSR_STAGE_CHECK("bin_scan");
@@ -1065,7 +1077,7 @@ int forward_finish(ForwardCall& fc) {
         GSR_HIP(gsr::launch_expand(ba, k, plan.bound[k], keys_in, list_in, (uint32_t*)(bbase + off_btmp),
                                    gsr::radix_count_stride(plan.bound[k], precount), gsr::radix_first_digit_mask(tile_bits), stream));
         GSR_STAGE_CHECK("expand");
-        stamp(kHeadEvents + kSlabEvents * k + 0, stream);
+        stamp(fc, kHeadEvents + kSlabEvents * k + 0);
         uint32_t *tk_sorted = keys_in, *pl_sorted = list_in;
         if (plan.bound[k] > 0) {
             gsr::RadixSortExtras tile_extras;
@@ -1085,16 +1097,13 @@ int forward_finish(ForwardCall& fc) {
                 return fail(GSR_ERR_INTERNAL, "depth slab %d: %u entries of the sorted list are out of (tile, depth, id) order "
                                               "(radix rank %s)", k, violations, gsr::radix_rank_mode(stream, nullptr) ? "LDS adds" : "ballots");
         }
-        stamp(kHeadEvents + kSlabEvents * k + 1, stream);
-        list_of[k] = pl_sorted;
+        stamp(fc, kHeadEvents + kSlabEvents * k + 1);
         tile_keys_sorted = tk_sorted;
         segs.ranges[k] = ranges;
         segs.point_list[k] = pl_sorted;
-        hb.slab_off[k] = (uint64_t)((char*)pl_sorted - bbase);
-        hi.slab_off[k] = (uint64_t)((char*)ranges - fc.ibase);
+        headers[1].slab_off[k] = (uint64_t)((char*)pl_sorted - bbase);
+        headers[2].slab_off[k] = (uint64_t)((char*)ranges - fc.ibase);
         const bool last = k == S - 1;
-        const gsr::ArenaHeader hs[3] = {hg, hb, hi};
-        void* const dsts[3] = {gbase, bbase, fc.ibase};
         // tile ranges (all (0,0) when nothing is live: rasterizer_impl.cu:311); the call's last duty also stamps the headers.
         // A call that evaluates deferred colours hands the duty to the first workgroups of its colour kernel (one launch
         // less, and the search latency hides behind the colour reads); otherwise it is a launch of its own.
@@ -1111,26 +1120,23 @@ int forward_finish(ForwardCall& fc) {
             while (mean > 3u) { mean >>= 1; ++order.shift; }
         }
         duty.order = order;
-        for (int i = 0; i < 3; ++i) { duty.headers[i] = hs[i]; duty.header_dst[i] = last ? dsts[i] : nullptr; }
+        for (int i = 0; i < 3; ++i) { duty.headers[i] = headers[i]; duty.header_dst[i] = last ? bases[i] : nullptr; }
         const bool colour_blocks_suffice = (S == 1 ? (P + 255) / 256 : (P + 1023) / 1024) >= gsr::ranges_duty_blocks(T);
         const bool fused_ranges = fc.defer_colour && colour_blocks_suffice && !debug;
         if (!fused_ranges) GSR_HIP(gsr::launch_tile_ranges(duty, stream));
         GSR_STAGE_CHECK("tile_ranges");
-        stamp(kHeadEvents + kSlabEvents * k + 2, stream);
+        stamp(fc, kHeadEvents + kSlabEvents * k + 2);
         if (fc.defer_colour && S == 1)
             GSR_HIP(gsr::launch_sh_colour_all(fc.in, cam, ga.radii, ga.rgb, fused_ranges ? &duty : nullptr, stream));
         else if (fc.defer_colour)
             GSR_HIP(gsr::launch_sh_colour_listed(fc.in, cam, ba.listed, k + 1, slab, ga.rgb, fused_ranges ? &duty : nullptr, stream));
-        stamp(kHeadEvents + kSlabEvents * k + 3, stream);
+        stamp(fc, kHeadEvents + kSlabEvents * k + 3);
         GSR_HIP(gsr::launch_blend(cam, segs, k, k + 1, /*fresh=*/k == 0, /*final=*/last, ga.raster, features, fc.background,
                                   fc.out_color, fc.out_depth, fc.out_alpha, n_contrib, ba.quad_done, ba.done_rows, fc.row_words, stream,
                                   fc.extra_features, fc.out_extra, &order));
         GSR_STAGE_CHECK("blend");
-        stamp(kHeadEvents + kSlabEvents * k + 4, stream);
-        if (last) {
-            const char* const bases[3] = {gbase, bbase, fc.ibase};
-            remember_headers(bases, hs);
-        }
+        stamp(fc, kHeadEvents + kSlabEvents * k + 4);
+        if (last) remember_headers(bases, headers);
     }
     if (fc.timed) { g_ev_slabs[fc.slot] = S; ++g_timed_calls; }
 
@@ -1139,9 +1145,7 @@ int forward_finish(ForwardCall& fc) {
         GSR_HIP(hipMemcpyAsync(reinterpret_cast<char*>(fc.pinned.host) + kSlabTableAt, ba.slabs, sizeof(gsr::SlabInfo) * S,
                                hipMemcpyDeviceToHost, stream));
     GSR_HIP(hipEventRecord(fc.pinned.finished, stream));
-    if (g_last_slot.host) g_pinned_draining.push_back(g_last_slot);  // (its copy may still be pending on another stream)
-    g_last_slot = fc.pinned;
-    fc.pinned = PinnedSlot();
+    g_pinned.adopt_as_last(fc.pinned);
     g_last_slabs = S;
     g_last_num_rendered = num_rendered;
 
@@ -1149,7 +1153,7 @@ int forward_finish(ForwardCall& fc) {
     for (int i = 0; i < GSR_GEOM_NUM_SLOTS; ++i) g_geom_off[i] = fc.geom_off[i] + fc.gshift;
     if (!(fc.defer_colour && S > 1)) g_geom_off[GSR_GEOM_LISTED] = 0;   // (single-slab calls colour every emitting splat)
     memcpy(g_img_off, fc.img_off, sizeof g_img_off);
-    g_bin_off[GSR_BIN_POINT_LIST] = (size_t)((char*)list_of[0] - braw);
+    g_bin_off[GSR_BIN_POINT_LIST] = (size_t)((char*)segs.point_list[0] - braw);
     g_bin_off[GSR_BIN_TILE_KEYS] = (size_t)((char*)tile_keys_sorted - braw);
     g_have_offsets = true;
     return (int)num_rendered;
@@ -1159,6 +1163,21 @@ int forward_finish(ForwardCall& fc) {
     geom_alloc, geom_user, binning_alloc, binning_user, image_alloc, image_user, P, D, M, background, width, height, \
         means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix,      \
         projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, out_color, out_depth, out_alpha, radii, debug, stream
+
+// gsr_forward_extra / gsr_forward_begin: a second feature set comes with its image (asked before anything else about the call)
+int check_extra(const float* extra_features, const float* out_extra) {
+    if ((extra_features != nullptr) == (out_extra != nullptr)) return GSR_OK;
+    return fail(GSR_ERR_INVALID_ARG, "extra_features and out_extra must be given together");
+}
+
+// gsr_forward_begin / gsr_forward_raw_begin: the call lives on the heap until gsr_forward_finish or gsr_forward_cancel
+template <typename Begin>
+void* begin_on_heap(Begin begin) {
+    ForwardCall* fc = new (std::nothrow) ForwardCall;
+    if (!fc) { fail(GSR_ERR_ALLOC, "out of host memory"); return nullptr; }
+    if (begin(*fc) < 0) { delete fc; return nullptr; }
+    return fc;
+}
 } // namespace
 
 extern "C" {
@@ -1183,8 +1202,7 @@ int gsr_forward_extra(gsr_alloc_fn geom_alloc, void* geom_user, gsr_alloc_fn bin
                       const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered, float* out_color,
                       float* out_depth, float* out_alpha, int* radii, const float* extra_features, float* out_extra,
                       unsigned flags, int debug, void* stream) {
-    if ((extra_features != nullptr) != (out_extra != nullptr))
-        return fail(GSR_ERR_INVALID_ARG, "extra_features and out_extra must be given together");
+    if (const int rc = check_extra(extra_features, out_extra)) return rc;
     ForwardCall fc;
     const int rc = forward_begin(fc, GSR_FORWARD_ARGS, extra_features, out_extra, flags);
     return rc < 0 ? rc : forward_finish(fc);
@@ -1228,18 +1246,11 @@ void* gsr_forward_raw_begin(gsr_alloc_fn geom_alloc, void* geom_user, gsr_alloc_
                             const float* projmatrix, const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered,
                             float* out_color, float* out_depth, float* out_alpha, int* radii, float* out_normal,
                             unsigned flags, int debug, void* stream) {
-    ForwardCall* fc = new (std::nothrow) ForwardCall;
-    if (!fc) {
-        fail(GSR_ERR_ALLOC, "out of host memory");
-        return nullptr;
-    }
-    if (raw_begin(*fc, geom_alloc, geom_user, binning_alloc, binning_user, image_alloc, image_user, P, D, M, background, width,
-                  height, raw, scale_modifier, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, out_color,
-                  out_depth, out_alpha, radii, out_normal, flags, debug, stream) < 0) {
-        delete fc;
-        return nullptr;
-    }
-    return fc;
+    return begin_on_heap([&](ForwardCall& fc) {
+        return raw_begin(fc, geom_alloc, geom_user, binning_alloc, binning_user, image_alloc, image_user, P, D, M, background, width,
+                         height, raw, scale_modifier, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, out_color,
+                         out_depth, out_alpha, radii, out_normal, flags, debug, stream);
+    });
 }
 
 void* gsr_forward_begin(gsr_alloc_fn geom_alloc, void* geom_user, gsr_alloc_fn binning_alloc, void* binning_user,
@@ -1250,20 +1261,8 @@ void* gsr_forward_begin(gsr_alloc_fn geom_alloc, void* geom_user, gsr_alloc_fn b
                         const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered, float* out_color,
                         float* out_depth, float* out_alpha, int* radii, const float* extra_features, float* out_extra,
                         unsigned flags, int debug, void* stream) {
-    if ((extra_features != nullptr) != (out_extra != nullptr)) {
-        fail(GSR_ERR_INVALID_ARG, "extra_features and out_extra must be given together");
-        return nullptr;
-    }
-    ForwardCall* fc = new (std::nothrow) ForwardCall;
-    if (!fc) {
-        fail(GSR_ERR_ALLOC, "out of host memory");
-        return nullptr;
-    }
-    if (forward_begin(*fc, GSR_FORWARD_ARGS, extra_features, out_extra, flags) < 0) {
-        delete fc;
-        return nullptr;
-    }
-    return fc;
+    if (check_extra(extra_features, out_extra) != GSR_OK) return nullptr;
+    return begin_on_heap([&](ForwardCall& fc) { return forward_begin(fc, GSR_FORWARD_ARGS, extra_features, out_extra, flags); });
 }
 
 int gsr_forward_finish(void* call) {
@@ -1288,8 +1287,8 @@ void gsr_forward_cancel(void* call) { delete static_cast<ForwardCall*>(call); }
 
 int gsr_plan_slabs(uint32_t live_pairs, int width, int height, uint32_t cuts[GSR_MAX_SLABS]) {
     if (width <= 0 || height <= 0 || !cuts) return fail(GSR_ERR_INVALID_ARG, "bad arguments");
-    const int gx = (width + gsr::kTile - 1) / gsr::kTile, gy = (height + gsr::kTile - 1) / gsr::kTile;
-    const SlabPlan p = plan_slabs(true, live_pairs, gx * gy, gy * ((gx + 31) / 32));
+    const gsr::Camera cam = make_camera(width, height, 1.0f, 1.0f, nullptr, nullptr, nullptr);
+    const SlabPlan p = plan_slabs(true, live_pairs, cam.grid_x * cam.grid_y, cam.grid_y * ((cam.grid_x + 31) / 32));
     for (int i = 0; i < GSR_MAX_SLABS; ++i) cuts[i] = i + 1 < p.slabs ? p.cut[i] : 0u;
     return p.slabs;
 }

@@ -135,15 +135,16 @@ struct GeometryArrays {
 
 // First 256 bytes of each scratch arena: what the backward pass needs to find the forward's arrays
 // again.  The reference re-derives its layout from sizes (rasterizer_impl.cu:381-383 fromChunk);
-// ours also depends on which radix ping-pong buffer ended up holding the sorted list, so it is recorded.
+// ours also depends on which radix ping-pong buffer ended up holding the sorted list, so it is recorded.  The slots below are
+// indexed by one writer and one reader, side by side in gsr_api.hip (scratch_headers, open_scratch), and by nobody else.
 constexpr uint32_t kArenaMagic = 0x47535231u;  // "GSR1"
 struct ArenaHeader {
     uint32_t magic;
     uint32_t kind;      // 0 geometry, 1 binning, 2 image
-    uint32_t count[4];  // geometry: P, num_rendered (reference), slabs, inference flag; binning: slabs; image: W, H, T, slabs
+    uint32_t count[4];  // geometry: P, num_rendered (reference), slabs, inference flag; binning: slabs, room of list 0; image: W, H, T, slabs
     uint32_t pad[2];
-    uint64_t off[8];    // byte offsets from the header's own address (geometry: 0 raster, 3 rgb, 4 radii, 5 slab table,
-                        // 6 quadrant bits, 7 tile bit rows; image: 1 n_contrib)
+    uint64_t off[8];    // byte offsets from the header's own address (geometry: 0 raster, 1 view normals or 0, 3 rgb, 4 radii,
+                        // 5 slab table, 6 quadrant bits, 7 tile bit rows; image: 1 n_contrib)
     uint64_t slab_off[kMaxSlabs];  // binning: the sorted point list of slab s; image: its tile ranges
 };
 static_assert(sizeof(ArenaHeader) <= 256, "arena headers occupy the first 256 bytes");
