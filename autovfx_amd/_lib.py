@@ -187,6 +187,10 @@ SIGNATURES = {
     "gsr_mesh_raster_count": (_i, [_i64, _i64, _p, _p, _p, _i, _i, _i, _p, _sz, ctypes.POINTER(_i64), _p]),   # F N face_verts first num H W cull plan plan_bytes pair_total stream
     "gsr_mesh_raster": (_i, [_i64, _i64, _p, _p, _p, _p, _i, _i, _f, _i, _i, _i, _i,   # F N face_verts first num neighbour H W blur_radius K perspective clip cull
                              _p, _sz, _i64, _p, _sz, _p, _p, _p, _p, _p]),             # plan plan_bytes pair_total pairs pair_bytes pix_to_face zbuf bary_coords dists stream
+    "gsr_face_areas_normals": (_i, [_i64, _i64, _p, _p, _p, _p, _p]),                        # V F verts faces areas normals stream
+    "gsr_face_areas_normals_backward": (_i, [_i64, _i64, _p, _p, _p, _p, _p, _p]),           # V F verts faces grad_areas grad_normals grad_verts stream
+    "gsr_interp_face_attrs": (_i, [_i64, _i64, _i, _p, _p, _p, _p, _p]),                     # P F D pix_to_face bary attrs out stream
+    "gsr_interp_face_attrs_backward": (_i, [_i64, _i64, _i, _p, _p, _p, _p, _p, _p, _p]),    # P F D pix_to_face bary attrs grad_out grad_bary grad_attrs stream
     "gsr_ssim_scratch_bytes": (_sz, [_i, _i, _i, _i]),                 # n c h w
     "gsr_ssim_forward": (_i, [_i, _i, _i, _i, _p, _p, _p, _i, _p, _p, _p, _sz, _p]),   # n c h w x y window11 per_image out coef_or_null scratch scratch_bytes stream
     "gsr_ssim_backward": (_i, [_i, _i, _i, _i, _p, _p, _p, _p, _i, _p, _p, _p]),       # n c h w x y coef window11 per_image grad_out grad_x stream

@@ -75,7 +75,20 @@ AutoVFX reaches the rasterizer through two imports (paths under the reference tr
     the hook's loader wrapper pass every ``*._C`` imported after ``install()`` through (``torch._C`` among them): it delegates to the real
     loader and the ``needs`` keep the patch off (tests/test_meshraster.py loads ``torch._C`` that way; other packages' ``_C`` are not tested).
 
-Items 2-13 are the rows of ``_TARGETS``, applied by ``_patch`` to every matching module, whether it was imported before
+14. the same ``..._C`` module, when it defines both ``face_areas_normals_forward`` and ``face_areas_normals_backward``, gets the pair replaced
+    by ``autovfx_amd.meshattrs.drop_in_face_areas_normals_forward`` / ``_backward(<the original>)``: the HIP kernels for CUDA float32
+    ``[V, 3]`` vertices with int64 ``[F, 3]`` faces on one device (``Meshes.faces_normals_packed()`` under ``SuGaR.quaternions``,
+    ``sugar_model.py:425-452``, several times per iteration of ``sugar_trainers/refine.py`` and differentiated into the vertices;
+    ``SuGaR.get_normals``, ``:835``; ``sugar_extractors/refined_mesh.py:134``), the originals for every other call.  pytorch3d's
+    ``_MeshFaceAreasNormals`` stays as it is: it looks both operators up on ``_C`` at call time.
+
+15. the same module, when it defines both ``interpolate_face_attributes_forward`` and ``interpolate_face_attributes_backward``, gets that
+    pair replaced by ``autovfx_amd.meshattrs.drop_in_interpolate_face_attributes_forward`` / ``_backward(<the original>)``: the HIP
+    kernels for int64 fragments (``[P]``, as pytorch3d's Python flattens them, or ``[N, H, W, K]``) with CUDA float32 barycentrics and ``[F, 3, D]`` attributes (every shader and
+    ``TexturesUV.sample_textures``: the texture extraction, ``refined_mesh.py:194-197``, ``sugar_model.py:2595-2596``;
+    ``metrics.py:274-290``), the originals for every other call.  A ``_C`` with only one operator of a pair keeps that pair.
+
+Items 2-15 are the rows of ``_TARGETS``, applied by ``_patch`` to every matching module, whether it was imported before
 ``install()`` or after (a ``sys.meta_path`` hook).  Each replaced attribute keeps the reference's original next to it as
 ``reference_<attr>`` on the module or class (``<module>.reference_render``, ``SceneRepresentation.reference_render_from_3DGS``, ...).
 ``uninstall()`` undoes every patch in reverse.
@@ -99,7 +112,7 @@ from typing import Callable, List, NamedTuple, Optional, Tuple
 
 _REPO_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _installed: Optional["_RendererHook"] = None
-patched_modules: List[str] = []          # names of the modules patched by items 2-7 and 10-13 (introspection / tests)
+patched_modules: List[str] = []          # names of the modules patched by items 2-7 and 10-15 (introspection / tests)
 patched_models: List[str] = []           # names of the modules whose ``GaussianModel.training_setup`` was wrapped (item 8)
 _strict = True                           # install(strict=...): may a failure to load the render path break the importing process?
 _gave_up = False                         # lenient mode: a replacement could not be loaded once; patch nothing more
@@ -216,6 +229,12 @@ def _with_hip_sugar_method(name: str, module: str = "field", what: str = "the HI
     return make
 
 
+def _with_mesh_attrs(name: str) -> Callable:
+    """make() for one operator of ``pytorch3d._C`` that ``autovfx_amd.meshattrs`` replaces: ``drop_in_<name>(original)``, built (torch,
+    libgsr_hip.so) when the patch is made, like the mesh rasterizer's."""
+    return lambda original: _mark(_load("meshattrs", "drop_in_" + name)(original))
+
+
 class _Target(NamedTuple):
     leaf: str                            # the last component of the module's name
     cls: Optional[str]                   # the class in the module that owns ``attr``; None: the module itself
@@ -265,6 +284,14 @@ _TARGETS = (
     # item 13: pytorch3d/_C, rasterize_meshes() under every MeshRasterizer (sugar_extractors/coarse_mesh.py:216-227); looked up at call time
     _Target("_C", None, "rasterize_meshes", lambda original: _mark(_load("meshraster", "drop_in")(original)), "the HIP mesh rasterizer",
             needs=("rasterize_meshes", "rasterize_meshes_backward")),
+    # item 14: pytorch3d/_C, the pair under Meshes.faces_normals_packed() (SuGaR.quaternions, sugar_model.py:425-452)
+    *(_Target("_C", None, name, _with_mesh_attrs(name), "the HIP face areas and normals",
+              needs=("face_areas_normals_forward", "face_areas_normals_backward"))
+      for name in ("face_areas_normals_forward", "face_areas_normals_backward")),
+    # item 15: pytorch3d/_C, the pair under every shader and texture sampler (refined_mesh.py:194-197, metrics.py:274-290)
+    *(_Target("_C", None, name, _with_mesh_attrs(name), "the HIP face-attribute interpolation",
+              needs=("interpolate_face_attributes_forward", "interpolate_face_attributes_backward"))
+      for name in ("interpolate_face_attributes_forward", "interpolate_face_attributes_backward")),
 )
 
 

@@ -42,7 +42,9 @@
 extern "C" {
 #endif
 
-/* Still 20: + the triangle-mesh z-buffer of SuGaR's mesh extraction (gsr_mesh_raster_plan_bytes, gsr_mesh_raster_pair_bytes,
+/* Still 20: + face areas / normals and face-attribute interpolation with their backwards (gsr_face_areas_normals,
+ * gsr_face_areas_normals_backward, gsr_interp_face_attrs, gsr_interp_face_attrs_backward).
+ * Still 20: + the triangle-mesh z-buffer of SuGaR's mesh extraction (gsr_mesh_raster_plan_bytes, gsr_mesh_raster_pair_bytes,
  * gsr_mesh_raster_count, gsr_mesh_raster).
  * Still 20: + the level-surface ray march of SuGaR's mesh extraction (gsr_level_surface).
  * Still 20: + SuGaR's density field (gsr_field_scratch_bytes, gsr_field_forward, gsr_field_backward).  They only add symbols
@@ -525,6 +527,38 @@ GSR_API int gsr_mesh_raster(int64_t F, int64_t N, const float* face_verts, const
                             int K, int perspective_correct, int clip_barycentric_coords, int cull_backfaces, void* plan,
                             size_t plan_bytes, int64_t pair_total, void* pairs, size_t pair_bytes, int64_t* pix_to_face, float* zbuf,
                             float* bary_coords, float* dists, void* stream);
+
+/* Face areas and normals, and the interpolation of per-face vertex attributes over a rasterizer's fragments: pytorch3d's
+ * _C.face_areas_normals_forward / _backward (under Meshes.faces_normals_packed(), SuGaR.quaternions, sugar_model.py:425-452) and
+ * _C.interpolate_face_attributes_forward / _backward (under every shader and texture sampler, refined_mesh.py:194-197) -- added under
+ * ABI 20.  All arrays are contiguous device memory; every operation is an fp32 one in the order written, nothing contracted, division
+ * and sqrt correctly rounded (the contract is the module docstring of autovfx_amd/meshattrs.py).
+ *   gsr_face_areas_normals           verts [V,3] fp32, faces [F,3] int64 -> areas [F], normals [F,3].  a = v1 - v0, b = v2 - v0, c = a x b =
+ *       (a.y b.z - a.z b.y, a.z b.x - a.x b.z, a.x b.y - a.y b.x), n = sqrtf((c.x c.x + c.y c.y) + c.z c.z), area = n / 2,
+ *       normal = c / fmaxf(n, 1e-6f).  A face with an index outside [0, V) gets area 0 and normal 0 and reads no vertex.
+ *   gsr_face_areas_normals_backward  + grad_areas [F], grad_normals [F,3] -> grad_verts [V,3], zeroed on the stream by the call, then one
+ *       float atomic add per face and vertex coordinate: g_c = (grad_area c) / (2 n) for n > 0, else 0, plus (g - m (m.g)) / n with
+ *       m = c / n for n >= 1e-6f, else g / 1e-6f; g_a = b x g_c, g_b = g_c x a; -(g_a + g_b), g_a, g_b go to v0, v1, v2.  Faces with an
+ *       index outside [0, V) add nothing.
+ *   gsr_interp_face_attrs            pix_to_face [P] int64, bary [P,3], attrs [F,3,D] -> out [P,D] =
+ *       (bary[p,0] attrs[f,0,d] + bary[p,1] attrs[f,1,d]) + bary[p,2] attrs[f,2,d] with f = pix_to_face[p]; a row of zeros where f is
+ *       outside [0, F).
+ *   gsr_interp_face_attrs_backward   + grad_out [P,D] -> grad_bary [P,3]: the sum over d ascending of grad_out[p,d] attrs[f,k,d], starting
+ *       from the d = 0 product, zero where f is outside [0, F), no atomics; and grad_attrs [F,3,D], zeroed on the stream by the call,
+ *       then one float atomic add of bary[p,k] grad_out[p,d] per slot with f in [0, F), corner and channel.
+ * Every output element is written.  The two atomically summed outputs hold the contract's fp32 terms added in an order that is free;
+ * everything else is the same bits on every run.  An array of no elements may be NULL; with F == 0 (or P == 0) nothing is launched
+ * beyond zeroing the gradient outputs.  Refused (GSR_ERR_INVALID_ARG, nothing launched, no device needed): a negative count, a count
+ * >= 2^31, D outside 1..65536, a null pointer to an array that has elements, misaligned pointers (floats 4 bytes, int64 8).  Enqueues
+ * on `stream` only: no scratch, no host synchronisation, no allocation; the only atomics are fp32 adds. */
+GSR_API int gsr_face_areas_normals(int64_t V, int64_t F, const float* verts, const int64_t* faces, float* areas, float* normals,
+                                   void* stream);
+GSR_API int gsr_face_areas_normals_backward(int64_t V, int64_t F, const float* verts, const int64_t* faces, const float* grad_areas,
+                                            const float* grad_normals, float* grad_verts, void* stream);
+GSR_API int gsr_interp_face_attrs(int64_t P, int64_t F, int D, const int64_t* pix_to_face, const float* bary, const float* attrs,
+                                  float* out, void* stream);
+GSR_API int gsr_interp_face_attrs_backward(int64_t P, int64_t F, int D, const int64_t* pix_to_face, const float* bary, const float* attrs,
+                                           const float* grad_out, float* grad_bary, float* grad_attrs, void* stream);
 
 /* Structural similarity (the training loops' loss_utils.ssim, loss_utils.py:33-62, window 11, sigma 1.5) -- ABI 17.
  * x, y: [n,c,h,w] fp32, contiguous, device memory.  Per plane, zero-padded outside the image: mx = w*x, my = w*y, Exx = w*x^2,
