@@ -191,6 +191,11 @@ SIGNATURES = {
     "gsr_face_areas_normals_backward": (_i, [_i64, _i64, _p, _p, _p, _p, _p, _p]),           # V F verts faces grad_areas grad_normals grad_verts stream
     "gsr_interp_face_attrs": (_i, [_i64, _i64, _i, _p, _p, _p, _p, _p]),                     # P F D pix_to_face bary attrs out stream
     "gsr_interp_face_attrs_backward": (_i, [_i64, _i64, _i, _p, _p, _p, _p, _p, _p, _p]),    # P F D pix_to_face bary attrs grad_out grad_bary grad_attrs stream
+    "gsr_normal_consistency_plan_scratch_bytes": (_sz, [_i64]),        # F
+    "gsr_normal_consistency_plan": (_i, [_i64, _i64, _p, _p, _p, _p, _p, _sz, _p]),   # V F faces order partners pairs scratch scratch_bytes stream
+    "gsr_normal_consistency_scratch_bytes": (_sz, [_i64]),             # F
+    "gsr_normal_consistency_forward": (_i, [_i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),   # V F verts faces order partners pairs loss terms_or_null scratch scratch_bytes stream
+    "gsr_normal_consistency_backward": (_i, [_i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p]),           # V F verts faces order partners pairs grad_loss grad_verts stream
     "gsr_ssim_scratch_bytes": (_sz, [_i, _i, _i, _i]),                 # n c h w
     "gsr_ssim_forward": (_i, [_i, _i, _i, _i, _p, _p, _p, _i, _p, _p, _p, _sz, _p]),   # n c h w x y window11 per_image out coef_or_null scratch scratch_bytes stream
     "gsr_ssim_backward": (_i, [_i, _i, _i, _i, _p, _p, _p, _p, _i, _p, _p, _p]),       # n c h w x y coef window11 per_image grad_out grad_x stream

@@ -88,7 +88,14 @@ AutoVFX reaches the rasterizer through two imports (paths under the reference tr
     ``TexturesUV.sample_textures``: the texture extraction, ``refined_mesh.py:194-197``, ``sugar_model.py:2595-2596``;
     ``metrics.py:274-290``), the originals for every other call.  A ``_C`` with only one operator of a pair keeps that pair.
 
-Items 2-15 are the rows of ``_TARGETS``, applied by ``_patch`` to every matching module, whether it was imported before
+16. a module named ``...mesh_normal_consistency`` that defines ``mesh_normal_consistency`` (``pytorch3d/loss/mesh_normal_consistency.py``)
+    gets that function replaced by ``autovfx_amd.meshloss.drop_in(<the original>)``: the fused HIP loss and its backward for one CUDA
+    float32 mesh with int64 faces (``sugar_trainers/refine.py:829-830``, every iteration of the refinement), the original for every
+    other call (batches, CPU meshes, an empty mesh).  The module is patched right after its body ran, so ``pytorch3d.loss``'s own
+    ``from .mesh_normal_consistency import mesh_normal_consistency`` already binds the replacement; when ``install()`` runs after the
+    import, ``pytorch3d.loss`` and every module that did ``from pytorch3d.loss import mesh_normal_consistency`` are rebound.
+
+Items 2-16 are the rows of ``_TARGETS``, applied by ``_patch`` to every matching module, whether it was imported before
 ``install()`` or after (a ``sys.meta_path`` hook).  Each replaced attribute keeps the reference's original next to it as
 ``reference_<attr>`` on the module or class (``<module>.reference_render``, ``SceneRepresentation.reference_render_from_3DGS``, ...).
 ``uninstall()`` undoes every patch in reverse.
@@ -112,7 +119,7 @@ from typing import Callable, List, NamedTuple, Optional, Tuple
 
 _REPO_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _installed: Optional["_RendererHook"] = None
-patched_modules: List[str] = []          # names of the modules patched by items 2-7 and 10-15 (introspection / tests)
+patched_modules: List[str] = []          # names of the modules patched by items 2-7 and 10-16 (introspection / tests)
 patched_models: List[str] = []           # names of the modules whose ``GaussianModel.training_setup`` was wrapped (item 8)
 _strict = True                           # install(strict=...): may a failure to load the render path break the importing process?
 _gave_up = False                         # lenient mode: a replacement could not be loaded once; patch nothing more
@@ -292,6 +299,9 @@ _TARGETS = (
     *(_Target("_C", None, name, _with_mesh_attrs(name), "the HIP face-attribute interpolation",
               needs=("interpolate_face_attributes_forward", "interpolate_face_attributes_backward"))
       for name in ("interpolate_face_attributes_forward", "interpolate_face_attributes_backward")),
+    # item 16: pytorch3d/loss/mesh_normal_consistency.py, the regulariser of sugar_trainers/refine.py:829-830
+    _Target("mesh_normal_consistency", None, "mesh_normal_consistency", lambda original: _mark(_load("meshloss", "drop_in")(original)),
+            "the HIP mesh normal consistency loss", needs=("mesh_normal_consistency",), rebind=True),
 )
 
 

@@ -42,7 +42,9 @@
 extern "C" {
 #endif
 
-/* Still 20: + face areas / normals and face-attribute interpolation with their backwards (gsr_face_areas_normals,
+/* Still 20: + the mesh normal consistency loss (gsr_normal_consistency_plan_scratch_bytes, gsr_normal_consistency_plan,
+ * gsr_normal_consistency_scratch_bytes, gsr_normal_consistency_forward, gsr_normal_consistency_backward).
+ * Still 20: + face areas / normals and face-attribute interpolation with their backwards (gsr_face_areas_normals,
  * gsr_face_areas_normals_backward, gsr_interp_face_attrs, gsr_interp_face_attrs_backward).
  * Still 20: + the triangle-mesh z-buffer of SuGaR's mesh extraction (gsr_mesh_raster_plan_bytes, gsr_mesh_raster_pair_bytes,
  * gsr_mesh_raster_count, gsr_mesh_raster).
@@ -559,6 +561,42 @@ GSR_API int gsr_interp_face_attrs(int64_t P, int64_t F, int D, const int64_t* pi
                                   float* out, void* stream);
 GSR_API int gsr_interp_face_attrs_backward(int64_t P, int64_t F, int D, const int64_t* pix_to_face, const float* bary, const float* attrs,
                                            const float* grad_out, float* grad_bary, float* grad_attrs, void* stream);
+
+/* The normal consistency loss of one triangle mesh: pytorch3d.loss.mesh_normal_consistency (sugar_trainers/refine.py:829-830, every
+ * iteration of the refinement) -- added under ABI 20.  The contract is the module docstring of autovfx_amd/meshloss.py.
+ * An incidence is a (face f, slot k) with id 3 f + k; its edge is (faces[f][(k+1)%3], faces[f][(k+2)%3]) ordered lo <= hi, its opposite
+ * vertex faces[f][k].  verts [V,3] fp32, faces [F,3] int64, contiguous device memory.
+ *   gsr_normal_consistency_plan      topology only -> order [3F] int32, the incidence ids ascending by (lo, hi, id); partners [3F] int32,
+ *       for the sorted position s the number of later positions on the same edge; pairs [1] int64, P = the sum of partners.  The
+ *       incidences of a face with an index outside [0, V) stand at the tail of `order`, in id order, with partners 0.  scratch:
+ *       gsr_normal_consistency_plan_scratch_bytes(F) bytes, 256-byte aligned, any content.
+ *   gsr_normal_consistency_forward   per incidence n = e x w with e = v_hi - v_lo, w = v_opp - v_lo, every component fl(fl(a b) - fl(c d)).
+ *       For sorted positions s < t on one edge the term is 1 + d / (a b), d = (n_s.x n_t.x + n_s.y n_t.y) + n_s.z n_t.z,
+ *       a = fmaxf(sqrtf((x x + y y) + z z), 1e-8f) of n_s, b of n_t.  T_s = the terms of s's later partners added in ascending order,
+ *       starting from 0.  loss[0] = S / (float)P, S the sum of the T_s in a fixed tree (a 256-leaf halving tree per 256 positions, then
+ *       per lane j of 1024 the partials j, j + 1024, ... in chunks of 64 and the chunk sums in order, then a 1024-leaf halving tree: at
+ *       most 146 additions on any path), 0 when P == 0.  terms_or_null: null, or [3F] floats that receive the T_s.  scratch:
+ *       gsr_normal_consistency_scratch_bytes(F) bytes, 4-byte aligned, any content.  No atomics: the same bits on every run.
+ *   gsr_normal_consistency_backward  + grad_loss [1] (device memory) -> grad_verts [V,3], zeroed on the stream by the call, then per pair
+ *       twelve float atomic adds: with c = grad_loss[0] / (float)P, q = a b, r = d / q, g_s = c (n_t / q - (r / (a a)) n_s) and
+ *       g_t = c (n_s / q - (r / (b b)) n_t), the subtracted part only where the unclamped norm is above 1e-8f:
+ *       g_e = w_s x g_s + w_t x g_t to hi, g_s x e to opp_s, g_t x e to opp_t, -(g_e + (g_s x e + g_t x e)) to lo.  A pair in which an
+ *       incidence repeats an index (its gradient is zero) adds nothing.
+ * The kernels check what they index: an id outside [0, 3F), a partner count past the end and a face with a bad index are skipped.
+ * F == 0: loss = 0, pairs = 0, grad_verts = 0, nothing else launched.  Refused (GSR_ERR_INVALID_ARG, nothing launched, no device needed):
+ * a negative count, 3 F >= 2^30 (the sort's limit), V >= 2^31, a null pointer to an array that has elements (but terms_or_null), misaligned
+ * pointers (floats and int32 4 bytes, int64 8, the plan's scratch 256), too little scratch; the ..._scratch_bytes return 0 for such F.
+ * Enqueue on `stream` only: no host synchronisation, no allocation; the plan's only atomics are 64-bit integer adds. */
+GSR_API size_t gsr_normal_consistency_plan_scratch_bytes(int64_t F);
+GSR_API int gsr_normal_consistency_plan(int64_t V, int64_t F, const int64_t* faces, int32_t* order, int32_t* partners, int64_t* pairs,
+                                        void* scratch, size_t scratch_bytes, void* stream);
+GSR_API size_t gsr_normal_consistency_scratch_bytes(int64_t F);
+GSR_API int gsr_normal_consistency_forward(int64_t V, int64_t F, const float* verts, const int64_t* faces, const int32_t* order,
+                                           const int32_t* partners, const int64_t* pairs, float* loss, float* terms_or_null, void* scratch,
+                                           size_t scratch_bytes, void* stream);
+GSR_API int gsr_normal_consistency_backward(int64_t V, int64_t F, const float* verts, const int64_t* faces, const int32_t* order,
+                                            const int32_t* partners, const int64_t* pairs, const float* grad_loss, float* grad_verts,
+                                            void* stream);
 
 /* Structural similarity (the training loops' loss_utils.ssim, loss_utils.py:33-62, window 11, sigma 1.5) -- ABI 17.
  * x, y: [n,c,h,w] fp32, contiguous, device memory.  Per plane, zero-padded outside the image: mx = w*x, my = w*y, Exx = w*x^2,
