@@ -176,6 +176,10 @@ SIGNATURES = {
     "gsr_knn3_mean_dist": (_i, [_u32, _p, _p, _p, _sz, _p]),           # n points out scratch scratch_bytes stream
     "gsr_knn_points_scratch_bytes": (_sz, [_i64, _i64, _i]),           # n1 n2 same
     "gsr_knn_points": (_i, [_i64, _p, _i64, _p, _i, _p, _p, _p, _sz, _p]),   # n1 p1 n2 p2 K dists idx scratch scratch_bytes stream
+    "gsr_closest_tri_plan_bytes": (_sz, [_i64]),                       # F
+    "gsr_closest_tri_plan_scratch_bytes": (_sz, [_i64]),               # F
+    "gsr_closest_tri_plan": (_i, [_i64, _p, _i64, _p, _p, _sz, _p, _sz, _p]),   # V verts F faces plan plan_bytes scratch scratch_bytes stream
+    "gsr_closest_tri_query": (_i, [_i64, _p, _p, _sz, _p, _p, _p, _p]),         # n points plan plan_bytes face_idx sq_dist closest stream
     # training: the density field, SSIM, Adam, densification
     "gsr_field_scratch_bytes": (_sz, [_i64]),                          # P
     "gsr_field_forward": (_i, _field_inputs + [_p, _p, _p, _p, _sz, _p]),            # ... density opacities beta scratch scratch_bytes stream

@@ -1,0 +1,577 @@
+// gsr_meshquery.hip -- the closest triangle of a mesh to every query point (include/gsr.h: gsr_closest_tri_plan, gsr_closest_tri_query).
+//
+// What Open3D's RaycastingScene.compute_closest_points answers for the melting frames of the frame loop (scene_representation.py:
+// 385-412) and for object extraction (extract/extract_object.py:105-110): primitive id, squared distance, closest point.  The result
+// is a pointwise function of the input: the valid face with the smallest (d(q, f), f), so any exact search gives the
+// same bits.  This one is the tree and walk of gsr_knn.hip over triangles, all stream-ordered, no host read, no float atomics:
+//
+//   plan    : bounds over the valid faces' centroids (per-workgroup partials); 63-bit Morton codes of the centroids, an invalid face
+//             (an index outside [0, V), a non-finite coordinate) gets 2^63 and sorts last; the library's radix sort, low word then
+//             high word, stable; one 48-byte record per face in sorted order (three float4 a, b, c, the face index in a.w; an invalid
+//             face: NaNs and index ~0); leaf boxes = the union of the 64 triangles' own boxes (valid members only); levels of 16;
+//             the header last, so that a plan is valid only once its build has run.
+//   query   : one wave per 64 queries, one lane per query, one slot (d, face) per lane: walk_tree below.
+// The plan is self-describing: its header holds F and the plan's size, and the query kernel derives every count and offset from that F
+// (tri_layout, the function the host sized the plan with) and compares the total with the plan_bytes it was handed BEFORE anything
+// indexes the plan.  A header that does not match answers every query (-1, +inf, 0 0 0): the host cannot see the header without a
+// device-to-host read, which a query never does.
+// Defines the entry points gsr_closest_tri_plan_bytes, gsr_closest_tri_plan_scratch_bytes, gsr_closest_tri_plan, gsr_closest_tri_query.
+#include "gsr_internal.h"
+
+#include <cfloat>
+
+namespace gsr {
+namespace {
+
+// The tree, the Morton codes and the walk follow gsr_knn.hip (same constants, same prune rule); the record is 48 bytes, not 16, and a
+// lane holds one slot, so the walk is a second copy here rather than a template over both.
+constexpr int kTriMaxLevels = 6;
+constexpr int kLeaf = 64;            // triangles per leaf: one wave
+constexpr int kFan = 16;             // children per box above the leaves
+constexpr int kStackDepth = 96;      // >= kFan + (kFan - 1) * (kTriMaxLevels - 1)
+constexpr int kBoundsBlocks = 128;   // partial bounds
+constexpr uint32_t kCellMax = (1u << 21) - 1u;
+constexpr uint32_t kInvalidKey = 1u << 31;       // the high word of an invalid face's code
+constexpr uint32_t kNoFace = ~0u;                // the index of an invalid face's record, and of an empty slot
+constexpr uint32_t kPlanMagic = 0x51495254u;     // "TRIQ"
+constexpr int64_t kMaxFaces = (int64_t)1 << 30;  // refused from here on (the radix sort's limit)
+constexpr int64_t kMaxVerts = (int64_t)1 << 31;
+constexpr int64_t kMaxQueries = (int64_t)1 << 31;
+constexpr size_t kAlign = 256;
+static_assert(kStackDepth >= kFan + (kFan - 1) * (kTriMaxLevels - 1), "stack too shallow for the tree");
+
+// The first 256 bytes of a plan.
+struct TriHeader {
+    uint32_t magic, F;
+    unsigned long long plan_bytes;
+};
+
+// Boxes over the Morton-sorted faces: level 0 = leaves of 64, every level above = 16 boxes of the one below, up to the first level of
+// at most 16 boxes (`top`).  A box is two float4 (lo, hi) at boxes[2 * (offset of its level + i)].  The counts and offsets of the
+// levels are not kept in a table: tri_level derives them from the number of leaves (a few scalar operations; a table indexed by a
+// run-time level would live in the kernel's scratch memory).
+struct TriTree {
+    uint32_t leaves;
+    int top;
+    size_t records, boxes, bytes;   // byte offsets in the plan; bytes = the whole
+};
+
+__host__ __device__ inline size_t align_up(size_t v) { return (v + kAlign - 1) & ~(kAlign - 1); }
+
+// boxes of `level` and boxes below it
+__host__ __device__ inline void tri_level(uint32_t leaves, int level, uint32_t& count, uint32_t& offset) {
+    count = leaves;
+    offset = 0;
+    for (int l = 0; l < level; ++l) {
+        offset += count;
+        count = (count + kFan - 1) / kFan;
+    }
+}
+
+// The layout of a plan over F < 2^30 faces: pure arithmetic, the same on the host that sizes a plan and in the kernel that reads one.
+__host__ __device__ inline TriTree tri_layout(uint32_t F) {
+    TriTree t = {};
+    t.leaves = (F + kLeaf - 1) / kLeaf;
+    uint32_t count = t.leaves, boxes = count;
+    while (count > (uint32_t)kFan && t.top + 1 < kTriMaxLevels) {
+        count = (count + kFan - 1) / kFan;
+        boxes += count;
+        ++t.top;
+    }
+    t.records = kAlign;
+    t.boxes = align_up(t.records + 48 * (size_t)F);
+    t.bytes = align_up(t.boxes + 32 * (size_t)boxes);
+    return t;
+}
+
+// Byte offsets of the regions of the build's scratch (each 256-byte aligned); bytes = the whole.
+struct TriScratch {
+    size_t keys, keys_alt, vals, vals_alt, key_hi, radix, partials, bytes;
+};
+TriScratch tri_scratch(uint32_t F) {
+    TriScratch L = {};
+    if (F == 0) return L;
+    size_t at = 0;
+    auto take = [&](size_t bytes) { const size_t here = at; at = align_up(at + bytes); return here; };
+    L.keys = take(4 * (size_t)F);
+    L.keys_alt = take(4 * (size_t)F);
+    L.vals = take(4 * (size_t)F);
+    L.vals_alt = take(4 * (size_t)F);
+    L.key_hi = take(4 * (size_t)F);
+    L.radix = take(radix_scratch_words(F) * sizeof(uint32_t));
+    L.partials = take(32 * (size_t)kBoundsBlocks);
+    L.bytes = at;
+    return L;
+}
+
+__device__ __forceinline__ void wave_sync() {   // a wave's LDS operations run in program order: keep the compiler to it
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+__device__ __forceinline__ float wave_min(float v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v = fminf(v, __shfl_xor(v, d, 64));
+    return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d, 64));
+    return v;
+}
+__device__ __forceinline__ float lane_value(float v, int lane) {   // lane: wave-uniform
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
+}
+__device__ __forceinline__ bool finite3(float x, float y, float z) {
+    return __builtin_isfinite(x) && __builtin_isfinite(y) && __builtin_isfinite(z);
+}
+
+struct Vec3 {
+    float x, y, z;
+};
+__device__ __forceinline__ Vec3 sub(const Vec3& u, const Vec3& v) { return {u.x - v.x, u.y - v.y, u.z - v.z}; }
+__device__ __forceinline__ Vec3 neg(const Vec3& u) { return {-u.x, -u.y, -u.z}; }
+// u + s v, a multiplication and an addition per axis (the build has -ffp-contract=off)
+__device__ __forceinline__ Vec3 along(const Vec3& u, float s, const Vec3& v) { return {u.x + s * v.x, u.y + s * v.y, u.z + s * v.z}; }
+__device__ __forceinline__ float dot(const Vec3& u, const Vec3& v) { return (u.x * v.x + u.y * v.y) + u.z * v.z; }
+__device__ __forceinline__ float guarded(float num, float den) { return den != 0.0f ? num / den : 0.0f; }
+
+// gsr_knn.hip's box_bound: the rounded operations of a squared distance on the gap to a box.  An empty box gives +inf.
+__device__ __forceinline__ float box_bound(const float4& lo, const float4& hi, float qx, float qy, float qz) {
+    const float gx = fmaxf(fmaxf(lo.x - qx, qx - hi.x), 0.0f);
+    const float gy = fmaxf(fmaxf(lo.y - qy, qy - hi.y), 0.0f);
+    const float gz = fmaxf(fmaxf(lo.z - qz, qz - hi.z), 0.0f);
+    return (gx * gx + gy * gy) + gz * gz;
+}
+
+// The three corners of face f; false for an invalid face (whose corners are then not read).
+__device__ __forceinline__ bool load_face(int64_t V, const float* __restrict__ verts, const long long* __restrict__ faces, uint32_t f,
+                                          Vec3& a, Vec3& b, Vec3& c) {
+    const long long i0 = faces[3 * (size_t)f], i1 = faces[3 * (size_t)f + 1], i2 = faces[3 * (size_t)f + 2];
+    if (i0 < 0 || i1 < 0 || i2 < 0 || i0 >= V || i1 >= V || i2 >= V) return false;
+    a = {verts[3 * (size_t)i0], verts[3 * (size_t)i0 + 1], verts[3 * (size_t)i0 + 2]};
+    b = {verts[3 * (size_t)i1], verts[3 * (size_t)i1 + 1], verts[3 * (size_t)i1 + 2]};
+    c = {verts[3 * (size_t)i2], verts[3 * (size_t)i2 + 1], verts[3 * (size_t)i2 + 2]};
+    return finite3(a.x, a.y, a.z) && finite3(b.x, b.y, b.z) && finite3(c.x, c.y, c.z);
+}
+// (it only steers the sort: an overflow to inf lands in cell 0 or the last one)
+__device__ __forceinline__ Vec3 centroid(const Vec3& a, const Vec3& b, const Vec3& c) {
+    return {((a.x + b.x) + c.x) / 3.0f, ((a.y + b.y) + c.y) / 3.0f, ((a.z + b.z) + c.z) / 3.0f};
+}
+
+__device__ __forceinline__ uint64_t spread21(uint32_t v) {   // bit k of v (k < 21) -> bit 3k
+    uint64_t x = v & 0x1FFFFFu;
+    x = (x | (x << 32)) & 0x001F00000000FFFFull;
+    x = (x | (x << 16)) & 0x001F0000FF0000FFull;
+    x = (x | (x << 8)) & 0x100F00F00F00F00Full;
+    x = (x | (x << 4)) & 0x10C30C30C30C30C3ull;
+    x = (x | (x << 2)) & 0x1249249249249249ull;
+    return x;
+}
+__device__ __forceinline__ uint32_t grid_cell(float x, float lo, float hi) {
+    const float extent = hi - lo;
+    const float t = extent > 0.0f ? (x - lo) / extent * (float)kCellMax : 0.0f;
+    return t >= 0.0f ? (uint32_t)fminf(t, (float)kCellMax) : 0u;   // (NaN -> 0: the code only steers the search, never its result)
+}
+
+// lo / hi of six floats reduced over the workgroup (256 lanes), result in every lane
+__device__ void block_minmax(float lo[3], float hi[3], float* s_red /* 6 * 4 floats */) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int a = 0; a < 3; ++a) { lo[a] = wave_min(lo[a]); hi[a] = wave_max(hi[a]); }
+    if (lane == 0)
+        for (int a = 0; a < 3; ++a) { s_red[a * 4 + wave] = lo[a]; s_red[(3 + a) * 4 + wave] = hi[a]; }
+    __syncthreads();
+    for (int a = 0; a < 3; ++a) {
+        lo[a] = fminf(fminf(s_red[a * 4], s_red[a * 4 + 1]), fminf(s_red[a * 4 + 2], s_red[a * 4 + 3]));
+        hi[a] = fmaxf(fmaxf(s_red[(3 + a) * 4], s_red[(3 + a) * 4 + 1]), fmaxf(s_red[(3 + a) * 4 + 2], s_red[(3 + a) * 4 + 3]));
+    }
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(256) void tri_bounds_kernel(int64_t V, const float* __restrict__ verts, uint32_t F,
+                                                         const long long* __restrict__ faces, float4* __restrict__ partials) {
+    __shared__ float s_red[24];
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (uint32_t f = blockIdx.x * 256u + threadIdx.x; f < F; f += kBoundsBlocks * 256u) {
+        Vec3 a, b, c;
+        if (load_face(V, verts, faces, f, a, b, c)) {
+            const Vec3 m = centroid(a, b, c);
+            lo[0] = fminf(lo[0], m.x); lo[1] = fminf(lo[1], m.y); lo[2] = fminf(lo[2], m.z);
+            hi[0] = fmaxf(hi[0], m.x); hi[1] = fmaxf(hi[1], m.y); hi[2] = fmaxf(hi[2], m.z);
+        }
+    }
+    block_minmax(lo, hi, s_red);
+    if (threadIdx.x == 0) {
+        partials[2 * blockIdx.x] = make_float4(lo[0], lo[1], lo[2], 0.0f);
+        partials[2 * blockIdx.x + 1] = make_float4(hi[0], hi[1], hi[2], 0.0f);
+    }
+}
+
+__global__ __launch_bounds__(256) void tri_codes_kernel(int64_t V, const float* __restrict__ verts, uint32_t F,
+                                                        const long long* __restrict__ faces, const float4* __restrict__ partials,
+                                                        uint32_t* __restrict__ key_lo, uint32_t* __restrict__ key_hi) {
+    __shared__ float s_red[24];
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    if (threadIdx.x < kBoundsBlocks) {
+        const float4 a = partials[2 * threadIdx.x], b = partials[2 * threadIdx.x + 1];
+        lo[0] = a.x; lo[1] = a.y; lo[2] = a.z; hi[0] = b.x; hi[1] = b.y; hi[2] = b.z;
+    }
+    block_minmax(lo, hi, s_red);
+    for (uint32_t f = blockIdx.x * 256u + threadIdx.x; f < F; f += gridDim.x * 256u) {
+        Vec3 a, b, c;
+        uint64_t code = (uint64_t)kInvalidKey << 32;
+        if (load_face(V, verts, faces, f, a, b, c)) {
+            const Vec3 m = centroid(a, b, c);
+            code = spread21(grid_cell(m.x, lo[0], hi[0])) | (spread21(grid_cell(m.y, lo[1], hi[1])) << 1) |
+                   (spread21(grid_cell(m.z, lo[2], hi[2])) << 2);
+        }
+        key_lo[f] = (uint32_t)code;
+        key_hi[f] = (uint32_t)(code >> 32);
+    }
+}
+
+// the high words in the order of the first sort (by the low words), for the second
+__global__ __launch_bounds__(256) void tri_gather_kernel(uint32_t n, const uint32_t* __restrict__ order, const uint32_t* __restrict__ key_hi,
+                                                         uint32_t* __restrict__ out) {
+    const uint32_t s = blockIdx.x * 256u + threadIdx.x;
+    if (s < n) out[s] = key_hi[order[s]];
+}
+
+// one wave per leaf: the sorted faces' records, the leaf's box (the union of its valid triangles' own boxes)
+__global__ __launch_bounds__(256) void tri_pack_kernel(int64_t V, const float* __restrict__ verts, uint32_t F,
+                                                       const long long* __restrict__ faces, const uint32_t* __restrict__ order,
+                                                       float4* __restrict__ records, float4* __restrict__ leaf_boxes) {
+    const uint32_t s = blockIdx.x * 256u + threadIdx.x;
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    if (s < F) {
+        const uint32_t f = order[s];
+        Vec3 a, b, c;
+        if (f < F && load_face(V, verts, faces, f, a, b, c)) {
+            records[3 * (size_t)s] = make_float4(a.x, a.y, a.z, __uint_as_float(f));
+            records[3 * (size_t)s + 1] = make_float4(b.x, b.y, b.z, 0.0f);
+            records[3 * (size_t)s + 2] = make_float4(c.x, c.y, c.z, 0.0f);
+            lo[0] = fminf(fminf(a.x, b.x), c.x); lo[1] = fminf(fminf(a.y, b.y), c.y); lo[2] = fminf(fminf(a.z, b.z), c.z);
+            hi[0] = fmaxf(fmaxf(a.x, b.x), c.x); hi[1] = fmaxf(fmaxf(a.y, b.y), c.y); hi[2] = fmaxf(fmaxf(a.z, b.z), c.z);
+        } else {
+            const float4 none = make_float4(NAN, NAN, NAN, __uint_as_float(kNoFace));
+            records[3 * (size_t)s] = none;
+            records[3 * (size_t)s + 1] = none;
+            records[3 * (size_t)s + 2] = none;
+        }
+    }
+    for (int a = 0; a < 3; ++a) { lo[a] = wave_min(lo[a]); hi[a] = wave_max(hi[a]); }
+    const uint32_t leaf = s / kLeaf;
+    if ((threadIdx.x & 63) == 0 && leaf * kLeaf < F) {
+        leaf_boxes[2 * (size_t)leaf] = make_float4(lo[0], lo[1], lo[2], 0.0f);
+        leaf_boxes[2 * (size_t)leaf + 1] = make_float4(hi[0], hi[1], hi[2], 0.0f);
+    }
+}
+
+__global__ __launch_bounds__(256) void tri_level_kernel(uint32_t n_parents, uint32_t n_children, const float4* __restrict__ children,
+                                                        float4* __restrict__ parents) {
+    const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+    if (p >= n_parents) return;
+    float4 lo = make_float4(INFINITY, INFINITY, INFINITY, 0.0f), hi = make_float4(-INFINITY, -INFINITY, -INFINITY, 0.0f);
+    const uint32_t end = min(n_children, (p + 1) * kFan);
+    for (uint32_t c = p * kFan; c < end; ++c) {
+        const float4 a = children[2 * (size_t)c], b = children[2 * (size_t)c + 1];
+        lo.x = fminf(lo.x, a.x); lo.y = fminf(lo.y, a.y); lo.z = fminf(lo.z, a.z);
+        hi.x = fmaxf(hi.x, b.x); hi.y = fmaxf(hi.y, b.y); hi.z = fmaxf(hi.z, b.z);
+    }
+    parents[2 * (size_t)p] = lo;
+    parents[2 * (size_t)p + 1] = hi;
+}
+
+// the last kernel of a build
+__global__ void tri_header_kernel(TriHeader* header, uint32_t F, unsigned long long plan_bytes) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        TriHeader h;
+        h.magic = kPlanMagic;
+        h.F = F;
+        h.plan_bytes = plan_bytes;
+        *header = h;
+    }
+}
+
+struct Query {
+    float x, y, z;
+    bool active;   // in range and finite: the others answer (-1, +inf, 0 0 0)
+};
+// A lane's slot: the best (d, face) so far and the point p' its d_tri used (relative to the query).
+struct Slot {
+    float d;
+    uint32_t face;
+    Vec3 p;
+};
+
+// d(q, f) of the contract (autovfx_amd/meshquery.py restates it in numpy, operation for operation).
+//   A = a - q, B = b - q, C = c - q: the triangle translated by -q, so that every later rounding error is relative to the distance
+//   scale, not to the coordinates.  p' = the closest point of (A, B, C) to the origin by the vertex / edge / interior region tests
+//   (Ericson, Real-Time Collision Detection 5.1.5), the first region that matches in the order below; every division is guarded (a zero
+//   denominator takes the region's first end point), so a degenerate triangle gives a finite answer.  d_tri = |p'|^2.
+//   d_box = box_bound of the triangle's own box (in the original coordinates), d_vtx = the smallest of |A|^2, |B|^2, |C|^2.
+//   d = fmin(fmax(d_tri, d_box), d_vtx): fmax / fmin ignore a NaN, so an overflowed d_tri falls back on the clamps.
+// The true distance lies in [d_box, d_vtx], so the clamps only remove rounding error -- and they make the search exact: see walk_tree.
+__device__ __forceinline__ float tri_dist(const Vec3& a, const Vec3& b, const Vec3& c, float d_box, const Query& q, Vec3& p) {
+    const Vec3 qv = {q.x, q.y, q.z};
+    const Vec3 A = sub(a, qv), B = sub(b, qv), C = sub(c, qv);
+    const Vec3 ab = sub(B, A), ac = sub(C, A);
+    const Vec3 ap = neg(A), bp = neg(B), cp = neg(C);
+    const float d1 = dot(ab, ap), d2 = dot(ac, ap);
+    const float d3 = dot(ab, bp), d4 = dot(ac, bp);
+    const float d5 = dot(ab, cp), d6 = dot(ac, cp);
+    const float vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
+    const float e = d4 - d3, g = d5 - d6;
+    if (d1 <= 0.0f && d2 <= 0.0f) {
+        p = A;
+    } else if (d3 >= 0.0f && d4 <= d3) {
+        p = B;
+    } else if (vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f) {
+        p = along(A, guarded(d1, d1 - d3), ab);
+    } else if (d6 >= 0.0f && d5 <= d6) {
+        p = C;
+    } else if (vb <= 0.0f && d2 >= 0.0f && d6 <= 0.0f) {
+        p = along(A, guarded(d2, d2 - d6), ac);
+    } else if (va <= 0.0f && e >= 0.0f && g >= 0.0f) {
+        p = along(B, guarded(e, e + g), sub(C, B));
+    } else {
+        const float den = (va + vb) + vc;
+        p = along(along(A, guarded(vb, den), ab), guarded(vc, den), ac);
+    }
+    const float d_tri = dot(p, p);
+    const float d_vtx = fminf(fminf(dot(A, A), dot(B, B)), dot(C, C));
+    return fminf(fmaxf(d_tri, d_box), d_vtx);
+}
+
+// `cnt` records of a leaf in LDS against the lane's slot.  A record whose own box is strictly farther than the slot cannot enter it
+// (d >= d_box by the clamp), so its region tests are skipped.
+__device__ __forceinline__ void slot_scan(const float4* leaf, int cnt, const Query& q, Slot& slot) {
+    for (int k = 0; k < cnt; ++k) {
+        const float4 ra = leaf[3 * k], rb = leaf[3 * k + 1], rc = leaf[3 * k + 2];
+        const uint32_t face = __float_as_uint(ra.w);
+        if (face == kNoFace) continue;   // an invalid face: never answered (wave-uniform)
+        const float4 lo = make_float4(fminf(fminf(ra.x, rb.x), rc.x), fminf(fminf(ra.y, rb.y), rc.y), fminf(fminf(ra.z, rb.z), rc.z), 0.0f);
+        const float4 hi = make_float4(fmaxf(fmaxf(ra.x, rb.x), rc.x), fmaxf(fmaxf(ra.y, rb.y), rc.y), fmaxf(fmaxf(ra.z, rb.z), rc.z), 0.0f);
+        const float d_box = box_bound(lo, hi, q.x, q.y, q.z);
+        if (!q.active || d_box > slot.d) continue;
+        Vec3 p;
+        const float d = tri_dist({ra.x, ra.y, ra.z}, {rb.x, rb.y, rb.z}, {rc.x, rc.y, rc.z}, d_box, q, p);
+        if (d < slot.d || (d == slot.d && face < slot.face)) {
+            slot.d = d;
+            slot.face = face;
+            slot.p = p;
+        }
+    }
+}
+
+// Children [first, first + cnt) of `level` kept by some lane, pushed farthest first so the nearest is popped next (gsr_knn.hip's
+// push_children without the own leaf).
+__device__ __forceinline__ void push_children(const float4* boxes /* of `level` */, int level, uint32_t first, int cnt, const Query& q,
+                                              float best, const float4& wlo, const float4& whi, uint32_t* stack, int& top, int lane) {
+    float4 clo = make_float4(INFINITY, INFINITY, INFINITY, 0.0f), chi = make_float4(-INFINITY, -INFINITY, -INFINITY, 0.0f);
+    if (lane < cnt) { clo = boxes[2 * (size_t)(first + lane)]; chi = boxes[2 * (size_t)(first + lane) + 1]; }
+    uint32_t keep = 0u;
+    for (int j = 0; j < cnt; ++j) {
+        const float4 lo = make_float4(lane_value(clo.x, j), lane_value(clo.y, j), lane_value(clo.z, j), 0.0f);
+        const float4 hi = make_float4(lane_value(chi.x, j), lane_value(chi.y, j), lane_value(chi.z, j), 0.0f);
+        const float lb = box_bound(lo, hi, q.x, q.y, q.z);
+        if (__ballot(q.active && !(lb > best)) != 0ull) keep |= 1u << j;
+    }
+    if (keep == 0u) return;
+    // order key: the gap between the child's box and the wave's queries' box
+    const float gx = fmaxf(fmaxf(clo.x - whi.x, wlo.x - chi.x), 0.0f);
+    const float gy = fmaxf(fmaxf(clo.y - whi.y, wlo.y - chi.y), 0.0f);
+    const float gz = fmaxf(fmaxf(clo.z - whi.z, wlo.z - chi.z), 0.0f);
+    const float key =(gx * gx + gy * gy) + gz * gz;   // never NaN: fmaxf drops one, and the terms are not negative
+    int rank = 0;   // kept children farther than this one (ties: the higher index counts as farther): a permutation of the kept
+    for (int j = 0; j < cnt; ++j) {
+        const float kj = lane_value(key, j);
+        rank += ((keep >> j) & 1u) && (kj > key || (kj == key && j > lane)) ? 1 : 0;
+    }
+    if (lane < cnt && ((keep >> lane) & 1u)) (stack + top)[rank] = ((uint32_t)level << 29) | (first + lane);
+    top += __popc(keep);
+    wave_sync();
+}
+
+// The walk of gsr_knn.hip over triangles: depth first from the top on the wave-uniform `stack` in LDS.  A node's children are kept if
+// some lane's lower bound is not above that lane's slot (a ballot per child) and pushed nearest first; a popped leaf is tested again,
+// the slots having tightened since the push, then staged into `leaf` with coalesced loads (3 KiB) between two wave_sync() and scanned
+// by all lanes at once.
+// Exactness.  d(q, f) = fmin(fmax(d_tri, d_box), d_vtx) never lies below d_box, the box_bound of the triangle's own box.  box_bound is
+// formed with the rounded operations of a squared distance (per axis the gap lo - q or q - hi, squared, summed in one order), and
+// rounding to nearest is monotone: a box that contains the triangle's box has gaps that are not larger on any axis, so its bound never
+// exceeds d_box, hence never d(q, f) -- however badly conditioned d_tri is for a sliver or a distant triangle.  (The same monotonicity
+// gives d_box <= d_vtx, a corner lying inside the triangle's box, so d really is clamped into [d_box, d_vtx].)  The prune rule, here,
+// in push_children and in slot_scan, is !(lb > best): a box is skipped only when its bound is strictly above the slot of every lane,
+// so that no member could enter one.  At equality a member with a lower face index still could: pruning on >= would return the right
+// distances and, above a shared vertex or on a duplicated face, the wrong index.  The slots start at (+inf, no face): a finite query
+// with a valid face always has an answer, at +inf if its distances overflow.
+__device__ __forceinline__ void walk_tree(const float4* boxes, const TriTree& tree, uint32_t F, const float4* records, const Query& q,
+                                          float4* leaf, uint32_t* stack, int lane, Slot& slot) {
+    if (__ballot(q.active) == 0ull) return;
+    const float4 wlo = make_float4(wave_min(q.active ? q.x : INFINITY), wave_min(q.active ? q.y : INFINITY),
+                                   wave_min(q.active ? q.z : INFINITY), 0.0f);
+    const float4 whi = make_float4(wave_max(q.active ? q.x : -INFINITY), wave_max(q.active ? q.y : -INFINITY),
+                                   wave_max(q.active ? q.z : -INFINITY), 0.0f);
+    int top = 0;
+    uint32_t count, offset;
+    tri_level(tree.leaves, tree.top, count, offset);
+    push_children(boxes + 2 * (size_t)offset, tree.top, 0u, (int)min(count, (uint32_t)kFan), q, slot.d, wlo, whi, stack, top, lane);
+    while (top > 0) {
+        const uint32_t e = (uint32_t)__builtin_amdgcn_readfirstlane((int)stack[--top]);
+        const int level = (int)(e >> 29);
+        const uint32_t node = e & ((1u << 29) - 1u);
+        if (level > 0) {
+            const uint32_t first = node * kFan;
+            tri_level(tree.leaves, level - 1, count, offset);
+            push_children(boxes + 2 * (size_t)offset, level - 1, first, (int)min((uint32_t)kFan, count - first), q, slot.d, wlo, whi, stack,
+                          top, lane);
+            continue;
+        }
+        const float4 lo = boxes[2 * (size_t)node], hi = boxes[2 * (size_t)node + 1];   // (leaves: level offset 0)
+        const float lb = box_bound(lo, hi, q.x, q.y, q.z);
+        if (__ballot(q.active && !(lb > slot.d)) == 0ull) continue;
+        const uint32_t base = node * kLeaf;
+        const int cnt = (int)min((uint32_t)kLeaf, F - base);
+        wave_sync();
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const int at = k * kLeaf + lane;
+            if (at < 3 * cnt) leaf[at] = records[3 * (size_t)base + at];
+        }
+        wave_sync();
+        slot_scan(leaf, cnt, q, slot);
+    }
+}
+
+__global__ __launch_bounds__(256) void tri_query_kernel(uint32_t n, const float* __restrict__ points, const unsigned char* __restrict__ plan,
+                                                        unsigned long long plan_bytes, long long* __restrict__ face_idx,
+                                                        float* __restrict__ sq_dist, float* __restrict__ closest) {
+    __shared__ float4 s_leaf[4][3 * kLeaf];
+    __shared__ uint32_t s_stack[4][kStackDepth];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t group = blockIdx.x * 4u + (uint32_t)wave;    // this wave's 64 queries
+    if ((unsigned long long)group * kLeaf >= n) return;
+    const uint32_t s = group * kLeaf + lane;
+    Query q = {0.0f, 0.0f, 0.0f, false};
+    if (s < n) {
+        const float x = points[3 * (size_t)s], y = points[3 * (size_t)s + 1], z = points[3 * (size_t)s + 2];
+        if (finite3(x, y, z)) q = {x, y, z, true};
+    }
+    // the header against the size the caller holds, before anything else of the plan is read (plan_bytes >= 256: checked by the host)
+    const TriHeader h = *reinterpret_cast<const TriHeader*>(plan);
+    Slot slot = {INFINITY, kNoFace, {0.0f, 0.0f, 0.0f}};
+    if (h.magic == kPlanMagic && h.plan_bytes == plan_bytes && h.F > 0u && h.F < (uint32_t)kMaxFaces) {
+        const TriTree tree = tri_layout(h.F);
+        if (tree.bytes == plan_bytes)
+            walk_tree(reinterpret_cast<const float4*>(plan + tree.boxes), tree, h.F, reinterpret_cast<const float4*>(plan + tree.records), q,
+                      s_leaf[wave], s_stack[wave], lane, slot);
+    }
+    if (s >= n) return;
+    const bool found = q.active && slot.face != kNoFace;
+    face_idx[s] = found ? (long long)slot.face : -1ll;
+    sq_dist[s] = found ? slot.d : INFINITY;
+    if (closest) {
+        closest[3 * (size_t)s] = found ? q.x + slot.p.x : 0.0f;
+        closest[3 * (size_t)s + 1] = found ? q.y + slot.p.y : 0.0f;
+        closest[3 * (size_t)s + 2] = found ? q.z + slot.p.z : 0.0f;
+    }
+}
+
+// bounds -> codes -> sort -> pack -> levels -> header.  scratch: tri_scratch(F).bytes; plan: tri_layout(F).bytes; F < 2^30
+hipError_t launch_plan(int64_t V, const float* verts, uint32_t F, const long long* faces, unsigned char* plan, void* scratch,
+                       hipStream_t stream) {
+    const TriTree tree = tri_layout(F);
+    if (F > 0) {
+        uint32_t count, offset;
+        tri_level(tree.leaves, tree.top, count, offset);
+        if (count > (uint32_t)kFan) return hipErrorInvalidValue;   // (F < 2^30 never gets here)
+        const TriScratch L = tri_scratch(F);
+        char* base = static_cast<char*>(scratch);
+        auto u32 = [&](size_t at) { return reinterpret_cast<uint32_t*>(base + at); };
+        uint32_t *keys = u32(L.keys), *keys_alt = u32(L.keys_alt), *vals = u32(L.vals), *vals_alt = u32(L.vals_alt), *key_hi = u32(L.key_hi);
+        float4* partials = reinterpret_cast<float4*>(base + L.partials);
+        float4* records = reinterpret_cast<float4*>(plan + tree.records);
+        float4* boxes = reinterpret_cast<float4*>(plan + tree.boxes);
+        const uint32_t blocks = (F + 255u) / 256u;
+        hipLaunchKernelGGL(tri_bounds_kernel, dim3(kBoundsBlocks), dim3(256), 0, stream, V, verts, F, faces, partials);
+        hipLaunchKernelGGL(tri_codes_kernel, dim3(min(blocks, 2048u)), dim3(256), 0, stream, V, verts, F, faces, (const float4*)partials, keys,
+                           key_hi);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        // the 63-bit codes, least significant word first (both sorts are stable)
+        uint32_t *ks = nullptr, *vs = nullptr;
+        e = radix_sort_pairs(u32(L.radix), F, 32, keys, keys_alt, vals, vals_alt, true, false, &ks, &vs, stream);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(tri_gather_kernel, dim3(blocks), dim3(256), 0, stream, F, (const uint32_t*)vs, (const uint32_t*)key_hi, keys);
+        e = radix_sort_pairs(u32(L.radix), F, 32, keys, keys_alt, vs, vs == vals ? vals_alt : vals, false, false, &ks, &vs, stream);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(tri_pack_kernel, dim3(blocks), dim3(256), 0, stream, V, verts, F, faces, (const uint32_t*)vs, records, boxes);
+        for (int level = 1; level <= tree.top; ++level) {
+            uint32_t below, below_at;
+            tri_level(tree.leaves, level - 1, below, below_at);
+            tri_level(tree.leaves, level, count, offset);
+            hipLaunchKernelGGL(tri_level_kernel, dim3((count + 255u) / 256u), dim3(256), 0, stream, count, below,
+                               (const float4*)(boxes + 2 * (size_t)below_at), boxes + 2 * (size_t)offset);
+        }
+    }
+    hipLaunchKernelGGL(tri_header_kernel, dim3(1), dim3(64), 0, stream, reinterpret_cast<TriHeader*>(plan), F, (unsigned long long)tree.bytes);
+    return hipGetLastError();
+}
+
+bool misaligned(const void* p, uintptr_t to) { return ((uintptr_t)p & (to - 1u)) != 0u; }
+
+}  // namespace
+}  // namespace gsr
+
+using gsr::fail;
+
+extern "C" {
+
+size_t gsr_closest_tri_plan_bytes(int64_t F) {
+    return (F < 0 || F >= gsr::kMaxFaces) ? 0 : gsr::tri_layout((uint32_t)F).bytes;
+}
+
+size_t gsr_closest_tri_plan_scratch_bytes(int64_t F) {
+    return (F < 0 || F >= gsr::kMaxFaces) ? 0 : gsr::tri_scratch((uint32_t)F).bytes;
+}
+
+int gsr_closest_tri_plan(int64_t V, const float* verts, int64_t F, const int64_t* faces, void* plan, size_t plan_bytes, void* scratch,
+                         size_t scratch_bytes, void* stream_) {
+    if (V < 0 || F < 0) return fail(GSR_ERR_INVALID_ARG, "gsr_closest_tri_plan: negative count (V %lld, F %lld)", (long long)V, (long long)F);
+    if (F >= gsr::kMaxFaces) return fail(GSR_ERR_INVALID_ARG, "gsr_closest_tri_plan: %lld faces (at most 2^30 - 1)", (long long)F);
+    if (V >= gsr::kMaxVerts) return fail(GSR_ERR_INVALID_ARG, "gsr_closest_tri_plan: %lld vertices (at most 2^31 - 1)", (long long)V);
+    const size_t need_plan = gsr_closest_tri_plan_bytes(F), need_scratch = gsr_closest_tri_plan_scratch_bytes(F);
+    if ((!verts && V > 0 && F > 0) || (!faces && F > 0) || !plan || (!scratch && need_scratch > 0))
+        return fail(GSR_ERR_INVALID_ARG, "gsr_closest_tri_plan: null pointer");
+    if (gsr::misaligned(verts, 4) || gsr::misaligned(faces, 8) || gsr::misaligned(plan, 256) || gsr::misaligned(scratch, 256))
+        return fail(GSR_ERR_INVALID_ARG, "gsr_closest_tri_plan: misaligned pointer (verts: 4 bytes, faces: 8 bytes, plan / scratch: 256 bytes)");
+    if (plan_bytes < need_plan) return fail(GSR_ERR_INVALID_ARG, "gsr_closest_tri_plan: plan too small (%zu of %zu bytes)", plan_bytes, need_plan);
+    if (scratch_bytes < need_scratch)
+        return fail(GSR_ERR_INVALID_ARG, "gsr_closest_tri_plan: scratch too small (%zu of %zu bytes)", scratch_bytes, need_scratch);
+    GSR_HIP(gsr::launch_plan(V, verts, (uint32_t)F, reinterpret_cast<const long long*>(faces), static_cast<unsigned char*>(plan), scratch,
+                             (hipStream_t)stream_));
+    return GSR_OK;
+}
+
+int gsr_closest_tri_query(int64_t n, const float* points, const void* plan, size_t plan_bytes, int64_t* face_idx, float* sq_dist,
+                          float* closest, void* stream_) {
+    if (n < 0) return fail(GSR_ERR_INVALID_ARG, "gsr_closest_tri_query: negative count (n %lld)", (long long)n);
+    if (n >= gsr::kMaxQueries) return fail(GSR_ERR_INVALID_ARG, "gsr_closest_tri_query: %lld queries (at most 2^31 - 1)", (long long)n);
+    if (n == 0) return GSR_OK;
+    if (!points || !plan || !face_idx || !sq_dist) return fail(GSR_ERR_INVALID_ARG, "gsr_closest_tri_query: null pointer");
+    if (gsr::misaligned(points, 4) || gsr::misaligned(plan, 256) || gsr::misaligned(face_idx, 8) || gsr::misaligned(sq_dist, 4) ||
+        gsr::misaligned(closest, 4))
+        return fail(GSR_ERR_INVALID_ARG, "gsr_closest_tri_query: misaligned pointer (points / sq_dist / closest: 4 bytes, face_idx: 8 bytes, "
+                                         "plan: 256 bytes)");
+    // every plan is a whole number of 256-byte blocks, the header first; the header itself is compared with plan_bytes on the device
+    if (plan_bytes < gsr::kAlign || (plan_bytes & (gsr::kAlign - 1)) != 0)
+        return fail(GSR_ERR_INVALID_ARG, "gsr_closest_tri_query: plan_bytes = %zu is not the size of a plan", plan_bytes);
+    const uint32_t groups = (uint32_t)((n + gsr::kLeaf - 1) / gsr::kLeaf);
+    hipLaunchKernelGGL(gsr::tri_query_kernel, dim3((groups + 3u) / 4u), dim3(256), 0, (hipStream_t)stream_, (uint32_t)n, points,
+                       static_cast<const unsigned char*>(plan), (unsigned long long)plan_bytes, reinterpret_cast<long long*>(face_idx), sq_dist,
+                       closest);
+    GSR_HIP(hipGetLastError());
+    return GSR_OK;
+}
+
+}  // extern "C"

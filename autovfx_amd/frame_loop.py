@@ -13,7 +13,8 @@ Here:
 * everything that does not depend on the frame is done ONCE per object -- its PLY, its mesh centre, (melting) the ray-casting
   scene and the Gaussians' closest triangles -- with the reference module's own functions (``load_gaussians``,
   ``get_center_of_mesh_2``, ``trimesh``, ``o3d`` are taken from the module that defines the scene class: nothing of them is
-  restated here);
+  restated here); with ``AUTOVFX_AMD_MELT_CLOSEST=gpu`` (opt-in, ``melt_closest_mode``) the melting branch's closest-triangle
+  questions go to ``autovfx_amd.meshquery`` instead of ``o3d``, and a frame's mask is built on the GPU;
 * a frame with placed objects is composed by ``DynamicScene`` -- one HIP kernel per placed object into resident, activated buffers
   (``gsr_place_object[_subset]``), bit-identical to transform -> merge -> activate; a frame without any renders the scene's own
   model, at its own SH degree, as the reference's deep copy does;
@@ -75,6 +76,26 @@ def _make_dynamic_scene(base, objects, device, sh_degree, slots, copies):
 def _side_streams(device, count):
     from .frame_parallel import side_streams
     return side_streams(device, count)
+
+
+def _make_mesh_scene(verts, faces, device):
+    from . import meshquery
+    return meshquery.Scene(np.asarray(verts, dtype=np.float32), np.asarray(faces, dtype=np.int64), device=device)
+
+
+MELT_CLOSEST_MODES = ("host", "gpu")
+
+
+def melt_closest_mode() -> str:
+    """Who answers the melting branch's closest-triangle questions: ``AUTOVFX_AMD_MELT_CLOSEST`` = ``host`` (the default, also when
+    unset: the scene module's own ``o3d``, as the reference) or ``gpu`` (``autovfx_amd.meshquery``: the plan of every object's
+    original mesh and its Gaussians' triangle ids once per call, one query per frame and melting mesh, the mask a device tensor;
+    ``o3d`` is not touched).  Opt-in, as the geometry cache is: Open3D's choice among near-equal distances is not specified, so the
+    GPU path does not stand in for it unasked.  Anything else raises ``ValueError``."""
+    mode = os.environ.get("AUTOVFX_AMD_MELT_CLOSEST", "host")
+    if mode not in MELT_CLOSEST_MODES:
+        raise ValueError(f"AUTOVFX_AMD_MELT_CLOSEST={mode!r}: expected one of {MELT_CLOSEST_MODES}")
+    return mode
 
 
 def png_mode() -> str:
@@ -223,21 +244,28 @@ class _MeltingPlan:
     closest triangle of the ORIGINAL mesh is also the closest triangle of some face centre of the frame's melting mesh
     (``NNN_obj.stl``, then ``NNN_obj_dup.stl``) are merged behind the scene, untransformed.  The original mesh, its ray-casting
     scene and the Gaussians' triangle ids do not depend on the frame: they are computed once per object here (the reference
-    recomputes them every frame), with the reference module's own ``trimesh`` / ``o3d``."""
+    recomputes them every frame), with the reference module's own ``trimesh`` / ``o3d`` -- or, with ``closest == "gpu"``
+    (``melt_closest_mode``), with ``autovfx_amd.meshquery``, the ids and every frame's mask staying on the GPU."""
 
-    def __init__(self, scene, mod, mesh_output_dir, streams):
-        self.scene, self.mod, self.objects = scene, mod, []
-        o3d, trimesh = mod.o3d, mod.trimesh
+    def __init__(self, scene, mod, mesh_output_dir, streams, closest="host"):
+        self.scene, self.mod, self.objects, self.closest = scene, mod, [], closest
+        trimesh = mod.trimesh
         models = {}
         for obj_id in sorted(os.listdir(mesh_output_dir)):                                               # (:377)
             obj_info = _object_info(scene, obj_id)
             orig_mesh_path = obj_info['object_path']
             orig_mesh = trimesh.load_mesh(orig_mesh_path)
             orig_gaussians = mod.load_gaussians(_object_gaussians_path(obj_info), scene.hparams.max_sh_degree - 1)
-            ray_scene = o3d.t.geometry.RaycastingScene()
-            ray_scene.add_triangles(o3d.t.geometry.TriangleMesh.from_legacy(orig_mesh.as_open3d))
-            xyz = orig_gaussians._xyz.detach().cpu().numpy()
-            ids = ray_scene.compute_closest_points(o3d.core.Tensor.from_numpy(xyz.astype(np.float32)))['primitive_ids'].cpu().numpy()
+            if closest == "gpu":
+                ray_scene = _make_mesh_scene(orig_mesh.vertices, orig_mesh.faces, scene.gaussians._xyz.device)
+                ids = ray_scene.compute_closest_points(orig_gaussians._xyz.detach())['primitive_ids']      # stays on the GPU
+                ids = torch.where(ids >= 0, ids, ray_scene.plan.F)     # (-1, no answer: the spare flag of _mask, always clear)
+            else:
+                o3d = mod.o3d
+                ray_scene = o3d.t.geometry.RaycastingScene()
+                ray_scene.add_triangles(o3d.t.geometry.TriangleMesh.from_legacy(orig_mesh.as_open3d))
+                xyz = orig_gaussians._xyz.detach().cpu().numpy()
+                ids = ray_scene.compute_closest_points(o3d.core.Tensor.from_numpy(xyz.astype(np.float32)))['primitive_ids'].cpu().numpy()
             self.objects.append((obj_id, os.path.join(mesh_output_dir, obj_id), ray_scene, ids))
             models[obj_id] = (orig_gaussians, (0.0, 0.0, 0.0))
         self.dynamic = None
@@ -246,8 +274,24 @@ class _MeltingPlan:
             # an object can be merged twice in one frame (its mesh and the mesh's duplicate): room for two copies of each
             self.dynamic = _make_dynamic_scene(base, models, base._xyz.device, int(base.active_sh_degree), max(1, streams), 2)
 
+    def _mask(self, ray_scene, triangle_ids_from_gaussians, centres):
+        """Which Gaussians stay: those whose triangle is the closest one of some face centre (:399-411)."""
+        if self.closest == "gpu":
+            # one query for the centres, a flag per original face set at the answered ids, gathered at the Gaussians' ids; an id of
+            # -1 (no valid face, a non-finite point) goes to a spare flag at the end, which is cleared again.  No host read here:
+            # the mask's count is read once, where compose_model sizes the frame (dynamic_scene.py)
+            ids = ray_scene.compute_closest_points(centres)['primitive_ids']
+            F = int(ray_scene.plan.F)
+            flags = torch.zeros(F + 1, dtype=torch.uint8, device=ids.device)
+            flags[torch.where(ids >= 0, ids, F)] = 1
+            flags[F] = 0
+            return flags[triangle_ids_from_gaussians].to(torch.bool)
+        o3d = self.mod.o3d
+        ids = ray_scene.compute_closest_points(o3d.core.Tensor.from_numpy(centres))['primitive_ids'].cpu().numpy()
+        return np.isin(triangle_ids_from_gaussians, ids)                                                  # (:411)
+
     def model_for_frame(self, idx, slot):
-        o3d, trimesh = self.mod.o3d, self.mod.trimesh
+        trimesh = self.mod.trimesh
         placed = []
         for obj_id, melting_mesh_dir, ray_scene, triangle_ids_from_gaussians in self.objects:
             for path in (os.path.join(melting_mesh_dir, '{0:03d}_obj.stl'.format(idx + 1)),
@@ -256,20 +300,18 @@ class _MeltingPlan:
                     continue
                 melting_mesh = trimesh.load_mesh(path)
                 centres = np.array(melting_mesh.triangles_center).astype(np.float32)
-                ids = ray_scene.compute_closest_points(o3d.core.Tensor.from_numpy(centres))['primitive_ids'].cpu().numpy()
-                mask = np.isin(triangle_ids_from_gaussians, ids)                                          # (:411)
-                placed.append((obj_id, None, None, None, mask))
+                placed.append((obj_id, None, None, None, self._mask(ray_scene, triangle_ids_from_gaussians, centres)))
         if not placed:
             return self.scene.gaussians
         return self.dynamic.compose_model(placed, slot=slot)
 
 
-def _plan(scene, mod, num_frames, streams):
+def _plan(scene, mod, num_frames, streams, closest="host"):
     if scene.rb_transform_info is not None:                                                               # (:357)
         return _RigidBodyPlan(scene, mod, num_frames, streams)
     mesh_output_dir = os.path.join(scene.blender_cache_dir, scene.hparams.blender_output_dir_name, 'melting_meshes')
     if os.path.exists(mesh_output_dir):                                                                   # (:373)
-        return _MeltingPlan(scene, mod, mesh_output_dir, streams)
+        return _MeltingPlan(scene, mod, mesh_output_dir, streams, closest)
     return _StaticPlan(scene)
 
 
@@ -277,6 +319,7 @@ def render_from_3DGS(self, render_video=False, post_rendering=False):
     """``SceneRepresentation.render_from_3DGS`` (``scene_representation.py:337-447``): same arguments, same directories and file
     names, same pixels and ``.npy`` bytes; see the module docstring for what is different underneath."""
     mod = sys.modules[type(self).__module__]           # the reference's module: its helpers and host libraries are used as they are
+    closest = melt_closest_mode()                      # (a wrong value raises here, before anything is loaded or written)
 
     self.load_scene()  # reload the scene to get the latest gaussians (:339)
 
@@ -297,7 +340,7 @@ def render_from_3DGS(self, render_video=False, post_rendering=False):
     names = [view.image_name for view in camera_views]
     with torch.no_grad():
         t0 = time.perf_counter()
-        plan = _plan(self, mod, len(camera_views), streams)
+        plan = _plan(self, mod, len(camera_views), streams, closest)
         t1 = time.perf_counter()
         mine = list(range(rank, len(camera_views), world))
         tqdm = getattr(mod, "tqdm", None)

@@ -1,0 +1,316 @@
+"""The closest triangle of a mesh to every query point, on the GPU: what Open3D's ``RaycastingScene.compute_closest_points``
+answers for the melting frames of the frame loop (``scene_representation.py:385-412``) and for object extraction
+(``extract/extract_object.py:105-110``).
+
+The contract, pointwise.  A face is *valid* when its three indices lie in ``[0, V)`` and its nine
+coordinates are finite.  The answer for query ``q`` is the valid face with the smallest ``(d(q, f), f)`` -- equal distances go to
+the lower face index -- where, all in fp32 elementwise operations (no fused multiply-add), with ``dot(u, v) = (ux vx + uy vy) + uz vz``:
+
+* ``A = a - q``, ``B = b - q``, ``C = c - q``; ``ab = B - A``, ``ac = C - A``; ``d1 = dot(ab, -A)``, ``d2 = dot(ac, -A)``,
+  ``d3 = dot(ab, -B)``, ``d4 = dot(ac, -B)``, ``d5 = dot(ab, -C)``, ``d6 = dot(ac, -C)``; ``vc = d1 d4 - d3 d2``, ``vb = d5 d2 - d1 d6``,
+  ``va = d3 d6 - d5 d4``; ``e = d4 - d3``, ``g = d5 - d6``;
+* ``p'`` is the first of (Ericson's regions): ``A`` if ``d1 <= 0 and d2 <= 0``; ``B`` if ``d3 >= 0 and d4 <= d3``;
+  ``A + (d1 / (d1 - d3)) ab`` if ``vc <= 0 and d1 >= 0 and d3 <= 0``; ``C`` if ``d6 >= 0 and d5 <= d6``;
+  ``A + (d2 / (d2 - d6)) ac`` if ``vb <= 0 and d2 >= 0 and d6 <= 0``; ``B + (e / (e + g)) (C - B)`` if ``va <= 0 and e >= 0 and g >= 0``;
+  else ``(A + (vb / s) ab) + (vc / s) ac`` with ``s = (va + vb) + vc``.  A quotient whose denominator is zero is 0: the region's first
+  end point, so a degenerate triangle gives a finite answer;
+* ``d_tri = dot(p', p')``; ``d_box`` = the squared gap between ``q`` and the triangle's own box, per axis
+  ``max(max(lo - q, q - hi), 0)``, summed like ``dot``; ``d_vtx = min(min(dot(A, A), dot(B, B)), dot(C, C))``;
+* ``d = fmin(fmax(d_tri, d_box), d_vtx)`` (a NaN ``d_tri``, from an overflow, is ignored); the closest point is ``q + p'``.
+
+The true distance lies in ``[d_box, d_vtx]``, so the clamps only remove rounding error; and the bound of any tree box that contains
+the triangle never exceeds ``d_box``, so the tree search of ``gsr_meshquery.hip`` finds exactly the brute-force answer, index ties
+included.  A non-finite query, and any query when no face is valid, gets ``(-1, +inf, (0, 0, 0))``.
+
+:func:`closest_triangles` runs the HIP kernels (C ABI ``gsr_closest_tri_plan`` / ``gsr_closest_tri_query``);
+:func:`closest_triangles_host` restates the contract in numpy by brute force, the checker of the tests; :class:`Scene` is a small
+adapter for code written against Open3D's ray-casting scene.  ``autovfx_amd.install()`` does not put it over Open3D: the frame loop
+uses it when ``AUTOVFX_AMD_MELT_CLOSEST=gpu`` (``autovfx_amd/frame_loop.py``).
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+import numpy as np
+import torch
+
+MAX_FACES = (1 << 30) - 1
+MAX_VERTS = (1 << 31) - 1
+MAX_QUERIES = (1 << 31) - 1
+_F = np.float32
+
+
+# ---- the contract in numpy ----------------------------------------------------------------------------------------------------------
+def _dot(u, v):
+    return (u[0] * v[0] + u[1] * v[1]) + u[2] * v[2]
+
+
+def _sub(u, v):
+    return (u[0] - v[0], u[1] - v[1], u[2] - v[2])
+
+
+def _neg(u):
+    return (-u[0], -u[1], -u[2])
+
+
+def _along(u, s, v):
+    return (u[0] + s * v[0], u[1] + s * v[1], u[2] + s * v[2])
+
+
+def _guarded(num, den):
+    ok = den != 0
+    return np.where(ok, num / np.where(ok, den, _F(1)), _F(0))
+
+
+def triangle_distance_host(q, a, b, c):
+    """``d(q, f)`` of the contract for float32 arrays ``q``, ``a``, ``b``, ``c`` of shape ``[..., 3]`` that broadcast against each
+    other.  Returns a dict of float32 arrays: ``d``, ``d_tri``, ``d_box``, ``d_vtx`` (shape ``[...]``) and ``p`` (``[..., 3]``, the point
+    ``d_tri`` used, relative to the query).  Overflow and NaN pass through as in the kernel."""
+    q, a, b, c = (np.asarray(t, dtype=_F) for t in (q, a, b, c))
+    xyz = lambda t: (t[..., 0], t[..., 1], t[..., 2])
+    qv, av, bv, cv = xyz(q), xyz(a), xyz(b), xyz(c)
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore", under="ignore"):
+        A, B, C = _sub(av, qv), _sub(bv, qv), _sub(cv, qv)
+        ab, ac = _sub(B, A), _sub(C, A)
+        ap, bp, cp = _neg(A), _neg(B), _neg(C)
+        d1, d2 = _dot(ab, ap), _dot(ac, ap)
+        d3, d4 = _dot(ab, bp), _dot(ac, bp)
+        d5, d6 = _dot(ab, cp), _dot(ac, cp)
+        vc, vb, va = d1 * d4 - d3 * d2, d5 * d2 - d1 * d6, d3 * d6 - d5 * d4
+        e, g = d4 - d3, d5 - d6
+        den = (va + vb) + vc
+        regions = [(d1 <= 0) & (d2 <= 0), (d3 >= 0) & (d4 <= d3), (vc <= 0) & (d1 >= 0) & (d3 <= 0), (d6 >= 0) & (d5 <= d6),
+                   (vb <= 0) & (d2 >= 0) & (d6 <= 0), (va <= 0) & (e >= 0) & (g >= 0)]
+        points = [A, B, _along(A, _guarded(d1, d1 - d3), ab), C, _along(A, _guarded(d2, d2 - d6), ac),
+                  _along(B, _guarded(e, e + g), _sub(C, B))]
+        inside = _along(_along(A, _guarded(vb, den), ab), _guarded(vc, den), ac)
+        shape = np.broadcast(d1).shape
+        p = tuple(np.select(regions, [np.broadcast_to(pt[k], shape) for pt in points], default=inside[k]).astype(_F, copy=False)
+                  for k in range(3))
+        d_tri = _dot(p, p)
+        d_vtx = np.fmin(np.fmin(_dot(A, A), _dot(B, B)), _dot(C, C))
+        gaps = []
+        for k in range(3):
+            lo, hi = np.fmin(np.fmin(av[k], bv[k]), cv[k]), np.fmax(np.fmax(av[k], bv[k]), cv[k])
+            gaps.append(np.fmax(np.fmax(lo - qv[k], qv[k] - hi), _F(0)))
+        d_box = (gaps[0] * gaps[0] + gaps[1] * gaps[1]) + gaps[2] * gaps[2]
+        d = np.fmin(np.fmax(d_tri, d_box), d_vtx)
+    return {"d": d, "d_tri": d_tri, "d_box": d_box, "d_vtx": d_vtx, "p": np.stack(p, -1)}
+
+
+def valid_faces_host(verts: np.ndarray, faces: np.ndarray) -> np.ndarray:
+    """The contract's validity, ``[F]`` bool: three indices in ``[0, V)``, nine finite coordinates."""
+    V = verts.shape[0]
+    ok = np.all((faces >= 0) & (faces < V), axis=1)
+    fine = np.all(np.isfinite(verts), axis=1)
+    ok[ok] = np.all(fine[faces[ok]], axis=1)
+    return ok
+
+
+def closest_triangles_host(points, verts, faces, chunk_elems: int = 1 << 20):
+    """The contract restated in numpy: brute force over all valid faces, every operation an fp32 elementwise one in the contract's
+    order, chunked over the queries.  ``points``, ``verts``: anything ``np.asarray`` takes, reshaped to ``[., 3]`` float32; ``faces``
+    to ``[F, 3]`` int64.  Returns ``face_idx [n]`` int64, ``sq_dist [n]`` float32, ``closest [n, 3]`` float32."""
+    pts = np.ascontiguousarray(np.asarray(points, dtype=_F).reshape(-1, 3))
+    v = np.ascontiguousarray(np.asarray(verts, dtype=_F).reshape(-1, 3))
+    f = np.ascontiguousarray(np.asarray(faces, dtype=np.int64).reshape(-1, 3))
+    n = pts.shape[0]
+    face_idx = np.full(n, -1, np.int64)
+    sq_dist = np.full(n, np.inf, _F)
+    closest = np.zeros((n, 3), _F)
+    ids = np.nonzero(valid_faces_host(v, f))[0]                 # ascending: the first minimum of a row is the lowest face index
+    rows = np.nonzero(np.all(np.isfinite(pts), axis=1))[0]
+    if ids.size == 0 or rows.size == 0:
+        return face_idx, sq_dist, closest
+    a, b, c = (v[f[ids, k]][None, :, :] for k in range(3))
+    step = max(1, chunk_elems // ids.size)
+    for at in range(0, rows.size, step):
+        r = rows[at:at + step]
+        q = pts[r]
+        got = triangle_distance_host(q[:, None, :], a, b, c)
+        best = np.argmin(got["d"], axis=1)                      # (d is never NaN: fmin / fmax drop one, d_box and d_vtx have none)
+        pick = np.arange(r.size)
+        face_idx[r] = ids[best]
+        sq_dist[r] = got["d"][pick, best]
+        with np.errstate(over="ignore", invalid="ignore"):
+            closest[r] = q + got["p"][pick, best]
+    return face_idx, sq_dist, closest
+
+
+# ---- the kernels ----------------------------------------------------------------------------------------------------------------------
+class Plan:
+    """The tree over one mesh: ``buffer``, one ``uint8`` device tensor (``gsr_closest_tri_plan``), and the mesh's ``F`` and ``V``."""
+    __slots__ = ("buffer", "F", "V")
+
+    def __init__(self, buffer: torch.Tensor, F: int, V: int):
+        self.buffer, self.F, self.V = buffer, int(F), int(V)
+
+    @property
+    def device(self):
+        return self.buffer.device
+
+
+def _why_not_mesh(verts, faces) -> Optional[str]:
+    if not (isinstance(verts, torch.Tensor) and isinstance(faces, torch.Tensor)):
+        return "verts and faces must be torch.Tensors"
+    if not (verts.is_cuda and faces.is_cuda):
+        return f"verts and faces must be on a GPU (got {verts.device} and {faces.device}); there is no CPU path, see closest_triangles_host"
+    if verts.device != faces.device:
+        return f"verts and faces must be on one device (got {verts.device} and {faces.device})"
+    if verts.dtype != torch.float32 or faces.dtype != torch.int64:
+        return f"verts must be float32 and faces int64 (got {verts.dtype} and {faces.dtype})"
+    if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
+        return f"verts must be [V, 3] and faces [F, 3] (got {list(verts.shape)} and {list(faces.shape)})"
+    if faces.shape[0] > MAX_FACES or verts.shape[0] > MAX_VERTS:
+        return f"{faces.shape[0]} faces and {verts.shape[0]} vertices: at most 2^30 - 1 and 2^31 - 1"
+    from . import _lib
+
+    if _lib.capturing():
+        return "the current stream is capturing a graph (the call allocates its buffers)"
+    return None
+
+
+def _why_not_points(points, device) -> Optional[str]:
+    if not isinstance(points, torch.Tensor):
+        return "points must be a torch.Tensor"
+    if not points.is_cuda:
+        return f"points must be on a GPU (got {points.device}); there is no CPU path, see closest_triangles_host"
+    if points.device != device:
+        return f"points and the mesh must be on one device (got {points.device} and {device})"
+    if points.dtype != torch.float32:
+        return f"points must be float32 (got {points.dtype})"
+    if points.dim() != 2 or points.shape[1] != 3:
+        return f"points must be [n, 3] (got {list(points.shape)})"
+    if points.shape[0] > MAX_QUERIES:
+        return f"{points.shape[0]} points: at most 2^31 - 1"
+    from . import _lib
+
+    if _lib.capturing():
+        return "the current stream is capturing a graph (the call allocates its outputs)"
+    return None
+
+
+def _plan_bytes(F: int) -> int:
+    """Bytes of the plan of a mesh of ``F`` faces (``gsr_closest_tri_plan_bytes``; 0: more faces than the kernels take)."""
+    from . import _lib
+
+    return int(_lib.lib.gsr_closest_tri_plan_bytes(int(F)))
+
+
+def _build(verts: torch.Tensor, faces: torch.Tensor) -> Plan:
+    from . import _lib
+
+    v, f = verts.detach().contiguous(), faces.detach().contiguous()
+    V, F = int(v.shape[0]), int(f.shape[0])
+    with torch.cuda.device(v.device):
+        buffer, plan_bytes = _lib.scratch("gsr_closest_tri_plan_bytes", F, device=v.device)
+        scratch, scratch_bytes = _lib.scratch("gsr_closest_tri_plan_scratch_bytes", F, device=v.device)
+        _lib.call("gsr_closest_tri_plan", V, _lib.ptr(v), F, _lib.ptr(f), buffer.data_ptr(), plan_bytes, _lib.ptr(scratch), scratch_bytes,
+                  device=v.device)
+    return Plan(buffer, F, V)
+
+
+def plan(verts: torch.Tensor, faces: torch.Tensor) -> Plan:
+    """The tree over the mesh ``verts [V, 3]`` float32, ``faces [F, 3]`` int64 (both on one GPU), built on the current stream: pass it
+    to :func:`closest_triangles` as often as the mesh is asked.  Raises ``ValueError`` with the reason for anything else."""
+    why = _why_not_mesh(verts, faces)
+    if why is not None:
+        raise ValueError("meshquery.plan: " + why)
+    return _build(verts, faces)
+
+
+def closest_triangles(points: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor, plan: Optional[Plan] = None,
+                      return_points: bool = False):
+    """For every point of ``points [n, 3]`` float32 the closest triangle of the mesh: ``face_idx [n]`` int64, ``sq_dist [n]`` float32
+    and, with ``return_points``, ``closest [n, 3]`` float32 (the module docstring has the contract).  ``plan``: what :func:`plan`
+    returned for this mesh (built here otherwise).  The queries are asked in Morton order and the answers put back (``_query``: the
+    same answers, much sooner unless the caller's order is coherent already).  Queued on the current stream, no host synchronisation;
+    not differentiable; non-contiguous inputs are copied.  Raises ``ValueError`` with the reason for CPU tensors, other dtypes or shapes, devices that
+    differ, a plan of another mesh or of another size than its ``F`` asks for, and under graph capture."""
+    why = _why_not_mesh(verts, faces) or _why_not_points(points, verts.device)
+    if why is None and plan is not None:
+        if not isinstance(plan, Plan):
+            why = f"plan must be a meshquery.Plan (got {type(plan).__name__})"
+        elif plan.F != int(faces.shape[0]) or plan.V != int(verts.shape[0]) or plan.device != verts.device:
+            why = (f"the plan is of a mesh with {plan.F} faces and {plan.V} vertices on {plan.device}, "
+                   f"not of this one ({int(faces.shape[0])}, {int(verts.shape[0])}, {verts.device})")
+        elif plan.buffer.dtype != torch.uint8 or int(plan.buffer.numel()) != _plan_bytes(plan.F):
+            why = (f"the plan's buffer is {int(plan.buffer.numel())} elements of {plan.buffer.dtype}, "
+                   f"a plan of {plan.F} faces is {_plan_bytes(plan.F)} bytes")
+    if why is not None:
+        raise ValueError("closest_triangles: " + why)
+    tree = plan if plan is not None else _build(verts, faces)
+    return _query(points, tree, return_points)
+
+
+def _spread21(x: torch.Tensor) -> torch.Tensor:
+    """Bit k of an int64 ``x < 2^21`` -> bit 3k (gsr_meshquery.hip's ``spread21``)."""
+    x = (x | (x << 32)) & 0x001F00000000FFFF
+    x = (x | (x << 16)) & 0x001F0000FF0000FF
+    x = (x | (x << 8)) & 0x100F00F00F00F00F
+    x = (x | (x << 4)) & 0x10C30C30C30C30C3
+    x = (x | (x << 2)) & 0x1249249249249249
+    return x
+
+
+def morton_order(points: torch.Tensor) -> torch.Tensor:
+    """Indices that put ``points [n, 3]`` in the order of their 63-bit Morton codes on their own bounds (non-finite coordinates count
+    as 0): torch ops on the points' device, no host read.  The order only groups neighbours into waves: it never changes an answer."""
+    p = torch.nan_to_num(points.detach(), nan=0.0, posinf=0.0, neginf=0.0)
+    lo = p.min(dim=0).values
+    extent = (p.max(dim=0).values - lo).clamp_min(torch.finfo(torch.float32).tiny)
+    cell = ((p - lo) / extent * float((1 << 21) - 1)).to(torch.int64).clamp_(0, (1 << 21) - 1)
+    code = _spread21(cell[:, 0]) | (_spread21(cell[:, 1]) << 1) | (_spread21(cell[:, 2]) << 2)
+    return torch.argsort(code)
+
+
+SORT_FROM = 128      # fewer queries than two waves are asked in the caller's order
+
+
+def _query(points: torch.Tensor, tree: Plan, return_points: bool, sort_queries: bool = True):
+    """The kernel gives a wave 64 consecutive queries and walks the tree once for all of them: it is fast when they are neighbours
+    (measured on an MI355X, 1 M faces and 1 M queries drawn around the surface in random order: 6.9 ms with the sort and the way
+    back in it, 215 ms asked as drawn; scripts/bench_meshquery.py).  So the queries are asked in Morton order and the answers put
+    back; every answer is a function of its own query alone.  ``sort_queries=False`` (the tests, the benchmark) asks in the
+    caller's order."""
+    from . import _lib
+
+    pts = points.detach().contiguous()
+    n = int(pts.shape[0])
+    face_idx = torch.empty(n, dtype=torch.int64, device=pts.device)
+    sq_dist = torch.empty(n, dtype=torch.float32, device=pts.device)
+    closest = torch.empty((n, 3), dtype=torch.float32, device=pts.device) if return_points else None
+    if n == 0:
+        return (face_idx, sq_dist, closest) if return_points else (face_idx, sq_dist)
+    order = morton_order(pts) if sort_queries and n >= SORT_FROM else None
+    asked = pts if order is None else pts[order]
+    out = (face_idx, sq_dist, closest) if order is None else tuple(None if t is None else torch.empty_like(t) for t in (face_idx, sq_dist, closest))
+    with torch.cuda.device(pts.device):
+        # the kernel reads the plan after this call returns, on THIS stream: a plan built on another one is not recycled under it
+        tree.buffer.record_stream(torch.cuda.current_stream(pts.device))
+        _lib.call("gsr_closest_tri_query", n, asked.data_ptr(), tree.buffer.data_ptr(), int(tree.buffer.numel()), out[0].data_ptr(),
+                  out[1].data_ptr(), _lib.ptr(out[2]), device=pts.device)
+    if order is not None:
+        for dst, src in zip((face_idx, sq_dist, closest), out):
+            if dst is not None:
+                dst.index_copy_(0, order, src)
+    return (face_idx, sq_dist, closest) if return_points else (face_idx, sq_dist)
+
+
+class Scene:
+    """A mesh to ask closest points of, for code written against ``open3d.t.geometry.RaycastingScene``: the plan is built once,
+    here.  ``verts``, ``faces``: numpy arrays or tensors (moved to ``device``, default the current GPU)."""
+
+    def __init__(self, verts, faces, device=None):
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.verts = torch.as_tensor(np.asarray(verts) if not isinstance(verts, torch.Tensor) else verts).to(dev, torch.float32).contiguous()
+        self.faces = torch.as_tensor(np.asarray(faces) if not isinstance(faces, torch.Tensor) else faces).to(dev, torch.int64).contiguous()
+        self.plan = plan(self.verts, self.faces)
+
+    def compute_closest_points(self, points) -> dict:
+        """``points``: ``[n, 3]``, numpy or torch, any float dtype.  Returns device tensors: ``primitive_ids`` int64 ``[n]`` (-1: no
+        answer), ``points`` float32 ``[n, 3]``, ``distances`` float32 ``[n]`` (Euclidean) and ``squared_distances``."""
+        pts = torch.as_tensor(np.asarray(points) if not isinstance(points, torch.Tensor) else points)
+        pts = pts.to(self.verts.device, torch.float32).reshape(-1, 3)
+        face_idx, sq_dist, closest = closest_triangles(pts, self.verts, self.faces, plan=self.plan, return_points=True)
+        return {"primitive_ids": face_idx, "points": closest, "distances": torch.sqrt(sq_dist), "squared_distances": sq_dist}

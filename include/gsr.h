@@ -42,7 +42,9 @@
 extern "C" {
 #endif
 
-/* Still 20: + the mesh normal consistency loss (gsr_normal_consistency_plan_scratch_bytes, gsr_normal_consistency_plan,
+/* Still 20: + the closest triangle of a mesh (gsr_closest_tri_plan_bytes, gsr_closest_tri_plan_scratch_bytes, gsr_closest_tri_plan,
+ * gsr_closest_tri_query).
+ * Still 20: + the mesh normal consistency loss (gsr_normal_consistency_plan_scratch_bytes, gsr_normal_consistency_plan,
  * gsr_normal_consistency_scratch_bytes, gsr_normal_consistency_forward, gsr_normal_consistency_backward).
  * Still 20: + face areas / normals and face-attribute interpolation with their backwards (gsr_face_areas_normals,
  * gsr_face_areas_normals_backward, gsr_interp_face_attrs, gsr_interp_face_attrs_backward).
@@ -444,6 +446,37 @@ GSR_API int gsr_knn3_mean_dist(uint32_t n, const float* points, float* out, void
 GSR_API size_t gsr_knn_points_scratch_bytes(int64_t n1, int64_t n2, int same);
 GSR_API int gsr_knn_points(int64_t n1, const float* p1, int64_t n2, const float* p2, int K, float* dists, int64_t* idx, void* scratch,
                            size_t scratch_bytes, void* stream);
+
+/* The closest triangle of a mesh to every query point (what Open3D's RaycastingScene.compute_closest_points answers for the melting
+ * frames, scene_representation.py:385-412, and for object extraction, extract/extract_object.py:105-110) -- added under ABI 20.
+ * verts [V,3] fp32, faces [F,3] int64, points [n,3] fp32 -> face_idx [n] int64, sq_dist [n] fp32, closest [n,3] fp32 (NULL: not wanted).
+ * A face is valid when its three indices lie in [0, V) and its nine coordinates are finite; invalid faces are never answered.  The
+ * answer for query q is the valid face with the smallest (d(q, f), f) -- equal distances go to the lower face index -- with, all in
+ * fp32 without fused multiply-adds (DESIGN.md 7l gives the operation order, autovfx_amd/meshquery.py restates it in numpy):
+ *   A = a - q, B = b - q, C = c - q;  p' = the closest point of triangle (A, B, C) to the origin by the vertex / edge / interior region
+ *   tests, every division guarded (a zero denominator takes the region's end point);  d_tri = (p'x p'x + p'y p'y) + p'z p'z;
+ *   d_box = the squared gap between q and the triangle's own box;  d_vtx = min(|A|^2, |B|^2, |C|^2);
+ *   d = min(max(d_tri, d_box), d_vtx) (a NaN d_tri is ignored);  closest = q + p'.
+ * The true distance lies in [d_box, d_vtx]: the clamps remove rounding error only, and they make the tree search exact, so the result
+ * is a pointwise function of the input.  A non-finite query, and any query when no face is valid, gets (-1, +inf, 0 0 0).  Every
+ * output element is written.
+ *   gsr_closest_tri_plan   builds the tree once per mesh into `plan` (gsr_closest_tri_plan_bytes(F) bytes, about 50 per face, 256-byte
+ *       aligned) with `scratch` (gsr_closest_tri_plan_scratch_bytes(F) bytes, about 21 per face, 256-byte aligned, any content; F == 0
+ *       needs none).  F == 0 builds a valid empty plan.  Both size queries return 0 for F outside 0 .. 2^30 - 1.
+ *   gsr_closest_tri_query  answers n queries from a plan; the same plan serves any number of calls, on any stream ordered after its
+ *       build.  n == 0 touches nothing.
+ * Refused (GSR_ERR_INVALID_ARG, nothing launched): a negative count, F >= 2^30, V >= 2^31, n >= 2^31, a null pointer to a non-empty
+ * array, misaligned pointers (verts / points / sq_dist / closest: 4 bytes; faces / face_idx: 8; plan / scratch: 256), too little plan
+ * or scratch, a plan_bytes that is not a whole number of 256-byte blocks.  The plan's header (F and its size) lives in device memory:
+ * the query kernel derives every count and offset from it and compares them with plan_bytes before anything indexes the plan, and a
+ * header that does not match answers every query (-1, +inf, 0 0 0) -- the host never reads the plan back.  Both calls enqueue on
+ * `stream` only: no host synchronisation, no device-to-host copy, no atomics. */
+GSR_API size_t gsr_closest_tri_plan_bytes(int64_t F);
+GSR_API size_t gsr_closest_tri_plan_scratch_bytes(int64_t F);
+GSR_API int gsr_closest_tri_plan(int64_t V, const float* verts, int64_t F, const int64_t* faces, void* plan, size_t plan_bytes,
+                                 void* scratch, size_t scratch_bytes, void* stream);
+GSR_API int gsr_closest_tri_query(int64_t n, const float* points, const void* plan, size_t plan_bytes, int64_t* face_idx, float* sq_dist,
+                                  float* closest, void* stream);
 
 /* SuGaR's density field over a neighbour list (SuGaR.get_field_values, sugar_model.py:1118-1187, and SuGaR.compute_density,
  * :1216-1239) -- added under ABI 20.  x [n,3], idx [n,K] int64, centers [P,3], M [P,3,3] row-major (the inverse scaled rotation,
