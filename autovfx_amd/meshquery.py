@@ -23,13 +23,14 @@ the triangle never exceeds ``d_box``, so the tree search of ``gsr_meshquery.hip`
 included.  A non-finite query, and any query when no face is valid, gets ``(-1, +inf, (0, 0, 0))``.
 
 :func:`closest_triangles` runs the HIP kernels (C ABI ``gsr_closest_tri_plan`` / ``gsr_closest_tri_query``);
-:func:`closest_triangles_host` restates the contract in numpy by brute force, the checker of the tests; :class:`Scene` is a small
+:func:`closest_triangles_host` restates the contract in numpy by brute force, the checker of the tests, :func:`plan_host` and
+:func:`plan_layout` restate the build and the layout of the plan; :class:`Scene` is a small
 adapter for code written against Open3D's ray-casting scene.  ``autovfx_amd.install()`` does not put it over Open3D: the frame loop
 uses it when ``AUTOVFX_AMD_MELT_CLOSEST=gpu`` (``autovfx_amd/frame_loop.py``).
 """
 from __future__ import annotations
 
-from typing import Optional
+from typing import NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -62,6 +63,12 @@ def _guarded(num, den):
     return np.where(ok, num / np.where(ok, den, _F(1)), _F(0))
 
 
+def _box_bound(lo, hi, q):
+    """gsr_meshquery.hip's ``box_bound`` on per-axis tuples: the squared gap between ``q`` and the box, summed like ``dot``."""
+    gaps = [np.fmax(np.fmax(lo[k] - q[k], q[k] - hi[k]), _F(0)) for k in range(3)]
+    return (gaps[0] * gaps[0] + gaps[1] * gaps[1]) + gaps[2] * gaps[2]
+
+
 def triangle_distance_host(q, a, b, c):
     """``d(q, f)`` of the contract for float32 arrays ``q``, ``a``, ``b``, ``c`` of shape ``[..., 3]`` that broadcast against each
     other.  Returns a dict of float32 arrays: ``d``, ``d_tri``, ``d_box``, ``d_vtx`` (shape ``[...]``) and ``p`` (``[..., 3]``, the point
@@ -89,11 +96,9 @@ def triangle_distance_host(q, a, b, c):
                   for k in range(3))
         d_tri = _dot(p, p)
         d_vtx = np.fmin(np.fmin(_dot(A, A), _dot(B, B)), _dot(C, C))
-        gaps = []
-        for k in range(3):
-            lo, hi = np.fmin(np.fmin(av[k], bv[k]), cv[k]), np.fmax(np.fmax(av[k], bv[k]), cv[k])
-            gaps.append(np.fmax(np.fmax(lo - qv[k], qv[k] - hi), _F(0)))
-        d_box = (gaps[0] * gaps[0] + gaps[1] * gaps[1]) + gaps[2] * gaps[2]
+        lo = tuple(np.fmin(np.fmin(av[k], bv[k]), cv[k]) for k in range(3))
+        hi = tuple(np.fmax(np.fmax(av[k], bv[k]), cv[k]) for k in range(3))
+        d_box = _box_bound(lo, hi, qv)
         d = np.fmin(np.fmax(d_tri, d_box), d_vtx)
     return {"d": d, "d_tri": d_tri, "d_box": d_box, "d_vtx": d_vtx, "p": np.stack(p, -1)}
 
@@ -107,10 +112,42 @@ def valid_faces_host(verts: np.ndarray, faces: np.ndarray) -> np.ndarray:
     return ok
 
 
-def closest_triangles_host(points, verts, faces, chunk_elems: int = 1 << 20):
+def _closest_pruned(pts, rows, v, f, ids, chunk_elems, face_idx, sq_dist, closest):
+    """``closest_triangles_host(..., pruned=True)`` for the finite queries ``rows`` and the valid faces ``ids`` (ascending)."""
+    a, b, c = (v[f[ids, k]] for k in range(3))
+    lo = tuple(np.fmin(np.fmin(a[:, k], b[:, k]), c[:, k])[None, :] for k in range(3))
+    hi = tuple(np.fmax(np.fmax(a[:, k], b[:, k]), c[:, k])[None, :] for k in range(3))
+    corners = v[np.unique(f[ids])]          # min over the faces of d_vtx = min over their corners of dot(A, A): the same values, once each
+    step = max(1, chunk_elems // ids.size)
+    with np.errstate(over="ignore", invalid="ignore"):
+        for at in range(0, rows.size, step):
+            r = rows[at:at + step]
+            q = pts[r]
+            qv = tuple(q[:, k][:, None] for k in range(3))
+            A = tuple(corners[:, k][None, :] - qv[k] for k in range(3))
+            u = np.min(_dot(A, A), axis=1)                          # (never NaN: a difference of finite numbers is none)
+            row, col = np.nonzero(_box_bound(lo, hi, qv) <= u[:, None])     # row-major: per query, ascending face index
+            starts = np.searchsorted(row, np.arange(r.size))
+            assert np.all(np.diff(np.append(starts, row.size)) > 0)         # the winner itself has d_box <= d <= u
+            got = triangle_distance_host(q[row], a[col], b[col], c[col])
+            least = np.minimum.reduceat(got["d"], starts)
+            first = np.nonzero(got["d"] == least[row])[0]
+            first = first[np.unique(row[first], return_index=True)[1]]      # the first minimum of every query
+            face_idx[r] = ids[col[first]]
+            sq_dist[r] = got["d"][first]
+            closest[r] = q + got["p"][first]
+
+
+def closest_triangles_host(points, verts, faces, chunk_elems: int = 1 << 20, pruned: bool = False):
     """The contract restated in numpy: brute force over all valid faces, every operation an fp32 elementwise one in the contract's
     order, chunked over the queries.  ``points``, ``verts``: anything ``np.asarray`` takes, reshaped to ``[., 3]`` float32; ``faces``
-    to ``[F, 3]`` int64.  Returns ``face_idx [n]`` int64, ``sq_dist [n]`` float32, ``closest [n, 3]`` float32."""
+    to ``[F, 3]`` int64.  Returns ``face_idx [n]`` int64, ``sq_dist [n]`` float32, ``closest [n, 3]`` float32.
+
+    ``pruned``: the same answers, bit for bit and ties included, in a fraction of the time on a large mesh (185 queries around a
+    sphere of 262145 faces: 0.9 s against 9 s), which is what makes meshes of 2^18 faces testable.  Per query ``u`` = the smallest ``d_vtx`` of any valid face, and ``d`` is evaluated only on the faces with
+    ``d_box <= u``, the first minimum in ascending face index taken.  The contract's clamp gives ``d_box <= d <= d_vtx`` in the
+    computed fp32 values, so the brute force's winner has ``d <= u``, hence ``d_box <= u``, and so has every face that ties with it.
+    No tree and no order of the faces is involved: it shares nothing with the kernels' search but the contract."""
     pts = np.ascontiguousarray(np.asarray(points, dtype=_F).reshape(-1, 3))
     v = np.ascontiguousarray(np.asarray(verts, dtype=_F).reshape(-1, 3))
     f = np.ascontiguousarray(np.asarray(faces, dtype=np.int64).reshape(-1, 3))
@@ -121,6 +158,9 @@ def closest_triangles_host(points, verts, faces, chunk_elems: int = 1 << 20):
     ids = np.nonzero(valid_faces_host(v, f))[0]                 # ascending: the first minimum of a row is the lowest face index
     rows = np.nonzero(np.all(np.isfinite(pts), axis=1))[0]
     if ids.size == 0 or rows.size == 0:
+        return face_idx, sq_dist, closest
+    if pruned:
+        _closest_pruned(pts, rows, v, f, ids, chunk_elems, face_idx, sq_dist, closest)
         return face_idx, sq_dist, closest
     a, b, c = (v[f[ids, k]][None, :, :] for k in range(3))
     step = max(1, chunk_elems // ids.size)
@@ -135,6 +175,117 @@ def closest_triangles_host(points, verts, faces, chunk_elems: int = 1 << 20):
         with np.errstate(over="ignore", invalid="ignore"):
             closest[r] = q + got["p"][pick, best]
     return face_idx, sq_dist, closest
+
+
+# ---- the plan in numpy ----------------------------------------------------------------------------------------------------------------
+LEAF = 64            # gsr_meshquery.hip's kLeaf, kFan, kTriMaxLevels, kAlign, kCellMax
+FAN = 16
+MAX_LEVELS = 6
+ALIGN = 256
+CELL_MAX = (1 << 21) - 1
+NO_FACE = 0xFFFFFFFF
+PLAN_MAGIC = b"TRIQ"
+
+
+class PlanLayout(NamedTuple):
+    """Where everything of a plan of ``F`` faces lies (gsr_meshquery.hip's ``tri_layout`` and ``tri_level``): ``counts[l]`` boxes
+    of level ``l`` (0: the leaves) start at box ``offsets[l]`` of the box region; ``records`` and ``boxes`` are byte offsets and
+    ``bytes`` the whole, in 256-byte blocks.  A record is 48 bytes, a box 32 (two ``float4``: lo, hi)."""
+    F: int
+    leaves: int
+    top: int
+    counts: Tuple[int, ...]
+    offsets: Tuple[int, ...]
+    records: int
+    boxes: int
+    bytes: int
+
+
+def _align_up(v: int) -> int:
+    return (v + ALIGN - 1) // ALIGN * ALIGN
+
+
+def plan_layout(F: int) -> PlanLayout:
+    """The layout of the plan of a mesh of ``0 <= F < 2^30`` faces: pure arithmetic, ``tri_layout`` in Python."""
+    F = int(F)
+    if not 0 <= F <= MAX_FACES:
+        raise ValueError(f"plan_layout: {F} faces (0 to 2^30 - 1)")
+    counts = [(F + LEAF - 1) // LEAF]
+    while counts[-1] > FAN and len(counts) < MAX_LEVELS:
+        counts.append((counts[-1] + FAN - 1) // FAN)
+    offsets = [sum(counts[:level]) for level in range(len(counts))]
+    records = ALIGN
+    boxes = _align_up(records + 48 * F)
+    return PlanLayout(F, counts[0], len(counts) - 1, tuple(counts), tuple(offsets), records, boxes, _align_up(boxes + 32 * sum(counts)))
+
+
+def _spread21_host(x: np.ndarray) -> np.ndarray:
+    x = x.astype(np.uint64) & np.uint64(0x1FFFFF)
+    for shift, mask in ((32, 0x001F00000000FFFF), (16, 0x001F0000FF0000FF), (8, 0x100F00F00F00F00F), (4, 0x10C30C30C30C30C3),
+                        (2, 0x1249249249249249)):
+        x = (x | (x << np.uint64(shift))) & np.uint64(mask)
+    return x
+
+
+def _grid_cell_host(x: np.ndarray, lo, hi) -> np.ndarray:
+    """``grid_cell``: ``t = (x - lo) / extent * 2097151`` when ``extent > 0``, else 0; the cell is ``uint(fmin(t, 2097151))`` when
+    ``t >= 0``, else 0 (so a NaN, from infinite bounds, gives 0)."""
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+        extent = _F(hi) - _F(lo)
+        t = (x - _F(lo)) / extent * _F(CELL_MAX) if extent > 0 else np.zeros_like(x)
+        keep = t >= 0
+        return np.where(keep, np.fmin(np.where(keep, t, _F(0)), _F(CELL_MAX)), _F(0)).astype(np.uint32)
+
+
+def morton_codes_host(verts, faces) -> np.ndarray:
+    """The sort keys of the build, ``[F]`` uint64: the 63-bit Morton code of a valid face's centroid ``((a + b) + c) / 3`` on the
+    bounds of the valid centroids, ``2^63`` for an invalid face.  All fp32, in the kernel's order."""
+    v = np.ascontiguousarray(np.asarray(verts, dtype=_F).reshape(-1, 3))
+    f = np.ascontiguousarray(np.asarray(faces, dtype=np.int64).reshape(-1, 3))
+    codes = np.full(f.shape[0], 1 << 63, np.uint64)
+    ids = np.nonzero(valid_faces_host(v, f))[0]
+    if ids.size:
+        with np.errstate(over="ignore", invalid="ignore"):
+            m = ((v[f[ids, 0]] + v[f[ids, 1]]) + v[f[ids, 2]]) / _F(3)
+        cells = [_spread21_host(_grid_cell_host(m[:, k], m[:, k].min(), m[:, k].max())) for k in range(3)]
+        codes[ids] = cells[0] | (cells[1] << np.uint64(1)) | (cells[2] << np.uint64(2))
+    return codes
+
+
+def plan_host(verts, faces):
+    """The build of ``gsr_meshquery.hip`` restated in numpy, operation for operation in fp32.  Returns ``order [F]`` int64 (the face
+    of every record: a stable sort of ``morton_codes_host``, so equal codes, the invalid tail included, come in ascending face
+    index), ``records [F, 3, 4]`` float32 (a valid face: ``(a, bits(f))``, ``(b, 0)``, ``(c, 0)``; an invalid one: NaN in x, y, z and
+    0xFFFFFFFF in w, all three rows) and one ``(lo [n, 3], hi [n, 3])`` pair per level of ``plan_layout(F)``: a leaf is the union of
+    its valid members' own boxes, every level above the union of up to 16 boxes below; a box without a valid member is
+    (+inf, -inf).  The sign of a zero in a box is that of numpy's reduction, not necessarily the kernel's."""
+    v = np.ascontiguousarray(np.asarray(verts, dtype=_F).reshape(-1, 3))
+    f = np.ascontiguousarray(np.asarray(faces, dtype=np.int64).reshape(-1, 3))
+    F = f.shape[0]
+    layout = plan_layout(F)
+    valid = valid_faces_host(v, f)
+    order = np.argsort(morton_codes_host(v, f), kind="stable")
+    ok = valid[order]
+    records = np.full((F, 3, 4), np.nan, _F)
+    words = records.view(np.uint32)
+    words[:, :, 3] = NO_FACE
+    corners = v[f[order[ok]]]                                        # [., 3 corners, 3 axes]
+    records[ok, :, :3] = corners
+    words[ok, 0, 3] = order[ok].astype(np.uint32)
+    words[ok, 1:, 3] = 0
+    lo = np.full((layout.leaves * LEAF, 3), np.inf, _F)
+    hi = np.full((layout.leaves * LEAF, 3), -np.inf, _F)
+    lo[:F][ok] = corners.min(axis=1)
+    hi[:F][ok] = corners.max(axis=1)
+    lo, hi = lo.reshape(layout.leaves, LEAF, 3).min(axis=1), hi.reshape(layout.leaves, LEAF, 3).max(axis=1)
+    levels = [(lo, hi)]
+    for count in layout.counts[1:]:
+        wide_lo = np.full((count * FAN, 3), np.inf, _F)
+        wide_hi = np.full((count * FAN, 3), -np.inf, _F)
+        wide_lo[:lo.shape[0]], wide_hi[:hi.shape[0]] = lo, hi
+        lo, hi = wide_lo.reshape(count, FAN, 3).min(axis=1), wide_hi.reshape(count, FAN, 3).max(axis=1)
+        levels.append((lo, hi))
+    return order, records, levels
 
 
 # ---- the kernels ----------------------------------------------------------------------------------------------------------------------

@@ -8,14 +8,15 @@
   by a normal step of two edge lengths) in random order.  ``query_unsorted_ms``: the same batch without the sort, the
   kernel on the caller's random order; ``query_presorted_ms``: likewise on the batch already in Morton order, the
   kernel alone at its best.
-  ``checked``: that many queries compared with the numpy restatement of the contract, bit for bit (``check_equal``).
+  ``checked``: that many queries compared with the numpy restatement of the contract (its pruned mode: the brute force's answers
+  in a fraction of its time), bit for bit (``check_equal``).
 * ``kind: "melt_mask"`` -- one melting frame's mask, from the face centres (a host float32 array) to the mask over the object's
   Gaussians, in both modes of ``AUTOVFX_AMD_MELT_CLOSEST``: ``gpu_ms`` (upload, one query, flag scatter and gather, host clock around
   a device synchronise) and ``host_ms`` (``compute_closest_points`` of the process's ``open3d``, ``np.isin``, the mask's upload).
   Without ``open3d`` there is no host time: the line says so (``host: "open3d is not installed: not measured"``).
 
 Usage: ``python scripts/bench_meshquery.py [--faces 100000 1000000] [--queries 60000 1000000 3000000] [--repeats 10] [--warmup 3]
-[--check 64] [--gaussians 200000] [--centres 50000]``.
+[--check 512] [--gaussians 200000] [--centres 50000]``.
 """
 import argparse
 import json
@@ -103,7 +104,7 @@ def main():
     ap.add_argument("--queries", type=int, nargs="+", default=[60_000, 1_000_000, 3_000_000])
     ap.add_argument("--repeats", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--check", type=int, default=64, help="queries compared with the numpy restatement per mesh (0: none)")
+    ap.add_argument("--check", type=int, default=512, help="queries compared with the numpy restatement per mesh (0: none)")
     ap.add_argument("--gaussians", type=int, default=200_000, help="melt_mask: Gaussians of the object")
     ap.add_argument("--centres", type=int, default=50_000, help="melt_mask: faces of the frame's melting mesh")
     args = ap.parse_args()
@@ -131,7 +132,7 @@ def main():
             row["query_presorted_ms"] = round(time_gpu(lambda: run(sorted_q, False), args.repeats, args.warmup), 4)
             if args.check and n == args.queries[0]:
                 got = [t[:args.check].cpu().numpy() for t in run(q)]
-                want = meshquery.closest_triangles_host(host_q[:args.check], verts, faces)
+                want = meshquery.closest_triangles_host(host_q[:args.check], verts, faces, pruned=True)
                 row["checked"] = args.check
                 row["check_equal"] = bool(np.array_equal(got[0], want[0]) and np.array_equal(got[1].view(np.uint32), want[1].view(np.uint32))
                                           and np.array_equal(got[2].view(np.uint32), want[2].view(np.uint32)))

@@ -1,4 +1,5 @@
-"""Meshes and queries shared by the closest-triangle tests (tests/test_meshquery.py, tests/test_meshquery_gpu.py)."""
+"""Meshes and queries shared by the closest-triangle tests (tests/test_meshquery.py, tests/test_meshquery_gpu.py,
+tests/test_meshquery_deep_gpu.py)."""
 from __future__ import annotations
 
 import numpy as np
@@ -50,6 +51,57 @@ def sphere_with_faces(F: int, seed: int = 0, radius: float = 1.0, centre=(0.3, -
     verts, faces = cube_sphere(n, radius, centre)
     keep = np.random.default_rng(seed).permutation(faces.shape[0])[:F]
     return verts, np.ascontiguousarray(faces[keep])
+
+
+def plane_in_random_order(nx: int, ny: int, seed: int = 0):
+    """``grid_plane(nx, ny)`` (integer coordinates: every tie is exact) with its faces in a random order."""
+    verts, faces = grid_plane(nx, ny, 1.0)
+    return verts, np.ascontiguousarray(faces[np.random.default_rng(seed).permutation(faces.shape[0])])
+
+
+def sphere_with_invalid(valid: int, invalid: int, seed: int = 0):
+    """``valid + invalid`` faces of a cube sphere of which ``invalid``, scattered through the face order, are invalid: the first half
+    of them by an index outside ``[0, V)``, the rest by a corner with a non-finite coordinate (vertices appended for that, which no
+    other face names).  Returns ``verts``, ``faces`` and the ascending indices of the invalid faces."""
+    verts, faces = sphere_with_faces(valid + invalid, seed)
+    faces = faces.copy()
+    g = np.random.default_rng(seed + 1)
+    bad = g.permutation(faces.shape[0])[:invalid]
+    half = invalid // 2
+    extra = np.full((invalid - half, 3), 0.5, F32)
+    extra[np.arange(invalid - half), g.integers(0, 3, invalid - half)] = np.resize(np.array([np.nan, np.inf, -np.inf], F32), invalid - half)
+    V = verts.shape[0] + extra.shape[0]
+    faces[bad[:half], g.integers(0, 3, half)] = np.resize(np.array([V, -1, 1 << 40, V + 7, -(1 << 33)], np.int64), half)
+    faces[bad[half:], g.integers(0, 3, invalid - half)] = verts.shape[0] + np.arange(invalid - half)
+    return np.concatenate((verts, extra)), faces, np.sort(bad)
+
+
+def sphere_with_spanners(F: int = 20000, spanners: int = 50, slivers: int = 200, seed: int = 0):
+    """``F`` faces of a cube sphere, ``spanners`` triangles whose corners lie near corners of the sphere's bounding box (each as wide
+    as the mesh) and ``slivers`` nearly collinear triangles about one radius long, all in a random order."""
+    verts, faces = sphere_with_faces(F, seed)
+    g = np.random.default_rng(seed + 2)
+    lo, hi = verts.min(axis=0).astype(np.float64), verts.max(axis=0).astype(np.float64)
+    at = g.integers(0, 2, (spanners, 3, 3))
+    at[:, 1] = 1 - at[:, 0]                                          # two corners diagonally opposite: the whole bounds
+    wide = lo + (hi - lo) * (at + g.uniform(-0.02, 0.02, at.shape))
+    a = g.uniform(lo, hi, (slivers, 3))
+    along = g.normal(size=(slivers, 3))
+    along /= np.linalg.norm(along, axis=1, keepdims=True)
+    thin = np.stack((a, a + along, a + 0.5 * along + 1e-6 * g.normal(size=(slivers, 3))), 1)
+    more = np.concatenate((wide, thin)).reshape(-1, 3).astype(F32)
+    faces = np.concatenate((faces, (np.arange(more.shape[0]).reshape(-1, 3) + verts.shape[0]).astype(np.int64)))
+    return np.concatenate((verts, more)), np.ascontiguousarray(faces[g.permutation(faces.shape[0])])
+
+
+def sphere_with_overflowing_centroid(F: int, seed: int = 0):
+    """``F`` faces of a cube sphere of which one (face 5, or the only one) has three finite corners near (3e38, -3e38, 1): a valid
+    face whose centroid sum overflows, so the bounds of the centroids hold +inf in x and -inf in y."""
+    verts, faces = sphere_with_faces(F, seed)
+    faces = faces.copy()
+    huge = np.array([[3.0e38, -3.0e38, 1.0], [3.1e38, -3.1e38, 1.5], [3.2e38, -2.9e38, 0.5]], F32)
+    faces[min(5, F - 1)] = verts.shape[0] + np.arange(3)
+    return np.concatenate((verts, huge)), faces
 
 
 def edge_lengths(verts, faces):
