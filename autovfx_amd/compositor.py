@@ -40,16 +40,30 @@ def smoke_depth_fill(s_f_c: torch.Tensor, s_f_d: torch.Tensor) -> torch.Tensor:
     return torch.where(mask, _percentile_linear(s_f_d, 0.001), s_f_d)    # (no boolean-mask assignment: that one waits for the GPU)
 
 
+def _resize_out(name: str, out: Optional[torch.Tensor], W: int, H: int, shape, dtype, device) -> torch.Tensor:
+    """The tensor a resize writes: a new one, or the caller's ``out`` once it is seen to be exactly what the kernel will write
+    through (the kernel gets its pointer and nothing else).  Refuses before anything is launched."""
+    if W <= 0 or H <= 0:
+        raise RuntimeError(f"{name}: the target size must be positive, got {W} x {H} (width x height)")
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if not isinstance(out, torch.Tensor):
+        raise RuntimeError(f"{name}: out must be a contiguous {dtype} tensor {shape} on {device}, got {type(out).__name__}")
+    if out.device != device or out.dtype != dtype or tuple(out.shape) != shape or not out.is_contiguous():
+        raise RuntimeError(f"{name}: out must be a contiguous {dtype} tensor {shape} on {device}, got {out.dtype} {tuple(out.shape)} "
+                           f"with strides {tuple(out.stride())} on {out.device}")
+    return out
+
+
 def resize_rgba8(image: torch.Tensor, size_wh, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``np.array(Image.fromarray(image).resize(size_wh, resample=Image.BILINEAR))`` for an RGBA8 ``[H,W,4]`` GPU tensor
     (``downsample_image`` of blend_all.py:21-28): same bytes as Pillow."""
     if not (image.is_cuda and image.dtype == torch.uint8 and image.dim() == 3 and image.shape[2] == 4):
         raise RuntimeError("resize_rgba8 expects a uint8 GPU tensor [H,W,4]")
     W, H = int(size_wh[0]), int(size_wh[1])
+    out = _resize_out("resize_rgba8", out, W, H, (H, W, 4), torch.uint8, image.device)
     src = image.contiguous()
     Hs, Ws = int(src.shape[0]), int(src.shape[1])
-    if out is None:
-        out = torch.empty((H, W, 4), dtype=torch.uint8, device=src.device)
     tmp = torch.empty((Hs, W, 4), dtype=torch.uint8, device=src.device) if (Ws != W and Hs != H) else None
     with torch.cuda.device(src.device):
         _lib.call("gsr_resize_rgba8_bilinear", src.data_ptr(), Ws, Hs, out.data_ptr(), W, H, _lib.ptr(tmp), device=src.device)
@@ -61,9 +75,8 @@ def resize_depth(depth: torch.Tensor, size_wh, out: Optional[torch.Tensor] = Non
     if not (depth.is_cuda and depth.dtype == torch.float32 and depth.dim() == 2):
         raise RuntimeError("resize_depth expects a float32 GPU tensor [H,W]")
     W, H = int(size_wh[0]), int(size_wh[1])
+    out = _resize_out("resize_depth", out, W, H, (H, W), torch.float32, depth.device)
     src = depth.contiguous()
-    if out is None:
-        out = torch.empty((H, W), dtype=torch.float32, device=src.device)
     with torch.cuda.device(src.device):
         _lib.call("gsr_resize_f32_nearest", src.data_ptr(), int(src.shape[1]), int(src.shape[0]), out.data_ptr(), W, H, device=src.device)
     return out
