@@ -180,6 +180,7 @@ SIGNATURES = {
     "gsr_closest_tri_plan_scratch_bytes": (_sz, [_i64]),               # F
     "gsr_closest_tri_plan": (_i, [_i64, _p, _i64, _p, _p, _sz, _p, _sz, _p]),   # V verts F faces plan plan_bytes scratch scratch_bytes stream
     "gsr_closest_tri_query": (_i, [_i64, _p, _p, _sz, _p, _p, _p, _p]),         # n points plan plan_bytes face_idx sq_dist closest stream
+    "gsr_ray_first_hit": (_i, [_i64, _p, _p, _p, _sz, _p, _p, _p, _p]),         # n origins dirs plan plan_bytes face_idx t bary stream
     # training: the density field, SSIM, Adam, densification
     "gsr_field_scratch_bytes": (_sz, [_i64]),                          # P
     "gsr_field_forward": (_i, _field_inputs + [_p, _p, _p, _p, _sz, _p]),            # ... density opacities beta scratch scratch_bytes stream

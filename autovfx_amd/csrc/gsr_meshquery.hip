@@ -15,7 +15,10 @@
 // (tri_layout, the function the host sized the plan with) and compares the total with the plan_bytes it was handed BEFORE anything
 // indexes the plan.  A header that does not match answers every query (-1, +inf, 0 0 0): the host cannot see the header without a
 // device-to-host read, which a query never does.
-// Defines the entry points gsr_closest_tri_plan_bytes, gsr_closest_tri_plan_scratch_bytes, gsr_closest_tri_plan, gsr_closest_tri_query.
+// The same plan answers the first triangle a ray hits (gsr_ray_first_hit, DESIGN.md 7m: what trimesh's mesh.ray answers for object
+// extraction and removal, extract/extract_object.py:115-159, :424-434, :476-482, :563-606): ray_walk further down.
+// Defines the entry points gsr_closest_tri_plan_bytes, gsr_closest_tri_plan_scratch_bytes, gsr_closest_tri_plan, gsr_closest_tri_query,
+// gsr_ray_first_hit.
 #include "gsr_internal.h"
 
 #include <cfloat>
@@ -477,6 +480,228 @@ __global__ __launch_bounds__(256) void tri_query_kernel(uint32_t n, const float*
     }
 }
 
+// ---- the first triangle a ray hits (gsr_ray_first_hit; meshquery.first_hits_host restates it in numpy) ----------------
+// The second query on the same plan: one wave per 64 rays, one lane per ray, one slot (t, face, barycentrics) per lane.  The answer is
+// the valid face with the smallest (t(ray, f), f) among the faces the ray hits, a pointwise function of the input like the closest
+// triangle: ray_walk below is walk_tree with a slab interval in the place of box_bound.
+
+constexpr float kSlabPad = 1.00000024f;   // 1 + 2 ulp on the far end of a slab interval (Ize, "Robust BVH Ray Traversal")
+
+// A lane's ray and what is computed of it once: the shear of the watertight test (Woop, Benthin, Wald: kz = the axis of the largest
+// |d|, ties to the lowest axis; kx, ky = the next two cyclically, swapped when d[kz] < 0; Sx = d[kx] / d[kz], Sy = d[ky] / d[kz],
+// Sz = 1 / d[kz]) and the reciprocals of the slab test (inv[k] = 1 / d[k], unused where d[k] == 0).
+struct Ray {
+    Vec3 o, d, inv;
+    int kx, ky, kz;
+    float Sx, Sy, Sz;
+    bool active;   // in range, six finite components, a direction that is not zero: the others answer (-1, +inf, 0 0 0)
+};
+struct HitSlot {
+    float t;
+    uint32_t face;
+    float u, v, w;   // U / det, V / det, W / det: the weights of the face's corners a, b, c
+};
+
+__device__ __forceinline__ float pick(const Vec3& v, int k) { return k == 0 ? v.x : (k == 1 ? v.y : v.z); }   // (selects, no scratch)
+
+__device__ __forceinline__ Ray make_ray(float ox, float oy, float oz, float dx, float dy, float dz) {
+    Ray r = {};
+    r.o = {ox, oy, oz};
+    r.d = {dx, dy, dz};
+    r.active = finite3(ox, oy, oz) && finite3(dx, dy, dz) && (dx != 0.0f || dy != 0.0f || dz != 0.0f);
+    int kz = 0;
+    float most = fabsf(dx);
+    if (fabsf(dy) > most) { kz = 1; most = fabsf(dy); }
+    if (fabsf(dz) > most) kz = 2;
+    int kx = kz == 2 ? 0 : kz + 1, ky = kx == 2 ? 0 : kx + 1;
+    const float dkz = pick(r.d, kz);
+    if (dkz < 0.0f) { const int s = kx; kx = ky; ky = s; }
+    r.kx = kx; r.ky = ky; r.kz = kz;
+    r.Sx = pick(r.d, kx) / dkz;
+    r.Sy = pick(r.d, ky) / dkz;
+    r.Sz = 1.0f / dkz;
+    r.inv = {1.0f / dx, 1.0f / dy, 1.0f / dz};
+    return r;
+}
+
+// One axis of the slab test: the interval of t in which o + t d lies between lo and hi on this axis.  d != 0: the two products
+// (lo - o) inv and (hi - o) inv, ordered by the sign of inv.  d == 0: all of the line when lo <= o <= hi, else nothing (+inf, -inf).
+__device__ __forceinline__ void slab_axis(float lo, float hi, float o, float d, float inv, float& near, float& far) {
+    if (d != 0.0f) {
+        const float a = (lo - o) * inv, b = (hi - o) * inv;
+        near = inv < 0.0f ? b : a;
+        far = inv < 0.0f ? a : b;
+    } else {
+        const bool in = lo <= o && o <= hi;
+        near = in ? -INFINITY : INFINITY;
+        far = in ? INFINITY : -INFINITY;
+    }
+}
+// t_enter = max(0, the three nears), t_exit = (min of the three fars) padded; fmaxf / fminf drop a NaN (0 times an overflowed inv).
+// The box is hit iff t_enter <= t_exit.  An empty box (+inf, -inf) never is.
+__device__ __forceinline__ void slab(const float4& lo, const float4& hi, const Ray& r, float& t_enter, float& t_exit) {
+    float n0, n1, n2, f0, f1, f2;
+    slab_axis(lo.x, hi.x, r.o.x, r.d.x, r.inv.x, n0, f0);
+    slab_axis(lo.y, hi.y, r.o.y, r.d.y, r.inv.y, n1, f1);
+    slab_axis(lo.z, hi.z, r.o.z, r.d.z, r.inv.z, n2, f2);
+    t_enter = fmaxf(fmaxf(fmaxf(0.0f, n0), n1), n2);
+    t_exit = fminf(fminf(f0, f1), f2) * kSlabPad;
+}
+
+// t(ray, f) of the contract; false: the ray misses the face.
+//   The corners translated by -o and sheared: Ax = A[kx] - Sx A[kz], Ay = A[ky] - Sy A[kz], Az = Sz A[kz], B and C alike.
+//   U = Cx By - Cy Bx, V = Ax Cy - Ay Cx, W = Bx Ay - By Ax: a miss when one of them is < 0 and another > 0 (two-sided).
+//   det = (U + V) + W: a miss when 0.  t_tri = ((U Az + V Bz) + W Cz) / det: a miss unless t_tri >= 0 (a NaN misses).
+//   t = fmin(fmax(t_tri, t_enter), t_exit) + 0 of the triangle's own box (the + 0 makes a -0 a +0); a t of +inf is a miss.
+// The caller has found t_enter <= t_exit.  No double-precision fallback: a ray through an edge may hit both faces or, rarely, neither.
+__device__ __forceinline__ bool ray_triangle(const Vec3& a, const Vec3& b, const Vec3& c, const Ray& r, float t_enter, float t_exit,
+                                             float& t, float& u, float& v, float& w) {
+    const Vec3 A = sub(a, r.o), B = sub(b, r.o), C = sub(c, r.o);
+    const float Akz = pick(A, r.kz), Bkz = pick(B, r.kz), Ckz = pick(C, r.kz);
+    const float Ax = pick(A, r.kx) - r.Sx * Akz, Ay = pick(A, r.ky) - r.Sy * Akz;
+    const float Bx = pick(B, r.kx) - r.Sx * Bkz, By = pick(B, r.ky) - r.Sy * Bkz;
+    const float Cx = pick(C, r.kx) - r.Sx * Ckz, Cy = pick(C, r.ky) - r.Sy * Ckz;
+    const float U = Cx * By - Cy * Bx, V = Ax * Cy - Ay * Cx, W = Bx * Ay - By * Ax;
+    if ((U < 0.0f || V < 0.0f || W < 0.0f) && (U > 0.0f || V > 0.0f || W > 0.0f)) return false;
+    const float det = (U + V) + W;
+    if (det == 0.0f) return false;
+    const float Az = r.Sz * Akz, Bz = r.Sz * Bkz, Cz = r.Sz * Ckz;
+    const float t_tri = ((U * Az + V * Bz) + W * Cz) / det;
+    if (!(t_tri >= 0.0f)) return false;
+    t = fminf(fmaxf(t_tri, t_enter), t_exit) + 0.0f;
+    u = U / det;
+    v = V / det;
+    w = W / det;
+    return t < INFINITY;
+}
+
+// `cnt` records of a leaf in LDS against the lane's slot.  A record whose own box is missed, or entered strictly after the slot's t,
+// cannot enter the slot (t >= t_enter by the clamp), so its triangle test is skipped.
+__device__ __forceinline__ void hit_scan(const float4* leaf, int cnt, const Ray& r, HitSlot& slot) {
+    for (int k = 0; k < cnt; ++k) {
+        const float4 ra = leaf[3 * k], rb = leaf[3 * k + 1], rc = leaf[3 * k + 2];
+        const uint32_t face = __float_as_uint(ra.w);
+        if (face == kNoFace) continue;   // an invalid face: never answered (wave-uniform)
+        const float4 lo = make_float4(fminf(fminf(ra.x, rb.x), rc.x), fminf(fminf(ra.y, rb.y), rc.y), fminf(fminf(ra.z, rb.z), rc.z), 0.0f);
+        const float4 hi = make_float4(fmaxf(fmaxf(ra.x, rb.x), rc.x), fmaxf(fmaxf(ra.y, rb.y), rc.y), fmaxf(fmaxf(ra.z, rb.z), rc.z), 0.0f);
+        float t_enter, t_exit;
+        slab(lo, hi, r, t_enter, t_exit);
+        if (!r.active || !(t_enter <= t_exit) || t_enter > slot.t) continue;
+        float t, u, v, w;
+        if (!ray_triangle({ra.x, ra.y, ra.z}, {rb.x, rb.y, rb.z}, {rc.x, rc.y, rc.z}, r, t_enter, t_exit, t, u, v, w)) continue;
+        if (t < slot.t || (t == slot.t && face < slot.face)) {
+            slot.t = t;
+            slot.face = face;
+            slot.u = u; slot.v = v; slot.w = w;
+        }
+    }
+}
+
+// push_children for rays: a child is kept if some lane's ray hits its box no later than that lane's slot; the kept are pushed farthest
+// first by the wave minimum of the keeping lanes' t_enter, so the box the wave's rays enter first is popped next.
+__device__ __forceinline__ void push_hit_children(const float4* boxes /* of `level` */, int level, uint32_t first, int cnt, const Ray& r,
+                                                  float best, uint32_t* stack, int& top, int lane) {
+    float4 clo = make_float4(INFINITY, INFINITY, INFINITY, 0.0f), chi = make_float4(-INFINITY, -INFINITY, -INFINITY, 0.0f);
+    if (lane < cnt) { clo = boxes[2 * (size_t)(first + lane)]; chi = boxes[2 * (size_t)(first + lane) + 1]; }
+    uint32_t keep = 0u;
+    float key = INFINITY;   // of child `lane`
+    for (int j = 0; j < cnt; ++j) {
+        const float4 lo = make_float4(lane_value(clo.x, j), lane_value(clo.y, j), lane_value(clo.z, j), 0.0f);
+        const float4 hi = make_float4(lane_value(chi.x, j), lane_value(chi.y, j), lane_value(chi.z, j), 0.0f);
+        float t_enter, t_exit;
+        slab(lo, hi, r, t_enter, t_exit);
+        const bool mine = r.active && t_enter <= t_exit && !(t_enter > best);
+        if (__ballot(mine) == 0ull) continue;
+        keep |= 1u << j;
+        const float first_in = wave_min(mine ? t_enter : INFINITY);
+        if (lane == j) key = first_in;
+    }
+    if (keep == 0u) return;
+    int rank = 0;   // kept children farther than this one (ties: the higher index counts as farther): a permutation of the kept
+    for (int j = 0; j < cnt; ++j) {
+        const float kj = lane_value(key, j);
+        rank += ((keep >> j) & 1u) && (kj > key || (kj == key && j > lane)) ? 1 : 0;
+    }
+    if (lane < cnt && ((keep >> lane) & 1u)) (stack + top)[rank] = ((uint32_t)level << 29) | (first + lane);
+    top += __popc(keep);
+    wave_sync();
+}
+
+// walk_tree for rays.  Exactness.  A face is hit only if its own box is (t_enter <= t_exit), and then t(ray, f) is clamped into
+// [t_enter, t_exit] of that box.  Both ends are formed by a subtraction from a fixed o_k and a multiplication by a fixed 1 / d_k (then
+// by a fixed pad), all monotone under rounding to nearest, and max / min are monotone too: a box that contains the triangle's box has
+// a t_enter that is not larger and a t_exit that is not smaller (on an axis with d_k == 0 it contains o_k whenever the triangle's box
+// does).  So a box is skipped, here, in push_hit_children and in hit_scan, only when the lane's ray misses it or enters it strictly
+// after the lane's slot: no member could then enter the slot, an equal t with a lower face index included.  The slots start at
+// (+inf, no face) and a t of +inf is a miss, so +inf is the answer of exactly the rays that hit nothing.
+__device__ __forceinline__ void ray_walk(const float4* boxes, const TriTree& tree, uint32_t F, const float4* records, const Ray& r,
+                                         float4* leaf, uint32_t* stack, int lane, HitSlot& slot) {
+    if (__ballot(r.active) == 0ull) return;
+    int top = 0;
+    uint32_t count, offset;
+    tri_level(tree.leaves, tree.top, count, offset);
+    push_hit_children(boxes + 2 * (size_t)offset, tree.top, 0u, (int)min(count, (uint32_t)kFan), r, slot.t, stack, top, lane);
+    while (top > 0) {
+        const uint32_t e = (uint32_t)__builtin_amdgcn_readfirstlane((int)stack[--top]);
+        const int level = (int)(e >> 29);
+        const uint32_t node = e & ((1u << 29) - 1u);
+        if (level > 0) {
+            const uint32_t first = node * kFan;
+            tri_level(tree.leaves, level - 1, count, offset);
+            push_hit_children(boxes + 2 * (size_t)offset, level - 1, first, (int)min((uint32_t)kFan, count - first), r, slot.t, stack, top,
+                              lane);
+            continue;
+        }
+        const float4 lo = boxes[2 * (size_t)node], hi = boxes[2 * (size_t)node + 1];   // (leaves: level offset 0)
+        float t_enter, t_exit;
+        slab(lo, hi, r, t_enter, t_exit);
+        if (__ballot(r.active && t_enter <= t_exit && !(t_enter > slot.t)) == 0ull) continue;
+        const uint32_t base = node * kLeaf;
+        const int cnt = (int)min((uint32_t)kLeaf, F - base);
+        wave_sync();
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const int at = k * kLeaf + lane;
+            if (at < 3 * cnt) leaf[at] = records[3 * (size_t)base + at];
+        }
+        wave_sync();
+        hit_scan(leaf, cnt, r, slot);
+    }
+}
+
+__global__ __launch_bounds__(256) void ray_hit_kernel(uint32_t n, const float* __restrict__ origins, const float* __restrict__ dirs,
+                                                      const unsigned char* __restrict__ plan, unsigned long long plan_bytes,
+                                                      long long* __restrict__ face_idx, float* __restrict__ t_hit, float* __restrict__ bary) {
+    __shared__ float4 s_leaf[4][3 * kLeaf];
+    __shared__ uint32_t s_stack[4][kStackDepth];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t group = blockIdx.x * 4u + (uint32_t)wave;    // this wave's 64 rays
+    if ((unsigned long long)group * kLeaf >= n) return;
+    const uint32_t s = group * kLeaf + lane;
+    Ray r = {};
+    if (s < n)
+        r = make_ray(origins[3 * (size_t)s], origins[3 * (size_t)s + 1], origins[3 * (size_t)s + 2], dirs[3 * (size_t)s],
+                     dirs[3 * (size_t)s + 1], dirs[3 * (size_t)s + 2]);
+    // the header against the size the caller holds, before anything else of the plan is read (plan_bytes >= 256: checked by the host)
+    const TriHeader h = *reinterpret_cast<const TriHeader*>(plan);
+    HitSlot slot = {INFINITY, kNoFace, 0.0f, 0.0f, 0.0f};
+    if (h.magic == kPlanMagic && h.plan_bytes == plan_bytes && h.F > 0u && h.F < (uint32_t)kMaxFaces) {
+        const TriTree tree = tri_layout(h.F);
+        if (tree.bytes == plan_bytes)
+            ray_walk(reinterpret_cast<const float4*>(plan + tree.boxes), tree, h.F, reinterpret_cast<const float4*>(plan + tree.records), r,
+                     s_leaf[wave], s_stack[wave], lane, slot);
+    }
+    if (s >= n) return;
+    const bool found = r.active && slot.face != kNoFace;
+    face_idx[s] = found ? (long long)slot.face : -1ll;
+    t_hit[s] = found ? slot.t : INFINITY;
+    if (bary) {
+        bary[3 * (size_t)s] = found ? slot.u : 0.0f;
+        bary[3 * (size_t)s + 1] = found ? slot.v : 0.0f;
+        bary[3 * (size_t)s + 2] = found ? slot.w : 0.0f;
+    }
+}
+
 // bounds -> codes -> sort -> pack -> levels -> header.  scratch: tri_scratch(F).bytes; plan: tri_layout(F).bytes; F < 2^30
 hipError_t launch_plan(int64_t V, const float* verts, uint32_t F, const long long* faces, unsigned char* plan, void* scratch,
                        hipStream_t stream) {
@@ -570,6 +795,27 @@ int gsr_closest_tri_query(int64_t n, const float* points, const void* plan, size
     hipLaunchKernelGGL(gsr::tri_query_kernel, dim3((groups + 3u) / 4u), dim3(256), 0, (hipStream_t)stream_, (uint32_t)n, points,
                        static_cast<const unsigned char*>(plan), (unsigned long long)plan_bytes, reinterpret_cast<long long*>(face_idx), sq_dist,
                        closest);
+    GSR_HIP(hipGetLastError());
+    return GSR_OK;
+}
+
+int gsr_ray_first_hit(int64_t n, const float* origins, const float* dirs, const void* plan, size_t plan_bytes, int64_t* face_idx, float* t,
+                      float* bary, void* stream_) {
+    if (n < 0) return fail(GSR_ERR_INVALID_ARG, "gsr_ray_first_hit: negative count (n %lld)", (long long)n);
+    if (n >= gsr::kMaxQueries) return fail(GSR_ERR_INVALID_ARG, "gsr_ray_first_hit: %lld rays (at most 2^31 - 1)", (long long)n);
+    if (n == 0) return GSR_OK;
+    if (!origins || !dirs || !plan || !face_idx || !t) return fail(GSR_ERR_INVALID_ARG, "gsr_ray_first_hit: null pointer");
+    if (gsr::misaligned(origins, 4) || gsr::misaligned(dirs, 4) || gsr::misaligned(plan, 256) || gsr::misaligned(face_idx, 8) ||
+        gsr::misaligned(t, 4) || gsr::misaligned(bary, 4))
+        return fail(GSR_ERR_INVALID_ARG, "gsr_ray_first_hit: misaligned pointer (origins / dirs / t / bary: 4 bytes, face_idx: 8 bytes, "
+                                         "plan: 256 bytes)");
+    // as in gsr_closest_tri_query: the header itself is compared with plan_bytes on the device
+    if (plan_bytes < gsr::kAlign || (plan_bytes & (gsr::kAlign - 1)) != 0)
+        return fail(GSR_ERR_INVALID_ARG, "gsr_ray_first_hit: plan_bytes = %zu is not the size of a plan", plan_bytes);
+    const uint32_t groups = (uint32_t)((n + gsr::kLeaf - 1) / gsr::kLeaf);
+    hipLaunchKernelGGL(gsr::ray_hit_kernel, dim3((groups + 3u) / 4u), dim3(256), 0, (hipStream_t)stream_, (uint32_t)n, origins, dirs,
+                       static_cast<const unsigned char*>(plan), (unsigned long long)plan_bytes, reinterpret_cast<long long*>(face_idx), t,
+                       bary);
     GSR_HIP(hipGetLastError());
     return GSR_OK;
 }

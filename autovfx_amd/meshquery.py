@@ -27,6 +27,37 @@ included.  A non-finite query, and any query when no face is valid, gets ``(-1, 
 :func:`plan_layout` restate the build and the layout of the plan; :class:`Scene` is a small
 adapter for code written against Open3D's ray-casting scene.  ``autovfx_amd.install()`` does not put it over Open3D: the frame loop
 uses it when ``AUTOVFX_AMD_MELT_CLOSEST=gpu`` (``autovfx_amd/frame_loop.py``).
+
+The same plan answers the other geometric question of the reference's own code, the first triangle a ray hits, which it asks of
+trimesh on the host (``extract/extract_object.py:115-159``, ``:424-434``, ``:476-482``, ``:563-606``; only ever the first hit).
+
+The ray contract, pointwise.  ``origins`` and ``dirs`` are fp32 and ``dirs`` are not normalised.  The answer
+for a ray ``(o, d)`` is the valid face with the smallest ``(t, f)`` among the faces it hits -- equal ``t`` go to the lower face index.
+A ray with a non-finite component or a zero direction, a ray that hits nothing, and any ray when no face is valid, gets
+``(-1, +inf, (0, 0, 0))``.  All in fp32 elementwise operations in the order written (no fused multiply-add), ``fmin`` / ``fmax``
+dropping a NaN:
+
+* the triangle test is the watertight one of Woop, Benthin and Wald without its double-precision fallback: ``kz`` = the axis of the
+  largest ``|d|`` (ties: the lowest axis), ``kx``, ``ky`` the next two cyclically, swapped when ``d[kz] < 0``; ``Sx = d[kx] / d[kz]``,
+  ``Sy = d[ky] / d[kz]``, ``Sz = 1 / d[kz]``; ``A = a - o`` (``B``, ``C`` alike); ``Ax = A[kx] - Sx A[kz]``, ``Ay = A[ky] - Sy A[kz]``,
+  ``Az = Sz A[kz]``; ``U = Cx By - Cy Bx``, ``V = Ax Cy - Ay Cx``, ``W = Bx Ay - By Ax``; a miss when one of them is ``< 0`` and
+  another ``> 0`` (two-sided); ``det = (U + V) + W``, a miss when 0; ``t_tri = ((U Az + V Bz) + W Cz) / det``, a miss unless
+  ``t_tri >= 0``; the barycentrics are ``U / det``, ``V / det``, ``W / det``, the weights of ``a``, ``b``, ``c``;
+* the triangle's own box is tested by slabs: on an axis with ``d_k != 0`` the products ``(lo_k - o_k) (1 / d_k)`` and
+  ``(hi_k - o_k) (1 / d_k)`` ordered by the sign of ``1 / d_k``, on an axis with ``d_k == 0`` all of the line when
+  ``lo_k <= o_k <= hi_k`` and nothing otherwise; ``t_enter = fmax(fmax(fmax(0, near_x), near_y), near_z)``,
+  ``t_exit = fmin(fmin(far_x, far_y), far_z) * 1.00000024f`` (the padding of Ize, "Robust BVH Ray Traversal");
+* a face is hit iff the triangle test hits, ``t_enter <= t_exit`` and ``t < +inf``, with
+  ``t = fmin(fmax(t_tri, t_enter), t_exit) + 0`` (the ``+ 0`` turns a ``-0`` into ``+0``).
+
+The clamp moves ``t`` by rounding error only, and it makes a box search exact: any box that contains the triangle's box has a
+``t_enter`` that is not larger and a ``t_exit`` that is not smaller, so skipping a box that is missed, or entered strictly after the
+best ``t`` so far, never skips the answer or a tie with it.
+
+:func:`first_hits` runs the HIP kernel (C ABI ``gsr_ray_first_hit``); :func:`first_hits_host` restates the contract in numpy;
+:meth:`Scene.cast_rays` and :class:`RayIntersector` are small adapters for code written against Open3D's scene and trimesh's
+``mesh.ray``; ``autovfx_amd.extract.triangle_votes`` is the voting loop of object extraction on top.  ``autovfx_amd.install()`` puts
+none of them over trimesh or Open3D, whose choices at ties and at grazing rays are not known here.
 """
 from __future__ import annotations
 
@@ -177,8 +208,135 @@ def closest_triangles_host(points, verts, faces, chunk_elems: int = 1 << 20, pru
     return face_idx, sq_dist, closest
 
 
+# ---- the ray contract in numpy --------------------------------------------------------------------------------------------------------
+SLAB_PAD = _F(1.00000024)     # gsr_meshquery.hip's kSlabPad: 1 + 2^-22
+
+
+def _pick(v, k):
+    """Component ``k`` (an int array) of the per-axis tuple ``v``: gsr_meshquery.hip's ``pick``."""
+    return np.where(k == 0, v[0], np.where(k == 1, v[1], v[2]))
+
+
+def _ray_shear(d):
+    """``kx, ky, kz, Sx, Sy, Sz`` of the per-axis tuple ``d`` (finite, not all zero): ``make_ray``."""
+    mag = tuple(np.abs(x) for x in d)
+    second = mag[1] > mag[0]
+    kz = np.where(mag[2] > np.where(second, mag[1], mag[0]), 2, np.where(second, 1, 0))
+    kx = (kz + 1) % 3
+    ky = (kx + 1) % 3
+    dkz = _pick(d, kz)
+    kx, ky = np.where(dkz < 0, ky, kx), np.where(dkz < 0, kx, ky)
+    return kx, ky, kz, _pick(d, kx) / dkz, _pick(d, ky) / dkz, _F(1) / dkz
+
+
+def slab_host(lo, hi, o, d):
+    """``t_enter``, ``t_exit`` of the contract for per-axis tuples of float32 arrays that broadcast: gsr_meshquery.hip's ``slab``.  The
+    box is hit iff ``t_enter <= t_exit``."""
+    inf = _F(np.inf)
+    near, far = [], []
+    for k in range(3):
+        moving = d[k] != 0
+        inv = _F(1) / np.where(moving, d[k], _F(1))
+        first, second = (lo[k] - o[k]) * inv, (hi[k] - o[k]) * inv
+        inside = (lo[k] <= o[k]) & (o[k] <= hi[k])
+        near.append(np.where(moving, np.where(inv < 0, second, first), np.where(inside, -inf, inf)))
+        far.append(np.where(moving, np.where(inv < 0, first, second), np.where(inside, inf, -inf)))
+    t_enter = np.fmax(np.fmax(np.fmax(_F(0), near[0]), near[1]), near[2])
+    t_exit = np.fmin(np.fmin(far[0], far[1]), far[2]) * SLAB_PAD
+    return t_enter, t_exit
+
+
+def ray_triangle_host(o, d, a, b, c):
+    """``t(ray, f)`` of the ray contract for float32 arrays ``o``, ``d``, ``a``, ``b``, ``c`` of shape ``[..., 3]`` that broadcast
+    against each other; the rays finite with a direction that is not zero, the corners finite.  Returns a dict of arrays of shape
+    ``[...]``: ``hit`` (bool), ``t`` (float32, meaningful where ``hit``), ``t_tri``, ``t_enter``, ``t_exit``, and ``bary``
+    ``[..., 3]`` (``U / det``, ``V / det``, ``W / det``).  Overflow and NaN pass through as in the kernel."""
+    o, d, a, b, c = (np.asarray(t, dtype=_F) for t in (o, d, a, b, c))
+    xyz = lambda t: (t[..., 0], t[..., 1], t[..., 2])
+    ov, dv, av, bv, cv = xyz(o), xyz(d), xyz(a), xyz(b), xyz(c)
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore", under="ignore"):
+        kx, ky, kz, Sx, Sy, Sz = _ray_shear(dv)
+        A, B, C = _sub(av, ov), _sub(bv, ov), _sub(cv, ov)
+        Akz, Bkz, Ckz = _pick(A, kz), _pick(B, kz), _pick(C, kz)
+        Ax, Ay = _pick(A, kx) - Sx * Akz, _pick(A, ky) - Sy * Akz
+        Bx, By = _pick(B, kx) - Sx * Bkz, _pick(B, ky) - Sy * Bkz
+        Cx, Cy = _pick(C, kx) - Sx * Ckz, _pick(C, ky) - Sy * Ckz
+        U, V, W = Cx * By - Cy * Bx, Ax * Cy - Ay * Cx, Bx * Ay - By * Ax
+        hit = ~(((U < 0) | (V < 0) | (W < 0)) & ((U > 0) | (V > 0) | (W > 0)))
+        det = (U + V) + W
+        hit &= det != 0
+        Az, Bz, Cz = Sz * Akz, Sz * Bkz, Sz * Ckz
+        t_tri = ((U * Az + V * Bz) + W * Cz) / det
+        hit &= t_tri >= 0
+        lo = tuple(np.fmin(np.fmin(av[k], bv[k]), cv[k]) for k in range(3))
+        hi = tuple(np.fmax(np.fmax(av[k], bv[k]), cv[k]) for k in range(3))
+        t_enter, t_exit = slab_host(lo, hi, ov, dv)
+        hit &= t_enter <= t_exit
+        t = np.fmin(np.fmax(t_tri, t_enter), t_exit) + _F(0)
+        hit &= t < _F(np.inf)
+        bary = np.stack(np.broadcast_arrays(U / det, V / det, W / det), -1)
+    return {"hit": hit, "t": t, "t_tri": t_tri, "t_enter": t_enter, "t_exit": t_exit, "bary": bary}
+
+
+def first_hits_host(origins, dirs, verts, faces, chunk_elems: int = 1 << 20, pruned: bool = False):
+    """The ray contract restated in numpy: brute force over all valid faces, every operation an fp32 elementwise one in the
+    contract's order, chunked over the rays.  ``origins``, ``dirs``, ``verts``: anything ``np.asarray`` takes, reshaped to ``[., 3]``
+    float32; ``faces`` to ``[F, 3]`` int64.  Returns ``face_idx [n]`` int64 (-1: no hit), ``t [n]`` float32 (+inf: no hit) and
+    ``bary [n, 3]`` float32 (zeros: no hit).
+
+    ``pruned``: the same answers, bit for bit and ties included, sooner on a large mesh.  The slab test of every triangle's own box
+    is evaluated for every ray (a few operations), the triangle test only where ``t_enter <= t_exit``, which a hit requires by the
+    contract; the first minimum in ascending face index is taken.  No tree and no order of the faces is involved."""
+    o = np.ascontiguousarray(np.asarray(origins, dtype=_F).reshape(-1, 3))
+    d = np.ascontiguousarray(np.asarray(dirs, dtype=_F).reshape(-1, 3))
+    v = np.ascontiguousarray(np.asarray(verts, dtype=_F).reshape(-1, 3))
+    f = np.ascontiguousarray(np.asarray(faces, dtype=np.int64).reshape(-1, 3))
+    if o.shape != d.shape:
+        raise ValueError(f"first_hits_host: {o.shape[0]} origins and {d.shape[0]} directions")
+    n = o.shape[0]
+    face_idx = np.full(n, -1, np.int64)
+    t_hit = np.full(n, np.inf, _F)
+    bary = np.zeros((n, 3), _F)
+    ids = np.nonzero(valid_faces_host(v, f))[0]                 # ascending: the first minimum of a row is the lowest face index
+    rows = np.nonzero(np.all(np.isfinite(o), axis=1) & np.all(np.isfinite(d), axis=1) & np.any(d != 0, axis=1))[0]
+    if ids.size == 0 or rows.size == 0:
+        return face_idx, t_hit, bary
+    a, b, c = (v[f[ids, k]] for k in range(3))
+    step = max(1, chunk_elems // ids.size)
+    inf = _F(np.inf)
+    for at in range(0, rows.size, step):
+        r = rows[at:at + step]
+        if pruned:
+            lo = tuple(np.fmin(np.fmin(a[:, k], b[:, k]), c[:, k])[None, :] for k in range(3))
+            hi = tuple(np.fmax(np.fmax(a[:, k], b[:, k]), c[:, k])[None, :] for k in range(3))
+            with np.errstate(over="ignore", invalid="ignore", divide="ignore", under="ignore"):
+                t_enter, t_exit = slab_host(lo, hi, tuple(o[r, k][:, None] for k in range(3)), tuple(d[r, k][:, None] for k in range(3)))
+            row, col = np.nonzero(t_enter <= t_exit)            # row-major: per ray, ascending face index
+            if row.size == 0:
+                continue
+            got = ray_triangle_host(o[r][row], d[r][row], a[col], b[col], c[col])
+            tt = np.where(got["hit"], got["t"], inf)
+            least = np.full(r.size, inf, _F)
+            np.minimum.at(least, row, tt)
+            first = np.nonzero((tt == least[row]) & (tt < inf))[0]
+            first = first[np.unique(row[first], return_index=True)[1]]      # the first minimum of every ray that hits
+            face_idx[r[row[first]]] = ids[col[first]]
+            t_hit[r[row[first]]] = tt[first]
+            bary[r[row[first]]] = got["bary"][first]
+            continue
+        got = ray_triangle_host(o[r][:, None, :], d[r][:, None, :], a[None], b[None], c[None])
+        tt = np.where(got["hit"], got["t"], inf)
+        best = np.argmin(tt, axis=1)
+        pick = np.arange(r.size)
+        found = tt[pick, best] < inf
+        face_idx[r[found]] = ids[best[found]]
+        t_hit[r[found]] = tt[pick, best][found]
+        bary[r[found]] = got["bary"][pick, best][found]
+    return face_idx, t_hit, bary
+
+
 # ---- the plan in numpy ----------------------------------------------------------------------------------------------------------------
-LEAF = 64            # gsr_meshquery.hip's kLeaf, kFan, kTriMaxLevels, kAlign, kCellMax
+LEAF = 64           # gsr_meshquery.hip's kLeaf, kFan, kTriMaxLevels, kAlign, kCellMax
 FAN = 16
 MAX_LEVELS = 6
 ALIGN = 256
@@ -341,6 +499,30 @@ def _why_not_points(points, device) -> Optional[str]:
     return None
 
 
+def _why_not_plan(plan, verts, faces) -> Optional[str]:
+    """``plan``: None, or the plan of this very mesh."""
+    if plan is None:
+        return None
+    if not isinstance(plan, Plan):
+        return f"plan must be a meshquery.Plan (got {type(plan).__name__})"
+    if plan.F != int(faces.shape[0]) or plan.V != int(verts.shape[0]) or plan.device != verts.device:
+        return (f"the plan is of a mesh with {plan.F} faces and {plan.V} vertices on {plan.device}, "
+                f"not of this one ({int(faces.shape[0])}, {int(verts.shape[0])}, {verts.device})")
+    if plan.buffer.dtype != torch.uint8 or int(plan.buffer.numel()) != _plan_bytes(plan.F):
+        return (f"the plan's buffer is {int(plan.buffer.numel())} elements of {plan.buffer.dtype}, "
+                f"a plan of {plan.F} faces is {_plan_bytes(plan.F)} bytes")
+    return None
+
+
+def _why_not_rays(origins, dirs, device) -> Optional[str]:
+    why = _why_not_points(origins, device) or _why_not_points(dirs, device)
+    if why is not None:
+        return why.replace("points", "origins and dirs")
+    if origins.shape[0] != dirs.shape[0]:
+        return f"{origins.shape[0]} origins and {dirs.shape[0]} dirs"
+    return None
+
+
 def _plan_bytes(F: int) -> int:
     """Bytes of the plan of a mesh of ``F`` faces (``gsr_closest_tri_plan_bytes``; 0: more faces than the kernels take)."""
     from . import _lib
@@ -378,16 +560,7 @@ def closest_triangles(points: torch.Tensor, verts: torch.Tensor, faces: torch.Te
     same answers, much sooner unless the caller's order is coherent already).  Queued on the current stream, no host synchronisation;
     not differentiable; non-contiguous inputs are copied.  Raises ``ValueError`` with the reason for CPU tensors, other dtypes or shapes, devices that
     differ, a plan of another mesh or of another size than its ``F`` asks for, and under graph capture."""
-    why = _why_not_mesh(verts, faces) or _why_not_points(points, verts.device)
-    if why is None and plan is not None:
-        if not isinstance(plan, Plan):
-            why = f"plan must be a meshquery.Plan (got {type(plan).__name__})"
-        elif plan.F != int(faces.shape[0]) or plan.V != int(verts.shape[0]) or plan.device != verts.device:
-            why = (f"the plan is of a mesh with {plan.F} faces and {plan.V} vertices on {plan.device}, "
-                   f"not of this one ({int(faces.shape[0])}, {int(verts.shape[0])}, {verts.device})")
-        elif plan.buffer.dtype != torch.uint8 or int(plan.buffer.numel()) != _plan_bytes(plan.F):
-            why = (f"the plan's buffer is {int(plan.buffer.numel())} elements of {plan.buffer.dtype}, "
-                   f"a plan of {plan.F} faces is {_plan_bytes(plan.F)} bytes")
+    why = _why_not_mesh(verts, faces) or _why_not_points(points, verts.device) or _why_not_plan(plan, verts, faces)
     if why is not None:
         raise ValueError("closest_triangles: " + why)
     tree = plan if plan is not None else _build(verts, faces)
@@ -448,9 +621,92 @@ def _query(points: torch.Tensor, tree: Plan, return_points: bool, sort_queries: 
     return (face_idx, sq_dist, closest) if return_points else (face_idx, sq_dist)
 
 
+def first_hits(origins: torch.Tensor, dirs: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor, plan: Optional[Plan] = None,
+               return_bary: bool = False, return_points: bool = False, sort: bool = True):
+    """For every ray ``origins [n, 3]``, ``dirs [n, 3]`` (float32, not normalised) the first triangle of the mesh it hits:
+    ``face_idx [n]`` int64 (-1: no hit) and ``t [n]`` float32 (+inf: no hit), then, with ``return_bary``, ``bary [n, 3]`` float32 (the
+    weights of the face's three corners, zeros on a miss) and, with ``return_points``, ``points [n, 3]`` float32 (``o + t d``, zeros on
+    a miss).  The contract is DESIGN.md 7m; :func:`first_hits_host` restates it.  ``plan``: what :func:`plan` returned for this mesh
+    (built here otherwise): the plan of :func:`closest_triangles`.  The rays are asked in a coherent order (:func:`ray_order`) and the
+    answers put back; ``sort=False`` asks them as given, which is sooner when they come side by side already, as the pixels of a
+    camera do (``_cast`` has the measurements).  The answers are the same either way.  Queued on the current stream, no host synchronisation; not differentiable; non-contiguous inputs are copied.  Raises
+    ``ValueError`` with the reason for what :func:`closest_triangles` refuses."""
+    why = _why_not_mesh(verts, faces) or _why_not_rays(origins, dirs, verts.device) or _why_not_plan(plan, verts, faces)
+    if why is not None:
+        raise ValueError("first_hits: " + why)
+    tree = plan if plan is not None else _build(verts, faces)
+    o, d = origins.detach().contiguous(), dirs.detach().contiguous()
+    face_idx, t, bary = _cast(o, d, tree, return_bary, order=ray_order(o, d, verts) if sort and o.shape[0] >= SORT_FROM else None)
+    out = [face_idx, t]
+    if return_bary:
+        out.append(bary)
+    if return_points:
+        # a multiplication, then an addition (no fused multiply-add), as first_hits_host's callers restate it
+        out.append(torch.where((face_idx >= 0)[:, None], o + torch.where(face_idx >= 0, t, 0.0)[:, None] * d, 0.0))
+    return tuple(out)
+
+
+def ray_order(origins: torch.Tensor, dirs: torch.Tensor, verts: torch.Tensor) -> torch.Tensor:
+    """Indices that put the rays in the Morton order of the point where each leaves the bounding box of the finite vertices (the
+    origin clamped into the box for a ray that misses it, or when there is no finite vertex): rays that leave the box side by side
+    cross much the same part of the tree.  torch ops on the rays' device, no host read.  The order only groups rays into waves: it
+    never changes an answer."""
+    o = torch.nan_to_num(origins.detach(), nan=0.0, posinf=0.0, neginf=0.0)
+    if verts.shape[0] == 0:
+        return morton_order(o)
+    d = torch.nan_to_num(dirs.detach(), nan=0.0, posinf=0.0, neginf=0.0)
+    v = verts.detach()
+    fine = torch.isfinite(v).all(dim=1, keepdim=True)
+    inf = float("inf")
+    lo, hi = torch.where(fine, v, inf).min(dim=0).values, torch.where(fine, v, -inf).max(dim=0).values
+    moving = d != 0
+    inv = 1.0 / torch.where(moving, d, 1.0)
+    inside = (lo <= o) & (o <= hi)
+    far = torch.where(moving, torch.maximum((lo - o) * inv, (hi - o) * inv), torch.where(inside, inf, -inf))
+    near = torch.where(moving, torch.minimum((lo - o) * inv, (hi - o) * inv), torch.where(inside, -inf, inf))
+    t_exit = far.min(dim=1).values
+    leaves = (near.max(dim=1).values.clamp_min(0.0) <= t_exit) & torch.isfinite(t_exit)
+    at = torch.where(leaves[:, None], o + torch.where(leaves, t_exit, 0.0)[:, None] * d, torch.maximum(torch.minimum(o, hi), lo))
+    return morton_order(at)
+
+
+def _cast(origins: torch.Tensor, dirs: torch.Tensor, tree: Plan, return_bary: bool, order: Optional[torch.Tensor] = None):
+    """``gsr_ray_first_hit`` on contiguous rays, asked in ``order`` (None: as given) and put back.  A wave takes 64 consecutive rays
+    and walks the tree once for all of them, so it is fast when they run side by side; every answer is a function of its own ray
+    alone.  Measured on an MI355X on 1 M faces (scripts/bench_meshrays.py): 1 M rays from inside in random directions and random
+    order 9.9 ms in ``ray_order`` (2.5 ms of it the order itself) with the way back, 26 ms as given; the 2 M rays of a 1080p camera
+    2.3 ms as given, in row-major pixel order, and 6.3 ms ordered -- the order costs more than it saves when the rays come side by
+    side already, hence ``first_hits(..., sort=False)``.  Returns ``face_idx``, ``t``, ``bary`` (None unless wanted)."""
+    from . import _lib
+
+    n = int(origins.shape[0])
+    dev = origins.device
+    face_idx = torch.empty(n, dtype=torch.int64, device=dev)
+    t = torch.empty(n, dtype=torch.float32, device=dev)
+    bary = torch.empty((n, 3), dtype=torch.float32, device=dev) if return_bary else None
+    if n == 0:
+        return face_idx, t, bary
+    o, d = (origins, dirs) if order is None else (origins[order], dirs[order])
+    out = (face_idx, t, bary) if order is None else tuple(None if x is None else torch.empty_like(x) for x in (face_idx, t, bary))
+    with torch.cuda.device(dev):
+        # the kernel reads the plan after this call returns, on THIS stream: a plan built on another one is not recycled under it
+        tree.buffer.record_stream(torch.cuda.current_stream(dev))
+        _lib.call("gsr_ray_first_hit", n, o.data_ptr(), d.data_ptr(), tree.buffer.data_ptr(), int(tree.buffer.numel()), out[0].data_ptr(),
+                  out[1].data_ptr(), _lib.ptr(out[2]), device=dev)
+    if order is not None:
+        for dst, src in zip((face_idx, t, bary), out):
+            if dst is not None:
+                dst.index_copy_(0, order, src)
+    return face_idx, t, bary
+
+
+def _as_tensor(x, device, dtype):
+    return torch.as_tensor(np.asarray(x) if not isinstance(x, torch.Tensor) else x).to(device, dtype)
+
+
 class Scene:
-    """A mesh to ask closest points of, for code written against ``open3d.t.geometry.RaycastingScene``: the plan is built once,
-    here.  ``verts``, ``faces``: numpy arrays or tensors (moved to ``device``, default the current GPU)."""
+    """A mesh to ask closest points and first hits of, for code written against ``open3d.t.geometry.RaycastingScene``: the plan is
+    built once, here.  ``verts``, ``faces``: numpy arrays or tensors (moved to ``device``, default the current GPU)."""
 
     def __init__(self, verts, faces, device=None):
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -465,3 +721,45 @@ class Scene:
         pts = pts.to(self.verts.device, torch.float32).reshape(-1, 3)
         face_idx, sq_dist, closest = closest_triangles(pts, self.verts, self.faces, plan=self.plan, return_points=True)
         return {"primitive_ids": face_idx, "points": closest, "distances": torch.sqrt(sq_dist), "squared_distances": sq_dist}
+
+    def cast_rays(self, rays) -> dict:
+        """``rays``: ``[n, 6]`` (origin, direction; the direction is not normalised and ``t_hit`` is in its units, as in Open3D),
+        numpy or torch, any float dtype.  Returns device tensors: ``t_hit`` float32 ``[n]`` (+inf: no hit), ``primitive_ids`` int64
+        ``[n]`` and ``primitive_uvs`` float32 ``[n, 2]`` (the weights of the face's second and third corner; zeros on a miss).
+        Unlike Open3D, whose ``primitive_ids`` are uint32 with 4294967295 for no hit, a miss is -1 here.  ``geometry_ids`` and
+        ``primitive_normals`` are not returned."""
+        r = _as_tensor(rays, self.verts.device, torch.float32).reshape(-1, 6)
+        face_idx, t, bary = first_hits(r[:, :3], r[:, 3:], self.verts, self.faces, plan=self.plan, return_bary=True)
+        return {"t_hit": t, "primitive_ids": face_idx, "primitive_uvs": bary[:, 1:].contiguous()}
+
+
+class RayIntersector:
+    """The first-hit questions of ``trimesh``'s ``mesh.ray`` on the GPU, numpy in and numpy out: ``RayIntersector(mesh.vertices,
+    mesh.faces)`` where the caller wrote ``mesh.ray``.  The answers follow this library's contract, whose choices at
+    ties and at grazing rays need not be trimesh's; locations are float32."""
+
+    def __init__(self, verts, faces, device=None):
+        self.scene = Scene(verts, faces, device=device)
+
+    def _ask(self, ray_origins, ray_directions, points: bool = False):
+        dev = self.scene.verts.device
+        o = _as_tensor(ray_origins, dev, torch.float32).reshape(-1, 3)
+        d = _as_tensor(ray_directions, dev, torch.float32).reshape(-1, 3)
+        return first_hits(o, d, self.scene.verts, self.scene.faces, plan=self.scene.plan, return_points=points)
+
+    def intersects_first(self, ray_origins, ray_directions) -> np.ndarray:
+        """The first face every ray hits, ``[n]`` int64, -1 for none."""
+        return self._ask(ray_origins, ray_directions)[0].cpu().numpy()
+
+    def intersects_any(self, ray_origins, ray_directions) -> np.ndarray:
+        """Whether every ray hits anything, ``[n]`` bool."""
+        return (self._ask(ray_origins, ray_directions)[0] >= 0).cpu().numpy()
+
+    def intersects_location(self, ray_origins, ray_directions, multiple_hits: bool = False):
+        """``(locations [m, 3] float32, index_ray [m] int64, index_tri [m] int64)`` of the rays that hit, in ray order: the first
+        hit of each.  ``multiple_hits=True`` (all hits of every ray) is not provided and raises ``NotImplementedError``."""
+        if multiple_hits:
+            raise NotImplementedError("RayIntersector.intersects_location: only the first hit of a ray is computed (multiple_hits=False)")
+        face_idx, _, points = self._ask(ray_origins, ray_directions, points=True)
+        index_ray = torch.nonzero(face_idx >= 0).reshape(-1)
+        return points[index_ray].cpu().numpy(), index_ray.cpu().numpy(), face_idx[index_ray].cpu().numpy()

@@ -42,7 +42,8 @@
 extern "C" {
 #endif
 
-/* Still 20: + the closest triangle of a mesh (gsr_closest_tri_plan_bytes, gsr_closest_tri_plan_scratch_bytes, gsr_closest_tri_plan,
+/* Still 20: + the first triangle a ray hits, on the closest-triangle plan (gsr_ray_first_hit).
+ * Still 20: + the closest triangle of a mesh (gsr_closest_tri_plan_bytes, gsr_closest_tri_plan_scratch_bytes, gsr_closest_tri_plan,
  * gsr_closest_tri_query).
  * Still 20: + the mesh normal consistency loss (gsr_normal_consistency_plan_scratch_bytes, gsr_normal_consistency_plan,
  * gsr_normal_consistency_scratch_bytes, gsr_normal_consistency_forward, gsr_normal_consistency_backward).
@@ -477,6 +478,32 @@ GSR_API int gsr_closest_tri_plan(int64_t V, const float* verts, int64_t F, const
                                  void* scratch, size_t scratch_bytes, void* stream);
 GSR_API int gsr_closest_tri_query(int64_t n, const float* points, const void* plan, size_t plan_bytes, int64_t* face_idx, float* sq_dist,
                                   float* closest, void* stream);
+
+/* The first triangle of a mesh that every ray hits (what trimesh's mesh.ray.intersects_first / intersects_location(multiple_hits=False)
+ * answer for object extraction and removal, extract/extract_object.py:115-159, :424-434, :476-482, :563-606) -- added under ABI 20.
+ * origins [n,3], dirs [n,3] fp32 (not normalised), a plan of gsr_closest_tri_plan -> face_idx [n] int64, t [n] fp32, bary [n,3] fp32
+ * (NULL: not wanted).  The answer for a ray is the valid face (as above) with the smallest (t, f) among the faces it hits -- equal t go
+ * to the lower face index -- with, all in fp32 without fused multiply-adds (DESIGN.md 7m gives the operation order,
+ * autovfx_amd/meshquery.py restates it in numpy):
+ *   the watertight test of Woop, Benthin and Wald without its double-precision fallback: kz = the axis of the largest |d| (ties: the
+ *   lowest), kx, ky the next two cyclically, swapped when d[kz] < 0; Sx = d[kx]/d[kz], Sy = d[ky]/d[kz], Sz = 1/d[kz]; the corners
+ *   translated by -o; Ax = A[kx] - Sx A[kz], Ay = A[ky] - Sy A[kz], Az = Sz A[kz] (B, C alike); U = Cx By - Cy Bx, V = Ax Cy - Ay Cx,
+ *   W = Bx Ay - By Ax; a miss when one is < 0 and another > 0 (two-sided); det = (U + V) + W, a miss when 0;
+ *   t_tri = ((U Az + V Bz) + W Cz) / det, a miss unless t_tri >= 0;
+ *   the triangle's own box by slabs: per axis with d_k != 0 the products (lo_k - o_k)(1/d_k) and (hi_k - o_k)(1/d_k) ordered by the sign
+ *   of 1/d_k, per axis with d_k == 0 everything when lo_k <= o_k <= hi_k, else nothing; t_enter = max(0, nears),
+ *   t_exit = min(fars) * 1.00000024f; a miss unless t_enter <= t_exit;
+ *   t = min(max(t_tri, t_enter), t_exit) + 0, a miss when +inf;  bary = U/det, V/det, W/det (the weights of the face's corners).
+ * The clamp moves t by rounding error only and makes the tree search exact, so the result is a pointwise function of the input.  A ray
+ * with a non-finite component or a zero direction, a ray that hits nothing, and any ray when no face is valid, gets (-1, +inf, 0 0 0).
+ * Every output element is written.  n == 0 touches nothing.  The plan is read only: one plan serves both queries, on any stream ordered
+ * after its build.
+ * Refused (GSR_ERR_INVALID_ARG, nothing launched): a negative n, n >= 2^31, a null pointer other than bary, misaligned pointers
+ * (origins / dirs / t / bary: 4 bytes; face_idx: 8; plan: 256), a plan_bytes that is not a whole number of 256-byte blocks.  The plan's
+ * header is checked on the device as in gsr_closest_tri_query: a header that does not match answers every ray (-1, +inf, 0 0 0).
+ * Enqueues on `stream` only: no host synchronisation, no device-to-host copy, no atomics. */
+GSR_API int gsr_ray_first_hit(int64_t n, const float* origins, const float* dirs, const void* plan, size_t plan_bytes, int64_t* face_idx,
+                              float* t, float* bary, void* stream);
 
 /* SuGaR's density field over a neighbour list (SuGaR.get_field_values, sugar_model.py:1118-1187, and SuGaR.compute_density,
  * :1216-1239) -- added under ABI 20.  x [n,3], idx [n,K] int64, centers [P,3], M [P,3,3] row-major (the inverse scaled rotation,
