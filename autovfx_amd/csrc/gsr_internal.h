@@ -398,4 +398,14 @@ hipError_t radix_sort_pairs(uint32_t* scratch, uint32_t n, int bits, uint32_t* k
                             uint32_t** keys_sorted, uint32_t** vals_sorted, hipStream_t stream,
                             const RadixSortExtras& extras = RadixSortExtras());
 
+// ---- the build steps the box trees of gsr_knn.hip and gsr_meshquery.hip share (gsr_tree.hip; the trees' shape: gsr_tree.h) ----
+// The order of n < 2^30 records by their 63-bit Morton codes: the low words in `keys` (overwritten), the high words in `key_hi`
+// (kept).  Two radix_sort_pairs, least significant word first, both stable, the high words gathered in between.  `radix`:
+// radix_scratch_words(n) words; keys, keys_alt, vals, vals_alt: n words each, any content.  *order: the sorted record indices, in
+// `vals` or `vals_alt`.
+hipError_t morton_sort(uint32_t* radix, uint32_t n, uint32_t* keys, uint32_t* keys_alt, uint32_t* vals, uint32_t* vals_alt,
+                       const uint32_t* key_hi, uint32_t** order, hipStream_t stream);
+// The box levels 1 .. top above the `leaves` leaf boxes that `boxes` begins with, each box the union of its 16 children.
+hipError_t tree_levels(float4* boxes, uint32_t leaves, int top, hipStream_t stream);
+
 } // namespace gsr

@@ -11,27 +11,26 @@
 //   codes   : 63-bit Morton codes on a (2^21)^3 grid of those bounds; a point with a non-finite coordinate gets 2^63 (sorts last).
 //             Far outliers stretch the bounds of a COLMAP cloud: with 10 bits per axis its dense part would share a handful of
 //             cells, the leaves would be random samples of it and the search quadratic;
-//   sort    : (code, index) by the library's radix sort, low word first (iota payload), then the high word (stable);
+//   sort    : (code, index) by the library's radix sort, low word first (iota payload), then the high word (stable): morton_sort;
 //   pack    : the points gathered once in sorted order into float4 (x, y, z, index bits); one wave per leaf of 64 points reduces
 //             the leaf's box (finite members only: a leaf of non-finite points has an empty box, lo = +inf, hi = -inf);
-//   levels  : boxes of 16 children each, level over level, until at most 16 boxes are left (six levels below 2^30 points);
+//   levels  : boxes of 16 children each, level over level, until at most 16 boxes are left (six levels below 2^30 points):
+//             tree_levels, like morton_sort in gsr_tree.hip, where gsr_meshquery.hip finds them too (the tree's shape: gsr_tree.h);
 //   search  : one wave per leaf, one lane per query: the slots are seeded with the wave's own leaf, then a depth-first walk over the
 //             tree from the top prunes by box bounds (walk_tree, further down: the walk, its prune rule and why it is exact).
 // Defines the entry points gsr_knn3_scratch_bytes, gsr_knn3_mean_dist, gsr_knn_points_scratch_bytes and gsr_knn_points.
-#include "gsr_internal.h"
+#include "gsr_tree.h"
 
 #include <cfloat>
 
 namespace gsr {
 namespace {
 
-// Boxes over the Morton-sorted points: level 0 = leaves of 64 points, every level above = 16 boxes of the one below, up to the first
-// level of at most 16 boxes (six levels for n < 2^30).  A box is two float4 (lo, hi; w unused) at boxes[2 * (offset[level] + i)].
-constexpr int kKnnMaxLevels = 6;
+// The tree of gsr_tree.h over points, as the by-value table the search kernels receive.
 struct KnnTree {
     const float4* boxes;
-    uint32_t count[kKnnMaxLevels];
-    uint32_t offset[kKnnMaxLevels];
+    uint32_t count[kTreeMaxLevels];
+    uint32_t offset[kTreeMaxLevels];
     int top;
 };
 // Byte offsets of the regions of the caller's scratch (each 256-byte aligned); bytes = the whole.
@@ -40,50 +39,12 @@ struct KnnLayout {
     KnnTree tree;
 };
 constexpr int kKnnPointsMaxK = 16;   // slots per query of gsr_knn_points
-
-constexpr int kLeaf = 64;            // points per leaf: one wave
-constexpr int kFan = 16;             // children per box above the leaves
-constexpr int kStackDepth = 96;      // >= kFan + (kFan - 1) * (kKnnMaxLevels - 1)
-constexpr int kBoundsBlocks = 128;   // partial bounds
-constexpr uint32_t kCellMax = (1u << 21) - 1u;   // 21 bits per axis: a 63-bit Morton code, sorted as two 32-bit words
 constexpr uint32_t kNonFiniteKey = 1u << 31;     // (the high word of a point with a non-finite coordinate)
-static_assert(kStackDepth >= kFan + (kFan - 1) * (kKnnMaxLevels - 1), "stack too shallow for the tree");
-
-__device__ __forceinline__ void wave_sync() {   // a wave's LDS operations run in program order: keep the compiler to it
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-__device__ __forceinline__ float wave_min(float v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = fminf(v, __shfl_xor(v, d, 64));
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d, 64));
-    return v;
-}
-__device__ __forceinline__ float lane_value(float v, int lane) {   // lane: wave-uniform
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
-}
-
-__device__ __forceinline__ bool finite3(float x, float y, float z) {
-    return __builtin_isfinite(x) && __builtin_isfinite(y) && __builtin_isfinite(z);
-}
 
 // d(i, j) of the contract: candidate minus query, squares summed left to right (the build has -ffp-contract=off)
 __device__ __forceinline__ float sq_dist(const float4& c, float qx, float qy, float qz) {
     const float dx = c.x - qx, dy = c.y - qy, dz = c.z - qz;
     return (dx * dx + dy * dy) + dz * dz;
-}
-
-// The same operations on the gap to a box: never above sq_dist of a member (see walk_tree).  An empty box gives +inf.
-__device__ __forceinline__ float box_bound(const float4& lo, const float4& hi, float qx, float qy, float qz) {
-    const float gx = fmaxf(fmaxf(lo.x - qx, qx - hi.x), 0.0f);
-    const float gy = fmaxf(fmaxf(lo.y - qy, qy - hi.y), 0.0f);
-    const float gz = fmaxf(fmaxf(lo.z - qz, qz - hi.z), 0.0f);
-    return (gx * gx + gy * gy) + gz * gz;
 }
 
 // s0 <= s1 <= s2 stay sorted; NaN / inf / FLT_MAX change nothing (as the reference's strict `knn[j] > dist`)
@@ -92,36 +53,6 @@ __device__ __forceinline__ void insert3(float d, float& s0, float& s1, float& s2
     s2 = fminf(s2, fmaxf(s1, d));
     s1 = fminf(s1, fmaxf(s0, d));
     s0 = fminf(s0, d);
-}
-
-__device__ __forceinline__ uint64_t spread21(uint32_t v) {   // bit k of v (k < 21) -> bit 3k
-    uint64_t x = v & 0x1FFFFFu;
-    x = (x | (x << 32)) & 0x001F00000000FFFFull;
-    x = (x | (x << 16)) & 0x001F0000FF0000FFull;
-    x = (x | (x << 8)) & 0x100F00F00F00F00Full;
-    x = (x | (x << 4)) & 0x10C30C30C30C30C3ull;
-    x = (x | (x << 2)) & 0x1249249249249249ull;
-    return x;
-}
-
-__device__ __forceinline__ uint32_t grid_cell(float x, float lo, float hi) {
-    const float extent = hi - lo;
-    const float t = extent > 0.0f ? (x - lo) / extent * (float)kCellMax : 0.0f;
-    return t >= 0.0f ? (uint32_t)fminf(t, (float)kCellMax) : 0u;   // (NaN -> 0: the code only steers the search, never its result)
-}
-
-// lo / hi of six floats reduced over the workgroup (256 lanes), result in every lane
-__device__ void block_minmax(float lo[3], float hi[3], float* s_red /* 6 * 4 floats */) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int a = 0; a < 3; ++a) { lo[a] = wave_min(lo[a]); hi[a] = wave_max(hi[a]); }
-    if (lane == 0)
-        for (int a = 0; a < 3; ++a) { s_red[a * 4 + wave] = lo[a]; s_red[(3 + a) * 4 + wave] = hi[a]; }
-    __syncthreads();
-    for (int a = 0; a < 3; ++a) {
-        lo[a] = fminf(fminf(s_red[a * 4], s_red[a * 4 + 1]), fminf(s_red[a * 4 + 2], s_red[a * 4 + 3]));
-        hi[a] = fmaxf(fmaxf(s_red[(3 + a) * 4], s_red[(3 + a) * 4 + 1]), fmaxf(s_red[(3 + a) * 4 + 2], s_red[(3 + a) * 4 + 3]));
-    }
-    __syncthreads();
 }
 
 __global__ __launch_bounds__(256) void knn_bounds_kernel(uint32_t n, const float* __restrict__ points, float4* __restrict__ partials) {
@@ -161,13 +92,6 @@ __global__ __launch_bounds__(256) void knn_codes_kernel(uint32_t n, const float*
     }
 }
 
-// the high words in the order of the first sort (by the low words), for the second
-__global__ __launch_bounds__(256) void knn_gather_kernel(uint32_t n, const uint32_t* __restrict__ order, const uint32_t* __restrict__ key_hi,
-                                                         uint32_t* __restrict__ out) {
-    const uint32_t s = blockIdx.x * 256u + threadIdx.x;
-    if (s < n) out[s] = key_hi[order[s]];
-}
-
 // one wave per leaf: the sorted points packed, the leaf's box (finite members)
 __global__ __launch_bounds__(256) void knn_pack_kernel(uint32_t n, const float* __restrict__ points, const uint32_t* __restrict__ order,
                                                        float4* __restrict__ packed, float4* __restrict__ leaf_boxes) {
@@ -185,21 +109,6 @@ __global__ __launch_bounds__(256) void knn_pack_kernel(uint32_t n, const float* 
         leaf_boxes[2 * leaf] = make_float4(lo[0], lo[1], lo[2], 0.0f);
         leaf_boxes[2 * leaf + 1] = make_float4(hi[0], hi[1], hi[2], 0.0f);
     }
-}
-
-__global__ __launch_bounds__(256) void knn_level_kernel(uint32_t n_parents, uint32_t n_children, const float4* __restrict__ children,
-                                                        float4* __restrict__ parents) {
-    const uint32_t p = blockIdx.x * 256u + threadIdx.x;
-    if (p >= n_parents) return;
-    float4 lo = make_float4(INFINITY, INFINITY, INFINITY, 0.0f), hi = make_float4(-INFINITY, -INFINITY, -INFINITY, 0.0f);
-    const uint32_t end = min(n_children, (p + 1) * kFan);
-    for (uint32_t c = p * kFan; c < end; ++c) {
-        const float4 a = children[2 * c], b = children[2 * c + 1];
-        lo.x = fminf(lo.x, a.x); lo.y = fminf(lo.y, a.y); lo.z = fminf(lo.z, a.z);
-        hi.x = fmaxf(hi.x, b.x); hi.y = fmaxf(hi.y, b.y); hi.z = fmaxf(hi.z, b.z);
-    }
-    parents[2 * p] = lo;
-    parents[2 * p + 1] = hi;
 }
 
 struct Query {
@@ -426,20 +335,12 @@ __global__ __launch_bounds__(256) void knn_points_search_kernel(uint32_t n1, con
     }
 }
 
-constexpr size_t kAlign = 256;
-size_t align_up(size_t v) { return (v + kAlign - 1) & ~(kAlign - 1); }
-
 KnnLayout knn3_layout(uint32_t n) {
     KnnLayout L = {};
     if (n == 0) return L;
-    uint32_t count = (n + kLeaf - 1) / kLeaf, boxes = 0;
-    for (int level = 0;; ++level) {
-        L.tree.count[level] = count;
-        L.tree.offset[level] = boxes;
-        boxes += count;
-        if (count <= (uint32_t)kFan || level + 1 == kKnnMaxLevels) { L.tree.top = level; break; }
-        count = (count + kFan - 1) / kFan;
-    }
+    const TreeShape shape = tree_shape(n);
+    L.tree.top = shape.top;
+    for (int level = 0; level <= shape.top; ++level) tree_level(shape.leaves, level, L.tree.count[level], L.tree.offset[level]);
     size_t at = 0;
     auto take = [&](size_t bytes) { const size_t here = at; at = align_up(at + bytes); return here; };
     L.keys = take(4 * (size_t)n);
@@ -449,7 +350,7 @@ KnnLayout knn3_layout(uint32_t n) {
     L.key_hi = take(4 * (size_t)n);
     L.radix = take(radix_scratch_words(n) * sizeof(uint32_t));
     L.packed = take(16 * (size_t)n);
-    L.boxes = take(32 * (size_t)boxes);
+    L.boxes = take(32 * (size_t)shape.boxes);
     L.partials = take(32 * (size_t)kBoundsBlocks);
     L.bytes = at;
     return L;
@@ -472,14 +373,10 @@ hipError_t knn_sort_and_pack(uint32_t n, const float* points, const float4* part
     hipLaunchKernelGGL(knn_codes_kernel, dim3(min(blocks, 2048u)), dim3(256), 0, stream, n, points, partials, r.keys, r.key_hi);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    // the 63-bit codes, least significant word first (both sorts are stable)
-    uint32_t *ks = nullptr, *vs = nullptr;
-    e = radix_sort_pairs(r.radix, n, 32, r.keys, r.keys_alt, r.vals, r.vals_alt, true, false, &ks, &vs, stream);
+    uint32_t* order = nullptr;
+    e = morton_sort(r.radix, n, r.keys, r.keys_alt, r.vals, r.vals_alt, r.key_hi, &order, stream);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(knn_gather_kernel, dim3(blocks), dim3(256), 0, stream, n, (const uint32_t*)vs, (const uint32_t*)r.key_hi, r.keys);
-    e = radix_sort_pairs(r.radix, n, 32, r.keys, r.keys_alt, vs, vs == r.vals ? r.vals_alt : r.vals, false, false, &ks, &vs, stream);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(knn_pack_kernel, dim3(blocks), dim3(256), 0, stream, n, points, (const uint32_t*)vs, r.packed, r.boxes);
+    hipLaunchKernelGGL(knn_pack_kernel, dim3(blocks), dim3(256), 0, stream, n, points, (const uint32_t*)order, r.packed, r.boxes);
     return hipGetLastError();
 }
 
@@ -489,11 +386,7 @@ hipError_t knn_build_tree(uint32_t n, const float* points, const KnnLayout& L, c
     hipLaunchKernelGGL(knn_bounds_kernel, dim3(kBoundsBlocks), dim3(256), 0, stream, n, points, r.partials);
     hipError_t e = knn_sort_and_pack(n, points, r.partials, r, stream);
     if (e != hipSuccess) return e;
-    for (int level = 1; level <= L.tree.top; ++level)
-        hipLaunchKernelGGL(knn_level_kernel, dim3((L.tree.count[level] + 255u) / 256u), dim3(256), 0, stream, L.tree.count[level],
-                           L.tree.count[level - 1], (const float4*)(r.boxes + 2 * (size_t)L.tree.offset[level - 1]),
-                           r.boxes + 2 * (size_t)L.tree.offset[level]);
-    return hipGetLastError();
+    return tree_levels(r.boxes, L.tree.count[0], L.tree.top, stream);
 }
 
 template <int S>

@@ -3,45 +3,37 @@
 // What Open3D's RaycastingScene.compute_closest_points answers for the melting frames of the frame loop (scene_representation.py:
 // 385-412) and for object extraction (extract/extract_object.py:105-110): primitive id, squared distance, closest point.  The result
 // is a pointwise function of the input: the valid face with the smallest (d(q, f), f), so any exact search gives the
-// same bits.  This one is the tree and walk of gsr_knn.hip over triangles, all stream-ordered, no host read, no float atomics:
+// same bits.  This one is the tree of gsr_knn.hip over triangles (gsr_tree.h), all stream-ordered, no host read, no float atomics:
 //
 //   plan    : bounds over the valid faces' centroids (per-workgroup partials); 63-bit Morton codes of the centroids, an invalid face
 //             (an index outside [0, V), a non-finite coordinate) gets 2^63 and sorts last; the library's radix sort, low word then
-//             high word, stable; one 48-byte record per face in sorted order (three float4 a, b, c, the face index in a.w; an invalid
-//             face: NaNs and index ~0); leaf boxes = the union of the 64 triangles' own boxes (valid members only); levels of 16;
-//             the header last, so that a plan is valid only once its build has run.
-//   query   : one wave per 64 queries, one lane per query, one slot (d, face) per lane: walk_tree below.
+//             high word, stable (morton_sort); one 48-byte record per face in sorted order (three float4 a, b, c, the face index in
+//             a.w; an invalid face: NaNs and index ~0); leaf boxes = the union of the 64 triangles' own boxes (valid members only);
+//             levels of 16 (tree_levels); the header last, so that a plan is valid only once its build has run.
+//   query   : one wave per 64 queries, one lane per query, one slot (d, face) per lane: walk_tree below, with a PointProbe.
 // The plan is self-describing: its header holds F and the plan's size, and the query kernel derives every count and offset from that F
 // (tri_layout, the function the host sized the plan with) and compares the total with the plan_bytes it was handed BEFORE anything
 // indexes the plan.  A header that does not match answers every query (-1, +inf, 0 0 0): the host cannot see the header without a
 // device-to-host read, which a query never does.
 // The same plan answers the first triangle a ray hits (gsr_ray_first_hit, DESIGN.md 7m: what trimesh's mesh.ray answers for object
-// extraction and removal, extract/extract_object.py:115-159, :424-434, :476-482, :563-606): ray_walk further down.
+// extraction and removal, extract/extract_object.py:115-159, :424-434, :476-482, :563-606): the same walk with a RayProbe, one slot
+// (t, face, barycentrics) per lane.  The walk is written once, over a per-lane probe that supplies what the two queries differ in: the
+// box test, the order of a node's children, the scan of a leaf.
 // Defines the entry points gsr_closest_tri_plan_bytes, gsr_closest_tri_plan_scratch_bytes, gsr_closest_tri_plan, gsr_closest_tri_query,
 // gsr_ray_first_hit.
-#include "gsr_internal.h"
+#include "gsr_tree.h"
 
 #include <cfloat>
 
 namespace gsr {
 namespace {
 
-// The tree, the Morton codes and the walk follow gsr_knn.hip (same constants, same prune rule); the record is 48 bytes, not 16, and a
-// lane holds one slot, so the walk is a second copy here rather than a template over both.
-constexpr int kTriMaxLevels = 6;
-constexpr int kLeaf = 64;            // triangles per leaf: one wave
-constexpr int kFan = 16;             // children per box above the leaves
-constexpr int kStackDepth = 96;      // >= kFan + (kFan - 1) * (kTriMaxLevels - 1)
-constexpr int kBoundsBlocks = 128;   // partial bounds
-constexpr uint32_t kCellMax = (1u << 21) - 1u;
 constexpr uint32_t kInvalidKey = 1u << 31;       // the high word of an invalid face's code
 constexpr uint32_t kNoFace = ~0u;                // the index of an invalid face's record, and of an empty slot
 constexpr uint32_t kPlanMagic = 0x51495254u;     // "TRIQ"
 constexpr int64_t kMaxFaces = (int64_t)1 << 30;  // refused from here on (the radix sort's limit)
 constexpr int64_t kMaxVerts = (int64_t)1 << 31;
 constexpr int64_t kMaxQueries = (int64_t)1 << 31;
-constexpr size_t kAlign = 256;
-static_assert(kStackDepth >= kFan + (kFan - 1) * (kTriMaxLevels - 1), "stack too shallow for the tree");
 
 // The first 256 bytes of a plan.
 struct TriHeader {
@@ -49,41 +41,21 @@ struct TriHeader {
     unsigned long long plan_bytes;
 };
 
-// Boxes over the Morton-sorted faces: level 0 = leaves of 64, every level above = 16 boxes of the one below, up to the first level of
-// at most 16 boxes (`top`).  A box is two float4 (lo, hi) at boxes[2 * (offset of its level + i)].  The counts and offsets of the
-// levels are not kept in a table: tri_level derives them from the number of leaves (a few scalar operations; a table indexed by a
-// run-time level would live in the kernel's scratch memory).
+// The tree of gsr_tree.h over the Morton-sorted faces, and where it lies in a plan over F < 2^30 faces: pure arithmetic, the same on
+// the host that sizes a plan and in the kernel that reads one.
 struct TriTree {
     uint32_t leaves;
     int top;
     size_t records, boxes, bytes;   // byte offsets in the plan; bytes = the whole
 };
-
-__host__ __device__ inline size_t align_up(size_t v) { return (v + kAlign - 1) & ~(kAlign - 1); }
-
-// boxes of `level` and boxes below it
-__host__ __device__ inline void tri_level(uint32_t leaves, int level, uint32_t& count, uint32_t& offset) {
-    count = leaves;
-    offset = 0;
-    for (int l = 0; l < level; ++l) {
-        offset += count;
-        count = (count + kFan - 1) / kFan;
-    }
-}
-
-// The layout of a plan over F < 2^30 faces: pure arithmetic, the same on the host that sizes a plan and in the kernel that reads one.
 __host__ __device__ inline TriTree tri_layout(uint32_t F) {
+    const TreeShape shape = tree_shape(F);
     TriTree t = {};
-    t.leaves = (F + kLeaf - 1) / kLeaf;
-    uint32_t count = t.leaves, boxes = count;
-    while (count > (uint32_t)kFan && t.top + 1 < kTriMaxLevels) {
-        count = (count + kFan - 1) / kFan;
-        boxes += count;
-        ++t.top;
-    }
+    t.leaves = shape.leaves;
+    t.top = shape.top;
     t.records = kAlign;
     t.boxes = align_up(t.records + 48 * (size_t)F);
-    t.bytes = align_up(t.boxes + 32 * (size_t)boxes);
+    t.bytes = align_up(t.boxes + 32 * (size_t)shape.boxes);
     return t;
 }
 
@@ -107,27 +79,6 @@ TriScratch tri_scratch(uint32_t F) {
     return L;
 }
 
-__device__ __forceinline__ void wave_sync() {   // a wave's LDS operations run in program order: keep the compiler to it
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-__device__ __forceinline__ float wave_min(float v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = fminf(v, __shfl_xor(v, d, 64));
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d, 64));
-    return v;
-}
-__device__ __forceinline__ float lane_value(float v, int lane) {   // lane: wave-uniform
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
-}
-__device__ __forceinline__ bool finite3(float x, float y, float z) {
-    return __builtin_isfinite(x) && __builtin_isfinite(y) && __builtin_isfinite(z);
-}
-
 struct Vec3 {
     float x, y, z;
 };
@@ -137,14 +88,6 @@ __device__ __forceinline__ Vec3 neg(const Vec3& u) { return {-u.x, -u.y, -u.z}; 
 __device__ __forceinline__ Vec3 along(const Vec3& u, float s, const Vec3& v) { return {u.x + s * v.x, u.y + s * v.y, u.z + s * v.z}; }
 __device__ __forceinline__ float dot(const Vec3& u, const Vec3& v) { return (u.x * v.x + u.y * v.y) + u.z * v.z; }
 __device__ __forceinline__ float guarded(float num, float den) { return den != 0.0f ? num / den : 0.0f; }
-
-// gsr_knn.hip's box_bound: the rounded operations of a squared distance on the gap to a box.  An empty box gives +inf.
-__device__ __forceinline__ float box_bound(const float4& lo, const float4& hi, float qx, float qy, float qz) {
-    const float gx = fmaxf(fmaxf(lo.x - qx, qx - hi.x), 0.0f);
-    const float gy = fmaxf(fmaxf(lo.y - qy, qy - hi.y), 0.0f);
-    const float gz = fmaxf(fmaxf(lo.z - qz, qz - hi.z), 0.0f);
-    return (gx * gx + gy * gy) + gz * gz;
-}
 
 // The three corners of face f; false for an invalid face (whose corners are then not read).
 __device__ __forceinline__ bool load_face(int64_t V, const float* __restrict__ verts, const long long* __restrict__ faces, uint32_t f,
@@ -159,35 +102,6 @@ __device__ __forceinline__ bool load_face(int64_t V, const float* __restrict__ v
 // (it only steers the sort: an overflow to inf lands in cell 0 or the last one)
 __device__ __forceinline__ Vec3 centroid(const Vec3& a, const Vec3& b, const Vec3& c) {
     return {((a.x + b.x) + c.x) / 3.0f, ((a.y + b.y) + c.y) / 3.0f, ((a.z + b.z) + c.z) / 3.0f};
-}
-
-__device__ __forceinline__ uint64_t spread21(uint32_t v) {   // bit k of v (k < 21) -> bit 3k
-    uint64_t x = v & 0x1FFFFFu;
-    x = (x | (x << 32)) & 0x001F00000000FFFFull;
-    x = (x | (x << 16)) & 0x001F0000FF0000FFull;
-    x = (x | (x << 8)) & 0x100F00F00F00F00Full;
-    x = (x | (x << 4)) & 0x10C30C30C30C30C3ull;
-    x = (x | (x << 2)) & 0x1249249249249249ull;
-    return x;
-}
-__device__ __forceinline__ uint32_t grid_cell(float x, float lo, float hi) {
-    const float extent = hi - lo;
-    const float t = extent > 0.0f ? (x - lo) / extent * (float)kCellMax : 0.0f;
-    return t >= 0.0f ? (uint32_t)fminf(t, (float)kCellMax) : 0u;   // (NaN -> 0: the code only steers the search, never its result)
-}
-
-// lo / hi of six floats reduced over the workgroup (256 lanes), result in every lane
-__device__ void block_minmax(float lo[3], float hi[3], float* s_red /* 6 * 4 floats */) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int a = 0; a < 3; ++a) { lo[a] = wave_min(lo[a]); hi[a] = wave_max(hi[a]); }
-    if (lane == 0)
-        for (int a = 0; a < 3; ++a) { s_red[a * 4 + wave] = lo[a]; s_red[(3 + a) * 4 + wave] = hi[a]; }
-    __syncthreads();
-    for (int a = 0; a < 3; ++a) {
-        lo[a] = fminf(fminf(s_red[a * 4], s_red[a * 4 + 1]), fminf(s_red[a * 4 + 2], s_red[a * 4 + 3]));
-        hi[a] = fmaxf(fmaxf(s_red[(3 + a) * 4], s_red[(3 + a) * 4 + 1]), fmaxf(s_red[(3 + a) * 4 + 2], s_red[(3 + a) * 4 + 3]));
-    }
-    __syncthreads();
 }
 
 __global__ __launch_bounds__(256) void tri_bounds_kernel(int64_t V, const float* __restrict__ verts, uint32_t F,
@@ -232,13 +146,6 @@ __global__ __launch_bounds__(256) void tri_codes_kernel(int64_t V, const float* 
     }
 }
 
-// the high words in the order of the first sort (by the low words), for the second
-__global__ __launch_bounds__(256) void tri_gather_kernel(uint32_t n, const uint32_t* __restrict__ order, const uint32_t* __restrict__ key_hi,
-                                                         uint32_t* __restrict__ out) {
-    const uint32_t s = blockIdx.x * 256u + threadIdx.x;
-    if (s < n) out[s] = key_hi[order[s]];
-}
-
 // one wave per leaf: the sorted faces' records, the leaf's box (the union of its valid triangles' own boxes)
 __global__ __launch_bounds__(256) void tri_pack_kernel(int64_t V, const float* __restrict__ verts, uint32_t F,
                                                        const long long* __restrict__ faces, const uint32_t* __restrict__ order,
@@ -267,21 +174,6 @@ __global__ __launch_bounds__(256) void tri_pack_kernel(int64_t V, const float* _
         leaf_boxes[2 * (size_t)leaf] = make_float4(lo[0], lo[1], lo[2], 0.0f);
         leaf_boxes[2 * (size_t)leaf + 1] = make_float4(hi[0], hi[1], hi[2], 0.0f);
     }
-}
-
-__global__ __launch_bounds__(256) void tri_level_kernel(uint32_t n_parents, uint32_t n_children, const float4* __restrict__ children,
-                                                        float4* __restrict__ parents) {
-    const uint32_t p = blockIdx.x * 256u + threadIdx.x;
-    if (p >= n_parents) return;
-    float4 lo = make_float4(INFINITY, INFINITY, INFINITY, 0.0f), hi = make_float4(-INFINITY, -INFINITY, -INFINITY, 0.0f);
-    const uint32_t end = min(n_children, (p + 1) * kFan);
-    for (uint32_t c = p * kFan; c < end; ++c) {
-        const float4 a = children[2 * (size_t)c], b = children[2 * (size_t)c + 1];
-        lo.x = fminf(lo.x, a.x); lo.y = fminf(lo.y, a.y); lo.z = fminf(lo.z, a.z);
-        hi.x = fmaxf(hi.x, b.x); hi.y = fmaxf(hi.y, b.y); hi.z = fmaxf(hi.z, b.z);
-    }
-    parents[2 * (size_t)p] = lo;
-    parents[2 * (size_t)p + 1] = hi;
 }
 
 // the last kernel of a build
@@ -366,124 +258,9 @@ __device__ __forceinline__ void slot_scan(const float4* leaf, int cnt, const Que
     }
 }
 
-// Children [first, first + cnt) of `level` kept by some lane, pushed farthest first so the nearest is popped next (gsr_knn.hip's
-// push_children without the own leaf).
-__device__ __forceinline__ void push_children(const float4* boxes /* of `level` */, int level, uint32_t first, int cnt, const Query& q,
-                                              float best, const float4& wlo, const float4& whi, uint32_t* stack, int& top, int lane) {
-    float4 clo = make_float4(INFINITY, INFINITY, INFINITY, 0.0f), chi = make_float4(-INFINITY, -INFINITY, -INFINITY, 0.0f);
-    if (lane < cnt) { clo = boxes[2 * (size_t)(first + lane)]; chi = boxes[2 * (size_t)(first + lane) + 1]; }
-    uint32_t keep = 0u;
-    for (int j = 0; j < cnt; ++j) {
-        const float4 lo = make_float4(lane_value(clo.x, j), lane_value(clo.y, j), lane_value(clo.z, j), 0.0f);
-        const float4 hi = make_float4(lane_value(chi.x, j), lane_value(chi.y, j), lane_value(chi.z, j), 0.0f);
-        const float lb = box_bound(lo, hi, q.x, q.y, q.z);
-        if (__ballot(q.active && !(lb > best)) != 0ull) keep |= 1u << j;
-    }
-    if (keep == 0u) return;
-    // order key: the gap between the child's box and the wave's queries' box
-    const float gx = fmaxf(fmaxf(clo.x - whi.x, wlo.x - chi.x), 0.0f);
-    const float gy = fmaxf(fmaxf(clo.y - whi.y, wlo.y - chi.y), 0.0f);
-    const float gz = fmaxf(fmaxf(clo.z - whi.z, wlo.z - chi.z), 0.0f);
-    const float key =(gx * gx + gy * gy) + gz * gz;   // never NaN: fmaxf drops one, and the terms are not negative
-    int rank = 0;   // kept children farther than this one (ties: the higher index counts as farther): a permutation of the kept
-    for (int j = 0; j < cnt; ++j) {
-        const float kj = lane_value(key, j);
-        rank += ((keep >> j) & 1u) && (kj > key || (kj == key && j > lane)) ? 1 : 0;
-    }
-    if (lane < cnt && ((keep >> lane) & 1u)) (stack + top)[rank] = ((uint32_t)level << 29) | (first + lane);
-    top += __popc(keep);
-    wave_sync();
-}
-
-// The walk of gsr_knn.hip over triangles: depth first from the top on the wave-uniform `stack` in LDS.  A node's children are kept if
-// some lane's lower bound is not above that lane's slot (a ballot per child) and pushed nearest first; a popped leaf is tested again,
-// the slots having tightened since the push, then staged into `leaf` with coalesced loads (3 KiB) between two wave_sync() and scanned
-// by all lanes at once.
-// Exactness.  d(q, f) = fmin(fmax(d_tri, d_box), d_vtx) never lies below d_box, the box_bound of the triangle's own box.  box_bound is
-// formed with the rounded operations of a squared distance (per axis the gap lo - q or q - hi, squared, summed in one order), and
-// rounding to nearest is monotone: a box that contains the triangle's box has gaps that are not larger on any axis, so its bound never
-// exceeds d_box, hence never d(q, f) -- however badly conditioned d_tri is for a sliver or a distant triangle.  (The same monotonicity
-// gives d_box <= d_vtx, a corner lying inside the triangle's box, so d really is clamped into [d_box, d_vtx].)  The prune rule, here,
-// in push_children and in slot_scan, is !(lb > best): a box is skipped only when its bound is strictly above the slot of every lane,
-// so that no member could enter one.  At equality a member with a lower face index still could: pruning on >= would return the right
-// distances and, above a shared vertex or on a duplicated face, the wrong index.  The slots start at (+inf, no face): a finite query
-// with a valid face always has an answer, at +inf if its distances overflow.
-__device__ __forceinline__ void walk_tree(const float4* boxes, const TriTree& tree, uint32_t F, const float4* records, const Query& q,
-                                          float4* leaf, uint32_t* stack, int lane, Slot& slot) {
-    if (__ballot(q.active) == 0ull) return;
-    const float4 wlo = make_float4(wave_min(q.active ? q.x : INFINITY), wave_min(q.active ? q.y : INFINITY),
-                                   wave_min(q.active ? q.z : INFINITY), 0.0f);
-    const float4 whi = make_float4(wave_max(q.active ? q.x : -INFINITY), wave_max(q.active ? q.y : -INFINITY),
-                                   wave_max(q.active ? q.z : -INFINITY), 0.0f);
-    int top = 0;
-    uint32_t count, offset;
-    tri_level(tree.leaves, tree.top, count, offset);
-    push_children(boxes + 2 * (size_t)offset, tree.top, 0u, (int)min(count, (uint32_t)kFan), q, slot.d, wlo, whi, stack, top, lane);
-    while (top > 0) {
-        const uint32_t e = (uint32_t)__builtin_amdgcn_readfirstlane((int)stack[--top]);
-        const int level = (int)(e >> 29);
-        const uint32_t node = e & ((1u << 29) - 1u);
-        if (level > 0) {
-            const uint32_t first = node * kFan;
-            tri_level(tree.leaves, level - 1, count, offset);
-            push_children(boxes + 2 * (size_t)offset, level - 1, first, (int)min((uint32_t)kFan, count - first), q, slot.d, wlo, whi, stack,
-                          top, lane);
-            continue;
-        }
-        const float4 lo = boxes[2 * (size_t)node], hi = boxes[2 * (size_t)node + 1];   // (leaves: level offset 0)
-        const float lb = box_bound(lo, hi, q.x, q.y, q.z);
-        if (__ballot(q.active && !(lb > slot.d)) == 0ull) continue;
-        const uint32_t base = node * kLeaf;
-        const int cnt = (int)min((uint32_t)kLeaf, F - base);
-        wave_sync();
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const int at = k * kLeaf + lane;
-            if (at < 3 * cnt) leaf[at] = records[3 * (size_t)base + at];
-        }
-        wave_sync();
-        slot_scan(leaf, cnt, q, slot);
-    }
-}
-
-__global__ __launch_bounds__(256) void tri_query_kernel(uint32_t n, const float* __restrict__ points, const unsigned char* __restrict__ plan,
-                                                        unsigned long long plan_bytes, long long* __restrict__ face_idx,
-                                                        float* __restrict__ sq_dist, float* __restrict__ closest) {
-    __shared__ float4 s_leaf[4][3 * kLeaf];
-    __shared__ uint32_t s_stack[4][kStackDepth];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t group = blockIdx.x * 4u + (uint32_t)wave;    // this wave's 64 queries
-    if ((unsigned long long)group * kLeaf >= n) return;
-    const uint32_t s = group * kLeaf + lane;
-    Query q = {0.0f, 0.0f, 0.0f, false};
-    if (s < n) {
-        const float x = points[3 * (size_t)s], y = points[3 * (size_t)s + 1], z = points[3 * (size_t)s + 2];
-        if (finite3(x, y, z)) q = {x, y, z, true};
-    }
-    // the header against the size the caller holds, before anything else of the plan is read (plan_bytes >= 256: checked by the host)
-    const TriHeader h = *reinterpret_cast<const TriHeader*>(plan);
-    Slot slot = {INFINITY, kNoFace, {0.0f, 0.0f, 0.0f}};
-    if (h.magic == kPlanMagic && h.plan_bytes == plan_bytes && h.F > 0u && h.F < (uint32_t)kMaxFaces) {
-        const TriTree tree = tri_layout(h.F);
-        if (tree.bytes == plan_bytes)
-            walk_tree(reinterpret_cast<const float4*>(plan + tree.boxes), tree, h.F, reinterpret_cast<const float4*>(plan + tree.records), q,
-                      s_leaf[wave], s_stack[wave], lane, slot);
-    }
-    if (s >= n) return;
-    const bool found = q.active && slot.face != kNoFace;
-    face_idx[s] = found ? (long long)slot.face : -1ll;
-    sq_dist[s] = found ? slot.d : INFINITY;
-    if (closest) {
-        closest[3 * (size_t)s] = found ? q.x + slot.p.x : 0.0f;
-        closest[3 * (size_t)s + 1] = found ? q.y + slot.p.y : 0.0f;
-        closest[3 * (size_t)s + 2] = found ? q.z + slot.p.z : 0.0f;
-    }
-}
-
 // ---- the first triangle a ray hits (gsr_ray_first_hit; meshquery.first_hits_host restates it in numpy) ----------------
-// The second query on the same plan: one wave per 64 rays, one lane per ray, one slot (t, face, barycentrics) per lane.  The answer is
-// the valid face with the smallest (t(ray, f), f) among the faces the ray hits, a pointwise function of the input like the closest
-// triangle: ray_walk below is walk_tree with a slab interval in the place of box_bound.
+// The second query on the same plan.  The answer is the valid face with the smallest (t(ray, f), f) among the faces the ray hits, a
+// pointwise function of the input like the closest triangle.
 
 constexpr float kSlabPad = 1.00000024f;   // 1 + 2 ulp on the far end of a slab interval (Ize, "Robust BVH Ray Traversal")
 
@@ -597,102 +374,218 @@ __device__ __forceinline__ void hit_scan(const float4* leaf, int cnt, const Ray&
     }
 }
 
-// push_children for rays: a child is kept if some lane's ray hits its box no later than that lane's slot; the kept are pushed farthest
-// first by the wave minimum of the keeping lanes' t_enter, so the box the wave's rays enter first is popped next.
-__device__ __forceinline__ void push_hit_children(const float4* boxes /* of `level` */, int level, uint32_t first, int cnt, const Ray& r,
-                                                  float best, uint32_t* stack, int& top, int lane) {
+// ---- the walk, written once over a per-lane probe ---------------------------------------------------------------------------------
+// A probe is a lane's question and its slot, plain scalars in a struct that lives in the kernel's registers.  It supplies:
+//   active()              whether the lane asks anything;
+//   begin()               what the wave works out once, before the walk (every lane calls it);
+//   reaches(lo, hi, at)   whether the box can still hold a member that enters the lane's slot, and the value that decides it;
+//   lanes_key / box_key   a kept child's order key, from one of two places -- the lanes that keep it (asked per child, wave-uniform) or
+//                         the child's own box (asked once per child lane); the hook a probe does not use passes through;
+//   scan(leaf, cnt)       `cnt` records of a leaf in LDS against the slot.
+// The two order keys are measured choices and stay different.
+
+// The closest triangle: box_bound against the slot's distance; children keyed by the gap between their box and the box of the wave's
+// queries (wlo, whi).
+struct PointProbe {
+    Query q;
+    Slot slot;
+    float4 wlo, whi;
+
+    __device__ __forceinline__ bool active() const { return q.active; }
+    __device__ __forceinline__ void begin() {
+        wlo = make_float4(wave_min(q.active ? q.x : INFINITY), wave_min(q.active ? q.y : INFINITY), wave_min(q.active ? q.z : INFINITY),
+                          0.0f);
+        whi = make_float4(wave_max(q.active ? q.x : -INFINITY), wave_max(q.active ? q.y : -INFINITY),
+                          wave_max(q.active ? q.z : -INFINITY), 0.0f);
+    }
+    __device__ __forceinline__ bool reaches(const float4& lo, const float4& hi, float& at) const {
+        at = box_bound(lo, hi, q.x, q.y, q.z);
+        return q.active && !(at > slot.d);
+    }
+    __device__ __forceinline__ float lanes_key(bool, float) const { return INFINITY; }
+    __device__ __forceinline__ float box_key(const float4& clo, const float4& chi, float) const {
+        const float gx = fmaxf(fmaxf(clo.x - whi.x, wlo.x - chi.x), 0.0f);
+        const float gy = fmaxf(fmaxf(clo.y - whi.y, wlo.y - chi.y), 0.0f);
+        const float gz = fmaxf(fmaxf(clo.z - whi.z, wlo.z - chi.z), 0.0f);
+        return (gx * gx + gy * gy) + gz * gz;   // never NaN: fmaxf drops one, and the terms are not negative
+    }
+    __device__ __forceinline__ void scan(const float4* leaf, int cnt) { slot_scan(leaf, cnt, q, slot); }
+};
+
+// The first hit: the slab interval against the slot's t; children keyed by the wave minimum of the keeping lanes' t_enter, so the
+// box the wave's rays enter first is popped next.
+struct RayProbe {
+    Ray r;
+    HitSlot slot;
+
+    __device__ __forceinline__ bool active() const { return r.active; }
+    __device__ __forceinline__ void begin() {}
+    __device__ __forceinline__ bool reaches(const float4& lo, const float4& hi, float& at) const {
+        float t_exit;
+        slab(lo, hi, r, at, t_exit);
+        return r.active && at <= t_exit && !(at > slot.t);
+    }
+    __device__ __forceinline__ float lanes_key(bool mine, float at) const { return wave_min(mine ? at : INFINITY); }
+    __device__ __forceinline__ float box_key(const float4&, const float4&, float key) const { return key; }
+    __device__ __forceinline__ void scan(const float4* leaf, int cnt) { hit_scan(leaf, cnt, r, slot); }
+};
+
+// What a wave of a query kernel walks with: its lane, its query number and its share of the LDS.
+struct Wave {
+    int lane;
+    uint32_t s;        // this lane's query
+    float4* leaf;      // 3 * kLeaf: a staged leaf
+    uint32_t* stack;   // kStackDepth
+};
+// The prologue of both query kernels (256 lanes, four waves of 64 queries each).  False: a wave past the n queries, which returns.
+__device__ __forceinline__ bool open_wave(uint32_t n, Wave& w) {
+    __shared__ float4 s_leaf[4][3 * kLeaf];
+    __shared__ uint32_t s_stack[4][kStackDepth];
+    const int wave = threadIdx.x >> 6;
+    const uint32_t group = blockIdx.x * 4u + (uint32_t)wave;    // this wave's 64 queries
+    if ((unsigned long long)group * kLeaf >= n) return false;
+    w.lane = threadIdx.x & 63;
+    w.s = group * kLeaf + w.lane;
+    w.leaf = s_leaf[wave];
+    w.stack = s_stack[wave];
+    return true;
+}
+
+// Children [first, first + cnt) of `level` kept by some lane, pushed farthest first by their order key so the nearest is popped next
+// (gsr_knn.hip's push_children without the own leaf).
+template <class Probe>
+__device__ __forceinline__ void push_children(const Wave& w, const float4* boxes /* of `level` */, int level, uint32_t first, int cnt,
+                                              const Probe& probe, int& top) {
+    const int lane = w.lane;
     float4 clo = make_float4(INFINITY, INFINITY, INFINITY, 0.0f), chi = make_float4(-INFINITY, -INFINITY, -INFINITY, 0.0f);
     if (lane < cnt) { clo = boxes[2 * (size_t)(first + lane)]; chi = boxes[2 * (size_t)(first + lane) + 1]; }
     uint32_t keep = 0u;
-    float key = INFINITY;   // of child `lane`
+    float lanes = INFINITY;   // child `lane`'s key from the lanes that keep it
     for (int j = 0; j < cnt; ++j) {
         const float4 lo = make_float4(lane_value(clo.x, j), lane_value(clo.y, j), lane_value(clo.z, j), 0.0f);
         const float4 hi = make_float4(lane_value(chi.x, j), lane_value(chi.y, j), lane_value(chi.z, j), 0.0f);
-        float t_enter, t_exit;
-        slab(lo, hi, r, t_enter, t_exit);
-        const bool mine = r.active && t_enter <= t_exit && !(t_enter > best);
+        float at;
+        const bool mine = probe.reaches(lo, hi, at);
         if (__ballot(mine) == 0ull) continue;
         keep |= 1u << j;
-        const float first_in = wave_min(mine ? t_enter : INFINITY);
-        if (lane == j) key = first_in;
+        const float kj = probe.lanes_key(mine, at);
+        if (lane == j) lanes = kj;
     }
     if (keep == 0u) return;
+    const float key = probe.box_key(clo, chi, lanes);
     int rank = 0;   // kept children farther than this one (ties: the higher index counts as farther): a permutation of the kept
     for (int j = 0; j < cnt; ++j) {
         const float kj = lane_value(key, j);
         rank += ((keep >> j) & 1u) && (kj > key || (kj == key && j > lane)) ? 1 : 0;
     }
-    if (lane < cnt && ((keep >> lane) & 1u)) (stack + top)[rank] = ((uint32_t)level << 29) | (first + lane);
+    if (lane < cnt && ((keep >> lane) & 1u)) (w.stack + top)[rank] = ((uint32_t)level << 29) | (first + lane);
     top += __popc(keep);
     wave_sync();
 }
 
-// walk_tree for rays.  Exactness.  A face is hit only if its own box is (t_enter <= t_exit), and then t(ray, f) is clamped into
-// [t_enter, t_exit] of that box.  Both ends are formed by a subtraction from a fixed o_k and a multiplication by a fixed 1 / d_k (then
-// by a fixed pad), all monotone under rounding to nearest, and max / min are monotone too: a box that contains the triangle's box has
-// a t_enter that is not larger and a t_exit that is not smaller (on an axis with d_k == 0 it contains o_k whenever the triangle's box
-// does).  So a box is skipped, here, in push_hit_children and in hit_scan, only when the lane's ray misses it or enters it strictly
-// after the lane's slot: no member could then enter the slot, an equal t with a lower face index included.  The slots start at
-// (+inf, no face) and a t of +inf is a miss, so +inf is the answer of exactly the rays that hit nothing.
-__device__ __forceinline__ void ray_walk(const float4* boxes, const TriTree& tree, uint32_t F, const float4* records, const Ray& r,
-                                         float4* leaf, uint32_t* stack, int lane, HitSlot& slot) {
-    if (__ballot(r.active) == 0ull) return;
+// The walk of gsr_knn.hip over triangles: depth first from the top on the wave-uniform stack in LDS.  A node's children are kept if
+// some lane's probe reaches them (a ballot per child) and pushed nearest first; a popped leaf is tested again, the slots having
+// tightened since the push, then staged into w.leaf with coalesced loads (3 KiB) between two wave_sync() and scanned by all lanes at
+// once.
+// Exactness.  A box is skipped -- here, in push_children and, for a record's own box, in slot_scan and hit_scan -- only when no member
+// could enter any lane's slot, an equal value with a lower face index included: the rule is !(bound > slot), never >=, which would
+// return the right values and, above a shared vertex or on a duplicated face, the wrong index.  That needs a member's value to be
+// never below the bound of a box that contains the member's own box, however badly conditioned the member's test is.  Both contracts
+// clamp the value into the bounds of the member's own box, and both bounds are monotone under rounding to nearest:
+//   point  d(q, f) = fmin(fmax(d_tri, d_box), d_vtx) >= d_box = box_bound of the triangle's box: per axis the gap lo - q or q - hi,
+//          squared, summed in one order.  A containing box has gaps that are not larger on any axis, so its bound never exceeds d_box.
+//          (The same gives d_box <= d_vtx, a corner lying inside the triangle's box: d really is clamped into [d_box, d_vtx].)
+//   ray    a face is hit only if its own box is (t_enter <= t_exit), and then t is clamped into [t_enter, t_exit] of that box: a
+//          subtraction from a fixed o_k, a multiplication by a fixed 1 / d_k (then by a fixed pad), max and min.  A containing box
+//          has a t_enter that is not larger and a t_exit that is not smaller (on an axis with d_k == 0 it contains o_k whenever the
+//          triangle's box does), so it is hit too, no later.
+// The slots start at (+inf, no face).  A finite query with a valid face always has an answer, at +inf if its distances overflow; a t
+// of +inf is a miss, so +inf is the answer of exactly the rays that hit nothing.
+template <class Probe>
+__device__ __forceinline__ void walk_tree(const Wave& w, const unsigned char* __restrict__ plan, unsigned long long plan_bytes,
+                                          Probe& probe) {
+    // No plan, nothing walked: the header does not describe a plan of the plan_bytes the caller holds.  It is compared before anything
+    // else of the plan is read (plan_bytes >= 256: checked by the host).  Here, not in open_wave: with the kernel's loads between the
+    // check and the walk the compiler carries the tree as run-time values behind a flag (tri_query_kernel: 57 VGPRs for 56).
+    const TriHeader h = *reinterpret_cast<const TriHeader*>(plan);
+    if (h.magic != kPlanMagic || h.plan_bytes != plan_bytes || h.F == 0u || h.F >= (uint32_t)kMaxFaces) return;
+    const TriTree tree = tri_layout(h.F);
+    if (tree.bytes != plan_bytes) return;
+    const float4* boxes = reinterpret_cast<const float4*>(plan + tree.boxes);
+    const float4* records = reinterpret_cast<const float4*>(plan + tree.records);
+    if (__ballot(probe.active()) == 0ull) return;
+    probe.begin();
     int top = 0;
     uint32_t count, offset;
-    tri_level(tree.leaves, tree.top, count, offset);
-    push_hit_children(boxes + 2 * (size_t)offset, tree.top, 0u, (int)min(count, (uint32_t)kFan), r, slot.t, stack, top, lane);
+    tree_level(tree.leaves, tree.top, count, offset);
+    push_children(w, boxes + 2 * (size_t)offset, tree.top, 0u, (int)min(count, (uint32_t)kFan), probe, top);
     while (top > 0) {
-        const uint32_t e = (uint32_t)__builtin_amdgcn_readfirstlane((int)stack[--top]);
+        const uint32_t e = (uint32_t)__builtin_amdgcn_readfirstlane((int)w.stack[--top]);
         const int level = (int)(e >> 29);
         const uint32_t node = e & ((1u << 29) - 1u);
         if (level > 0) {
             const uint32_t first = node * kFan;
-            tri_level(tree.leaves, level - 1, count, offset);
-            push_hit_children(boxes + 2 * (size_t)offset, level - 1, first, (int)min((uint32_t)kFan, count - first), r, slot.t, stack, top,
-                              lane);
+            tree_level(tree.leaves, level - 1, count, offset);
+            push_children(w, boxes + 2 * (size_t)offset, level - 1, first, (int)min((uint32_t)kFan, count - first), probe, top);
             continue;
         }
         const float4 lo = boxes[2 * (size_t)node], hi = boxes[2 * (size_t)node + 1];   // (leaves: level offset 0)
-        float t_enter, t_exit;
-        slab(lo, hi, r, t_enter, t_exit);
-        if (__ballot(r.active && t_enter <= t_exit && !(t_enter > slot.t)) == 0ull) continue;
+        float bound;
+        if (__ballot(probe.reaches(lo, hi, bound)) == 0ull) continue;
         const uint32_t base = node * kLeaf;
-        const int cnt = (int)min((uint32_t)kLeaf, F - base);
+        const int cnt = (int)min((uint32_t)kLeaf, h.F - base);
         wave_sync();
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            const int at = k * kLeaf + lane;
-            if (at < 3 * cnt) leaf[at] = records[3 * (size_t)base + at];
+            const int at = k * kLeaf + w.lane;
+            if (at < 3 * cnt) w.leaf[at] = records[3 * (size_t)base + at];
         }
         wave_sync();
-        hit_scan(leaf, cnt, r, slot);
+        probe.scan(w.leaf, cnt);
     }
 }
 
+// gsr_closest_tri_query: one lane per query point
+__global__ __launch_bounds__(256) void tri_query_kernel(uint32_t n, const float* __restrict__ points, const unsigned char* __restrict__ plan,
+                                                        unsigned long long plan_bytes, long long* __restrict__ face_idx,
+                                                        float* __restrict__ sq_dist, float* __restrict__ closest) {
+    Wave w;
+    if (!open_wave(n, w)) return;
+    const uint32_t s = w.s;
+    Query q = {0.0f, 0.0f, 0.0f, false};
+    if (s < n) {
+        const float x = points[3 * (size_t)s], y = points[3 * (size_t)s + 1], z = points[3 * (size_t)s + 2];
+        if (finite3(x, y, z)) q = {x, y, z, true};
+    }
+    PointProbe probe = {q, {INFINITY, kNoFace, {0.0f, 0.0f, 0.0f}}};
+    walk_tree(w, plan, plan_bytes, probe);
+    if (s >= n) return;
+    const Slot& slot = probe.slot;
+    const bool found = q.active && slot.face != kNoFace;
+    face_idx[s] = found ? (long long)slot.face : -1ll;
+    sq_dist[s] = found ? slot.d : INFINITY;
+    if (closest) {
+        closest[3 * (size_t)s] = found ? q.x + slot.p.x : 0.0f;
+        closest[3 * (size_t)s + 1] = found ? q.y + slot.p.y : 0.0f;
+        closest[3 * (size_t)s + 2] = found ? q.z + slot.p.z : 0.0f;
+    }
+}
+
+// gsr_ray_first_hit: one lane per ray
 __global__ __launch_bounds__(256) void ray_hit_kernel(uint32_t n, const float* __restrict__ origins, const float* __restrict__ dirs,
                                                       const unsigned char* __restrict__ plan, unsigned long long plan_bytes,
                                                       long long* __restrict__ face_idx, float* __restrict__ t_hit, float* __restrict__ bary) {
-    __shared__ float4 s_leaf[4][3 * kLeaf];
-    __shared__ uint32_t s_stack[4][kStackDepth];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t group = blockIdx.x * 4u + (uint32_t)wave;    // this wave's 64 rays
-    if ((unsigned long long)group * kLeaf >= n) return;
-    const uint32_t s = group * kLeaf + lane;
-    Ray r = {};
+    Wave w;
+    if (!open_wave(n, w)) return;
+    const uint32_t s = w.s;
+    RayProbe probe = {{}, {INFINITY, kNoFace, 0.0f, 0.0f, 0.0f}};
     if (s < n)
-        r = make_ray(origins[3 * (size_t)s], origins[3 * (size_t)s + 1], origins[3 * (size_t)s + 2], dirs[3 * (size_t)s],
-                     dirs[3 * (size_t)s + 1], dirs[3 * (size_t)s + 2]);
-    // the header against the size the caller holds, before anything else of the plan is read (plan_bytes >= 256: checked by the host)
-    const TriHeader h = *reinterpret_cast<const TriHeader*>(plan);
-    HitSlot slot = {INFINITY, kNoFace, 0.0f, 0.0f, 0.0f};
-    if (h.magic == kPlanMagic && h.plan_bytes == plan_bytes && h.F > 0u && h.F < (uint32_t)kMaxFaces) {
-        const TriTree tree = tri_layout(h.F);
-        if (tree.bytes == plan_bytes)
-            ray_walk(reinterpret_cast<const float4*>(plan + tree.boxes), tree, h.F, reinterpret_cast<const float4*>(plan + tree.records), r,
-                     s_leaf[wave], s_stack[wave], lane, slot);
-    }
+        probe.r = make_ray(origins[3 * (size_t)s], origins[3 * (size_t)s + 1], origins[3 * (size_t)s + 2], dirs[3 * (size_t)s],
+                           dirs[3 * (size_t)s + 1], dirs[3 * (size_t)s + 2]);
+    walk_tree(w, plan, plan_bytes, probe);
     if (s >= n) return;
-    const bool found = r.active && slot.face != kNoFace;
+    const HitSlot& slot = probe.slot;
+    const bool found = probe.r.active && slot.face != kNoFace;
     face_idx[s] = found ? (long long)slot.face : -1ll;
     t_hit[s] = found ? slot.t : INFINITY;
     if (bary) {
@@ -708,7 +601,7 @@ hipError_t launch_plan(int64_t V, const float* verts, uint32_t F, const long lon
     const TriTree tree = tri_layout(F);
     if (F > 0) {
         uint32_t count, offset;
-        tri_level(tree.leaves, tree.top, count, offset);
+        tree_level(tree.leaves, tree.top, count, offset);
         if (count > (uint32_t)kFan) return hipErrorInvalidValue;   // (F < 2^30 never gets here)
         const TriScratch L = tri_scratch(F);
         char* base = static_cast<char*>(scratch);
@@ -723,27 +616,37 @@ hipError_t launch_plan(int64_t V, const float* verts, uint32_t F, const long lon
                            key_hi);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
-        // the 63-bit codes, least significant word first (both sorts are stable)
-        uint32_t *ks = nullptr, *vs = nullptr;
-        e = radix_sort_pairs(u32(L.radix), F, 32, keys, keys_alt, vals, vals_alt, true, false, &ks, &vs, stream);
+        uint32_t* order = nullptr;
+        e = morton_sort(u32(L.radix), F, keys, keys_alt, vals, vals_alt, key_hi, &order, stream);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(tri_gather_kernel, dim3(blocks), dim3(256), 0, stream, F, (const uint32_t*)vs, (const uint32_t*)key_hi, keys);
-        e = radix_sort_pairs(u32(L.radix), F, 32, keys, keys_alt, vs, vs == vals ? vals_alt : vals, false, false, &ks, &vs, stream);
+        hipLaunchKernelGGL(tri_pack_kernel, dim3(blocks), dim3(256), 0, stream, V, verts, F, faces, (const uint32_t*)order, records, boxes);
+        e = tree_levels(boxes, tree.leaves, tree.top, stream);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(tri_pack_kernel, dim3(blocks), dim3(256), 0, stream, V, verts, F, faces, (const uint32_t*)vs, records, boxes);
-        for (int level = 1; level <= tree.top; ++level) {
-            uint32_t below, below_at;
-            tri_level(tree.leaves, level - 1, below, below_at);
-            tri_level(tree.leaves, level, count, offset);
-            hipLaunchKernelGGL(tri_level_kernel, dim3((count + 255u) / 256u), dim3(256), 0, stream, count, below,
-                               (const float4*)(boxes + 2 * (size_t)below_at), boxes + 2 * (size_t)offset);
-        }
     }
     hipLaunchKernelGGL(tri_header_kernel, dim3(1), dim3(64), 0, stream, reinterpret_cast<TriHeader*>(plan), F, (unsigned long long)tree.bytes);
     return hipGetLastError();
 }
 
 bool misaligned(const void* p, uintptr_t to) { return ((uintptr_t)p & (to - 1u)) != 0u; }
+
+// The argument checks of the two query entry points, in the order their refusals come: n, then the entry point's own pointers (`null`,
+// `unaligned`: what it found of them; `alignments`: the text of that refusal), then plan_bytes -- every plan is a whole number of
+// 256-byte blocks, the header first; the header itself is compared with plan_bytes on the device.  `what`: "queries" or "rays".
+// GSR_OK with *grid == 0: n == 0, nothing to do.  Otherwise *grid workgroups of four waves of 64.
+int check_query(const char* name, const char* what, int64_t n, bool null, bool unaligned, const char* alignments, size_t plan_bytes,
+                uint32_t* grid) {
+    *grid = 0u;
+    if (n < 0) return fail(GSR_ERR_INVALID_ARG, "%s: negative count (n %lld)", name, (long long)n);
+    if (n >= kMaxQueries) return fail(GSR_ERR_INVALID_ARG, "%s: %lld %s (at most 2^31 - 1)", name, (long long)n, what);
+    if (n == 0) return GSR_OK;
+    if (null) return fail(GSR_ERR_INVALID_ARG, "%s: null pointer", name);
+    if (unaligned) return fail(GSR_ERR_INVALID_ARG, "%s: misaligned pointer (%s)", name, alignments);
+    if (plan_bytes < kAlign || (plan_bytes & (kAlign - 1)) != 0)
+        return fail(GSR_ERR_INVALID_ARG, "%s: plan_bytes = %zu is not the size of a plan", name, plan_bytes);
+    const uint32_t groups = (uint32_t)((n + kLeaf - 1) / kLeaf);
+    *grid = (groups + 3u) / 4u;
+    return GSR_OK;
+}
 
 }  // namespace
 }  // namespace gsr
@@ -780,19 +683,13 @@ int gsr_closest_tri_plan(int64_t V, const float* verts, int64_t F, const int64_t
 
 int gsr_closest_tri_query(int64_t n, const float* points, const void* plan, size_t plan_bytes, int64_t* face_idx, float* sq_dist,
                           float* closest, void* stream_) {
-    if (n < 0) return fail(GSR_ERR_INVALID_ARG, "gsr_closest_tri_query: negative count (n %lld)", (long long)n);
-    if (n >= gsr::kMaxQueries) return fail(GSR_ERR_INVALID_ARG, "gsr_closest_tri_query: %lld queries (at most 2^31 - 1)", (long long)n);
-    if (n == 0) return GSR_OK;
-    if (!points || !plan || !face_idx || !sq_dist) return fail(GSR_ERR_INVALID_ARG, "gsr_closest_tri_query: null pointer");
-    if (gsr::misaligned(points, 4) || gsr::misaligned(plan, 256) || gsr::misaligned(face_idx, 8) || gsr::misaligned(sq_dist, 4) ||
-        gsr::misaligned(closest, 4))
-        return fail(GSR_ERR_INVALID_ARG, "gsr_closest_tri_query: misaligned pointer (points / sq_dist / closest: 4 bytes, face_idx: 8 bytes, "
-                                         "plan: 256 bytes)");
-    // every plan is a whole number of 256-byte blocks, the header first; the header itself is compared with plan_bytes on the device
-    if (plan_bytes < gsr::kAlign || (plan_bytes & (gsr::kAlign - 1)) != 0)
-        return fail(GSR_ERR_INVALID_ARG, "gsr_closest_tri_query: plan_bytes = %zu is not the size of a plan", plan_bytes);
-    const uint32_t groups = (uint32_t)((n + gsr::kLeaf - 1) / gsr::kLeaf);
-    hipLaunchKernelGGL(gsr::tri_query_kernel, dim3((groups + 3u) / 4u), dim3(256), 0, (hipStream_t)stream_, (uint32_t)n, points,
+    uint32_t grid;
+    const int status = gsr::check_query("gsr_closest_tri_query", "queries", n, !points || !plan || !face_idx || !sq_dist,
+                                        gsr::misaligned(points, 4) || gsr::misaligned(plan, 256) || gsr::misaligned(face_idx, 8) ||
+                                            gsr::misaligned(sq_dist, 4) || gsr::misaligned(closest, 4),
+                                        "points / sq_dist / closest: 4 bytes, face_idx: 8 bytes, plan: 256 bytes", plan_bytes, &grid);
+    if (status != GSR_OK || grid == 0u) return status;
+    hipLaunchKernelGGL(gsr::tri_query_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream_, (uint32_t)n, points,
                        static_cast<const unsigned char*>(plan), (unsigned long long)plan_bytes, reinterpret_cast<long long*>(face_idx), sq_dist,
                        closest);
     GSR_HIP(hipGetLastError());
@@ -801,19 +698,13 @@ int gsr_closest_tri_query(int64_t n, const float* points, const void* plan, size
 
 int gsr_ray_first_hit(int64_t n, const float* origins, const float* dirs, const void* plan, size_t plan_bytes, int64_t* face_idx, float* t,
                       float* bary, void* stream_) {
-    if (n < 0) return fail(GSR_ERR_INVALID_ARG, "gsr_ray_first_hit: negative count (n %lld)", (long long)n);
-    if (n >= gsr::kMaxQueries) return fail(GSR_ERR_INVALID_ARG, "gsr_ray_first_hit: %lld rays (at most 2^31 - 1)", (long long)n);
-    if (n == 0) return GSR_OK;
-    if (!origins || !dirs || !plan || !face_idx || !t) return fail(GSR_ERR_INVALID_ARG, "gsr_ray_first_hit: null pointer");
-    if (gsr::misaligned(origins, 4) || gsr::misaligned(dirs, 4) || gsr::misaligned(plan, 256) || gsr::misaligned(face_idx, 8) ||
-        gsr::misaligned(t, 4) || gsr::misaligned(bary, 4))
-        return fail(GSR_ERR_INVALID_ARG, "gsr_ray_first_hit: misaligned pointer (origins / dirs / t / bary: 4 bytes, face_idx: 8 bytes, "
-                                         "plan: 256 bytes)");
-    // as in gsr_closest_tri_query: the header itself is compared with plan_bytes on the device
-    if (plan_bytes < gsr::kAlign || (plan_bytes & (gsr::kAlign - 1)) != 0)
-        return fail(GSR_ERR_INVALID_ARG, "gsr_ray_first_hit: plan_bytes = %zu is not the size of a plan", plan_bytes);
-    const uint32_t groups = (uint32_t)((n + gsr::kLeaf - 1) / gsr::kLeaf);
-    hipLaunchKernelGGL(gsr::ray_hit_kernel, dim3((groups + 3u) / 4u), dim3(256), 0, (hipStream_t)stream_, (uint32_t)n, origins, dirs,
+    uint32_t grid;
+    const int status = gsr::check_query("gsr_ray_first_hit", "rays", n, !origins || !dirs || !plan || !face_idx || !t,
+                                        gsr::misaligned(origins, 4) || gsr::misaligned(dirs, 4) || gsr::misaligned(plan, 256) ||
+                                            gsr::misaligned(face_idx, 8) || gsr::misaligned(t, 4) || gsr::misaligned(bary, 4),
+                                        "origins / dirs / t / bary: 4 bytes, face_idx: 8 bytes, plan: 256 bytes", plan_bytes, &grid);
+    if (status != GSR_OK || grid == 0u) return status;
+    hipLaunchKernelGGL(gsr::ray_hit_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream_, (uint32_t)n, origins, dirs,
                        static_cast<const unsigned char*>(plan), (unsigned long long)plan_bytes, reinterpret_cast<long long*>(face_idx), t,
                        bary);
     GSR_HIP(hipGetLastError());

@@ -95,7 +95,7 @@ def _guarded(num, den):
 
 
 def _box_bound(lo, hi, q):
-    """gsr_meshquery.hip's ``box_bound`` on per-axis tuples: the squared gap between ``q`` and the box, summed like ``dot``."""
+    """gsr_tree.h's ``box_bound`` on per-axis tuples: the squared gap between ``q`` and the box, summed like ``dot``."""
     gaps = [np.fmax(np.fmax(lo[k] - q[k], q[k] - hi[k]), _F(0)) for k in range(3)]
     return (gaps[0] * gaps[0] + gaps[1] * gaps[1]) + gaps[2] * gaps[2]
 
@@ -336,7 +336,7 @@ def first_hits_host(origins, dirs, verts, faces, chunk_elems: int = 1 << 20, pru
 
 
 # ---- the plan in numpy ----------------------------------------------------------------------------------------------------------------
-LEAF = 64           # gsr_meshquery.hip's kLeaf, kFan, kTriMaxLevels, kAlign, kCellMax
+LEAF = 64           # gsr_tree.h's kLeaf, kFan, kTreeMaxLevels, kAlign, kCellMax
 FAN = 16
 MAX_LEVELS = 6
 ALIGN = 256
@@ -346,8 +346,8 @@ PLAN_MAGIC = b"TRIQ"
 
 
 class PlanLayout(NamedTuple):
-    """Where everything of a plan of ``F`` faces lies (gsr_meshquery.hip's ``tri_layout`` and ``tri_level``): ``counts[l]`` boxes
-    of level ``l`` (0: the leaves) start at box ``offsets[l]`` of the box region; ``records`` and ``boxes`` are byte offsets and
+    """Where everything of a plan of ``F`` faces lies (gsr_meshquery.hip's ``tri_layout``, gsr_tree.h's ``tree_level``): ``counts[l]``
+    boxes of level ``l`` (0: the leaves) start at box ``offsets[l]`` of the box region; ``records`` and ``boxes`` are byte offsets and
     ``bytes`` the whole, in 256-byte blocks.  A record is 48 bytes, a box 32 (two ``float4``: lo, hi)."""
     F: int
     leaves: int
@@ -568,7 +568,7 @@ def closest_triangles(points: torch.Tensor, verts: torch.Tensor, faces: torch.Te
 
 
 def _spread21(x: torch.Tensor) -> torch.Tensor:
-    """Bit k of an int64 ``x < 2^21`` -> bit 3k (gsr_meshquery.hip's ``spread21``)."""
+    """Bit k of an int64 ``x < 2^21`` -> bit 3k (gsr_tree.h's ``spread21``)."""
     x = (x | (x << 32)) & 0x001F00000000FFFF
     x = (x | (x << 16)) & 0x001F0000FF0000FF
     x = (x | (x << 8)) & 0x100F00F00F00F00F
@@ -597,28 +597,35 @@ def _query(points: torch.Tensor, tree: Plan, return_points: bool, sort_queries: 
     back in it, 215 ms asked as drawn; scripts/bench_meshquery.py).  So the queries are asked in Morton order and the answers put
     back; every answer is a function of its own query alone.  ``sort_queries=False`` (the tests, the benchmark) asks in the
     caller's order."""
-    from . import _lib
-
     pts = points.detach().contiguous()
     n = int(pts.shape[0])
     face_idx = torch.empty(n, dtype=torch.int64, device=pts.device)
     sq_dist = torch.empty(n, dtype=torch.float32, device=pts.device)
     closest = torch.empty((n, 3), dtype=torch.float32, device=pts.device) if return_points else None
+    _ask("gsr_closest_tri_query", (pts,), tree, (face_idx, sq_dist, closest), morton_order(pts) if sort_queries and n >= SORT_FROM else None)
+    return (face_idx, sq_dist, closest) if return_points else (face_idx, sq_dist)
+
+
+def _ask(entry: str, inputs, tree: Plan, outputs, order: Optional[torch.Tensor]) -> None:
+    """A query entry point of the C ABI (``n``, the inputs, the plan and its size, the outputs) on the contiguous ``inputs [n, ...]``,
+    asked in ``order`` (None: as given), the answers put back into ``outputs`` (each ``[n, ...]``, or None for one that is not
+    wanted).  Nothing is asked of ``n == 0``."""
+    from . import _lib
+
+    n, dev = int(inputs[0].shape[0]), inputs[0].device
     if n == 0:
-        return (face_idx, sq_dist, closest) if return_points else (face_idx, sq_dist)
-    order = morton_order(pts) if sort_queries and n >= SORT_FROM else None
-    asked = pts if order is None else pts[order]
-    out = (face_idx, sq_dist, closest) if order is None else tuple(None if t is None else torch.empty_like(t) for t in (face_idx, sq_dist, closest))
-    with torch.cuda.device(pts.device):
+        return
+    asked = inputs if order is None else [t[order] for t in inputs]
+    out = outputs if order is None else [None if t is None else torch.empty_like(t) for t in outputs]
+    with torch.cuda.device(dev):
         # the kernel reads the plan after this call returns, on THIS stream: a plan built on another one is not recycled under it
-        tree.buffer.record_stream(torch.cuda.current_stream(pts.device))
-        _lib.call("gsr_closest_tri_query", n, asked.data_ptr(), tree.buffer.data_ptr(), int(tree.buffer.numel()), out[0].data_ptr(),
-                  out[1].data_ptr(), _lib.ptr(out[2]), device=pts.device)
+        tree.buffer.record_stream(torch.cuda.current_stream(dev))
+        _lib.call(entry, n, *[t.data_ptr() for t in asked], tree.buffer.data_ptr(), int(tree.buffer.numel()), *[_lib.ptr(t) for t in out],
+                  device=dev)
     if order is not None:
-        for dst, src in zip((face_idx, sq_dist, closest), out):
+        for dst, src in zip(outputs, out):
             if dst is not None:
                 dst.index_copy_(0, order, src)
-    return (face_idx, sq_dist, closest) if return_points else (face_idx, sq_dist)
 
 
 def first_hits(origins: torch.Tensor, dirs: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor, plan: Optional[Plan] = None,
@@ -677,26 +684,11 @@ def _cast(origins: torch.Tensor, dirs: torch.Tensor, tree: Plan, return_bary: bo
     order 9.9 ms in ``ray_order`` (2.5 ms of it the order itself) with the way back, 26 ms as given; the 2 M rays of a 1080p camera
     2.3 ms as given, in row-major pixel order, and 6.3 ms ordered -- the order costs more than it saves when the rays come side by
     side already, hence ``first_hits(..., sort=False)``.  Returns ``face_idx``, ``t``, ``bary`` (None unless wanted)."""
-    from . import _lib
-
-    n = int(origins.shape[0])
-    dev = origins.device
+    n, dev = int(origins.shape[0]), origins.device
     face_idx = torch.empty(n, dtype=torch.int64, device=dev)
     t = torch.empty(n, dtype=torch.float32, device=dev)
     bary = torch.empty((n, 3), dtype=torch.float32, device=dev) if return_bary else None
-    if n == 0:
-        return face_idx, t, bary
-    o, d = (origins, dirs) if order is None else (origins[order], dirs[order])
-    out = (face_idx, t, bary) if order is None else tuple(None if x is None else torch.empty_like(x) for x in (face_idx, t, bary))
-    with torch.cuda.device(dev):
-        # the kernel reads the plan after this call returns, on THIS stream: a plan built on another one is not recycled under it
-        tree.buffer.record_stream(torch.cuda.current_stream(dev))
-        _lib.call("gsr_ray_first_hit", n, o.data_ptr(), d.data_ptr(), tree.buffer.data_ptr(), int(tree.buffer.numel()), out[0].data_ptr(),
-                  out[1].data_ptr(), _lib.ptr(out[2]), device=dev)
-    if order is not None:
-        for dst, src in zip((face_idx, t, bary), out):
-            if dst is not None:
-                dst.index_copy_(0, order, src)
+    _ask("gsr_ray_first_hit", (origins, dirs), tree, (face_idx, t, bary), order)
     return face_idx, t, bary
 
 
