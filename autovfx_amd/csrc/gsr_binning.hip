@@ -54,33 +54,6 @@ constexpr int kPairsPerLane = kPairTile / 256;  // consecutive pairs of one lane
 constexpr int kMaxDoneWords = 4096;             // most tile bit rows the slab kernels hold in LDS (16 KB; an 8K x 8K image has 1 024)
 static_assert(kDupTile == 1024, "256 lanes x 4 consecutive positions");
 
-// Sum over the workgroup's 256 lanes, returned to every lane; scratch is 4 words of LDS.
-__device__ __forceinline__ uint32_t block_sum_256(uint32_t v, uint32_t* scratch) {
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const uint32_t total = scratch[0] + scratch[1] + scratch[2] + scratch[3];
-    __syncthreads();
-    return total;
-}
-
-// Inclusive scan of one value per lane over the 256 lanes; returns the exclusive prefix, *total = sum of all.
-__device__ __forceinline__ uint32_t block_exclusive_256(uint32_t mine, uint32_t* s_wave, uint32_t* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t incl = wave_inclusive_scan(mine);
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    uint32_t before = incl - mine, all = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-        if (w < wave) before += s_wave[w];
-        all += s_wave[w];
-    }
-    __syncthreads();
-    *total = all;
-    return before;
-}
-
 __device__ __forceinline__ bool rec_is_masked(uint32_t wh) { return (wh & 0xFFFFu) * (wh >> 16) <= kMaskTiles; }
 
 // Bits [x0, x0 + w) of tile bit row `ty` (w <= 64), right-aligned.
@@ -369,7 +342,7 @@ __global__ void __launch_bounds__(256, 7) bin_gather_kernel(BinningArrays a) {
     GSR_BTRACE(blockIdx.x, 2);
     const uint32_t mine = count[0] + count[1] + count[2] + count[3];
     uint32_t tile_total;
-    const uint32_t before = block_exclusive_256(mine, s_wave, &tile_total);
+    const uint32_t before = block_exclusive_scan(mine, s_wave, &tile_total);
     GSR_BTRACE(blockIdx.x, 3);
     if (tid == 0) a.tile_totals[blockIdx.x] = tile_total;
     const uint32_t o0 = before + count[0], o1 = o0 + count[1], o2 = o1 + count[2], o3 = o2 + count[3];
@@ -406,7 +379,7 @@ __global__ void __launch_bounds__(256) bin_offsets_kernel(int P, int V, const ui
     const int upto = min((int)blockIdx.x, tiles_v);
     uint32_t part = 0;
     for (int t = threadIdx.x; t < upto; t += 256) part += tile_totals[t];
-    const uint32_t before = block_sum_256(part, s_scratch);
+    const uint32_t before = block_sum(part, s_scratch);
     const bool has_pairs = (int)blockIdx.x < tiles_v;
     const uint32_t tile_end = has_pairs ? before + tile_totals[blockIdx.x] : before;
     if (threadIdx.x == 0 && has_pairs) tile_ends[blockIdx.x] = tile_end;
@@ -435,7 +408,7 @@ __global__ void __launch_bounds__(256) bin_offsets_kernel(int P, int V, const ui
 #pragma unroll
         for (int j = 0; j < 4; ++j)
             if (k0 + j < V && (beyond || mine[j] <= cut)) ++n_le;
-        const uint32_t below = block_sum_256(n_le, s_scratch);   // this tile's positions that stay in slab s (a prefix of them)
+        const uint32_t below = block_sum(n_le, s_scratch);   // this tile's positions that stay in slab s (a prefix of them)
         const uint32_t pos = (uint32_t)blockIdx.x * kDupTile + below;
         if (threadIdx.x == 0) {
             slabs[s].end = pos;
@@ -484,7 +457,7 @@ __global__ void __launch_bounds__(256, 7) slab_recount_kernel(BinningArrays a, i
         const uint32_t cols = (uint32_t)min(32, a.grid_x - 32 * word);
         done_tiles += (uint32_t)__popc(s_done[i] & (cols >= 32u ? ~0u : (1u << cols) - 1u));
     }
-    const bool nothing_left = block_sum_256(done_tiles, s_wave) == (uint32_t)(a.grid_x * a.grid_y);
+    const bool nothing_left = block_sum(done_tiles, s_wave) == (uint32_t)(a.grid_x * a.grid_y);
     GSR_BTRACE(8192 + blockIdx.x, 2);
     uint32_t count[4];
     uint4 rec[4];
@@ -554,9 +527,9 @@ __global__ void __launch_bounds__(256, 7) slab_recount_kernel(BinningArrays a, i
     GSR_BTRACE(8192 + blockIdx.x, 4);
     const uint32_t mine = count[0] + count[1] + count[2] + count[3];
     uint32_t tile_total;
-    const uint32_t before = block_exclusive_256(mine, s_wave, &tile_total);
+    const uint32_t before = block_exclusive_scan(mine, s_wave, &tile_total);
     const uint32_t emitting = (count[0] != 0u) + (count[1] != 0u) + (count[2] != 0u) + (count[3] != 0u);
-    const uint32_t tile_emitting = block_sum_256(emitting, s_wave);
+    const uint32_t tile_emitting = block_sum(emitting, s_wave);
     if (threadIdx.x == 0) {
         a.slab_tile_totals[blockIdx.x] = tile_total;
         a.slab_tile_totals[a.tiles_p + blockIdx.x] = tile_emitting;
@@ -583,8 +556,8 @@ __global__ void __launch_bounds__(256) slab_compact_kernel(BinningArrays a, int 
     if (blockIdx.x == 0) {  // the slab's counts (also when the slab is empty)
         uint32_t pp = 0, ee = 0;
         for (uint32_t t = threadIdx.x; t < tiles; t += 256) { pp += pair_totals[t]; ee += emit_totals[t]; }
-        const uint32_t all_pairs = block_sum_256(pp, s_scratch);
-        const uint32_t all_emit = block_sum_256(ee, s_scratch);
+        const uint32_t all_pairs = block_sum(pp, s_scratch);
+        const uint32_t all_emit = block_sum(ee, s_scratch);
         if (threadIdx.x == 0) {
             a.slabs[slab].pairs = all_pairs; a.slabs[slab].emitters = all_emit;
             if (a.slabs_host != nullptr) a.slabs_host[slab].pairs = all_pairs;
@@ -593,8 +566,8 @@ __global__ void __launch_bounds__(256) slab_compact_kernel(BinningArrays a, int 
     if (blockIdx.x >= tiles) return;
     uint32_t pp = 0, ee = 0;
     for (uint32_t t = threadIdx.x; t < blockIdx.x; t += 256) { pp += pair_totals[t]; ee += emit_totals[t]; }
-    const uint32_t pairs_before = block_sum_256(pp, s_scratch);
-    const uint32_t emit_before = block_sum_256(ee, s_scratch);
+    const uint32_t pairs_before = block_sum(pp, s_scratch);
+    const uint32_t emit_before = block_sum(ee, s_scratch);
     const uint32_t tile_first = first + blockIdx.x * (uint32_t)kDupTile;
     const uint32_t k0 = tile_first + 4u * threadIdx.x;
     uint32_t incl[4], prev = 0u;  // tile-local inclusive offsets of my 4 positions, and of the position before them
@@ -607,7 +580,7 @@ __global__ void __launch_bounds__(256) slab_compact_kernel(BinningArrays a, int 
         prev = incl[j];
     }
     uint32_t tile_emit;
-    uint32_t rank = emit_before + block_exclusive_256((uint32_t)__popc(flags), s_wave, &tile_emit);  // (syncs: reads above, writes below)
+    uint32_t rank = emit_before + block_exclusive_scan((uint32_t)__popc(flags), s_wave, &tile_emit);  // (syncs: reads above, writes below)
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         if (k0 + j >= end) continue;
@@ -680,7 +653,7 @@ __global__ void __launch_bounds__(256, 7) expand_kernel(BinningArrays a, int sla
         const uint32_t tile_end = (tile_ends != nullptr && (t + 1) * kDupTile <= V) ? tile_ends[t] : offsets[min((t + 1) * kDupTile, V) - 1];
         n_le += tile_end <= p_begin ? 1u : 0u;
     }
-    const int tile0 = (int)block_sum_256(n_le, s_scratch);  // tiles that end at or before p_begin
+    const int tile0 = (int)block_sum(n_le, s_scratch);  // tiles that end at or before p_begin
     n_le = 0;
     {
         const int k0 = tile0 * kDupTile + 4 * tid;
@@ -688,7 +661,7 @@ __global__ void __launch_bounds__(256, 7) expand_kernel(BinningArrays a, int sla
         for (int j = 0; j < 4; ++j)
             if (k0 + j < V) n_le += offsets[k0 + j] <= p_begin ? 1u : 0u;
     }
-    int s0 = tile0 * kDupTile + (int)block_sum_256(n_le, s_scratch);
+    int s0 = tile0 * kDupTile + (int)block_sum(n_le, s_scratch);
     GSR_BTRACE(16384 + 8192 * slab + blockIdx.x, 2);
 
     const uint32_t my_begin = p_begin + per_lane * (uint32_t)tid;

@@ -182,32 +182,19 @@ __global__ __launch_bounds__(kThreads) void densify_classify_kernel(const Densif
 
 // one workgroup: exclusive prefix of each class's per-workgroup counts, and the three totals
 __global__ __launch_bounds__(kThreads) void densify_scan_kernel(const DensifyPlanArgs p) {
-    __shared__ uint32_t buf[kThreads];
-    __shared__ uint32_t carry;
+    __shared__ uint32_t s_wave[kWaves];
     for (int cls = 0; cls < 3; ++cls) {
-        if (threadIdx.x == 0) carry = 0u;
-        __syncthreads();
         const uint32_t* in = p.block_counts + (size_t)cls * p.blocks;
         uint32_t* out = p.block_offsets + (size_t)cls * p.blocks;
+        uint32_t carry = 0u;   // the class's counts in front of this round (the same in every lane)
         for (uint32_t base = 0; base < p.blocks; base += kThreads) {
             const uint32_t b = base + threadIdx.x;
-            const uint32_t mine = b < p.blocks ? in[b] : 0u;
-            buf[threadIdx.x] = mine;
-            __syncthreads();
-            for (int d = 1; d < kThreads; d <<= 1) {   // inclusive Hillis-Steele
-                const uint32_t add = (int)threadIdx.x >= d ? buf[threadIdx.x - d] : 0u;
-                __syncthreads();
-                buf[threadIdx.x] += add;
-                __syncthreads();
-            }
-            const uint32_t before = carry;
-            if (b < p.blocks) out[b] = before + buf[threadIdx.x] - mine;
-            __syncthreads();
-            if (threadIdx.x == kThreads - 1) carry = before + buf[threadIdx.x];
-            __syncthreads();
+            uint32_t round_total;
+            const uint32_t before = carry + block_exclusive_scan<kWaves>(b < p.blocks ? in[b] : 0u, s_wave, &round_total);
+            if (b < p.blocks) out[b] = before;
+            carry += round_total;
         }
         if (threadIdx.x == 0) p.counts[cls] = (int32_t)carry;
-        __syncthreads();
     }
     if (threadIdx.x == 0) p.counts[3] = 0;
 }

@@ -1,8 +1,12 @@
-// gsr_device.h -- device-side helpers shared by the two kernel translation units (gsr_kernels.hip: forward and
-// auxiliary kernels; gsr_backward.hip: the backward pass, built with different code-generation flags, see
-// autovfx_amd/build.py).  Everything here is inline and lives in an unnamed namespace: each unit gets its own copy.
+// gsr_device.h -- device-side helpers of the rasterizer's kernel units.  Included by gsr_kernels.hip (forward and auxiliary
+// kernels), gsr_binning.hip, gsr_blend.hip, gsr_backward.hip (the backward pass) and gsr_densify.hip (for torch_sigmoid).  What is
+// in it: the tile-ranges duty, the small vector and matrix types, the SH evaluation, the restatements of the reference's PyTorch
+// preparation (torch_*), the exact-image tile culling (live_region / row_run), the quadrant blend's entry and power terms, the
+// XCD placement helpers and exp_nonpositive.  The wave and workgroup sums and scans are in gsr_wave.h, which this header includes.
+// Everything here is inline and lives in an unnamed namespace: each unit gets its own copy.
 #pragma once
 #include "gsr_internal.h"
+#include "gsr_wave.h"
 
 namespace gsr {
 namespace {
@@ -66,41 +70,6 @@ __device__ __forceinline__ void tile_ranges_duty(const RangesDuty& d, uint32_t b
         if (mine) d.order.table[(size_t)cell * d.order.cap + s_cell[8 * kOrderClasses + cell] + rank] = (uint32_t)t;
     }
     __syncthreads();   // (the caller may reuse the LDS)
-}
-
-// ------------------------------------------------------------------------------------------------
-// Wave64 inclusive scan and sum of one integer per lane, in six data-parallel-primitive (DPP) adds: four shifts inside
-// the rows of 16 lanes (row_shr 1, 2, 4, 8), then lane 15 of rows 0 and 2 broadcast into rows 1 and 3 (row_bcast15, row
-// mask 0b1010) and lane 31 into rows 2 and 3 (row_bcast31, row mask 0b1100).  A lane without a source, or in a row the
-// mask leaves out, adds zero.  The __shfl_up form of the same scan costs a ds_bpermute_b32 with its address arithmetic,
-// a compare and a select per step.  Every lane of the wave must be active.  Integer sums: the same result in any order.
-//
-// The steps are written once over a lane-move policy, so that a host program can run THESE steps on a 64-lane model
-// of the moves (tests/test_wave_scan_host.py) and compare with a serial scan.
-// ------------------------------------------------------------------------------------------------
-constexpr int kDppRowShr = 0x110, kDppRowBcast15 = 0x142, kDppRowBcast31 = 0x143;   // dpp_ctrl encodings (gfx9)
-
-struct WaveDpp {   // the hardware's moves: source lane's value, or zero
-    template <int kCtrl, int kRowMask>
-    static __device__ __forceinline__ uint32_t moved(uint32_t v) {
-        return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, kCtrl, kRowMask, 0xF, false);
-    }
-};
-
-template <class Moves, class T>
-__host__ __device__ __forceinline__ T wave_scan_steps(T v) {
-    v = v + Moves::template moved<kDppRowShr + 1, 0xF>(v);
-    v = v + Moves::template moved<kDppRowShr + 2, 0xF>(v);
-    v = v + Moves::template moved<kDppRowShr + 4, 0xF>(v);
-    v = v + Moves::template moved<kDppRowShr + 8, 0xF>(v);
-    v = v + Moves::template moved<kDppRowBcast15, 0xA>(v);
-    v = v + Moves::template moved<kDppRowBcast31, 0xC>(v);
-    return v;
-}
-
-__device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t v) { return wave_scan_steps<WaveDpp>(v); }
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {   // to every lane
-    return (uint32_t)__builtin_amdgcn_readlane((int)wave_inclusive_scan(v), 63);
 }
 
 // 4-byte aligned aggregates: the compiler may still fuse them into dwordx3/x4 accesses, but no

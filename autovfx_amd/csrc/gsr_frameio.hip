@@ -29,6 +29,7 @@
 // Defines the entry points gsr_frame_files(_deflate), gsr_png_size, gsr_png_room, gsr_png_encode, gsr_png_deflate_max_size / _room /
 // _scratch and gsr_png_encode_deflate.
 #include "gsr_internal.h"
+#include "gsr_wave.h"
 
 #include <algorithm>
 #include <initializer_list>
@@ -91,11 +92,8 @@ struct PngLayout {
 __device__ __forceinline__ void adler_workgroup_sums(unsigned long long a1, unsigned long long a2,
                                                      unsigned long long* __restrict__ partials /*[workgroups][2], every entry written*/) {
     __shared__ unsigned long long s_sum[4][2];
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        a1 += __shfl_xor(a1, d);
-        a2 += __shfl_xor(a2, d);
-    }
+    a1 = wave_fold(a1, [](unsigned long long x, unsigned long long y) { return x + y; });
+    a2 = wave_fold(a2, [](unsigned long long x, unsigned long long y) { return x + y; });
     if ((threadIdx.x & 63) == 0) { s_sum[threadIdx.x >> 6][0] = a1; s_sum[threadIdx.x >> 6][1] = a2 % 65521ull; }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -255,8 +253,7 @@ __device__ __forceinline__ uint32_t crc_chunk_term(const uint8_t* __restrict__ f
 // The workgroup's XOR of its lanes' terms, one plain store.  (XOR: any order, same result)
 __device__ __forceinline__ void crc_workgroup_xor(uint32_t crc, uint32_t* __restrict__ crc_partials /*[workgroups], every entry written*/) {
     __shared__ uint32_t s_crc[4];
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) crc ^= (uint32_t)__shfl_xor((int)crc, d);
+    crc = wave_fold(crc, [](uint32_t x, uint32_t y) { return x ^ y; });
     if ((threadIdx.x & 63) == 0) s_crc[threadIdx.x >> 6] = crc;
     __syncthreads();
     if (threadIdx.x == 0) crc_partials[blockIdx.x] = s_crc[0] ^ s_crc[1] ^ s_crc[2] ^ s_crc[3];
@@ -286,12 +283,9 @@ __device__ __forceinline__ void png_write_checksums(uint8_t* __restrict__ out, u
     uint32_t crc_sum = 0u;
     for (uint32_t i = threadIdx.x; i < adler_groups; i += 64u) { a1 += adler_partials[2 * (size_t)i]; a2 += adler_partials[2 * (size_t)i + 1]; }
     for (uint32_t i = threadIdx.x; i < crc_groups; i += 64u) crc_sum ^= crc_partials[i];
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        a1 += __shfl_xor(a1, d);
-        a2 += __shfl_xor(a2, d);
-        crc_sum ^= (uint32_t)__shfl_xor((int)crc_sum, d);
-    }
+    a1 = wave_fold(a1, [](unsigned long long x, unsigned long long y) { return x + y; });
+    a2 = wave_fold(a2, [](unsigned long long x, unsigned long long y) { return x + y; });
+    crc_sum = wave_fold(crc_sum, [](uint32_t x, uint32_t y) { return x ^ y; });
     if (threadIdx.x != 0) return;
     const uint32_t s1 = (uint32_t)((1ull + a1) % 65521ull);
     const uint32_t s2 = (uint32_t)((N % 65521ull + a2) % 65521ull);
@@ -737,8 +731,7 @@ __global__ void __launch_bounds__(256) png_size_kernel(PngBatch B) {
         const uint32_t sym = q * 64u + lane;
         if (sym < 286u) bits += J.hist[(size_t)b * kDefSyms + sym] * ((J.dyn->table[sym] >> 16) + length_symbol_extra_bits(sym));
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) bits += __shfl_xor(bits, d);
+    bits = wave_fold(bits, [](uint32_t x, uint32_t y) { return x + y; });
     if (lane == 0u) {
         const uint32_t blen = block_length(J.L, b);
         const unsigned long long all = (unsigned long long)kDefHeaderBits + bits;
@@ -792,12 +785,7 @@ __global__ void __launch_bounds__(256) png_deflate_kernel(PngBatch B, PngTables 
     uint32_t before_bytes = 0u;
     const uint32_t upto = block == 0u ? blocks : block;
     for (uint32_t b = t; b < upto; b += 256u) before_bytes += J.block_off[b] & 0x7FFFFFFFu;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) before_bytes += __shfl_xor(before_bytes, d);
-    if ((t & 63u) == 0u) s_wave[t >> 6] = before_bytes;
-    __syncthreads();
-    const uint32_t summed = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-    __syncthreads();
+    const uint32_t summed = block_sum(before_bytes, s_wave);
     const uint32_t off = block == 0u ? 0u : summed;
     const uint32_t mine = J.block_off[block];
     const bool stored = (mine >> 31) != 0u;
@@ -835,9 +823,7 @@ __global__ void __launch_bounds__(256) png_deflate_kernel(PngBatch B, PngTables 
     SizeTokens sz = {s_table, 0u};
     if (count) walk_piece(s_stream + t * kDefPitch, prev, count, sz);
     // exclusive prefix sum of the lanes' bit counts
-    uint32_t incl = sz.bits;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const uint32_t v = __shfl_up(incl, d); if ((t & 63u) >= (uint32_t)d) incl += v; }
+    const uint32_t incl = wave_inclusive_scan(sz.bits);   // (every lane is here: the returns above are workgroup-uniform)
     if ((t & 63u) == 63u) s_wave[t >> 6] = incl;
     // the block header's bytes, meanwhile (byte granular: the block starts on a byte)
     if (t < kDefHeaderBytes) {

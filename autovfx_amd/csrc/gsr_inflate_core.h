@@ -18,6 +18,7 @@
 #include <stdint.h>
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
+#include "gsr_wave.h"   // the device instantiation's sum over the wave
 #define GSR_HD __host__ __device__
 #else
 #define GSR_HD
@@ -132,9 +133,7 @@ struct Exec<64> {                                  // device: a single-wave work
     }
     static __device__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }   // the value is the same in every lane: say so
     static __device__ uint64_t sum(uint64_t v) {
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) v += (uint64_t)__shfl_xor((unsigned long long)v, d, 64);
-        return v;
+        return wave_fold((unsigned long long)v, [](unsigned long long a, unsigned long long b) { return a + b; });
     }
     // The stream's words, 64 at a time: lane k holds word base + k of the current piece and of the next (one coalesced 256-byte load
     // each, the second in flight while the first is being used); the reader takes a word with v_readlane -- no memory access, and so

@@ -25,6 +25,7 @@
 // Defines the entry points gsr_png_unfilter_scratch, gsr_png_unfilter(_batch), gsr_exr_unpack_channel and gsr_inflate_zlib_blocks.
 #include "gsr_internal.h"
 #include "gsr_inflate_core.h"
+#include "gsr_wave.h"
 
 #include <algorithm>
 #include <mutex>
@@ -231,7 +232,6 @@ __global__ void __launch_bounds__(kExrThreads) exr_unpack_channel_kernel(ExrPlan
     const uint8_t* t = p.blocks + (size_t)y0 * p.bytes_per_line;
     const bool aligned = (reinterpret_cast<uintptr_t>(t) & 15u) == 0;
     const uint32_t c_at = (uint32_t)p.c_at, c_end = (uint32_t)(p.c_at + p.c_bytes);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     uint32_t carry = 0;                                                     // the running sum in front of the tile (mod 256 at use)
     for (uint32_t tile = 0; tile < n; tile += kExrTile) {
         const uint32_t at = tile + threadIdx.x * 16u;
@@ -245,21 +245,9 @@ __global__ void __launch_bounds__(kExrThreads) exr_unpack_channel_kernel(ExrPlan
         uint32_t sum = 0;
 #pragma unroll
         for (int k = 0; k < 4; ++k) sum = __builtin_amdgcn_sad_u8(q[k], 0u, sum);
-        uint32_t incl = sum;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t o = __shfl_up(incl, d, 64);
-            if (lane >= d) incl += o;
-        }
-        __syncthreads();                                                    // (s_wave of the previous tile has been read)
-        if (lane == 63) s_wave[wave] = incl;
-        __syncthreads();
-        uint32_t before = carry + incl - sum, total = 0;
-#pragma unroll
-        for (int w = 0; w < kExrThreads / 64; ++w) {
-            if (w < wave) before += s_wave[w];
-            total += s_wave[w];
-        }
+        // (no barrier in front: the scan's own trailing barrier stands between the previous tile's reads of s_wave and this write)
+        uint32_t total;
+        const uint32_t before = carry + block_exclusive_scan<kExrThreads / 64>(sum, s_wave, &total);
         carry += total;
         if (at >= n) continue;
         // the thread's bytes: where byte `at` of the block lands in the block's lines

@@ -15,6 +15,7 @@
 // A rectangle of more than kWaveRect tiles is walked by the whole wave, not by the lane that owns the face.
 // fp32 throughout, -ffp-contract=off, IEEE division, no transcendental: the numpy restatement computes the same bits.
 #include "gsr_internal.h"
+#include "gsr_wave.h"
 
 #include <limits.h>
 #include <math.h>
@@ -259,7 +260,7 @@ __global__ __launch_bounds__(kMeshThreads) void mesh_fill_kernel(const MeshBinAr
 // One workgroup: offsets = exclusive prefix of counts, counts cleared, the total into the header.  Sums in 64 bits (the offsets are
 // stored in 32: a total they cannot hold is refused by gsr_mesh_raster before anything reads them).
 __global__ __launch_bounds__(kMeshThreads) void mesh_scan_kernel(uint32_t* counts, uint32_t* offsets, long long tiles, MeshPlanHeader* header) {
-    __shared__ unsigned long long sums[kMeshThreads];   // 64 bits: a round of 4096 tiles may hold 2^32 pairs, and the total decides a refusal
+    __shared__ unsigned long long s_wave[kMeshThreads / 64];   // 64 bits: a round of 4096 tiles may hold 2^32 pairs, and the total decides a refusal
     const int t = threadIdx.x;
     unsigned long long running = 0;
     for (long long start = 0; start < tiles; start += (long long)kMeshThreads * kScanPerLane) {
@@ -271,17 +272,9 @@ __global__ __launch_bounds__(kMeshThreads) void mesh_scan_kernel(uint32_t* count
             v[i] = mine + i < tiles ? counts[mine + i] : 0u;
             sum += v[i];
         }
-        sums[t] = sum;
-        __syncthreads();
-        for (int d = 1; d < kMeshThreads; d <<= 1) {
-            const unsigned long long add = t >= d ? sums[t - d] : 0ull;
-            __syncthreads();
-            sums[t] += add;
-            __syncthreads();
-        }
-        unsigned long long at = running + (sums[t] - sum);
-        running += sums[kMeshThreads - 1];
-        __syncthreads();
+        unsigned long long round_total;
+        unsigned long long at = running + block_exclusive_scan<kMeshThreads / 64>(sum, s_wave, &round_total);
+        running += round_total;
 #pragma unroll
         for (int i = 0; i < kScanPerLane; ++i) {
             if (mine + i < tiles) {

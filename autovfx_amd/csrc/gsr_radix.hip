@@ -39,6 +39,7 @@
 // and stores how many were kept; the later passes read that count (n_device) and sort the kept ones only.
 // Defines the entry points gsr_radix_scratch_bytes, gsr_radix_sort_pairs and gsr_selftest_lds_atomic_order.
 #include "gsr_internal.h"
+#include "gsr_wave.h"
 
 #include <mutex>
 
@@ -58,33 +59,6 @@ __device__ unsigned long long* g_radix_trace = nullptr;
 #else
 #define GSR_TRACE(slot) do { } while (0)
 #endif
-
-__device__ __forceinline__ uint32_t wave_inclusive_sum(uint32_t v, int lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = (uint32_t)__shfl_up((int)v, d);
-        if (lane >= d) v += o;
-    }
-    return v;
-}
-
-// Exclusive sum over the 256 lanes of the workgroup; `scratch` is kWaves words of LDS; *total = sum of all.
-__device__ __forceinline__ uint32_t block_exclusive_sum(uint32_t v, uint32_t* scratch, int tid, uint32_t* total = nullptr) {
-    const int lane = tid & 63, wave = tid >> 6;
-    const uint32_t incl = wave_inclusive_sum(v, lane);
-    if (lane == 63) scratch[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) {
-        const uint32_t t = scratch[w];
-        if (w < wave) before += t;
-        all += t;
-    }
-    __syncthreads();
-    if (total) *total = all;
-    return before + incl - v;
-}
 
 // ------------------------------------------------------------------------------------------------
 // The projection kernel's tallies, summed by ONE workgroup (gsr_internal.h: TallyDuty): the totals go straight into the call's
@@ -122,7 +96,7 @@ __device__ __forceinline__ void counter_tally_duty(const TallyDuty& d, int group
             flag |= t[j].w >> 31;
         }
         uint32_t round_total;
-        uint32_t before = big + block_exclusive_sum(mine, s_scan, tid, &round_total);   // (big: the same in every lane)
+        uint32_t before = big + block_exclusive_scan<kWaves>(mine, s_scan, &round_total);   // (big: the same in every lane)
         big += round_total;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -132,12 +106,9 @@ __device__ __forceinline__ void counter_tally_duty(const TallyDuty& d, int group
     }
     uint32_t* z = reinterpret_cast<uint32_t*>(d.zero_block);
     for (int i = first; i < d.zero_words; i += stride) z[i] = 0u;
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) {
-        tot += __shfl_xor(tot, s);
-        vis += (uint32_t)__shfl_xor((int)vis, s);
-        flag |= (uint32_t)__shfl_xor((int)flag, s);
-    }
+    tot = wave_fold(tot, [](unsigned long long a, unsigned long long b) { return a + b; });
+    vis = wave_fold(vis, [](uint32_t a, uint32_t b) { return a + b; });
+    flag = wave_fold(flag, [](uint32_t a, uint32_t b) { return a | b; });
     if (lane == 0) { s_tot[wave] = tot; s_vis[wave] = vis; s_flag[wave] = flag; }
     __syncthreads();   // (one group, totals into the zero block itself: it is cleared before they land in it)
     if (tid == 0) {
@@ -259,7 +230,7 @@ __global__ void __launch_bounds__(kThreads) radix_scan_kernel(uint32_t* __restri
         if (t + 2 >= tiles) v.z = 0u;
         if (t + 3 >= tiles) v.w = 0u;
         uint32_t chunk_total;
-        const uint32_t before = carry + block_exclusive_sum(v.x + v.y + v.z + v.w, s_scan, tid, &chunk_total);
+        const uint32_t before = carry + block_exclusive_scan<kWaves>(v.x + v.y + v.z + v.w, s_scan, &chunk_total);
         if (t < tiles_pad) row[t / 4u] = make_uint4(before, before + v.x, before + v.x + v.y, before + v.x + v.y + v.z);
         carry += chunk_total;
     }
@@ -387,8 +358,8 @@ __global__ void __launch_bounds__(kThreads) radix_scatter_kernel(const uint32_t*
         total += c;
     }
     uint32_t tile_kept;   // = tile_n unless keys were dropped
-    const uint32_t seg_start = block_exclusive_sum(total, s_scan, tid, &tile_kept);
-    const uint32_t digit_start = block_exclusive_sum(digit_total, s_scan, tid);  // keys with a smaller digit
+    const uint32_t seg_start = block_exclusive_scan<kWaves>(total, s_scan, &tile_kept);
+    const uint32_t digit_start = block_exclusive_scan<kWaves>(digit_total, s_scan);  // keys with a smaller digit
     s_seg_start[tid] = seg_start;
     s_dst_base[tid] = digit_start + tile_offset - seg_start;
     if (kIota && kept_out != nullptr && block == 0u && tid == 255) *kept_out = digit_start + digit_total;  // what the later passes sort

@@ -21,6 +21,7 @@
 // No atomics anywhere: two calls on the same inputs give the same bits, forward and backward.
 // Defines the entry points gsr_ssim_scratch_bytes, gsr_ssim_forward and gsr_ssim_backward.
 #include "gsr_internal.h"
+#include "gsr_wave.h"
 
 namespace gsr {
 namespace {
@@ -47,12 +48,6 @@ struct SsimShape {
     int tiles_x;
     uint32_t tiles_per_plane, blocks;   // blocks = n c tiles_per_plane (one partial sum each)
 };
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
 
 struct TileAt {
     int x0, y0;      // first output pixel of the tile
@@ -156,7 +151,7 @@ __global__ __launch_bounds__(kThreads) void ssim_forward_kernel(SsimShape s, Ssi
                 coef[2 * total + off] = (2.0f * A1) / D;
             }
         }
-        sum = wave_sum(sum);
+        sum = wave_fold(sum, [](float a, float b) { return a + b; });   // the butterfly pairing: part of the fixed order
         if ((t & 63) == 0) wave_sums[t >> 6] = sum;
         __syncthreads();
         if (t == 0) partials[b] = ((wave_sums[0] + wave_sums[1]) + wave_sums[2]) + wave_sums[3];

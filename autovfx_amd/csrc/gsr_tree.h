@@ -4,6 +4,7 @@
 #pragma once
 
 #include "gsr_internal.h"
+#include "gsr_wave.h"
 
 namespace gsr {
 
@@ -53,16 +54,8 @@ __device__ __forceinline__ void wave_sync() {   // a wave's LDS operations run i
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
 }
-__device__ __forceinline__ float wave_min(float v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = fminf(v, __shfl_xor(v, d, 64));
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d, 64));
-    return v;
-}
+__device__ __forceinline__ float wave_min(float v) { return wave_fold(v, [](float a, float b) { return fminf(a, b); }); }
+__device__ __forceinline__ float wave_max(float v) { return wave_fold(v, [](float a, float b) { return fmaxf(a, b); }); }
 __device__ __forceinline__ float lane_value(float v, int lane) {   // lane: wave-uniform
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
 }

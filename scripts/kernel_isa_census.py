@@ -5,8 +5,9 @@ Compiles a unit of autovfx_amd/csrc with the library's flags to gfx950 assembly 
 vector instructions (and of the kinds the projection kernel was trimmed for: moves, selects, compares, cross-lane
 moves, division and square-root pieces), scalar, LDS and memory instructions, and the register / LDS figures of the
 kernel descriptor.
-    python scripts/kernel_isa_census.py [--markdown] [--tree DIR]
+    python scripts/kernel_isa_census.py [--markdown] [--tree DIR] [--units UNIT.hip ...]
 DIR is another checkout of this repository (its csrc is compiled with this checkout's flags), for a before / after.
+--units: every kernel of the named units instead of the three of the table below.
 """
 import os
 import re
@@ -76,7 +77,16 @@ def main():
         csrc = os.path.join(os.path.abspath(sys.argv[sys.argv.index("--tree") + 1]), "autovfx_amd", "csrc")
     units = {}
     rows = []
-    for unit, part, name in KERNELS:
+    kernels = KERNELS
+    if "--units" in sys.argv:   # every kernel the unit's assembly declares, under its mangled name
+        kernels = []
+        for unit in sys.argv[sys.argv.index("--units") + 1:]:
+            if unit.startswith("--"):
+                break
+            units[unit] = assembly(csrc, unit)
+            names = [l.split()[1] for l in units[unit] if l.strip().startswith(".amdhsa_kernel ")]
+            kernels += [(unit, n + ":", unit[:-4] + " " + re.sub(r"^_ZN3gsr(\d+_GLOBAL__N_1)?\d+", "", n)[:48]) for n in names]
+    for unit, part, name in kernels:
         if unit not in units:
             units[unit] = assembly(csrc, unit)
         rows.append((name, census(units[unit], part)))
@@ -87,7 +97,7 @@ def main():
             print(f"| `{name}` | " + " | ".join(str(c[k]) for k in COLS) + " |")
     else:
         for name, c in rows:
-            print(f"{name:26s} " + "  ".join(f"{k}={c[k]}" for k in COLS))
+            print((f"{name:26s} " if kernels is KERNELS else f"{name:64s} ") + "  ".join(f"{k}={c[k]}" for k in COLS))
 
 
 if __name__ == "__main__":
