@@ -196,6 +196,9 @@ SIGNATURES = {
     "gsr_face_areas_normals_backward": (_i, [_i64, _i64, _p, _p, _p, _p, _p, _p]),           # V F verts faces grad_areas grad_normals grad_verts stream
     "gsr_interp_face_attrs": (_i, [_i64, _i64, _i, _p, _p, _p, _p, _p]),                     # P F D pix_to_face bary attrs out stream
     "gsr_interp_face_attrs_backward": (_i, [_i64, _i64, _i, _p, _p, _p, _p, _p, _p, _p]),    # P F D pix_to_face bary attrs grad_out grad_bary grad_attrs stream
+    "gsr_texture_texels": (_i, [_i64, _i64, _i, _p, _p, _p, _p, _p, _p]),                    # P F T pix_to_face bary zbuf face_uvs texel stream
+    "gsr_texture_bake_view": (_i, [_i64, _i64, _i, _p, _p, _p, _p, _p, _i64, _p, _p, _p, _p]),   # P F T pix_to_face bary zbuf face_uvs rgb rgb_stride tex count owner stream
+    "gsr_texture_fill": (_i, [_i64, _i64, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p]),   # V F G A S n verts faces centers inv_scaled_rot features texel_offset texel_bary tex stream
     "gsr_normal_consistency_plan_scratch_bytes": (_sz, [_i64]),        # F
     "gsr_normal_consistency_plan": (_i, [_i64, _i64, _p, _p, _p, _p, _p, _sz, _p]),   # V F faces order partners pairs scratch scratch_bytes stream
     "gsr_normal_consistency_scratch_bytes": (_sz, [_i64]),             # F

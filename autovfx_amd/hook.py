@@ -95,7 +95,14 @@ AutoVFX reaches the rasterizer through two imports (paths under the reference tr
     ``from .mesh_normal_consistency import mesh_normal_consistency`` already binds the replacement; when ``install()`` runs after the
     import, ``pytorch3d.loss`` and every module that did ``from pytorch3d.loss import mesh_normal_consistency`` are rebound.
 
-Items 2-16 are the rows of ``_TARGETS``, applied by ``_patch`` to every matching module, whether it was imported before
+17. the same ``...sugar_model`` module, when it defines both ``extract_texture_image_and_uv_from_gaussians`` and ``SuGaR``, gets that function
+    (``sugar_model.py:2398-2614``, the last step before the textured ``.obj``) replaced by ``autovfx_amd.texture.drop_in(<the original>)``:
+    the UV atlas with the reference's values, the initial fill in one HIP pass, and per training camera the reference's render and
+    ``MeshRasterizer`` followed by two HIP launches on the fragments -- no shader, no index map, no ``nonzero``; ``texture_with_gaussian_renders=False``,
+    a CPU model, ``square_size`` outside 4..32, more than 8 Gaussians per triangle and calls under autograd run the original.
+    ``sugar_extractors/refined_mesh.py:9`` imports the function by name, so modules that already hold it are rebound.
+
+Items 2-17 are the rows of ``_TARGETS``, applied by ``_patch`` to every matching module, whether it was imported before
 ``install()`` or after (a ``sys.meta_path`` hook).  Each replaced attribute keeps the reference's original next to it as
 ``reference_<attr>`` on the module or class (``<module>.reference_render``, ``SceneRepresentation.reference_render_from_3DGS``, ...).
 ``uninstall()`` undoes every patch in reverse.
@@ -119,7 +126,7 @@ from typing import Callable, List, NamedTuple, Optional, Tuple
 
 _REPO_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _installed: Optional["_RendererHook"] = None
-patched_modules: List[str] = []          # names of the modules patched by items 2-7 and 10-16 (introspection / tests)
+patched_modules: List[str] = []          # names of the modules patched by items 2-7 and 10-17 (introspection / tests)
 patched_models: List[str] = []           # names of the modules whose ``GaussianModel.training_setup`` was wrapped (item 8)
 _strict = True                           # install(strict=...): may a failure to load the render path break the importing process?
 _gave_up = False                         # lenient mode: a replacement could not be loaded once; patch nothing more
@@ -302,6 +309,9 @@ _TARGETS = (
     # item 16: pytorch3d/loss/mesh_normal_consistency.py, the regulariser of sugar_trainers/refine.py:829-830
     _Target("mesh_normal_consistency", None, "mesh_normal_consistency", lambda original: _mark(_load("meshloss", "drop_in")(original)),
             "the HIP mesh normal consistency loss", needs=("mesh_normal_consistency",), rebind=True),
+    # item 17: sugar/sugar_scene/sugar_model.py, the texture of the refined mesh (:2398-2614), imported by name at refined_mesh.py:9
+    _Target("sugar_model", None, "extract_texture_image_and_uv_from_gaussians", lambda original: _mark(_load("texture", "drop_in")(original)),
+            "the HIP texture bake", needs=("extract_texture_image_and_uv_from_gaussians", "SuGaR"), rebind=True),
 )
 
 

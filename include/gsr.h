@@ -42,7 +42,8 @@
 extern "C" {
 #endif
 
-/* Still 20: + the first triangle a ray hits, on the closest-triangle plan (gsr_ray_first_hit).
+/* Still 20: + the texture bake of SuGaR's refined mesh (gsr_texture_texels, gsr_texture_bake_view, gsr_texture_fill).
+ * Still 20: + the first triangle a ray hits, on the closest-triangle plan (gsr_ray_first_hit).
  * Still 20: + the closest triangle of a mesh (gsr_closest_tri_plan_bytes, gsr_closest_tri_plan_scratch_bytes, gsr_closest_tri_plan,
  * gsr_closest_tri_query).
  * Still 20: + the mesh normal consistency loss (gsr_normal_consistency_plan_scratch_bytes, gsr_normal_consistency_plan,
@@ -621,6 +622,40 @@ GSR_API int gsr_interp_face_attrs(int64_t P, int64_t F, int D, const int64_t* pi
                                   float* out, void* stream);
 GSR_API int gsr_interp_face_attrs_backward(int64_t P, int64_t F, int D, const int64_t* pix_to_face, const float* bary, const float* attrs,
                                            const float* grad_out, float* grad_bary, float* grad_attrs, void* stream);
+
+/* The texture bake of SuGaR's refined mesh: extract_texture_image_and_uv_from_gaussians (sugar_model.py:2398-2614, called by
+ * sugar_extractors/refined_mesh.py:195) -- added under ABI 20.  The contract is the module docstring of autovfx_amd/texture.py (DESIGN.md
+ * 7n).  All arrays are contiguous device memory but rgb, whose rows are rgb_stride floats apart; every operation is an fp32 one in the
+ * order written, nothing contracted, division correctly rounded.  T is the atlas's edge in texels, a texel's index is row * T + col.
+ *   gsr_texture_texels     pix_to_face [P] int64, bary [P,3], zbuf [P], face_uvs [F,3,2] -> texel [P] int32.  Pixel p with f = pix_to_face[p]
+ *       is valid iff 0 <= f < F and zbuf[p] > 0 (a NaN zbuf is invalid).  Then, for c = 0, 1:
+ *       uv_c = (bary[p,0] face_uvs[f,0,c] + bary[p,1] face_uvs[f,1,c]) + bary[p,2] face_uvs[f,2,c]; g_c = uv_c * 2 - 1;
+ *       x_c = ((g_c + 1) / 2) * (T - 1), a NaN x_c makes the pixel invalid; i_c = rintf(fminf(T - 1, fmaxf(x_c, 0))), half to even;
+ *       texel = (T - 1 - i_1) * T + i_0.  An invalid pixel gets -1.
+ *   gsr_texture_bake_view  + rgb (pixel p's colour at rgb + p * rgb_stride, three floats), tex [T*T,3], count [T*T] fp32, owner [T*T]
+ *       uint32, all 0xFFFFFFFF on entry and again on return.  Two launches: every valid pixel does atomicMin(owner[texel], p); then the
+ *       pixel whose index equals owner[texel] writes tex[texel] = count[texel] == 0 ? rgb[p] : tex[texel] + rgb[p], count[texel] += 1 and
+ *       owner[texel] = 0xFFFFFFFF.  Of one call's pixels on a texel the lowest index is taken; no float atomics: the same bits on every run.
+ *   gsr_texture_fill       verts [V,3], faces [F,3] int64, centers [F*G,3], inv_scaled_rot [F*G,3,3], features [F*G,3], texel_offset
+ *       [2,n,2] int32, texel_bary [2,n,3] (row 0 for even faces, row 1 for odd ones) -> tex [T*T,3] with T = A * S, every element
+ *       written: 0.5, then per face f (square s = f >> 1 at (a, b) = (s / A, s % A)) and texel t of its table
+ *       x = (bary_0 v0 + bary_1 v1) + bary_2 v2; per Gaussian g < G of the face q_g as gsr_field_forward's (s = x - c, w = M^T s, the
+ *       square sum, the clamp to [0, 1e8] that leaves a NaN one); the first NaN q, else the first smallest q, chooses g, and
+ *       features[f*G+g] * 0.28209479177387814f + 0.5f goes to texel (T - 1 - (b S + o_1), a S + o_0).  A face with a vertex index outside
+ *       [0, V) and a table entry with an offset outside [0, S) write nothing.
+ * P == 0 (and, for the bake, F == 0) succeeds and launches nothing.  Refused (GSR_ERR_INVALID_ARG, nothing launched, no device needed): a
+ * negative count, P > 2^32 - 2, F >= 2^31 (the fill: F >= 2^28, V >= 2^31), T outside 1..46340 (T * T < 2^31), rgb_stride outside
+ * 3..2^31 - 1, G outside 1..8, S outside 4..32, A < 1 or A * S > 46340, more than A * A squares' worth of faces, n outside 1..S*S, a null
+ * pointer to an array that has elements (tex, count, owner and the tables always have), misaligned pointers (4 bytes, int64 8).  Enqueues on
+ * `stream` only: no scratch, no host synchronisation, no allocation. */
+GSR_API int gsr_texture_texels(int64_t P, int64_t F, int T, const int64_t* pix_to_face, const float* bary, const float* zbuf,
+                               const float* face_uvs, int32_t* texel, void* stream);
+GSR_API int gsr_texture_bake_view(int64_t P, int64_t F, int T, const int64_t* pix_to_face, const float* bary, const float* zbuf,
+                                  const float* face_uvs, const float* rgb, int64_t rgb_stride, float* tex, float* count, uint32_t* owner,
+                                  void* stream);
+GSR_API int gsr_texture_fill(int64_t V, int64_t F, int G, int A, int S, int n, const float* verts, const int64_t* faces,
+                             const float* centers, const float* inv_scaled_rot, const float* features, const int32_t* texel_offset,
+                             const float* texel_bary, float* tex, void* stream);
 
 /* The normal consistency loss of one triangle mesh: pytorch3d.loss.mesh_normal_consistency (sugar_trainers/refine.py:829-830, every
  * iteration of the refinement) -- added under ABI 20.  The contract is the module docstring of autovfx_amd/meshloss.py.
