@@ -9,8 +9,10 @@
 //   * a quadrant stops as soon as ITS 64 pixels are done, and a tile whose list is long or never saturates does not
 //     pin one 256-thread block for the whole launch;
 //   * while staging a batch of 64 list entries each lane runs the conservative reach test of its entry against the
-//     quadrant (gsr_device.h: splat_reaches_rect); the wave then walks only the set bits of the ballot, so entries
-//     that cannot touch the quadrant cost no LDS read and no per-pixel work at all;
+//     quadrant (gsr_device.h: splat_reaches_rect, the minimum of q over the two lines of the quadrant the centre can see;
+//     balloted per comparison, so which entries reach, which are staged in this round and which are left are scalar masks
+//     from the start); the wave then walks only the set bits, so entries that cannot touch the quadrant cost no LDS read
+//     and no per-pixel work at all;
 //   * the entries that reach are parked in LDS slots in list order, each with the terms of `power` that depend only on
 //     the pixel's column or only on its row (gsr_device.h: blend_power_terms), computed by the entry's own lane while it
 //     stages: the walk reads its column's pair and its row's pair and is left with an add, a multiply and a subtract
@@ -236,9 +238,9 @@ __global__ void __launch_bounds__(64, 8) blend_quadrant_kernel(BlendArgs a) {
         if (count > 0) gather(0);
 
         for (uint32_t first = 0; first < count; first += 64) {
-            const bool mine = first + (uint32_t)lane < count;
-            bool reach = mine && splat_reaches_rect(g_co, g_skip, g_xy, qx0, qy0, kQ, kQ);
-            unsigned long long todo = __ballot(reach);
+            // (the masks stay wave-uniform scalars: ballots of single comparisons, combined and consumed without a vector register)
+            unsigned long long todo = __ballot(first + (uint32_t)lane < count) &
+                                      splat_reaches_rect_ballot(g_co, g_skip, g_xy, qfx[0], qfx[kQ - 1], qfy[0], qfy[kQ - 1]);
             // The reaching entries are walked in rounds of at most Slots::kCount (C3: about 22 of a batch's 64 reach, so nearly
             // always one round); a later round builds its slots from the same g_* registers, which is why the next batch is
             // prefetched into them only once the batch's LAST round is built.
@@ -247,9 +249,9 @@ __global__ void __launch_bounds__(64, 8) blend_quadrant_kernel(BlendArgs a) {
                 if (todo != 0ull) {
                     // lane = entry: a reaching entry takes the slot of its rank among the reaching ones, so slots are in list order
                     const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(todo >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)todo, 0u));
-                    const bool staged = reach && rank < (uint32_t)Slots::kCount;
+                    const unsigned long long taken = todo & __ballot(rank < (uint32_t)Slots::kCount);
                     __syncthreads();  // single-wave workgroup: orders this wave's LDS reads / writes only
-                    if (staged) {
+                    if (__builtin_amdgcn_inverse_ballot_w64(taken)) {
                         char* slot = s_slots + rank * (uint32_t)Slots::kStride;
                         // The conic's diagonal goes in already multiplied by -0.5: scaling by a power of two commutes with every
                         // rounding of -0.5 * (cxx*dx*dx + cyy*dy*dy), so the terms give the same bits with one multiply less.
@@ -263,10 +265,8 @@ __global__ void __launch_bounds__(64, 8) blend_quadrant_kernel(BlendArgs a) {
                         else *reinterpret_cast<uint32_t*>(tail) = (uint32_t)lane;
                     }
                     __syncthreads();
-                    const unsigned long long taken = __ballot(staged);
                     n = (uint32_t)__popcll(taken);
                     todo &= ~taken;
-                    reach = reach && !staged;
                 }
                 if (todo == 0ull && first + 64 < count) gather(first + 64);
 

@@ -323,7 +323,7 @@ __device__ __forceinline__ F3 view_normal_rgb(F3 p, F3 cam, F3 axis) {
 // would skip the pair at every pixel.  This predicate returns false only when that is provable:
 // with q(d) = 0.5 (A dx^2 + C dy^2) + B dx dy  (power = -q, forward.cu:338), alpha >= 1/255 needs
 // q <= ln(255 o); q is convex, so its minimum over the tile's pixel rectangle is 0 if the centre is
-// inside and otherwise lies on one of the four edges, where it has a closed form.  The comparison
+// inside and otherwise lies on an edge the centre can see, where it has a closed form.  The comparison
 // keeps a 0.2 % + 1e-3 margin, ~10x the worst-case fp32 rounding of q for |rho| < 0.995
 // (error <= 4e-7 (1+|rho|)/(1-|rho|) q); anything less regular is never culled.  Dropping such a
 // pair cannot change any pixel, bit for bit (tests compare culled and unculled renders exactly).
@@ -343,20 +343,63 @@ __device__ __forceinline__ float edge_q(float A, float B, float C, float dx, flo
 // ln(255 o) is recovered from it; o <= 0 gives budget -inf (nothing visible), NaN keeps the pair.
 __device__ __forceinline__ float blend_skip_below(float opacity) { return -logf(255.0f * opacity) - 1.0e-4f; }
 
-__device__ __forceinline__ bool splat_reaches_rect(float4 co, float skip_below, float2 c, int px_first, int py_first, int w,
-                                                   int h) {
+// The minimum of q over the rectangle is taken over TWO lines, not four edges: only an edge that is visible from the
+// centre c (d = 0) can hold it.  Suppose the constrained minimiser x* sat on an edge c cannot see: the segment from x*
+// towards c would enter the rectangle, and q, convex with its minimum at c, is strictly smaller on that segment than at
+// x* -- a contradiction.  At most two edges are visible, the nearer vertical and the nearer horizontal one:
+//     the vertical line    x_e = clamp(0, x_lo, x_hi)  with  y = clamp(nb_c x_e, y_lo, y_hi)
+//     the horizontal line  y_e = clamp(0, y_lo, y_hi)  with  x = clamp(nb_a y_e, x_lo, x_hi)
+// (d = centre - pixel, so [x_lo, x_hi] x [y_lo, y_hi] is the rectangle seen from the centre).  Where the centre lies
+// within an interval the clamp gives 0 and the line runs through the rectangle's interior: that can only add a value
+// >= the true minimum.  A centre inside the rectangle gives q(0, 0) = 0 on both lines, so there is no separate "centre
+// inside" test; such a splat is then dropped only when its budget is below -1e-3, that is when alpha < 1/255 even at
+// the centre.
+// Non-finite operands never drop an entry the four-edge form kept.  The clamps are fminf(hi, fmaxf(lo, .)), which return
+// the other operand for a NaN, so one NaN centre coordinate leaves the unclamped minimiser of the other line, exactly as
+// it did on that line's edges; a line's clamped coordinate has the sign of the edges' and at most their magnitude, so an
+// infinite conic entry gives inf or NaN here wherever it gave that on every edge; a NaN q keeps the entry through the
+// negated comparison.  Two cases need the last term: a centre with BOTH coordinates NaN made every edge NaN, where the
+// clamps of 0 give the finite q(0, 0), and a budget of -inf (opacity 0) was kept by the centre-inside test.  budget + x_lo
+// is NaN or -inf in both and finite or +inf otherwise (also -inf for a centre at x = -inf, which is then kept too).
+// (tests/test_reach_lines_host.py holds both forms to each other and to the fp64 truth.)
+struct ReachTerms { float t, budget, guard; };   // the entry is dropped when t > budget and guard > -inf (regular conics only)
+
+__device__ __forceinline__ ReachTerms reach_terms(float A, float B, float C, float skip_below, float2 c, float fx_first, float fx_last,
+                                                  float fy_first, float fy_last) {
+    const float budget = -skip_below - 1.0e-4f;
+    const float x_lo = c.x - fx_last, x_hi = c.x - fx_first;
+    const float y_lo = c.y - fy_last, y_hi = c.y - fy_first;
+    const float nb_c = -B * __builtin_amdgcn_rcpf(C), nb_a = -B * __builtin_amdgcn_rcpf(A);
+    const float x_e = fminf(x_hi, fmaxf(x_lo, 0.f)), y_e = fminf(y_hi, fmaxf(y_lo, 0.f));
+    float qmin = edge_q(A, B, C, x_e, fminf(y_hi, fmaxf(y_lo, nb_c * x_e)));
+    qmin = fminf(qmin, edge_q(A, B, C, fminf(x_hi, fmaxf(x_lo, nb_a * y_e)), y_e));
+    return ReachTerms{qmin * 0.998f - 1.0e-3f, budget, budget + x_lo};
+}
+
+__device__ __forceinline__ bool splat_reaches_rect(float4 co, float skip_below, float2 c, float fx_first, float fx_last,
+                                                   float fy_first, float fy_last) {
     const float A = co.x, B = co.y, C = co.z;
     if (!(A > 0.f) || !(C > 0.f) || !((B * B) < 0.99f * (A * C))) return true;
-    const float budget = -skip_below - 1.0e-4f;
-    const float x_lo = c.x - (float)(px_first + w - 1), x_hi = c.x - (float)px_first;
-    const float y_lo = c.y - (float)(py_first + h - 1), y_hi = c.y - (float)py_first;
-    if (x_lo <= 0.f && x_hi >= 0.f && y_lo <= 0.f && y_hi >= 0.f) return true;  // centre inside the rectangle
-    const float nb_c = -B * __builtin_amdgcn_rcpf(C), nb_a = -B * __builtin_amdgcn_rcpf(A);
-    float qmin = edge_q(A, B, C, x_lo, fminf(y_hi, fmaxf(y_lo, nb_c * x_lo)));
-    qmin = fminf(qmin, edge_q(A, B, C, x_hi, fminf(y_hi, fmaxf(y_lo, nb_c * x_hi))));
-    qmin = fminf(qmin, edge_q(A, B, C, fminf(x_hi, fmaxf(x_lo, nb_a * y_lo)), y_lo));
-    qmin = fminf(qmin, edge_q(A, B, C, fminf(x_hi, fmaxf(x_lo, nb_a * y_hi)), y_hi));
-    return !(qmin * 0.998f - 1.0e-3f > budget);
+    const ReachTerms r = reach_terms(A, B, C, skip_below, c, fx_first, fx_last, fy_first, fy_last);
+    return !(r.t > r.budget) || !(r.guard > -__builtin_huge_valf());
+}
+
+// The same predicate for every lane of a wave at once, as the 64-bit mask __ballot(splat_reaches_rect(...)) would give in
+// uniform control flow: each comparison is balloted on its own and the masks are combined in scalar registers, where the
+// ballot of the lane-wise disjunction goes through a vector register and back and the early return costs exec-mask branches.
+// Every lane runs the arithmetic (an irregular conic's terms are garbage that its own mask bits override).
+__device__ __forceinline__ unsigned long long splat_reaches_rect_ballot(float4 co, float skip_below, float2 c, float fx_first,
+                                                                        float fx_last, float fy_first, float fy_last) {
+    const float A = co.x, B = co.y, C = co.z;
+    const ReachTerms r = reach_terms(A, B, C, skip_below, c, fx_first, fx_last, fy_first, fy_last);
+    return __ballot(!(A > 0.f)) | __ballot(!(C > 0.f)) | __ballot(!((B * B) < 0.99f * (A * C))) | __ballot(!(r.t > r.budget)) |
+           __ballot(!(r.guard > -__builtin_huge_valf()));
+}
+
+__device__ __forceinline__ bool splat_reaches_rect(float4 co, float skip_below, float2 c, int px_first, int py_first, int w,
+                                                   int h) {
+    return splat_reaches_rect(co, skip_below, c, (float)px_first, (float)(px_first + w - 1), (float)py_first,
+                              (float)(py_first + h - 1));
 }
 
 __device__ __forceinline__ bool splat_reaches_tile(float4 co, float skip_below, float2 c, int tile_x, int tile_y) {

@@ -12,9 +12,9 @@ the stages an entry can stop at:
                                bound check that leads to the next slot / the loop tail
 and prints per stage VALU (of which comparisons / transcendental / packed), SALU, LDS and wait instructions, averaged
 over the entries of the body.
-    python scripts/blend_isa_census.py [--markdown] [--extra] [--tree DIR] [--dump]
+    python scripts/blend_isa_census.py [--markdown] [--extra] [--tree DIR] [--dump] [--staging]
 --extra: blend_quadrant_kernel<true>.  DIR is another checkout of this repository (its csrc is compiled with this
-checkout's flags), for a before / after.
+checkout's flags), for a before / after.  --staging: the per-batch staging block of both kernels instead (staging_census).
 """
 import os
 import re
@@ -134,8 +134,28 @@ def stage_table(mangled_part="blend_quadrant_kernelILb0", csrc=None):
     return len(ent), rows
 
 
+def staging_census(asm, mangled_part="blend_quadrant_kernelILb0"):
+    """What a batch of 64 list entries costs before its walk starts: the instructions laid out between the header of the loop
+    that encloses the walk loop (the batch loop: reach test, rank, slot build, the next batch's gather) and the walk loop's own
+    header, by kind.  A static count of the straight-line layout: every lane runs the reach test, the staged lanes the slot build."""
+    body = kernel_body(asm, mangled_part)
+    first = body.index(walk_loop(body)[0])
+    parents = [m.group(1) for m in (re.search(r"Parent Loop (BB\d+_\d+) ", l) for l in body[first:first + 8]) if m]
+    header = next(i for i, l in enumerate(body) if l.startswith(".L" + parents[-1] + ":"))
+    kinds = [k for k, _ in instructions(body[header:first])]
+    cnt = {c: kinds.count(c) for c in KINDS}
+    return {"VALU": cnt["valu"] + cnt["v_cmp"] + cnt["trans"] + cnt["v_pk"], "v_cmp": cnt["v_cmp"], "trans": cnt["trans"],
+            "SALU": cnt["salu"] + cnt["branch"], "lds": cnt["lds"], "vmem": cnt["vmem"], "wait": cnt["wait"]}
+
+
 def main():
-    part = "blend_quadrant_kernelILb1" if "--extra" in sys.argv else "blend_quadrant_kernelILb0"
+    if "--staging" in sys.argv:
+        csrc = os.path.join(os.path.abspath(sys.argv[sys.argv.index("--tree") + 1]), "autovfx_amd", "csrc") if "--tree" in sys.argv else None
+        asm = assembly(csrc)
+        for part in ("blend_quadrant_kernelILb0", "blend_quadrant_kernelILb1"):
+            print(part, "staging per batch of 64 entries:", staging_census(asm, part))
+        return
+    part ="blend_quadrant_kernelILb1" if "--extra" in sys.argv else "blend_quadrant_kernelILb0"
     csrc = None
     if "--tree" in sys.argv:
         csrc = os.path.join(os.path.abspath(sys.argv[sys.argv.index("--tree") + 1]), "autovfx_amd", "csrc")

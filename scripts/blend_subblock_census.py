@@ -38,14 +38,14 @@ def reach(A, B, C, o, cx, cy, x0, y0, w, h):
     ok_reg = (A > 0) & (C > 0) & (B * B < 0.99 * A * C)
     x_lo, x_hi = cx - (x0 + w - 1), cx - x0
     y_lo, y_hi = cy - (y0 + h - 1), cy - y0
-    inside = (x_lo <= 0) & (x_hi >= 0) & (y_lo <= 0) & (y_hi >= 0)
     nb_c, nb_a = -B / C, -B / A
     q = lambda dx, dy: 0.5 * (A * dx * dx + C * dy * dy) + B * dx * dy
-    qmin = q(x_lo, np.minimum(y_hi, np.maximum(y_lo, nb_c * x_lo)))
-    qmin = np.minimum(qmin, q(x_hi, np.minimum(y_hi, np.maximum(y_lo, nb_c * x_hi))))
-    qmin = np.minimum(qmin, q(np.minimum(x_hi, np.maximum(x_lo, nb_a * y_lo)), y_lo))
-    qmin = np.minimum(qmin, q(np.minimum(x_hi, np.maximum(x_lo, nb_a * y_hi)), y_hi))
-    return (~ok_reg) | inside | ~(qmin * 0.998 - 1e-3 > budget)
+    # the minimum over the rectangle lies on an edge the centre can see: the vertical and the horizontal line through the
+    # rectangle's point nearest the centre (a centre inside gives q = 0 on both)
+    x_e, y_e = np.minimum(x_hi, np.maximum(x_lo, 0.0)), np.minimum(y_hi, np.maximum(y_lo, 0.0))
+    qmin = q(x_e, np.minimum(y_hi, np.maximum(y_lo, nb_c * x_e)))
+    qmin = np.minimum(qmin, q(np.minimum(x_hi, np.maximum(x_lo, nb_a * y_e)), y_e))
+    return (~ok_reg) | ~(qmin * 0.998 - 1e-3 > budget) | ~(budget + x_lo > -np.inf)
 
 rs = np.random.default_rng(0)
 tiles = rs.choice(gx * gy, NTILES, replace=False)
