@@ -196,6 +196,8 @@ SIGNATURES = {
     "gsr_face_areas_normals_backward": (_i, [_i64, _i64, _p, _p, _p, _p, _p, _p]),           # V F verts faces grad_areas grad_normals grad_verts stream
     "gsr_interp_face_attrs": (_i, [_i64, _i64, _i, _p, _p, _p, _p, _p]),                     # P F D pix_to_face bary attrs out stream
     "gsr_interp_face_attrs_backward": (_i, [_i64, _i64, _i, _p, _p, _p, _p, _p, _p, _p]),    # P F D pix_to_face bary attrs grad_out grad_bary grad_attrs stream
+    "gsr_bound_gaussians": (_i, [_i64, _i64, _i, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p]),   # V F G verts faces bary complex log_scales thickness standardize points scaling quaternions stream
+    "gsr_bound_gaussians_backward": (_i, [_i64, _i64, _i, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p]),   # V F G verts faces bary complex log_scales standardize g_points g_scaling g_quaternions grad_verts grad_complex grad_log_scales stream
     "gsr_texture_texels": (_i, [_i64, _i64, _i, _p, _p, _p, _p, _p, _p]),                    # P F T pix_to_face bary zbuf face_uvs texel stream
     "gsr_texture_bake_view": (_i, [_i64, _i64, _i, _p, _p, _p, _p, _p, _i64, _p, _p, _p, _p]),   # P F T pix_to_face bary zbuf face_uvs rgb rgb_stride tex count owner stream
     "gsr_texture_fill": (_i, [_i64, _i64, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p]),   # V F G A S n verts faces centers inv_scaled_rot features texel_offset texel_bary tex stream

@@ -102,7 +102,17 @@ AutoVFX reaches the rasterizer through two imports (paths under the reference tr
     a CPU model, ``square_size`` outside 4..32, more than 8 Gaussians per triangle and calls under autograd run the original.
     ``sugar_extractors/refined_mesh.py:9`` imports the function by name, so modules that already hold it are rebound.
 
-Items 2-17 are the rows of ``_TARGETS``, applied by ``_patch`` to every matching module, whether it was imported before
+18. the same ``SuGaR`` class, when it has ``surface_mesh`` and ``get_covariance``, gets the getters of its properties ``points``,
+    ``scaling`` and ``quaternions`` (``sugar_model.py:376-391``, ``:408-423``, ``:425-452``: each read once per
+    ``render_image_gaussian_rasterizer`` call of the refinement and differentiated into the vertices, ``_scales`` and ``_quaternions``)
+    replaced by ``autovfx_amd.bound.drop_in_points`` / ``_scaling`` / ``_quaternions(<the original getter>)``: for a model bound to a
+    surface mesh, one fused HIP launch per access with only that output wanted, one more for its backward, no host synchronisation
+    (the reference's ``matrix_to_quaternion`` ends in a ``nonzero``); an unbound model, ``editable=True``, a ``scale_activation`` that is not
+    ``torch.exp``, a CPU model, other dtypes and graph capture run the original getter.  The target is a ``property``: it is replaced by
+    ``property(<ours>, original.fset, original.fdel)``, and ``SuGaR.reference_<name>`` is the original property.  torch and the library
+    are imported at the first access.  The geometry-reuse wrapper of item 4 is unaffected.
+
+Items 2-18 are the rows of ``_TARGETS``, applied by ``_patch`` to every matching module, whether it was imported before
 ``install()`` or after (a ``sys.meta_path`` hook).  Each replaced attribute keeps the reference's original next to it as
 ``reference_<attr>`` on the module or class (``<module>.reference_render``, ``SceneRepresentation.reference_render_from_3DGS``, ...).
 ``uninstall()`` undoes every patch in reverse.
@@ -126,7 +136,7 @@ from typing import Callable, List, NamedTuple, Optional, Tuple
 
 _REPO_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _installed: Optional["_RendererHook"] = None
-patched_modules: List[str] = []          # names of the modules patched by items 2-7 and 10-17 (introspection / tests)
+patched_modules: List[str] = []          # names of the modules patched by items 2-7 and 10-18 (introspection / tests)
 patched_models: List[str] = []           # names of the modules whose ``GaussianModel.training_setup`` was wrapped (item 8)
 _strict = True                           # install(strict=...): may a failure to load the render path break the importing process?
 _gave_up = False                         # lenient mode: a replacement could not be loaded once; patch nothing more
@@ -220,8 +230,8 @@ def _with_hip_densify(name: str) -> Callable:
 
 
 def _with_hip_sugar_method(name: str, module: str = "field", what: str = "the HIP density field") -> Callable:
-    """make() for a ``SuGaR`` method with a drop-in of its own (``compute_density`` / ``get_field_values`` in ``field``,
-    ``compute_level_surface_points_from_camera_fast`` in ``levelset``): ``autovfx_amd.<module>.drop_in_<name>(original)``, built (torch, libgsr_hip.so) at the first call; it runs ``original`` itself for
+    """make() for a ``SuGaR`` method or property getter with a drop-in of its own (``compute_density`` / ``get_field_values`` in ``field``,
+    ``compute_level_surface_points_from_camera_fast`` in ``levelset``, ``points`` / ``scaling`` / ``quaternions`` in ``bound``): ``autovfx_amd.<module>.drop_in_<name>(original)``, built (torch, libgsr_hip.so) at the first call; it runs ``original`` itself for
     the calls its kernels do not take."""
     def make(original: Callable) -> Callable:
         built = []
@@ -252,10 +262,10 @@ def _with_mesh_attrs(name: str) -> Callable:
 class _Target(NamedTuple):
     leaf: str                            # the last component of the module's name
     cls: Optional[str]                   # the class in the module that owns ``attr``; None: the module itself
-    attr: str                            # what is replaced; the original stays as ``reference_<attr>`` on the owner
+    attr: str                            # what is replaced (a property: its getter); the original stays as ``reference_<attr>`` on the owner
     make: Callable                       # make(original) -> the replacement; raises when torch or the library cannot be loaded
     what: str                            # the lenient stderr line: "<module>.<attr> left as the reference's: <what> could not be loaded"
-    needs: Tuple[str, ...] = ()          # names that must all be callable in the owner's own namespace
+    needs: Tuple[str, ...] = ()          # names that must all be callable, or properties, in the owner's own namespace
     rebind: bool = False                 # also rebind already-imported modules that hold the original
     record: List[str] = patched_modules
 
@@ -312,6 +322,10 @@ _TARGETS = (
     # item 17: sugar/sugar_scene/sugar_model.py, the texture of the refined mesh (:2398-2614), imported by name at refined_mesh.py:9
     _Target("sugar_model", None, "extract_texture_image_and_uv_from_gaussians", lambda original: _mark(_load("texture", "drop_in")(original)),
             "the HIP texture bake", needs=("extract_texture_image_and_uv_from_gaussians", "SuGaR"), rebind=True),
+    # item 18: the same class's properties that turn the bound surface mesh into Gaussians (:376-391, :408-423, :425-452)
+    *(_Target("sugar_model", "SuGaR", name, _with_hip_sugar_method(name, "bound", "the HIP bound Gaussians"), "the HIP bound Gaussians",
+              needs=("surface_mesh", "get_covariance"))
+      for name in ("points", "scaling", "quaternions")),
 )
 
 
@@ -354,10 +368,12 @@ def _patch_row(module: types.ModuleType, t: _Target) -> None:
         return
     d = vars(owner)
     original = d.get(t.attr)
-    if original is None or _is_ours(original) or not all(callable(d.get(k)) for k in t.needs):
+    getter = isinstance(original, property)          # a property target: its fget is what make() wraps
+    if original is None or _is_ours(original.fget if getter else original) or \
+            not all(callable(d.get(k)) or isinstance(d.get(k), property) for k in t.needs):
         return
     try:
-        ours = t.make(original)
+        ours = property(t.make(original.fget), original.fset, original.fdel) if getter else t.make(original)
     except Exception as e:   # torch absent, libgsr_hip.so not built / stale ABI, a GPU-less helper that inherited the environment
         where = module.__name__ if t.cls is None else f"{module.__name__}.{t.cls}"
         _could_not_load(f"{where}.{t.attr} left as the reference's: {t.what}", e)

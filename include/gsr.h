@@ -42,7 +42,8 @@
 extern "C" {
 #endif
 
-/* Still 20: + the texture bake of SuGaR's refined mesh (gsr_texture_texels, gsr_texture_bake_view, gsr_texture_fill).
+/* Still 20: + the Gaussians bound to a surface mesh, with their backward (gsr_bound_gaussians, gsr_bound_gaussians_backward).
+ * Still 20: + the texture bake of SuGaR's refined mesh (gsr_texture_texels, gsr_texture_bake_view, gsr_texture_fill).
  * Still 20: + the first triangle a ray hits, on the closest-triangle plan (gsr_ray_first_hit).
  * Still 20: + the closest triangle of a mesh (gsr_closest_tri_plan_bytes, gsr_closest_tri_plan_scratch_bytes, gsr_closest_tri_plan,
  * gsr_closest_tri_query).
@@ -622,6 +623,35 @@ GSR_API int gsr_interp_face_attrs(int64_t P, int64_t F, int D, const int64_t* pi
                                   float* out, void* stream);
 GSR_API int gsr_interp_face_attrs_backward(int64_t P, int64_t F, int D, const int64_t* pix_to_face, const float* bary, const float* attrs,
                                            const float* grad_out, float* grad_bary, float* grad_attrs, void* stream);
+
+/* The Gaussians SuGaR binds to a surface mesh: SuGaR.points, SuGaR.scaling and SuGaR.quaternions with binded_to_surface_mesh set
+ * (sugar_model.py:376-391, :408-423, :425-452), G Gaussians per face, and their backward -- added under ABI 20.  All arrays are contiguous
+ * device memory; every operation is an fp32 one in the order written, nothing contracted, division and sqrt correctly rounded, expf the
+ * device library's (the contract, operation by operation, is the module docstring of autovfx_amd/bound.py).
+ *   gsr_bound_gaussians           verts [V,3] fp32, faces [F,3] int64, bary [G,3], complex [F G,2] (the raw _quaternions), log_scales [F G,2]
+ *       (the raw _scales), thickness: ONE float in device memory, read by the kernel -> points [F G,3] = (v0 b0 + v1 b1) + v2 b2,
+ *       scaling [F G,3] = (thickness, expf(s0), expf(s1)), quaternions [F G,4] (w, x, y, z): the face normal of
+ *       gsr_face_areas_normals re-normalised (R_0), normalize(v0 - v1) and normalize(R_0 x that) turned by normalize(complex) (R_1, R_2),
+ *       pytorch3d 0.7.4's matrix_to_quaternion of [R_0 | R_1 | R_2] (the first of the largest q_abs, floor 0.1), normalised; standardize
+ *       != 0 negates a row whose real part is negative (later pytorch3d releases).  Any of the three outputs may be NULL and is then
+ *       neither computed nor stored; the inputs only the skipped outputs read may be NULL too.  A face with an index outside [0, V)
+ *       reads no vertex and gets points 0 and quaternions 0; scaling does not depend on the face.
+ *   gsr_bound_gaussians_backward  + grad_points, grad_scaling, grad_quaternions (any may be NULL: no gradient arrives there) ->
+ *       grad_complex [F G,2] and grad_log_scales [F G,2], plain stores, every element written; grad_verts [V,3], zeroed on the stream by
+ *       the call, then nine float atomic adds per face: its three vertex gradients summed in registers over its G Gaussians and the
+ *       outputs.  The forward is recomputed; every clamp takes the branch autograd takes; the candidates not taken get nothing; the
+ *       thickness gets no gradient.  Faces with an index outside [0, V) add nothing and get grad_complex 0.
+ * grad_verts holds the contract's fp32 terms added in an order that is free; everything else is the same bits on every run.  Refused
+ * (GSR_ERR_INVALID_ARG, nothing launched, no device needed): a negative count, G outside 1..8, V or F G >= 2^31, a null pointer to an
+ * array that is needed and has elements, misaligned pointers (floats 4 bytes, int64 8).  Enqueues on `stream` only: no scratch, no host
+ * synchronisation, no allocation; the only atomics are fp32 adds. */
+GSR_API int gsr_bound_gaussians(int64_t V, int64_t F, int G, const float* verts, const int64_t* faces, const float* bary,
+                                const float* complex_, const float* log_scales, const float* thickness, int standardize, float* points,
+                                float* scaling, float* quaternions, void* stream);
+GSR_API int gsr_bound_gaussians_backward(int64_t V, int64_t F, int G, const float* verts, const int64_t* faces, const float* bary,
+                                         const float* complex_, const float* log_scales, int standardize, const float* grad_points,
+                                         const float* grad_scaling, const float* grad_quaternions, float* grad_verts,
+                                         float* grad_complex, float* grad_log_scales, void* stream);
 
 /* The texture bake of SuGaR's refined mesh: extract_texture_image_and_uv_from_gaussians (sugar_model.py:2398-2614, called by
  * sugar_extractors/refined_mesh.py:195) -- added under ABI 20.  The contract is the module docstring of autovfx_amd/texture.py (DESIGN.md

@@ -1,0 +1,335 @@
+"""The bound Gaussians on the GPU: the kernels of gsr_bound.hip against the numpy restatement of autovfx_amd/bound.py, bit for bit where the
+contract fixes the bits (``expf`` within its 2-step window, ``grad_verts`` through the bound on an atomically summed element), at every size,
+output subset, vertex layout, candidate and degenerate row, and the drop-ins under ``install()`` against the original getters.  Every GPU
+result is read after ``torch.cuda.synchronize()``, which raises if a kernel faulted: a fault fails the test that caused it."""
+from __future__ import annotations
+
+import itertools
+import sys
+import types
+
+import numpy as np
+import pytest
+import torch
+
+import bound_cases as BC
+from autovfx_amd import bound, hook
+from meshattrs_cases import atomic_sum_check
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+F32 = np.float32
+INPUTS = ("verts", "faces", "bary", "complex", "log_scales", "thickness")
+matrix_to_quaternion = BC.matrix_to_quaternion       # what the probe of a getter defined in this module finds in its globals
+
+
+def same_bits(got, want, what):
+    got, want = np.ascontiguousarray(got, F32), np.ascontiguousarray(want, F32)
+    assert got.shape == want.shape, what
+    nan = np.isnan(want)
+    assert np.array_equal(np.isnan(got), nan), f"{what}: the NaNs sit elsewhere"
+    assert np.array_equal(got.view(np.uint32)[~nan], want.view(np.uint32)[~nan]), \
+        f"{what}: {int((got.view(np.uint32)[~nan] != want.view(np.uint32)[~nan]).sum())} elements differ"
+
+
+def exp_window(got, log_scales, what):
+    """``expf`` is the one operation whose bits may differ: within 2 steps of the correctly rounded value (7g)."""
+    e0 = np.exp(np.asarray(log_scales, np.float64)).astype(F32)
+    lo = hi = e0
+    for _ in range(2):
+        lo, hi = np.nextafter(lo, F32(-np.inf)), np.nextafter(hi, F32(np.inf))
+    assert np.all((got >= lo) & (got <= hi)), what
+
+
+def run(case, want=BC.OUTPUTS, standardize=False):
+    """The node on the GPU with the case's upstream gradients for the wanted outputs: outputs and gradients as numpy arrays."""
+    t = {k: torch.from_numpy(np.ascontiguousarray(case[k])).to(DEV) for k in INPUTS}
+    for k in ("verts", "complex", "log_scales"):
+        t[k].requires_grad_(True)
+    outs = dict(zip(want, bound.bound_gaussians(*(t[k] for k in INPUTS), want=want, standardize=standardize)))
+    sum((outs[name] * torch.from_numpy(case["grad_" + name]).to(DEV)).sum() for name in want).backward()
+    torch.cuda.synchronize()
+    got = {name: o.detach().cpu().numpy() for name, o in outs.items()}
+    got.update(grad_verts=t["verts"].grad.cpu().numpy(), grad_complex=t["complex"].grad.cpu().numpy(), grad_log_scales=t["log_scales"].grad.cpu().numpy())
+    return got
+
+
+def against_the_restatement(case, got, want=BC.OUTPUTS, standardize=False, what="", finite=True):
+    c = case
+    points, scaling, quaternions = bound.bound_gaussians_host(*(c[k] for k in INPUTS), standardize)
+    assert sorted(k for k in got if k in BC.OUTPUTS) == sorted(want)
+    if "points" in want:
+        same_bits(got["points"], points, what + ": points")
+    if "quaternions" in want:
+        same_bits(got["quaternions"], quaternions, what + ": quaternions")
+    if "scaling" in want:
+        same_bits(got["scaling"][:, 0], scaling[:, 0], what + ": thickness")
+        exp_window(got["scaling"][:, 1:], c["log_scales"], what + ": exp")
+        with np.errstate(all="ignore"):
+            same_bits(got["grad_log_scales"], c["grad_scaling"][:, 1:] * got["scaling"][:, 1:], what + ": grad_log_scales")
+    else:
+        assert not got["grad_log_scales"].any(), what
+    up = {name: (c["grad_" + name] if name in want else None) for name in BC.OUTPUTS}
+    _gv, grad_complex, _gl, added, rows = bound.bound_gaussians_backward_host(*(c[k] for k in INPUTS[:5]), up["points"], up["scaling"],
+                                                                             up["quaternions"], standardize)
+    same_bits(got["grad_complex"], grad_complex, what + ": grad_complex")
+    if finite:
+        return atomic_sum_check(got["grad_verts"], added, rows, len(c["verts"]), what + ": grad_verts")
+
+
+# ---- every size ---------------------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("G", [1, 3, 4, 6, 8])
+@pytest.mark.parametrize("n_faces", [1, 63, 64, 65, 255, 256, 257, 4097])
+def test_against_the_restatement_at_every_size(n_faces, G):
+    case = BC.sized_case(n_faces, G, seed=n_faces % 97 + G)
+    against_the_restatement(case, run(case), what=f"F = {n_faces}, G = {G}")
+
+
+@pytest.mark.parametrize("want", [w for r in (1, 2) for w in itertools.combinations(BC.OUTPUTS, r)], ids="+".join)
+def test_output_subsets(want):
+    """Each single output and each pair: null outputs in the forward, null upstream gradients in the backward."""
+    case = BC.sized_case(257, 3, seed=12)
+    against_the_restatement(case, run(case, want), want, what="+".join(want))
+
+
+def test_vertices_spread_to_the_last_index():
+    case = BC.sized_case(130, 4, seed=5, V=100_000, spread=True)
+    assert case["faces"].max() == 99_999
+    got = run(case)
+    against_the_restatement(case, got, what="spread")
+    unused = np.ones(100_000, bool)
+    unused[case["faces"].reshape(-1)] = False
+    assert not got["grad_verts"][unused].any()
+
+
+def test_300_faces_share_three_vertices():
+    case = BC.shared_case(300, 6, seed=8)
+    worst = against_the_restatement(case, run(case), what="shared")
+    print(f"300 terms per element: {worst:.3f} of the bound")
+
+
+# ---- candidates and the standardize flag --------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("standardize", [False, True])
+@pytest.mark.parametrize("k", range(4))
+def test_the_four_branches(k, standardize):
+    case = BC.branch_case(k, 64, 3, seed=2)
+    got = run(case, standardize=standardize)
+    against_the_restatement(case, got, standardize=standardize, what=f"candidate {k}")
+    BC.check(case, {n: got[n] for n in BC.OUTPUTS + BC.GRADS}, standardize, what=f"candidate {k} against the truth")
+    if standardize:
+        assert (got["quaternions"][:, 0] >= 0).all()
+    elif k:
+        assert (got["quaternions"][:, 0] < 0).any()
+
+
+def test_an_exact_tie_goes_to_the_lowest_index():
+    case = BC.tie_case()
+    got = run(case)
+    against_the_restatement(case, got, what="tie")
+    half = np.sqrt(F32(0.5))
+    assert np.allclose(got["quaternions"][0], [half, half, 0, 0], atol=1e-7) and got["quaternions"][0, 0] > 0
+
+
+def test_standardize_flips_a_row_with_negative_real_part_and_its_gradient():
+    case = BC.branch_case(1, 64, 3, seed=6)
+    plain, flagged = run(case, ("quaternions",)), run(case, ("quaternions",), standardize=True)
+    negative = plain["quaternions"][:, 0] < 0
+    assert negative.any() and (~negative).any()
+    same_bits(flagged["quaternions"], np.where(negative[:, None], -plain["quaternions"], plain["quaternions"]), "the flipped rows")
+    mirrored = dict(case, grad_quaternions=np.where(negative[:, None], -case["grad_quaternions"], case["grad_quaternions"]))
+    other = run(mirrored, ("quaternions",))
+    same_bits(flagged["grad_complex"], other["grad_complex"], "the flipped rows' gradient")
+    same_bits(flagged["grad_verts"], other["grad_verts"], "the flipped rows' vertex gradient")      # (every face has its own vertices)
+
+
+# ---- degenerate rows ----------------------------------------------------------------------------------------------------------------------
+
+def _neighbours_untouched(case, plain_got, got, faces_changed, G):
+    keep = np.ones(len(case["complex"]), bool)
+    for f in faces_changed:
+        keep[G * f:G * (f + 1)] = False
+    for name in BC.OUTPUTS + ("grad_complex", "grad_log_scales"):
+        same_bits(got[name][keep], plain_got[name][keep], f"neighbours: {name}")
+
+
+def test_degenerate_rows():
+    G = 3
+    plain = BC.branch_case(0, 40, G, seed=4)          # every face has its own vertices: a face's trouble stays with it
+    plain_got = run(plain)
+    case = {k: v.copy() for k, v in plain.items()}
+    case["verts"][3 * 5 + 1] = case["verts"][3 * 5]                                   # face 5: v1 = v0, zero area and no first edge
+    case["verts"][3 * 6 + 2] = 0.5 * (case["verts"][3 * 6] + case["verts"][3 * 6 + 1])   # face 6: (nearly) collinear
+    case["complex"][G * 7 + 1] = 0.0                                                  # a Gaussian of face 7: complex = (0, 0)
+    case["faces"][9] = [27, 28, 3 * 40]                                               # face 9: an index past the end
+    case["faces"][10] = [-1, 31, 32]                                                  # face 10: a negative index
+    got = run(case)
+    against_the_restatement(case, got, what="degenerate")
+    for name in BC.OUTPUTS + BC.GRADS:
+        assert np.isfinite(got[name]).all(), name
+    for f in (9, 10):
+        rows = slice(G * f, G * (f + 1))
+        assert not got["points"][rows].any() and not got["quaternions"][rows].any() and not got["grad_complex"][rows].any()
+    assert not got["grad_verts"][[27, 28, 29, 30, 31, 32]].any()
+    _neighbours_untouched(case, plain_got, got, (5, 6, 7, 9, 10), G)
+    same_bits(got["scaling"], plain_got["scaling"], "scaling does not depend on the face")
+
+
+def test_a_non_finite_vertex_stays_with_its_face():
+    G = 3
+    plain = BC.branch_case(0, 40, G, seed=4)
+    plain_got = run(plain)
+    case = {k: v.copy() for k, v in plain.items()}
+    case["verts"][3 * 11 + 2, 1] = np.nan
+    case["verts"][3 * 12, 0] = np.inf
+    got = run(case)
+    against_the_restatement(case, got, what="non-finite", finite=False)
+    _neighbours_untouched(case, plain_got, got, (11, 12), G)
+    others = np.ones(len(case["verts"]), bool)
+    others[33:39] = False
+    same_bits(got["grad_verts"][others], plain_got["grad_verts"][others], "the other faces' vertices")
+
+
+# ---- determinism --------------------------------------------------------------------------------------------------------------------------
+
+def test_the_same_bits_on_every_run_and_on_a_side_stream():
+    case = BC.branch_case(2, 300, 6, seed=9)         # every face has its own vertices: one atomic term per element, so fixed bits
+    first, second = run(case), run(case)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        third = run(case)
+    side.synchronize()
+    for name in BC.OUTPUTS + BC.GRADS:
+        same_bits(second[name], first[name], f"second run: {name}")
+        same_bits(third[name], first[name], f"side stream: {name}")
+
+
+@pytest.mark.parametrize("want", [BC.OUTPUTS, ("points",), ("scaling", "quaternions")], ids="+".join)
+def test_outputs_prefilled_with_nan_come_back_fully_written(want):
+    from autovfx_amd import _lib
+    case = BC.sized_case(257, 4, seed=13)
+    case["faces"][100] = [0, 1, len(case["verts"])]
+    t = {k: torch.from_numpy(np.ascontiguousarray(case[k])).to(DEV) for k in INPUTS}
+    t["thickness"] = t["thickness"].reshape(1)
+    V, F, G, N = len(case["verts"]), len(case["faces"]), 4, len(case["complex"])
+    nan = lambda *shape: torch.full(shape, float("nan"), device=DEV)
+    out = {name: (nan(N, width) if name in want else None) for name, width in zip(BC.OUTPUTS, (3, 3, 4))}
+    _lib.call("gsr_bound_gaussians", V, F, G, *(_lib.ptr(t[k]) for k in INPUTS), 0, *(_lib.ptr(out[n]) for n in BC.OUTPUTS), device=t["verts"].device)
+    up = {name: (torch.from_numpy(case["grad_" + name]).to(DEV) if name in want else None) for name in BC.OUTPUTS}
+    grad_verts, grad_complex, grad_log_scales = nan(V, 3), nan(N, 2), nan(N, 2)
+    _lib.call("gsr_bound_gaussians_backward", V, F, G, *(_lib.ptr(t[k]) for k in INPUTS[:5]), 0, *(_lib.ptr(up[n]) for n in BC.OUTPUTS),
+              _lib.ptr(grad_verts), _lib.ptr(grad_complex), _lib.ptr(grad_log_scales), device=t["verts"].device)
+    torch.cuda.synchronize()
+    got = {name: o.cpu().numpy() for name, o in out.items() if o is not None}
+    got.update(grad_verts=grad_verts.cpu().numpy(), grad_complex=grad_complex.cpu().numpy(), grad_log_scales=grad_log_scales.cpu().numpy())
+    for name, a in got.items():
+        assert not np.isnan(a).any(), f"{name}: an element left unwritten"
+    against_the_restatement(case, got, want, what="C ABI, " + "+".join(want))
+
+
+# ---- refusals that need a GPU -------------------------------------------------------------------------------------------------------------
+
+def test_mixed_devices_and_graph_capture_are_refused(monkeypatch):
+    from autovfx_amd import _lib
+    case = BC.sized_case(4, 3, seed=1)
+    t = {k: torch.from_numpy(np.ascontiguousarray(case[k])).to(DEV) for k in INPUTS}
+    with pytest.raises(ValueError, match="complex must be on cuda"):
+        bound.bound_gaussians(*(t[k].cpu() if k == "complex" else t[k] for k in INPUTS))
+    with pytest.raises(ValueError, match="must be on a GPU"):
+        bound.bound_gaussians(*(t[k].cpu() for k in INPUTS))
+    seen = []
+    getter = bound.drop_in_points(lambda self: seen.append(self) or "original")
+    model = BC.StubSuGaR(case, DEV)
+    assert isinstance(getter(model), torch.Tensor) and not seen
+    monkeypatch.setattr(_lib, "capturing", lambda: True)
+    with pytest.raises(ValueError, match="capturing a graph"):
+        bound.bound_gaussians(*(t[k] for k in INPUTS))
+    assert getter(model) == "original" and seen == [model]
+
+
+# ---- the drop-ins under install() ---------------------------------------------------------------------------------------------------------
+
+@pytest.fixture
+def stub_module():
+    name = "stubboundgpu.sugar_model"
+    mod = types.ModuleType(name)
+    mod.SuGaR = type("SuGaR", (object,), {k: v for k, v in vars(BC.StubSuGaR).items() if k not in ("__dict__", "__weakref__")})
+    mod.SuGaR.__module__ = name
+    sys.modules[name] = mod
+    try:
+        hook.install(path=False)
+        yield mod
+    finally:
+        hook.uninstall()
+        sys.modules.pop(name, None)
+
+
+def _getters(model, which):
+    """The three tensors of ``model`` and their gradients for the case's upstream gradients; ``which``: ``"{}"`` or ``"reference_{}"``."""
+    outs = {name: getattr(model, which.format(name)) for name in BC.OUTPUTS}
+    sum((outs[name] * torch.from_numpy(model.case["grad_" + name]).to(DEV)).sum() for name in BC.OUTPUTS).backward()
+    torch.cuda.synchronize()
+    got = {name: o.detach().cpu().numpy() for name, o in outs.items()}
+    got.update(grad_verts=model._points.grad.cpu().numpy(), grad_complex=model._quaternions.grad.cpu().numpy(), grad_log_scales=model._scales.grad.cpu().numpy())
+    return got
+
+
+@pytest.mark.parametrize("G", [1, 6])
+def test_the_drop_ins_equal_the_original_getters_within_the_cpu_bars(stub_module, G):
+    SuGaR = stub_module.SuGaR
+    assert all(isinstance(vars(SuGaR)["reference_" + n], property) and hook._is_ours(vars(SuGaR)[n].fget) for n in BC.OUTPUTS)
+    case = BC.torus_case(15, 10, G, seed=50 + G)
+    want = BC.truth(case)
+    found, got = {}, {}
+    for which in ("{}", "reference_{}"):
+        model = SuGaR(case, DEV, requires_grad=True)
+        model.case = case
+        got[which] = _getters(model, which)
+        found[which] = BC.check(case, got[which], what=which.format("getter"), want=want)
+    # ... and the two against each other, the original's result in the truth's place (the near-tie rows are the truth's)
+    found["direct"] = BC.check(case, got["{}"], what="the drop-ins against the original getters", want=dict(got["reference_{}"], q_abs=want["q_abs"]))
+    print({k: tuple(round(found[w][k], 2) for w in ("{}", "reference_{}", "direct")) for k in found["{}"]})
+    ours = SuGaR(case, DEV)
+    same_bits(ours.points.cpu().numpy(), bound.bound_gaussians_host(*(case[k] for k in INPUTS))[0], "the drop-in runs the kernel")
+
+
+def test_the_excluded_models_reach_the_original(stub_module):
+    """``editable=True``, an unbound model and a foreign ``scale_activation`` run the original getter, shown by a recording original."""
+    case = BC.sized_case(4, 3, seed=2)
+    seen = []
+    getters = {n: getattr(bound, "drop_in_" + n)(lambda self, n=n: seen.append(n) or n) for n in BC.OUTPUTS}
+    for change in (dict(editable=True), dict(binded_to_surface_mesh=False), dict(scale_activation=torch.nn.functional.softplus)):
+        model = BC.StubSuGaR(case, DEV)
+        vars(model).update(change)
+        del seen[:]
+        assert [getters[n](model) for n in BC.OUTPUTS] == list(BC.OUTPUTS) and seen == list(BC.OUTPUTS), change
+    model = BC.StubSuGaR(case, DEV)
+    del seen[:]
+    assert all(isinstance(getters[n](model), torch.Tensor) for n in BC.OUTPUTS) and seen == []
+    unbound = stub_module.SuGaR(case, DEV)
+    unbound.binded_to_surface_mesh = False
+    assert unbound.points is unbound._points                                          # through the hook: the original's own branch
+
+
+def test_one_access_to_quaternions_performs_no_host_synchronisation(stub_module):
+    case = BC.torus_case(15, 10, 6, seed=3)
+    model = stub_module.SuGaR(case, DEV, requires_grad=True)
+    warm = model.quaternions                                                          # (the probe runs once, on the host, at the first access)
+    grad = torch.from_numpy(case["grad_quaternions"]).to(DEV)
+    torch.cuda.synchronize()
+    torch.cuda.set_sync_debug_mode("error")
+    try:
+        q = model.quaternions
+        (q * grad).sum().backward()
+    finally:
+        torch.cuda.set_sync_debug_mode("default")
+    torch.cuda.synchronize()
+    same_bits(q.detach().cpu().numpy(), warm.detach().cpu().numpy(), "the second access")
+    with pytest.raises(RuntimeError):                                                 # the check does see the original's nonzero
+        torch.cuda.set_sync_debug_mode("error")
+        try:
+            model.reference_quaternions
+        finally:
+            torch.cuda.set_sync_debug_mode("default")
