@@ -86,11 +86,13 @@ from typing import Callable, Optional, Sequence
 import numpy as np
 import torch
 
+from . import _mesh_host
+from ._mesh_host import cross as _cross, dot as _dot, norm as _norm
+
 MAX_COUNT = (1 << 31) - 1
 MAX_G = 8
 OUTPUTS = ("points", "scaling", "quaternions")
 _F = np.float32
-FACE_EPS = _F(1e-6)
 UNIT_EPS = _F(1e-12)
 QUAT_FLOOR = _F(0.1)
 
@@ -265,25 +267,6 @@ def drop_in_quaternions(original_fget: Callable) -> Callable:
 
 # ---- the contract in numpy ------------------------------------------------------------------------------------------------------------
 
-def _norm(w: np.ndarray) -> np.ndarray:
-    acc = w[..., 0] * w[..., 0]
-    for i in range(1, w.shape[-1]):
-        acc = acc + w[..., i] * w[..., i]
-    return np.sqrt(acc)
-
-
-def _dot(u: np.ndarray, w: np.ndarray) -> np.ndarray:
-    acc = u[..., 0] * w[..., 0]
-    for i in range(1, u.shape[-1]):
-        acc = acc + u[..., i] * w[..., i]
-    return acc
-
-
-def _cross(u: np.ndarray, w: np.ndarray) -> np.ndarray:
-    return np.stack((u[..., 1] * w[..., 2] - u[..., 2] * w[..., 1], u[..., 2] * w[..., 0] - u[..., 0] * w[..., 2],
-                     u[..., 0] * w[..., 1] - u[..., 1] * w[..., 0]), axis=-1)
-
-
 def _unit(w: np.ndarray, m: np.ndarray) -> np.ndarray:
     return w / np.fmax(m, UNIT_EPS)[..., None]
 
@@ -296,8 +279,7 @@ def _unit_backward(x: np.ndarray, m: np.ndarray, g: np.ndarray) -> np.ndarray:
 
 
 def _inputs(verts, faces, bary, complex, log_scales):
-    verts = np.ascontiguousarray(np.asarray(verts, dtype=_F).reshape(-1, 3))
-    faces = np.ascontiguousarray(np.asarray(faces, dtype=np.int64).reshape(-1, 3))
+    verts, faces = _mesh_host.verts_faces(verts, faces)
     bary = np.asarray(bary, dtype=_F).reshape(-1, 3)
     G, N = bary.shape[0], faces.shape[0] * bary.shape[0]
     return verts, faces, bary, np.asarray(complex, dtype=_F).reshape(N, 2), np.asarray(log_scales, dtype=_F).reshape(N, 2), G
@@ -305,18 +287,10 @@ def _inputs(verts, faces, bary, complex, log_scales):
 
 def _frame(verts: np.ndarray, faces: np.ndarray) -> dict:
     """Per face: ``valid`` and the contract's a, b, c, n, normal, m0, r0, e, me, b1, x, mx, b2 (zeros for the faces that are not valid)."""
-    V = verts.shape[0]
-    valid = ((faces >= 0) & (faces < V)).all(axis=1)
-    idx = np.where(valid[:, None], faces, 0)
-    t = {"valid": valid}
-    if V == 0:
-        t["v0"] = t["v1"] = t["v2"] = np.zeros((faces.shape[0], 3), _F)
-    else:
-        t["v0"], t["v1"], t["v2"] = (np.where(valid[:, None], verts[idx[:, i]], _F(0.0)) for i in range(3))
-    t["a"], t["b"] = t["v1"] - t["v0"], t["v2"] - t["v0"]
-    t["c"] = _cross(t["a"], t["b"])
-    t["n"] = _norm(t["c"])
-    t["normal"] = t["c"] / np.fmax(t["n"], FACE_EPS)[:, None]
+    t = {}
+    t["valid"], t["v0"], t["v1"], t["v2"] = _mesh_host.face_corners(verts, faces)
+    t["a"], t["b"], t["c"], t["n"] = _mesh_host.face_cross(t["v0"], t["v1"], t["v2"])
+    t["normal"] = t["c"] / np.fmax(t["n"], _mesh_host.FACE_NORMAL_EPS)[:, None]
     t["m0"] = _norm(t["normal"])
     t["r0"] = _unit(t["normal"], t["m0"])
     t["e"] = t["v0"] - t["v1"]
@@ -453,9 +427,7 @@ def bound_gaussians_backward_host(verts, faces, bary, complex, log_scales, grad_
             G0, G1 = G0 + _cross(t["b1"], gx), G1 + _cross(gx, t["r0"])
             ge = _unit_backward(t["e"], t["me"], G1)
             gn = _unit_backward(t["normal"], t["m0"], G0)
-            n = t["n"]
-            m = t["c"] / n[:, None]
-            g_c = np.where((n >= FACE_EPS)[:, None], (gn - m * _dot(m, gn)[:, None]) / n[:, None], gn / FACE_EPS)
+            g_c = _mesh_host.normal_backward(t["c"], t["n"], gn)
             g_a, g_b = _cross(t["b"], g_c), _cross(g_c, t["a"])
             terms = [(P[0] + ge) + (-(g_a + g_b)), (P[1] + (-ge)) + g_a, P[2] + g_b]
     keep = np.nonzero(t["valid"])[0]

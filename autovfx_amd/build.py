@@ -16,7 +16,7 @@ OUT_DIR = os.path.join(HERE, "lib")
 LIB = os.path.join(OUT_DIR, "libgsr_hip.so")
 SOURCES = ["gsr_kernels.hip", "gsr_binning.hip", "gsr_blend.hip", "gsr_backward.hip", "gsr_radix.hip", "gsr_frameio.hip", "gsr_resample.hip", "gsr_layerio.hip", "gsr_layerfiles.hip", "gsr_panorama.hip", "gsr_tree.hip", "gsr_knn.hip", "gsr_meshquery.hip", "gsr_ssim.hip", "gsr_adam.hip", "gsr_densify.hip", "gsr_field.hip", "gsr_meshraster.hip", "gsr_meshattrs.hip", "gsr_meshloss.hip", "gsr_texture.hip", "gsr_bound.hip", "gsr_api.hip"]
 HEADERS = [os.path.join(CSRC, "gsr_internal.h"), os.path.join(CSRC, "gsr_device.h"), os.path.join(CSRC, "gsr_inflate_core.h"),
-           os.path.join(CSRC, "gsr_tree.h"), os.path.join(CSRC, "gsr_wave.h"), os.path.join(HERE, "..", "include", "gsr.h")]
+           os.path.join(CSRC, "gsr_tree.h"), os.path.join(CSRC, "gsr_wave.h"), os.path.join(CSRC, "gsr_vec3.h"), os.path.join(HERE, "..", "include", "gsr.h")]
 # -ffp-contract=off: the parity contract is fp32 in the reference's operation order;
 # no -ffast-math: IEEE divide / sqrt, accurate expf.
 # -fno-slp-vectorize: on gfx950 packed fp32 multiply / add issue at half rate (only the packed fma is full rate), so

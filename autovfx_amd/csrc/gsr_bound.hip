@@ -24,6 +24,7 @@ constexpr float kUnitEps = 1e-12f;       // the clamp of F.normalize
 constexpr float kQuatFloor = 0.1f;       // matrix_to_quaternion's floor on the divisor
 
 // ---- the contract's arithmetic: restated operation by operation in autovfx_amd/bound.py ------------------------------------------------
+// (Arrays and the unit's own gather, not gsr_vec3.h's Vec3: with it the forward measured slower than this text)
 
 __device__ inline float norm3(const float (&v)[3]) { return sqrtf((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]); }
 __device__ inline float dot3(const float (&a)[3], const float (&b)[3]) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
@@ -325,9 +326,6 @@ const char* bad_bound_sizes(int64_t V, int64_t F, int G) {
     if (V >= ((int64_t)1 << 31) || F * (int64_t)G >= ((int64_t)1 << 31)) return "2^31 or more vertices or Gaussians";
     return nullptr;
 }
-
-inline bool aligned8(const void* p) { return ((uintptr_t)p & 7u) == 0u; }
-inline unsigned blocks_of(int64_t n, int64_t per) { return (unsigned)((n + per - 1) / per); }
 
 }  // namespace
 }  // namespace gsr

@@ -348,7 +348,7 @@ int gsr_densify_plan(int64_t n, const float* accum, const float* denom, const fl
     if (!accum || !denom || !scaling || !opacity || !src_of || !split_idx || !counts || !scratch)
         return fail(GSR_ERR_INVALID_ARG, "gsr_densify_plan: null pointer");
     if (!aligned4(accum) || !aligned4(denom) || !aligned4(scaling) || !aligned4(opacity) || !aligned4(src_of) || !aligned4(split_idx) ||
-        !aligned4(counts) || ((uintptr_t)scratch & 255u) != 0u)
+        !aligned4(counts) || !gsr::aligned256(scratch))
         return fail(GSR_ERR_INVALID_ARG, "gsr_densify_plan: misaligned pointer (arrays: 4 bytes, scratch: 256 bytes)");
     const gsr::DensifyPlanLayout l = gsr::densify_plan_layout(n);
     if (scratch_bytes < l.bytes) return fail(GSR_ERR_INVALID_ARG, "gsr_densify_plan: scratch too small (%zu of %zu bytes)", scratch_bytes, l.bytes);

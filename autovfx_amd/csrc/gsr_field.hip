@@ -452,7 +452,7 @@ int field_check(const char* who, const gsr::FieldInputs& in, bool wants_beta, co
         return fail(GSR_ERR_INVALID_ARG, "%s: null pointer", who);
     if (wants_beta && !in.min_scaling) return fail(GSR_ERR_INVALID_ARG, "%s: beta needs min_scaling", who);
     if ((((uintptr_t)in.x | (uintptr_t)in.centers | (uintptr_t)in.M | (uintptr_t)in.strengths | (uintptr_t)in.min_scaling) & 3u) != 0u ||
-        ((uintptr_t)in.idx & 7u) != 0u || ((uintptr_t)scratch & 255u) != 0u)
+        !gsr::aligned8(in.idx) || !gsr::aligned256(scratch))
         return fail(GSR_ERR_INVALID_ARG, "%s: misaligned pointer (floats: 4 bytes, idx: 8, scratch: 256)", who);
     const size_t need = gsr::field_scratch_bytes(in.P);
     if (scratch_bytes < need) return fail(GSR_ERR_INVALID_ARG, "%s: scratch too small (%zu of %zu bytes)", who, scratch_bytes, need);

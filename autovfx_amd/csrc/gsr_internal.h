@@ -13,6 +13,10 @@ namespace gsr {
 // Formats the calling thread's error message and returns `code`.
 int fail(gsr_status code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 inline bool aligned4(const void* p) { return ((uintptr_t)p & 3u) == 0u; }
+inline bool aligned8(const void* p) { return ((uintptr_t)p & 7u) == 0u; }
+inline bool aligned256(const void* p) { return ((uintptr_t)p & 255u) == 0u; }
+// workgroups of `per` items that cover n items
+inline unsigned blocks_of(int64_t n, int64_t per) { return (unsigned)((n + per - 1) / per); }
 
 #define GSR_HIP(expr)                                                                          \
     do {                                                                                       \

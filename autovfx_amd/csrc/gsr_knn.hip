@@ -461,7 +461,7 @@ int gsr_knn3_mean_dist(uint32_t n, const float* points, float* out, void* scratc
     if (n == 0) return GSR_OK;
     if (n >= gsr::kKnn3MaxPoints) return fail(GSR_ERR_INVALID_ARG, "gsr_knn3_mean_dist: %u points (at most 2^30 - 1)", n);
     if (!points || !out || !scratch) return fail(GSR_ERR_INVALID_ARG, "null pointer");
-    if (((uintptr_t)points & 3u) != 0u || ((uintptr_t)out & 3u) != 0u || ((uintptr_t)scratch & 255u) != 0u)
+    if (((uintptr_t)points & 3u) != 0u || ((uintptr_t)out & 3u) != 0u || !gsr::aligned256(scratch))
         return fail(GSR_ERR_INVALID_ARG, "gsr_knn3_mean_dist: misaligned pointer (points / out: 4 bytes, scratch: 256 bytes)");
     if (scratch_bytes < gsr_knn3_scratch_bytes(n))
         return fail(GSR_ERR_INVALID_ARG, "gsr_knn3_mean_dist: scratch too small (%zu of %zu bytes)", scratch_bytes, gsr_knn3_scratch_bytes(n));
@@ -486,7 +486,7 @@ int gsr_knn_points(int64_t n1, const float* p1, int64_t n2, const float* p2, int
     // K = 4, 8, 16 rows are written with 16-byte stores; every other K element by element
     const bool wide = K == 4 || K == 8 || K == 16;
     if (((uintptr_t)p1 & 3u) != 0u || ((uintptr_t)p2 & 3u) != 0u || ((uintptr_t)dists & (wide ? 15u : 3u)) != 0u ||
-        ((uintptr_t)idx & (wide ? 15u : 7u)) != 0u || ((uintptr_t)scratch & 255u) != 0u)
+        ((uintptr_t)idx & (wide ? 15u : 7u)) != 0u || !gsr::aligned256(scratch))
         return fail(GSR_ERR_INVALID_ARG, "gsr_knn_points: misaligned pointer (p1 / p2: 4 bytes; dists / idx: 16 bytes for K = 4, 8, 16, "
                                          "else 4 / 8 bytes; scratch: 256 bytes)");
     const size_t need = gsr_knn_points_scratch_bytes(n1, n2, p1 == p2 && n1 == n2);

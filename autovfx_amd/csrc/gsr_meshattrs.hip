@@ -14,6 +14,7 @@
 // fp32 throughout, -ffp-contract=off, IEEE division and sqrt: the numpy restatements compute the same bits; only the order in which the
 // atomics arrive is free.
 #include "gsr_internal.h"
+#include "gsr_vec3.h"
 
 #include <limits.h>
 #include <math.h>
@@ -26,29 +27,21 @@ constexpr uint32_t kSlots = 256;         // slots per workgroup of the three slo
 constexpr int kAttrMaxD = 65536;         // kSlots * 3 * D stays below 2^32
 constexpr float kNormalEps = 1e-6f;
 
-// ---- the contract's arithmetic: restated operation by operation in autovfx_amd/meshattrs.py -------------------------------------------
+// ---- the contract's arithmetic: restated operation by operation in autovfx_amd/meshattrs.py (the 3-vectors and the gather: gsr_vec3.h) ---
 
-struct FaceGeom {
-    long long i0, i1, i2;
-    float ax, ay, az, bx, by, bz;        // a = v1 - v0, b = v2 - v0
-    float cx, cy, cz, n;                 // c = a x b, n = |c|
-};
-
-// false: an index outside [0, V), nothing read from verts
-__device__ inline bool face_geom(const float* __restrict__ verts, const long long* __restrict__ faces, long long V, size_t f, FaceGeom& g) {
-    g.i0 = faces[3 * f + 0], g.i1 = faces[3 * f + 1], g.i2 = faces[3 * f + 2];
-    if (g.i0 < 0 || g.i0 >= V || g.i1 < 0 || g.i1 >= V || g.i2 < 0 || g.i2 >= V) return false;
-    const float* v0 = verts + 3 * (size_t)g.i0;
-    const float* v1 = verts + 3 * (size_t)g.i1;
-    const float* v2 = verts + 3 * (size_t)g.i2;
-    const float x0 = v0[0], y0 = v0[1], z0 = v0[2];
-    g.ax = v1[0] - x0, g.ay = v1[1] - y0, g.az = v1[2] - z0;
-    g.bx = v2[0] - x0, g.by = v2[1] - y0, g.bz = v2[2] - z0;
-    g.cx = g.ay * g.bz - g.az * g.by;
-    g.cy = g.az * g.bx - g.ax * g.bz;
-    g.cz = g.ax * g.by - g.ay * g.bx;
-    g.n = sqrtf((g.cx * g.cx + g.cy * g.cy) + g.cz * g.cz);
-    return true;
+// a = v1 - v0, b = v2 - v0, c = a x b, n = |c|
+__device__ __forceinline__ void face_cross(const FaceCorners& t, Vec3& a, Vec3& b, Vec3& c, float& n) {
+    a = sub(t.v1, t.v0), b = sub(t.v2, t.v0);
+    c = cross(a, b);
+    n = norm(c);
+}
+// g_c from the normal's gradient gn: the projection off m = c / n, over n; below the clamp (and for a NaN n) the forward is c / 1e-6
+__device__ __forceinline__ Vec3 normal_backward(const Vec3& c, float n, const Vec3& gn) {
+    if (n >= kNormalEps) {
+        const Vec3 m = over(c, n);
+        return over(sub(gn, scale(dot(m, gn), m)), n);
+    }
+    return over(gn, kNormalEps);
 }
 
 __global__ void __launch_bounds__(kAttrThreads) face_areas_normals_kernel(long long V, long long F, const float* __restrict__ verts,
@@ -56,15 +49,18 @@ __global__ void __launch_bounds__(kAttrThreads) face_areas_normals_kernel(long l
                                                                           float* __restrict__ normals) {
     const long long f = (long long)blockIdx.x * kAttrThreads + threadIdx.x;
     if (f >= F) return;
-    FaceGeom g;
-    float area = 0.0f, nx = 0.0f, ny = 0.0f, nz = 0.0f;
-    if (face_geom(verts, faces, V, (size_t)f, g)) {
-        const float den = fmaxf(g.n, kNormalEps);
-        area = g.n / 2.0f;
-        nx = g.cx / den, ny = g.cy / den, nz = g.cz / den;
+    FaceCorners t;
+    float area = 0.0f;
+    Vec3 normal = {0.0f, 0.0f, 0.0f};
+    if (load_face_checked(verts, faces, V, (size_t)f, t)) {
+        Vec3 a, b, c;
+        float n;
+        face_cross(t, a, b, c, n);
+        area = n / 2.0f;
+        normal = over(c, fmaxf(n, kNormalEps));
     }
     areas[f] = area;
-    normals[3 * f + 0] = nx, normals[3 * f + 1] = ny, normals[3 * f + 2] = nz;
+    normals[3 * f + 0] = normal.x, normals[3 * f + 1] = normal.y, normals[3 * f + 2] = normal.z;
 }
 
 __global__ void __launch_bounds__(kAttrThreads) face_areas_normals_backward_kernel(long long V, long long F, const float* __restrict__ verts,
@@ -74,34 +70,24 @@ __global__ void __launch_bounds__(kAttrThreads) face_areas_normals_backward_kern
                                                                                    float* __restrict__ grad_verts) {
     const long long f = (long long)blockIdx.x * kAttrThreads + threadIdx.x;
     if (f >= F) return;
-    FaceGeom g;
-    if (!face_geom(verts, faces, V, (size_t)f, g)) return;
-    const float ga = grad_areas[f];
-    const float gx = grad_normals[3 * f + 0], gy = grad_normals[3 * f + 1], gz = grad_normals[3 * f + 2];
+    FaceCorners t;
+    if (!load_face_checked(verts, faces, V, (size_t)f, t)) return;
+    const float garea = grad_areas[f];                   // (both gradients are asked for before the arithmetic waits for the corners)
+    const Vec3 gn = load3(grad_normals, (size_t)f);
+    Vec3 a, b, c;
+    float n;
+    face_cross(t, a, b, c, n);
     // the area's part: d(n / 2) / dc = c / (2 n), nothing at n == 0
-    float hx = 0.0f, hy = 0.0f, hz = 0.0f;
-    if (g.n > 0.0f) {
-        const float two_n = 2.0f * g.n;
-        hx = (ga * g.cx) / two_n, hy = (ga * g.cy) / two_n, hz = (ga * g.cz) / two_n;
-    }
-    // the normal's part: the projection off m = c / n, over n; below the clamp the forward is c / 1e-6
-    float px, py, pz;
-    if (g.n >= kNormalEps) {
-        const float mx = g.cx / g.n, my = g.cy / g.n, mz = g.cz / g.n;
-        const float dot = (mx * gx + my * gy) + mz * gz;
-        px = (gx - mx * dot) / g.n, py = (gy - my * dot) / g.n, pz = (gz - mz * dot) / g.n;
-    } else {
-        px = gx / kNormalEps, py = gy / kNormalEps, pz = gz / kNormalEps;
-    }
-    const float qx = hx + px, qy = hy + py, qz = hz + pz;             // g_c
-    const float gax = g.by * qz - g.bz * qy, gay = g.bz * qx - g.bx * qz, gaz = g.bx * qy - g.by * qx;   // g_a = b x g_c
-    const float gbx = qy * g.az - qz * g.ay, gby = qz * g.ax - qx * g.az, gbz = qx * g.ay - qy * g.ax;   // g_b = g_c x a
-    float* d0 = grad_verts + 3 * (size_t)g.i0;
-    float* d1 = grad_verts + 3 * (size_t)g.i1;
-    float* d2 = grad_verts + 3 * (size_t)g.i2;
-    atomicAdd(d0 + 0, -(gax + gbx)), atomicAdd(d0 + 1, -(gay + gby)), atomicAdd(d0 + 2, -(gaz + gbz));
-    atomicAdd(d1 + 0, gax), atomicAdd(d1 + 1, gay), atomicAdd(d1 + 2, gaz);
-    atomicAdd(d2 + 0, gbx), atomicAdd(d2 + 1, gby), atomicAdd(d2 + 2, gbz);
+    Vec3 h = {0.0f, 0.0f, 0.0f};
+    if (n > 0.0f) h = over(scale(garea, c), 2.0f * n);
+    const Vec3 gc = add(h, normal_backward(c, n, gn));
+    const Vec3 ga = cross(b, gc), gb = cross(gc, a);
+    float* d0 = grad_verts + 3 * (size_t)t.i0;
+    float* d1 = grad_verts + 3 * (size_t)t.i1;
+    float* d2 = grad_verts + 3 * (size_t)t.i2;
+    atomicAdd(d0 + 0, -(ga.x + gb.x)), atomicAdd(d0 + 1, -(ga.y + gb.y)), atomicAdd(d0 + 2, -(ga.z + gb.z));
+    atomicAdd(d1 + 0, ga.x), atomicAdd(d1 + 1, ga.y), atomicAdd(d1 + 2, ga.z);
+    atomicAdd(d2 + 0, gb.x), atomicAdd(d2 + 1, gb.y), atomicAdd(d2 + 2, gb.z);
 }
 
 // The slots [p0, p0 + slots) of a workgroup, `width` work items per slot: item l belongs to slot p0 + l / width.
@@ -171,9 +157,6 @@ const char* bad_counts(int64_t a, int64_t b) {
     if (a >= ((int64_t)1 << 31) || b >= ((int64_t)1 << 31)) return "a count of 2^31 or more";
     return nullptr;
 }
-
-inline bool aligned8(const void* p) { return ((uintptr_t)p & 7u) == 0u; }
-inline unsigned blocks_of(int64_t n, int64_t per) { return (unsigned)((n + per - 1) / per); }
 
 }  // namespace
 }  // namespace gsr

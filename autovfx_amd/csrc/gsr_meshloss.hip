@@ -15,6 +15,7 @@
 // The kernels trust nothing in a plan: an id outside [0, 3F), a partner count past the end and a face with a bad index are skipped.
 // fp32 throughout, -ffp-contract=off, IEEE division and sqrt: the numpy restatements compute the same bits.
 #include "gsr_internal.h"
+#include "gsr_vec3.h"
 
 #include <math.h>
 
@@ -103,20 +104,7 @@ __global__ void __launch_bounds__(kLossThreads) nc_partners_kernel(uint32_t n, u
     if (threadIdx.x == 0 && s_count[0] != 0ull) atomicAdd(pairs, s_count[0]);
 }
 
-// ---- the contract's arithmetic: restated operation by operation in autovfx_amd/meshloss.py ----------------------------------------------
-
-struct Vec3 {
-    float x, y, z;
-};
-__device__ inline Vec3 load3(const float* __restrict__ verts, uint32_t i) {
-    const float* p = verts + 3 * (size_t)i;
-    return {p[0], p[1], p[2]};
-}
-__device__ inline Vec3 sub(const Vec3& a, const Vec3& b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ inline Vec3 add(const Vec3& a, const Vec3& b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ inline Vec3 cross(const Vec3& a, const Vec3& b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-__device__ inline float dot(const Vec3& a, const Vec3& b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-__device__ inline float norm(const Vec3& a) { return sqrtf((a.x * a.x + a.y * a.y) + a.z * a.z); }
+// ---- the contract's arithmetic: restated operation by operation in autovfx_amd/meshloss.py (the 3-vectors: gsr_vec3.h) -----------------
 
 // The sum of a workgroup's N values (a power of two) by halving in LDS: leaf i + N/2 onto leaf i, then N/4, ...: log2 N additions on
 // every path.  The result is valid in thread 0.
@@ -220,17 +208,11 @@ __global__ void __launch_bounds__(kLossThreads) nc_backward_kernel(uint32_t n, l
         const float q = a * b;
         const float r = dot(k.n, nt) / q;
         // d term / d n_s = n_t / q - (r / a^2) n_s, the second part only above the clamp; likewise for n_t
-        Vec3 us = {nt.x / q, nt.y / q, nt.z / q};
-        if (ra > kCosEps) {
-            const float m = r / (a * a);
-            us = {us.x - m * k.n.x, us.y - m * k.n.y, us.z - m * k.n.z};
-        }
-        Vec3 ut = {k.n.x / q, k.n.y / q, k.n.z / q};
-        if (rb > kCosEps) {
-            const float m = r / (b * b);
-            ut = {ut.x - m * nt.x, ut.y - m * nt.y, ut.z - m * nt.z};
-        }
-        const Vec3 gs = {c * us.x, c * us.y, c * us.z}, gt = {c * ut.x, c * ut.y, c * ut.z};
+        Vec3 us = over(nt, q);
+        if (ra > kCosEps) us = sub(us, scale(r / (a * a), k.n));
+        Vec3 ut = over(k.n, q);
+        if (rb > kCosEps) ut = sub(ut, scale(r / (b * b), nt));
+        const Vec3 gs = scale(c, us), gt = scale(c, ut);
         // n = e x w: d / de = w x g, d / dw = g x e
         const Vec3 ge = add(cross(k.w, gs), cross(wt, gt));
         const Vec3 ws = cross(gs, k.e), wtg = cross(gt, k.e);
@@ -271,15 +253,13 @@ int bit_length(uint64_t v) {
     return bits;
 }
 
-inline unsigned blocks_of(uint32_t n) { return (n + (uint32_t)kLossThreads - 1u) / (uint32_t)kLossThreads; }
-
 hipError_t launch_plan(uint32_t n, int64_t V, const long long* faces, int* order, int* partners, unsigned long long* pairs, void* scratch,
                        hipStream_t stream) {
     const PlanLayout L = plan_layout(n);
     char* base = static_cast<char*>(scratch);
     auto u32 = [&](size_t at) { return reinterpret_cast<uint32_t*>(base + at); };
     uint32_t *keys = u32(L.keys), *keys_alt = keys + n, *vals = u32(L.vals), *vals_alt = u32(L.vals_alt), *key_lo = u32(L.key_lo);
-    const dim3 grid(blocks_of(n)), block(kLossThreads);
+    const dim3 grid(blocks_of(n, kLossThreads)), block(kLossThreads);
     hipLaunchKernelGGL(nc_keys_kernel, grid, block, 0, stream, n, (long long)V, faces, keys, key_lo);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
@@ -304,9 +284,6 @@ const char* bad_mesh(int64_t V, int64_t F) {
     if (V >= ((int64_t)1 << 31)) return "V of 2^31 or more";
     return nullptr;
 }
-
-inline bool aligned8(const void* p) { return ((uintptr_t)p & 7u) == 0u; }
-inline bool aligned256(const void* p) { return ((uintptr_t)p & 255u) == 0u; }
 
 }  // namespace
 }  // namespace gsr
@@ -339,7 +316,7 @@ int gsr_normal_consistency_plan(int64_t V, int64_t F, const int64_t* faces, int3
 
 size_t gsr_normal_consistency_scratch_bytes(int64_t F) {
     if (F < 0 || F > gsr::kMaxFaces) return 0;
-    return sizeof(float) * (size_t)gsr::blocks_of((uint32_t)(3 * F));
+    return sizeof(float) * (size_t)gsr::blocks_of(3 * F, gsr::kLossThreads);
 }
 
 int gsr_normal_consistency_forward(int64_t V, int64_t F, const float* verts, const int64_t* faces, const int32_t* order, const int32_t* partners,
@@ -358,7 +335,7 @@ int gsr_normal_consistency_forward(int64_t V, int64_t F, const float* verts, con
         GSR_HIP(hipMemsetAsync(loss, 0, sizeof(float), stream));
         return GSR_OK;
     }
-    const uint32_t n = (uint32_t)(3 * F), blocks = gsr::blocks_of(n);
+    const uint32_t n = (uint32_t)(3 * F), blocks = gsr::blocks_of(n, gsr::kLossThreads);
     float* partials = static_cast<float*>(scratch);
     hipLaunchKernelGGL(gsr::nc_forward_kernel, dim3(blocks), dim3(gsr::kLossThreads), 0, stream, n, (long long)V, verts,
                        reinterpret_cast<const long long*>(faces), order, partners, partials, terms_or_null);
@@ -381,7 +358,7 @@ int gsr_normal_consistency_backward(int64_t V, int64_t F, const float* verts, co
     GSR_HIP(hipMemsetAsync(grad_verts, 0, (size_t)V * 3u * sizeof(float), stream));
     if (F == 0) return GSR_OK;
     const uint32_t n = (uint32_t)(3 * F);
-    hipLaunchKernelGGL(gsr::nc_backward_kernel, dim3(gsr::blocks_of(n)), dim3(gsr::kLossThreads), 0, stream, n, (long long)V, verts,
+    hipLaunchKernelGGL(gsr::nc_backward_kernel, dim3(gsr::blocks_of(n, gsr::kLossThreads)), dim3(gsr::kLossThreads), 0, stream, n, (long long)V, verts,
                        reinterpret_cast<const long long*>(faces), order, partners, reinterpret_cast<const long long*>(pairs), grad_loss,
                        grad_verts);
     GSR_HIP(hipGetLastError());

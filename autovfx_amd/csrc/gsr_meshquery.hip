@@ -22,6 +22,7 @@
 // Defines the entry points gsr_closest_tri_plan_bytes, gsr_closest_tri_plan_scratch_bytes, gsr_closest_tri_plan, gsr_closest_tri_query,
 // gsr_ray_first_hit.
 #include "gsr_tree.h"
+#include "gsr_vec3.h"
 
 #include <cfloat>
 
@@ -79,24 +80,15 @@ TriScratch tri_scratch(uint32_t F) {
     return L;
 }
 
-struct Vec3 {
-    float x, y, z;
-};
-__device__ __forceinline__ Vec3 sub(const Vec3& u, const Vec3& v) { return {u.x - v.x, u.y - v.y, u.z - v.z}; }
-__device__ __forceinline__ Vec3 neg(const Vec3& u) { return {-u.x, -u.y, -u.z}; }
-// u + s v, a multiplication and an addition per axis (the build has -ffp-contract=off)
-__device__ __forceinline__ Vec3 along(const Vec3& u, float s, const Vec3& v) { return {u.x + s * v.x, u.y + s * v.y, u.z + s * v.z}; }
-__device__ __forceinline__ float dot(const Vec3& u, const Vec3& v) { return (u.x * v.x + u.y * v.y) + u.z * v.z; }
 __device__ __forceinline__ float guarded(float num, float den) { return den != 0.0f ? num / den : 0.0f; }
 
-// The three corners of face f; false for an invalid face (whose corners are then not read).
+// The three corners of face f; false for an invalid face: an index outside [0, V) (the corners are then not read) or a coordinate
+// that is not finite.
 __device__ __forceinline__ bool load_face(int64_t V, const float* __restrict__ verts, const long long* __restrict__ faces, uint32_t f,
                                           Vec3& a, Vec3& b, Vec3& c) {
-    const long long i0 = faces[3 * (size_t)f], i1 = faces[3 * (size_t)f + 1], i2 = faces[3 * (size_t)f + 2];
-    if (i0 < 0 || i1 < 0 || i2 < 0 || i0 >= V || i1 >= V || i2 >= V) return false;
-    a = {verts[3 * (size_t)i0], verts[3 * (size_t)i0 + 1], verts[3 * (size_t)i0 + 2]};
-    b = {verts[3 * (size_t)i1], verts[3 * (size_t)i1 + 1], verts[3 * (size_t)i1 + 2]};
-    c = {verts[3 * (size_t)i2], verts[3 * (size_t)i2 + 1], verts[3 * (size_t)i2 + 2]};
+    FaceCorners t;
+    if (!load_face_checked(verts, faces, V, f, t)) return false;
+    a = t.v0, b = t.v1, c = t.v2;
     return finite3(a.x, a.y, a.z) && finite3(b.x, b.y, b.z) && finite3(c.x, c.y, c.z);
 }
 // (it only steers the sort: an overflow to inf lands in cell 0 or the last one)

@@ -448,8 +448,7 @@ int gsr_mesh_raster_count(int64_t F, int64_t N, const float* face_verts, const i
     *pair_total = 0;
     if (F == 0 || N == 0) return GSR_OK;
     if (!face_verts || !mesh_to_face_first_idx || !num_faces_per_mesh || !plan) return fail(GSR_ERR_INVALID_ARG, "gsr_mesh_raster_count: null pointer");
-    if (((uintptr_t)face_verts & 3u) != 0u || ((uintptr_t)mesh_to_face_first_idx & 7u) != 0u || ((uintptr_t)num_faces_per_mesh & 7u) != 0u ||
-        ((uintptr_t)plan & 255u) != 0u)
+    if (((uintptr_t)face_verts & 3u) != 0u || !gsr::aligned8(mesh_to_face_first_idx) || !gsr::aligned8(num_faces_per_mesh) || !gsr::aligned256(plan))
         return fail(GSR_ERR_INVALID_ARG, "gsr_mesh_raster_count: misaligned pointer (face_verts: 4 bytes, the index arrays: 8, plan: 256)");
     const size_t need = gsr_mesh_raster_plan_bytes(F, N, H, W);
     if (plan_bytes < need) return fail(GSR_ERR_INVALID_ARG, "gsr_mesh_raster_count: scratch too small (%zu of %zu bytes)", plan_bytes, need);
@@ -484,7 +483,7 @@ int gsr_mesh_raster(int64_t F, int64_t N, const float* face_verts, const int64_t
     if (pair_total >= ((int64_t)1 << 31)) return fail(GSR_ERR_INVALID_ARG, "gsr_mesh_raster: %lld (tile, face) pairs (at most 2^31 - 1)", (long long)pair_total);
     if (N == 0) return GSR_OK;
     if (!pix_to_face || !zbuf || !bary_coords || !dists) return fail(GSR_ERR_INVALID_ARG, "gsr_mesh_raster: null pointer (outputs)");
-    if (((uintptr_t)pix_to_face & 7u) != 0u || ((uintptr_t)zbuf & 3u) != 0u || ((uintptr_t)bary_coords & 3u) != 0u || ((uintptr_t)dists & 3u) != 0u)
+    if (!gsr::aligned8(pix_to_face) || ((uintptr_t)zbuf & 3u) != 0u || ((uintptr_t)bary_coords & 3u) != 0u || ((uintptr_t)dists & 3u) != 0u)
         return fail(GSR_ERR_INVALID_ARG, "gsr_mesh_raster: misaligned pointer (pix_to_face: 8 bytes, zbuf / bary_coords / dists: 4)");
     hipStream_t stream = (hipStream_t)stream_;
     if (F == 0) {
@@ -497,8 +496,8 @@ int gsr_mesh_raster(int64_t F, int64_t N, const float* face_verts, const int64_t
     }
     if (!face_verts || !mesh_to_face_first_idx || !num_faces_per_mesh || !clipped_faces_neighbor_idx || !plan || !pairs)
         return fail(GSR_ERR_INVALID_ARG, "gsr_mesh_raster: null pointer");
-    if (((uintptr_t)face_verts & 3u) != 0u || ((uintptr_t)mesh_to_face_first_idx & 7u) != 0u || ((uintptr_t)num_faces_per_mesh & 7u) != 0u ||
-        ((uintptr_t)clipped_faces_neighbor_idx & 7u) != 0u || ((uintptr_t)plan & 255u) != 0u || ((uintptr_t)pairs & 255u) != 0u)
+    if (((uintptr_t)face_verts & 3u) != 0u || !gsr::aligned8(mesh_to_face_first_idx) || !gsr::aligned8(num_faces_per_mesh) ||
+        !gsr::aligned8(clipped_faces_neighbor_idx) || !gsr::aligned256(plan) || !gsr::aligned256(pairs))
         return fail(GSR_ERR_INVALID_ARG, "gsr_mesh_raster: misaligned pointer (face_verts: 4 bytes, the index arrays: 8, plan / pairs: 256)");
     const size_t need_plan = gsr_mesh_raster_plan_bytes(F, N, H, W), need_pairs = gsr_mesh_raster_pair_bytes(pair_total);
     if (plan_bytes < need_plan) return fail(GSR_ERR_INVALID_ARG, "gsr_mesh_raster: plan scratch too small (%zu of %zu bytes)", plan_bytes, need_plan);

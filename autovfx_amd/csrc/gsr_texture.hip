@@ -11,6 +11,7 @@
 //                density field's q, gsr_field.hip), the colour of the first Gaussian with the smallest q
 // fp32 throughout, -ffp-contract=off, IEEE division, rintf to nearest even: the numpy restatements compute the same bits.
 #include "gsr_internal.h"
+#include "gsr_vec3.h"
 
 #include <math.h>
 
@@ -102,18 +103,13 @@ __global__ void __launch_bounds__(kTexThreads) texture_fill_kernel(long long V, 
     const uint32_t df = l / n, t = l - df * n;
     const long long f = f0 + df;
     if (f >= F) return;
-    const long long i0 = faces[3 * f + 0], i1 = faces[3 * f + 1], i2 = faces[3 * f + 2];
-    if (i0 < 0 || i0 >= V || i1 < 0 || i1 >= V || i2 < 0 || i2 >= V) return;
+    FaceCorners corners;
+    if (!load_face_checked(verts, faces, V, (size_t)f, corners)) return;
     const size_t row_of_tables = (size_t)(f & 1) * n + t;
     const int o0 = texel_offset[2 * row_of_tables + 0], o1 = texel_offset[2 * row_of_tables + 1];
     if (o0 < 0 || o0 >= S || o1 < 0 || o1 >= S) return;        // (the tables are the caller's: nothing is written outside the face's square)
     const float w0 = texel_bary[3 * row_of_tables + 0], w1 = texel_bary[3 * row_of_tables + 1], w2 = texel_bary[3 * row_of_tables + 2];
-    const float* v0 = verts + 3 * (size_t)i0;
-    const float* v1 = verts + 3 * (size_t)i1;
-    const float* v2 = verts + 3 * (size_t)i2;
-    float x[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) x[c] = (w0 * v0[c] + w1 * v1[c]) + w2 * v2[c];
+    const Vec3 x = add(add(scale(w0, corners.v0), scale(w1, corners.v1)), scale(w2, corners.v2));
 
     int best = 0;
     float best_q = 0.0f;
@@ -121,7 +117,7 @@ __global__ void __launch_bounds__(kTexThreads) texture_fill_kernel(long long V, 
         const size_t j = (size_t)f * (size_t)G + (size_t)g;
         const float* c = centers + 3 * j;
         const float* m = M + 9 * j;
-        const float s0 = x[0] - c[0], s1 = x[1] - c[1], s2 = x[2] - c[2];
+        const float s0 = x.x - c[0], s1 = x.y - c[1], s2 = x.z - c[2];
         float w[3];
 #pragma unroll
         for (int a = 0; a < 3; ++a) w[a] = (m[a] * s0 + m[3 + a] * s1) + m[6 + a] * s2;
@@ -138,9 +134,6 @@ __global__ void __launch_bounds__(kTexThreads) texture_fill_kernel(long long V, 
 #pragma unroll
     for (int c = 0; c < 3; ++c) tex[at + c] = feat[c] * kShC0 + 0.5f;
 }
-
-inline bool aligned8(const void* p) { return ((uintptr_t)p & 7u) == 0u; }
-inline unsigned blocks_of(int64_t n, int64_t per) { return (unsigned)((n + per - 1) / per); }
 
 // What the three per-pixel entry points refuse, or nullptr.
 const char* bad_view(int64_t P, int64_t F, int T, const int64_t* pix_to_face, const float* bary, const float* zbuf, const float* face_uvs) {

@@ -69,10 +69,11 @@ from typing import Callable, Optional, Tuple
 import numpy as np
 import torch
 
+from . import _mesh_host
+
 MAX_COUNT = (1 << 31) - 1
 MAX_D = 65536
 _F = np.float32
-NORMAL_EPS = _F(1e-6)
 
 
 # ---- which calls the kernels take -----------------------------------------------------------------------------------------------------
@@ -307,34 +308,15 @@ def drop_in_interpolate_face_attributes_backward(original: Callable) -> Callable
 
 # ---- the contract in numpy ------------------------------------------------------------------------------------------------------------
 
-def _face_geometry(verts: np.ndarray, faces: np.ndarray):
-    """``valid [F]``, and ``a, b, c [F, 3]``, ``n [F]`` of the valid faces' rows (zeros elsewhere), as the forward computes them."""
-    V = verts.shape[0]
-    valid = ((faces >= 0) & (faces < V)).all(axis=1)
-    idx = np.where(valid[:, None], faces, 0)
-    if V == 0:
-        zero = np.zeros((faces.shape[0], 3), _F)
-        return valid, zero, zero.copy(), zero.copy(), np.zeros(faces.shape[0], _F)
-    v0, v1, v2 = verts[idx[:, 0]], verts[idx[:, 1]], verts[idx[:, 2]]
-    with np.errstate(all="ignore"):
-        a, b = v1 - v0, v2 - v0
-        c = np.stack((a[:, 1] * b[:, 2] - a[:, 2] * b[:, 1], a[:, 2] * b[:, 0] - a[:, 0] * b[:, 2], a[:, 0] * b[:, 1] - a[:, 1] * b[:, 0]), axis=1)
-        n = np.sqrt((c[:, 0] * c[:, 0] + c[:, 1] * c[:, 1]) + c[:, 2] * c[:, 2])
-    return valid, a, b, c, n
-
-
-def _verts_faces(verts, faces):
-    return (np.ascontiguousarray(np.asarray(verts, dtype=_F).reshape(-1, 3)), np.ascontiguousarray(np.asarray(faces, dtype=np.int64).reshape(-1, 3)))
-
-
 def face_areas_normals_host(verts, faces):
     """The forward of the module's contract in numpy, every operation an fp32 elementwise one in the contract's order.  Returns
     ``(areas [F], normals [F, 3])``."""
-    verts, faces = _verts_faces(verts, faces)
-    valid, _a, _b, c, n = _face_geometry(verts, faces)
+    verts, faces = _mesh_host.verts_faces(verts, faces)
+    valid, v0, v1, v2 = _mesh_host.face_corners(verts, faces)
     with np.errstate(all="ignore"):
+        _a, _b, c, n = _mesh_host.face_cross(v0, v1, v2)
         areas = n / _F(2.0)
-        normals = c / np.fmax(n, NORMAL_EPS)[:, None]
+        normals = c / np.fmax(n, _mesh_host.FACE_NORMAL_EPS)[:, None]
     return np.where(valid, areas, _F(0.0)).astype(_F), np.where(valid[:, None], normals, _F(0.0)).astype(_F)
 
 
@@ -342,20 +324,16 @@ def face_areas_normals_backward_host(grad_areas, grad_normals, verts, faces):
     """The backward of the module's contract in numpy.  Returns ``(grad_verts [V, 3], contributions [F, 3, 3])``: ``contributions[f, i]`` is
     what face f adds to its vertex i (zeros for a face with an out-of-range index), each an fp32 value fixed by the contract;
     ``grad_verts`` is their fp32 sum in face order, one of the orders the kernel's atomics may take."""
-    verts, faces = _verts_faces(verts, faces)
+    verts, faces = _mesh_host.verts_faces(verts, faces)
     F = faces.shape[0]
     ga = np.asarray(grad_areas, dtype=_F).reshape(F)
     g = np.asarray(grad_normals, dtype=_F).reshape(F, 3)
-    valid, a, b, c, n = _face_geometry(verts, faces)
+    valid, v0, v1, v2 = _mesh_host.face_corners(verts, faces)
     with np.errstate(all="ignore"):
+        a, b, c, n = _mesh_host.face_cross(v0, v1, v2)
         h = np.where((n > _F(0.0))[:, None], (ga[:, None] * c) / (_F(2.0) * n)[:, None], _F(0.0))
-        m = c / n[:, None]
-        dot = (m[:, 0] * g[:, 0] + m[:, 1] * g[:, 1]) + m[:, 2] * g[:, 2]
-        q = np.where((n >= NORMAL_EPS)[:, None], (g - m * dot[:, None]) / n[:, None], g / NORMAL_EPS)
-        gc = (h + q).astype(_F)
-        cross = lambda u, w: np.stack((u[:, 1] * w[:, 2] - u[:, 2] * w[:, 1], u[:, 2] * w[:, 0] - u[:, 0] * w[:, 2],
-                                       u[:, 0] * w[:, 1] - u[:, 1] * w[:, 0]), axis=1)
-        g_a, g_b = cross(b, gc), cross(gc, a)
+        gc = (h + _mesh_host.normal_backward(c, n, g)).astype(_F)
+        g_a, g_b = _mesh_host.cross(b, gc), _mesh_host.cross(gc, a)
         contributions = np.stack((-(g_a + g_b), g_a, g_b), axis=1).astype(_F)
     contributions[~valid] = _F(0.0)
     grad_verts = np.zeros((verts.shape[0], 3), _F)

@@ -67,6 +67,8 @@ import numpy as np
 import torch
 from torch.autograd.function import once_differentiable
 
+from ._mesh_host import cross as _cross, dot as _dot, norm as _norm, verts_faces as _verts_faces
+
 MAX_INCIDENCES = 1 << 30
 MAX_VERTS = 1 << 31
 _F = np.float32
@@ -266,10 +268,6 @@ def drop_in(original: Callable) -> Callable:
 
 # ---- the contract in numpy ------------------------------------------------------------------------------------------------------------
 
-def _verts_faces(verts, faces):
-    return (np.ascontiguousarray(np.asarray(verts, dtype=_F).reshape(-1, 3)), np.ascontiguousarray(np.asarray(faces, dtype=np.int64).reshape(-1, 3)))
-
-
 def _incidences(faces: np.ndarray, V: int, ids: np.ndarray):
     """``valid, lo, hi, opp`` of the incidences ``ids`` (an id outside ``[0, 3F)`` is not valid; ``lo = hi = V`` where not valid)."""
     n = 3 * faces.shape[0]
@@ -304,18 +302,6 @@ def plan_host(faces, V: int):
         partners = ends[np.cumsum(first) - 1] - 1 - np.arange(n)
         partners[lo_s == V] = 0
     return order.astype(np.int32), partners.astype(np.int32), int(partners.sum())
-
-
-def _cross(u, w):
-    return np.stack((u[:, 1] * w[:, 2] - u[:, 2] * w[:, 1], u[:, 2] * w[:, 0] - u[:, 0] * w[:, 2], u[:, 0] * w[:, 1] - u[:, 1] * w[:, 0]), axis=1)
-
-
-def _dot(u, w):
-    return (u[:, 0] * w[:, 0] + u[:, 1] * w[:, 1]) + u[:, 2] * w[:, 2]
-
-
-def _norm(u):
-    return np.sqrt((u[:, 0] * u[:, 0] + u[:, 1] * u[:, 1]) + u[:, 2] * u[:, 2])
 
 
 class _Walks(NamedTuple):

@@ -58,6 +58,8 @@ from typing import Callable, Optional
 import numpy as np
 import torch
 
+from . import _mesh_host
+
 MAX_G = 8
 MIN_S, MAX_S = 4, 32
 MAX_T = 46340                     # T * T < 2^31
@@ -174,9 +176,8 @@ def _q_host(x, centers, M):
 
 def fill_host(verts, faces, centers, inv_scaled_rot, features, texel_offset, texel_bary, A: int, S: int, return_q: bool = False):
     """The initial atlas ``[T, T, 3]`` (with ``return_q`` also ``q [F, n, G]``)."""
-    verts = np.asarray(verts, _F).reshape(-1, 3)
-    faces = np.asarray(faces, np.int64).reshape(-1, 3)
-    F, V = faces.shape[0], verts.shape[0]
+    verts, faces = _mesh_host.verts_faces(verts, faces)
+    F = faces.shape[0]
     offs = np.asarray(texel_offset, np.int32)
     bary = np.asarray(texel_bary, _F)
     n = offs.shape[1]
@@ -186,12 +187,11 @@ def fill_host(verts, faces, centers, inv_scaled_rot, features, texel_offset, tex
     feat = np.asarray(features, _F).reshape(F, G, 3)
     T = A * S
     tex = np.full((T, T, 3), _F(0.5), _F)
-    ok = ((faces >= 0) & (faces < V)).all(axis=1)
-    fv = verts[np.where(ok[:, None], faces, 0)]                                        # [F, 3, 3]
+    ok, v0, v1, v2 = _mesh_host.face_corners(verts, faces)
     parity = np.arange(F) & 1
     w = bary[parity]                                                                   # [F, n, 3]
     with np.errstate(over="ignore", invalid="ignore"):
-        x = (w[..., 0:1] * fv[:, None, 0] + w[..., 1:2] * fv[:, None, 1]) + w[..., 2:3] * fv[:, None, 2]     # [F, n, 3]
+        x = (w[..., 0:1] * v0[:, None] + w[..., 1:2] * v1[:, None]) + w[..., 2:3] * v2[:, None]              # [F, n, 3]
         q = _q_host(x[:, :, None, :], c, M)                                            # [F, n, G]
         nan = np.isnan(q)
         best = np.where(nan.any(axis=-1), nan.argmax(axis=-1), np.where(nan, _F(np.inf), q).argmin(axis=-1))
