@@ -62,13 +62,7 @@ def test_pruned_equals_brute_force_on_16385_faces():
     assert 96 <= hits < 192                                      # hits and misses both
 
 
-def _closed_faces_at(verts, faces, x, y):
-    """The faces of a z = 0 mesh whose closed triangle holds (x, y): orientation tests, exact on halves of integers."""
-    t = verts.astype(np.float64)[faces][:, :, :2]
-    p = np.array([x, y], np.float64)
-    side = lambda u, v: (v[:, 0] - u[:, 0]) * (p[1] - u[:, 1]) - (v[:, 1] - u[:, 1]) * (p[0] - u[:, 0])
-    s = np.stack([side(t[:, 0], t[:, 1]), side(t[:, 1], t[:, 2]), side(t[:, 2], t[:, 0])], 1)
-    return np.nonzero((s >= 0).all(1) | (s <= 0).all(1))[0]
+_closed_faces_at = rays.closed_faces_at
 
 
 @pytest.mark.parametrize("down", [True, False])
@@ -165,3 +159,65 @@ def test_the_clamp_moves_t_by_rounding_error_only():
     # both t_tri (a dozen rounded operations) and the interval's ends (two each, and the pad of 2 ulp) are within a few ulp of the truth
     assert np.abs(got["t"] - got["t_tri"]).max() <= 16 * np.finfo(F32).eps * t.max()
     assert (got["t_enter"] <= got["t"]).all() and (got["t"] <= got["t_exit"]).all()
+
+
+# ---- the branches of the contract, family by family (meshrays_cases; tests/test_meshrays_gpu.py asks the kernel the same rays) --------
+def _both_forms(case, what):
+    """The brute-force answers of the restatement, which its pruned form must equal in their bits."""
+    with np.errstate(all="ignore"):
+        brute = first_hits_host(case.o, case.d, case.verts, case.faces)
+        assert_same(first_hits_host(case.o, case.d, case.verts, case.faces, pruned=True), brute, what + ", pruned")
+    return brute
+
+
+@pytest.mark.parametrize("mesh", ["cube", "icosphere"])
+def test_every_shear_and_the_ties_between_them(mesh):
+    case = rays.shears(mesh)
+    rays.expect_shears(case, *_both_forms(case, mesh))
+
+
+def test_axis_parallel_rays_from_both_sides_with_negative_zeros():
+    case = rays.axis_parallel()
+    rays.expect_axis_parallel(case, *_both_forms(case, "axis-parallel"))
+
+
+def test_the_clamp_is_active_on_flat_boxes():
+    """At least one hit in twenty has t != t_tri at every distance, and over the three both ends of the interval are taken."""
+    enter = leave = 0
+    for distance in (3.0, 1e2, 1e4):
+        case = rays.oblique_onto_cube(distance)
+        counts = rays.expect_oblique_onto_cube(case, *_both_forms(case, f"from {distance}"))
+        enter, leave = enter + counts[1], leave + counts[2]
+    assert enter >= 1 and leave >= 1
+
+
+def test_origins_on_the_surface_and_faces_without_area():
+    case = rays.surface_origins()
+    rays.expect_surface_origins(case, *_both_forms(case, "origins on the surface"))
+
+
+def test_denormal_components_and_overflow():
+    case = rays.denormal_rays()
+    rays.expect_denormal_rays(case, *_both_forms(case, "denormal components"))
+    rays.expect_all_miss(case.huge, *_both_forms(case.huge, "coordinates of 1e38"))
+
+
+@pytest.mark.parametrize("F", [1025, 16385])
+def test_comb_rays_that_prune_nothing_and_exact_hits(F):
+    case = rays.comb(F)
+    rays.expect_comb(case, *_both_forms(case, f"a comb of {F}"))
+
+
+def test_ties_between_the_leaves_of_a_plan():
+    case = rays.copies()
+    rays.expect_copies(case, *_both_forms(case, "301 copies of one face"))
+    case = rays.plane_vertex_rays(9, 7, 5)
+    assert len(case.o) == 6 * 80
+    rays.expect_plane_vertex_rays(case, *_both_forms(case, "diagonal rays through the vertices of a plane"))
+
+
+def test_four_levels_pruned_in_two_chunk_sizes():
+    case = rays.four_levels()
+    got = first_hits_host(case.o, case.d, case.verts, case.faces, pruned=True)
+    assert_same(first_hits_host(case.o, case.d, case.verts, case.faces, pruned=True, chunk_elems=1 << 17), got, "smaller chunks")
+    rays.expect_four_levels(case, *got)

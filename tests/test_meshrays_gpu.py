@@ -312,3 +312,78 @@ def test_triangle_votes_against_a_numpy_restatement():
     # masks as 0 / 255 images, poses and K as numpy: the same votes
     again = extract.triangle_votes(scene, [(m * 255).astype(np.uint8) for m in masks], c2ws, K, h, w)
     assert torch.equal(again[0], counter) and torch.equal(again[1], naive)
+
+
+# ---- the branches of the contract, family by family (meshrays_cases; tests/test_meshrays.py holds the restatement to the same rays) ---
+def _check_case(case, what, pruned=False):
+    """``check`` on a family: the kernel against the restatement in every bit, three ways; returns the restatement's answers."""
+    with np.errstate(all="ignore"):
+        return check(case.o, case.d, case.verts, case.faces, what, pruned=pruned)[:3]
+
+
+def _kernel(case):
+    return tuple(x.cpu().numpy() for x in meshquery.first_hits(*_on_gpu(case.o, case.d, case.verts, case.faces), return_bary=True))
+
+
+@pytest.mark.parametrize("mesh", ["cube", "icosphere"])
+def test_every_shear_and_the_ties_between_them(mesh):
+    """kz at exact ties of |d| (to the lowest axis), the kx / ky swap on each axis, -0.0 components, Sz != +-1."""
+    case = rays.shears(mesh)
+    rays.expect_shears(case, *_check_case(case, f"shears, {mesh}"))
+
+
+def test_axis_parallel_rays_and_flat_boxes():
+    """d_k == 0 (and -0.0) on two axes with lo_k == o_k == hi_k on flat boxes: the exact t, the near side."""
+    case = rays.axis_parallel()
+    rays.expect_axis_parallel(case, *_check_case(case, "axis-parallel"))
+    rays.expect_axis_parallel(case, *_kernel(case))
+
+
+@pytest.mark.parametrize("distance", [3.0, 1e2, 1e4])
+def test_the_clamp_at_work_on_flat_boxes(distance):
+    """Oblique rays onto the cube: one hit in six has t != t_tri (asserted by the family: one in twenty at least), so the bits of t
+    are those of the clamp."""
+    case = rays.oblique_onto_cube(distance)
+    rays.expect_oblique_onto_cube(case, *_check_case(case, f"oblique from {distance}"))
+
+
+def test_origins_on_the_surface_and_faces_without_area():
+    """t == +0.0 (never -0.0) from an origin on a face, det == 0 in a face's plane and on faces of zero area."""
+    case = rays.surface_origins()
+    rays.expect_surface_origins(case, *_check_case(case, "origins on the surface"))
+    face, t, _ = _kernel(case)
+    assert not np.signbit(t).any() and (t[case.normal] == 0).all() and not np.isin(face, case.degenerate).any()
+
+
+def test_denormal_components_and_overflow():
+    """Denormal components of d are kept (1 / d_k finite or +-inf by the value, 0 * inf dropped by fmax / fmin); overflowing
+    determinants are a miss."""
+    case = rays.denormal_rays()
+    rays.expect_denormal_rays(case, *_check_case(case, "denormal components"))
+    rays.expect_all_miss(case.huge, *_check_case(case.huge, "coordinates of 1e38"))
+
+
+@pytest.mark.parametrize("F", [1025, 16385])
+def test_comb_rays_that_prune_nothing_and_exact_hits(F):
+    """Whole waves that enter every leaf and hit nothing, waves that hit the first, the last and a middle plane, and all of them
+    mixed: the exact t and the plane."""
+    case = rays.comb(F)
+    rays.expect_comb(case, *_check_case(case, f"a comb of {F}"))
+    rays.expect_comb(case, *_kernel(case))
+
+
+def test_ties_between_leaves():
+    """An equal t with a lower face index in a leaf that is popped later: 301 copies of one face over five leaves, and diagonal rays
+    through the vertices of the integer plane, where up to six faces of several leaves tie."""
+    case = rays.copies()
+    rays.expect_copies(case, *_check_case(case, "301 copies of one face"))
+    assert (_kernel(case)[0] == case.same.min()).all()
+    case = rays.plane_vertex_rays(30, 20, 6)                          # the plane of test_exact_ties_on_the_gpu
+    rays.expect_plane_vertex_rays(case, *_check_case(case, "diagonal rays through the vertices of a plane"))
+    rays.expect_plane_vertex_rays(case, *_kernel(case))
+
+
+def test_four_levels():
+    """F = 262145: 4097 leaves under 257, 17 and 2 boxes, the level of a stack entry one higher than any other ray test has it."""
+    case = rays.four_levels()
+    rays.expect_four_levels(case, *_check_case(case, "four levels", pruned=True))
