@@ -86,7 +86,7 @@ from typing import Callable, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _mesh_host
+from . import _mesh_host, _takes
 from ._mesh_host import cross as _cross, dot as _dot, norm as _norm
 
 MAX_COUNT = (1 << 31) - 1
@@ -101,45 +101,26 @@ QUAT_FLOOR = _F(0.1)
 
 def _why_not(verts, faces, bary, complex, log_scales, thickness, want) -> Optional[str]:
     """None when the kernels take the call, else the reason they do not."""
-    if not all(isinstance(t, torch.Tensor) for t in (verts, faces, bary, complex, log_scales, thickness)):
-        return "every argument must be a torch.Tensor"
     if not want or any(w not in OUTPUTS for w in want) or len(set(want)) != len(want):
         return f"want must name some of {OUTPUTS}, each once (got {tuple(want)!r})"
-    for name, t in (("verts", verts), ("bary", bary), ("complex", complex), ("log_scales", log_scales), ("thickness", thickness)):
-        if t.dtype != torch.float32:
-            return f"{name} must be float32 (got {t.dtype})"
-    if faces.dtype != torch.int64:
-        return f"faces must be int64 (got {faces.dtype})"
-    if verts.dim() != 2 or verts.shape[1] != 3:
-        return f"verts must be [V, 3] (got {list(verts.shape)})"
-    if faces.dim() != 2 or faces.shape[1] != 3:
-        return f"faces must be [F, 3] (got {list(faces.shape)})"
-    if bary.dim() != 2 or bary.shape[1] != 3 or bary.shape[0] < 1:
-        return f"bary must be [G, 3] with G >= 1 (got {list(bary.shape)})"
+    why = (_takes.mesh(verts, faces, "bound_gaussians_host")
+           or _takes.tensors(tuple((name, t, torch.float32) for name, t in (("bary", bary), ("complex", complex), ("log_scales", log_scales),
+                                                                            ("thickness", thickness))), verts, "bound_gaussians_host")
+           or _takes.shaped("bary", bary, "[G, 3] with G >= 1", bary.dim() == 2 and bary.shape[1] == 3 and bary.shape[0] >= 1))
+    if why is not None:
+        return why
     G, F = int(bary.shape[0]), int(faces.shape[0])
     if G > MAX_G:
         return f"G = {G} Gaussians per face: at most {MAX_G}"
-    for name, t in (("complex", complex), ("log_scales", log_scales)):
-        if tuple(t.shape) != (F * G, 2):
-            return f"{name} must be [F G, 2] = [{F * G}, 2] (got {list(t.shape)})"
+    why = (_takes.shaped("complex", complex, f"[F G, 2] = [{F * G}, 2]", tuple(complex.shape) == (F * G, 2))
+           or _takes.shaped("log_scales", log_scales, f"[F G, 2] = [{F * G}, 2]", tuple(log_scales.shape) == (F * G, 2)))
+    if why is not None:
+        return why
     if thickness.numel() != 1:
         return f"thickness must hold one element (got {list(thickness.shape)})"
-    if not verts.is_cuda:
-        return f"verts must be on a GPU (got {verts.device}); there is no CPU path, see bound_gaussians_host"
-    for name, t in (("faces", faces), ("bary", bary), ("complex", complex), ("log_scales", log_scales), ("thickness", thickness)):
-        if t.device != verts.device:
-            return f"{name} must be on {verts.device} (got {t.device})"
     if verts.shape[0] > MAX_COUNT or F * G > MAX_COUNT:
         return f"{verts.shape[0]} vertices, {F * G} Gaussians: at most 2^31 - 1 of each"
-    from . import _lib
-
-    if _lib.capturing():
-        return "the current stream is capturing a graph (the call allocates its outputs)"
-    return None
-
-
-def _c(t: torch.Tensor) -> torch.Tensor:
-    return t.detach().contiguous()
+    return _takes.capturing("the call allocates its outputs")
 
 
 class _BoundGaussians(torch.autograd.Function):
@@ -147,7 +128,8 @@ class _BoundGaussians(torch.autograd.Function):
     def forward(ctx, verts, faces, bary, complex, log_scales, thickness, want, standardize):
         from . import _lib
 
-        v, f, b, z, s, th = _c(verts), _c(faces), _c(bary), _c(complex), _c(log_scales), _c(thickness).reshape(1)
+        v, f, b, z, s, th = _takes.cs(verts, faces, bary, complex, log_scales, thickness)
+        th = th.reshape(1)
         V, F, G = int(v.shape[0]), int(f.shape[0]), int(b.shape[0])
         out = {name: torch.empty((F * G, width), dtype=torch.float32, device=v.device) if name in want else None
                for name, width in zip(OUTPUTS, (3, 3, 4))}
@@ -166,7 +148,7 @@ class _BoundGaussians(torch.autograd.Function):
 
         v, f, b, z, s = ctx.saved_tensors
         V, F, G = int(v.shape[0]), int(f.shape[0]), int(b.shape[0])
-        grads = [None if g is None else _c(g) for g in (grad_points, grad_scaling, grad_quaternions)]
+        grads = [None if g is None else _takes.c(g) for g in (grad_points, grad_scaling, grad_quaternions)]
         grad_verts = torch.empty((V, 3), dtype=torch.float32, device=v.device)
         grad_complex = torch.empty((F * G, 2), dtype=torch.float32, device=v.device)
         grad_log_scales = torch.empty((F * G, 2), dtype=torch.float32, device=v.device)
@@ -186,9 +168,7 @@ def bound_gaussians(verts, faces, bary, complex, log_scales, thickness, *, want:
     ``matrix_to_quaternion`` does from pytorch3d 0.7.5 on.  No host synchronisation.  CPU tensors, other dtypes or shapes, mixed devices,
     ``G > 8`` and graph capture raise ``ValueError`` with the reason."""
     want = tuple(want)
-    why = _why_not(verts, faces, bary, complex, log_scales, thickness, want)
-    if why is not None:
-        raise ValueError("bound_gaussians: " + why)
+    _takes.refuse("bound_gaussians", _why_not(verts, faces, bary, complex, log_scales, thickness, want))
     out = dict(zip(OUTPUTS, _BoundGaussians.apply(verts, faces, bary, complex, log_scales, thickness, want, bool(standardize))))
     return tuple(out[name] for name in want)
 
@@ -223,8 +203,6 @@ def _why_original(self) -> Optional[str]:
 
 
 def _drop_in(name: str, original_fget: Callable) -> Callable:
-    from . import _lib  # noqa: F401  (a missing library shows when the patch is made)
-
     probed = []
 
     def fget(self):
@@ -241,10 +219,7 @@ def _drop_in(name: str, original_fget: Callable) -> Callable:
         return bound_gaussians(self._points, self._surface_mesh_faces, self.surface_triangle_bary_coords[..., 0], self._quaternions, self._scales,
                                self.surface_mesh_thickness, want=(name,), standardize=standardize)[0]
 
-    fget.__name__ = fget.__qualname__ = name
-    fget.fallback = original_fget
-    fget.__doc__ = (f"SuGaR.{name}: the fused HIP bound Gaussians where they apply (autovfx_amd/bound.py), the reference's getter otherwise.")
-    return fget
+    return _takes.dressed(fget, name, original_fget, f"SuGaR.{name}", "bound")
 
 
 def drop_in_points(original_fget: Callable) -> Callable:

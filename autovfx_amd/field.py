@@ -31,6 +31,8 @@ import numpy as np
 import torch
 from torch.autograd.function import once_differentiable
 
+from . import _takes
+
 MAX_K = 64
 MAX_COUNT = (1 << 30) - 1
 Q_MAX = 1e8
@@ -38,43 +40,21 @@ Q_MAX = 1e8
 
 def _why_not(x, idx, centers, inv_scaled_rotation, strengths, min_scaling=None, want_beta=False) -> Optional[str]:
     """None when the kernels take the call, else the reason they do not."""
-    named = (("x", x), ("idx", idx), ("centers", centers), ("inv_scaled_rotation", inv_scaled_rotation), ("strengths", strengths))
-    if min_scaling is not None:
-        named += (("min_scaling", min_scaling),)
-    for name, t in named:
-        if not isinstance(t, torch.Tensor):
-            return f"{name} must be a torch.Tensor, not {type(t).__name__}"
-    for name, t in named:
-        if not t.is_cuda:
-            return f"{name} must be on a GPU (got {t.device}); there is no CPU path, see field_values_host"
-        if t.device != x.device:
-            return f"all tensors must be on one device ({name} is on {t.device}, x on {x.device})"
-        if t.dtype != (torch.int64 if name == "idx" else torch.float32):
-            return f"{name} must be {'int64' if name == 'idx' else 'float32'} (got {t.dtype})"
-    if x.dim() != 2 or x.shape[1] != 3:
-        return f"x must be [N, 3] (got {list(x.shape)})"
-    if idx.dim() != 2 or idx.shape[0] != x.shape[0]:
-        return f"idx must be [N, K] with N = {x.shape[0]} (got {list(idx.shape)})"
-    if not 1 <= idx.shape[1] <= MAX_K:
-        return f"K must be in 1..{MAX_K} (got {idx.shape[1]})"
-    if centers.dim() != 2 or centers.shape[1] != 3:
-        return f"centers must be [P, 3] (got {list(centers.shape)})"
+    f32 = torch.float32
+    named = (("x", x, f32), ("idx", idx, torch.int64), ("centers", centers, f32), ("inv_scaled_rotation", inv_scaled_rotation, f32),
+             ("strengths", strengths, f32)) + ((("min_scaling", min_scaling, f32),) if min_scaling is not None else ())
+    why = (_takes.tensors(named, host="field_values_host") or _takes.shaped("x", x, "[N, 3]", x.dim() == 2 and x.shape[1] == 3)
+           or _takes.gaussians(x.shape[0], idx, centers, inv_scaled_rotation, strengths, MAX_K, "N"))
+    if why is not None:
+        return why
     P = centers.shape[0]
-    if tuple(inv_scaled_rotation.shape) != (P, 3, 3):
-        return f"inv_scaled_rotation must be [P, 3, 3] with P = {P} (got {list(inv_scaled_rotation.shape)})"
-    if tuple(strengths.shape) not in ((P,), (P, 1)):
-        return f"strengths must be [P] or [P, 1] with P = {P} (got {list(strengths.shape)})"
     if min_scaling is not None and tuple(min_scaling.shape) != (P,):
-        return f"min_scaling must be [P] with P = {P} (got {list(min_scaling.shape)})"
+        return _takes.shaped("min_scaling", min_scaling, f"[P] with P = {P}", False)
     if want_beta and min_scaling is None:
         return "beta needs min_scaling"
     if x.shape[0] > MAX_COUNT or P > MAX_COUNT:
         return f"{x.shape[0]} samples and {P} Gaussians: at most 2^30 - 1 each"
-    from . import _lib
-
-    if _lib.capturing():
-        return "the current stream is capturing a graph (the call allocates its scratch)"
-    return None
+    return _takes.capturing("the call allocates its scratch")
 
 
 def field_takes(x, idx, centers, inv_scaled_rotation, strengths, min_scaling=None, density_factor=1.0, want_opacities=False,
@@ -94,8 +74,8 @@ class _Field(torch.autograd.Function):
         from . import _lib
 
         ctx.set_materialize_grads(False)      # an output nobody differentiates reaches the kernel as NULL, not as [N, K] zeros
-        xs, ix, cs, Ms, ss = (t.detach().contiguous() for t in (x, idx, centers, M, strengths))
-        ms = None if min_scaling is None else min_scaling.detach().contiguous()
+        xs, ix, cs, Ms, ss = _takes.cs(x, idx, centers, M, strengths)
+        ms = None if min_scaling is None else _takes.c(min_scaling)
         N, K, P = int(xs.shape[0]), int(ix.shape[1]), int(cs.shape[0])
         dev = xs.device
         density = torch.empty(N, dtype=torch.float32, device=dev)
@@ -150,10 +130,8 @@ def field_values(x, idx, centers, inv_scaled_rotation, strengths, min_scaling=No
     synchronisation.  Gradients flow into ``x``, ``centers``, ``inv_scaled_rotation``, ``strengths`` and ``min_scaling``, each only if it
     requires one.  A call :func:`field_takes` rejects raises ``ValueError`` with the reason."""
     if isinstance(density_factor, torch.Tensor) or not isinstance(density_factor, (int, float)):
-        raise ValueError(f"field_values: density_factor must be a host number (got {type(density_factor).__name__})")
-    why = _why_not(x, idx, centers, inv_scaled_rotation, strengths, min_scaling, want_beta)
-    if why is not None:
-        raise ValueError("field_values: " + why)
+        _takes.refuse("field_values", f"density_factor must be a host number (got {type(density_factor).__name__})")
+    _takes.refuse("field_values", _why_not(x, idx, centers, inv_scaled_rotation, strengths, min_scaling, want_beta))
     return _Field.apply(x, idx, centers, inv_scaled_rotation, strengths, min_scaling if want_beta else None, float(density_factor),
                         bool(want_opacities), bool(want_beta))
 
@@ -241,17 +219,13 @@ def field_grads_host(x, idx, centers, inv_scaled_rotation, strengths, min_scalin
 # ---- what install() puts on SuGaR ----
 def _quick_no(x) -> bool:
     """Calls that go to the reference before any input is built: not a CUDA float32 [N, 3] sample tensor, or under graph capture."""
-    from . import _lib
-
     return (not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] != 3
-            or _lib.capturing())
+            or _takes.capturing("") is not None)
 
 
 def drop_in_compute_density(original: Callable) -> Callable:
     """``SuGaR.compute_density`` (``sugar_model.py:1216-1239``): the inputs are built as the reference builds them, the gather, product,
     ``exp`` and sum are :func:`field_values`.  A call the kernels do not take (CPU tensors, another dtype, ...) runs ``original``."""
-    from . import _lib  # noqa: F401   (a missing library shows when the patch is made)
-
     def compute_density(self, x, closest_gaussians_idx=None, density_factor=1., return_closest_gaussian_opacities=False):
         if _quick_no(x):
             return original(self, x, closest_gaussians_idx=closest_gaussians_idx, density_factor=density_factor,
@@ -268,9 +242,7 @@ def drop_in_compute_density(original: Callable) -> Callable:
                                                         want_opacities=return_closest_gaussian_opacities)
         return (densities, neighbor_opacities) if return_closest_gaussian_opacities else densities
 
-    compute_density.fallback = original
-    compute_density.__doc__ = "SuGaR.compute_density: the fused HIP density field where it applies (autovfx_amd/field.py), the reference's otherwise."
-    return compute_density
+    return _takes.dressed(compute_density, "compute_density", original, "SuGaR.compute_density", "field")
 
 
 def drop_in_get_field_values(original: Callable) -> Callable:
@@ -278,8 +250,6 @@ def drop_in_get_field_values(original: Callable) -> Callable:
     gather / product / ``exp`` / sum (and ``get_beta``'s ``'average'`` mode) in :func:`field_values`, then the reference's own statements:
     the ``density`` clone, the ``>= 1`` renormalisation, ``get_beta`` for the other modes, the clamped densities, the ``sdf`` value.
     ``return_sdf_grad=True`` (no trainer passes it) and every call the kernels do not take run ``original``."""
-    from . import _lib  # noqa: F401
-
     def get_field_values(self, x, gaussian_idx=None, closest_gaussians_idx=None, gaussian_strengths=None, gaussian_centers=None,
                          gaussian_inv_scaled_rotation=None, return_sdf=True, density_threshold=1., density_factor=1.,
                          return_sdf_grad=False, sdf_grad_max_value=10., opacity_min_clamp=1e-16,
@@ -331,6 +301,4 @@ def drop_in_get_field_values(original: Callable) -> Callable:
             fields["sdf"] = beta * (torch.sqrt(-2.0 * torch.log(densities.clamp(min=opacity_min_clamp))) - level)
         return fields
 
-    get_field_values.fallback = original
-    get_field_values.__doc__ = "SuGaR.get_field_values: the fused HIP density field where it applies (autovfx_amd/field.py), the reference's otherwise."
-    return get_field_values
+    return _takes.dressed(get_field_values, "get_field_values", original, "SuGaR.get_field_values", "field")

@@ -32,6 +32,8 @@ from typing import Callable, NamedTuple, Optional
 import numpy as np
 import torch
 
+from . import _takes
+
 FLT_MAX = float(np.finfo(np.float32).max)
 MAX_POINTS = (1 << 30) - 1
 MAX_K = 16
@@ -40,14 +42,13 @@ MAX_K = 16
 def _check(points) -> None:
     if not isinstance(points, torch.Tensor):
         raise TypeError(f"points must be a torch.Tensor, not {type(points).__name__}")
-    if points.device.type != "cuda":
-        raise ValueError(f"points must be on a GPU (got a tensor on {points.device}); there is no CPU path, see mean_dist3_host")
-    if points.dim() != 2 or points.shape[1] != 3:
-        raise ValueError(f"points must be [P, 3] (got {list(points.shape)})")
+    # (the dtype is judged after the shape and with the reference's exception: here any dtype passes)
+    _takes.refuse("mean_dist3", _takes.tensors((("points", points, points.dtype),), host="mean_dist3_host")
+                  or _takes.shaped("points", points, "[P, 3]", points.dim() == 2 and points.shape[1] == 3))
     if points.dtype != torch.float32:
         raise RuntimeError(f"expected a float32 tensor of points, got {points.dtype}")
     if points.shape[0] > MAX_POINTS:
-        raise ValueError(f"{points.shape[0]} points: at most 2^30 - 1")
+        _takes.refuse("mean_dist3", f"{points.shape[0]} points: at most 2^30 - 1")
 
 
 def mean_dist3(points: torch.Tensor) -> torch.Tensor:
@@ -57,7 +58,7 @@ def mean_dist3(points: torch.Tensor) -> torch.Tensor:
     from . import _lib
 
     _check(points)
-    pts = points.detach().contiguous()
+    pts = _takes.c(points)
     P = int(pts.shape[0])
     out = torch.empty(P, dtype=torch.float32, device=pts.device)
     if P == 0:
@@ -110,16 +111,11 @@ class KNN(NamedTuple):
 
 def _why_not(p1, p2, lengths1, lengths2, norm, K) -> Optional[str]:
     """None when the kernels take the call, else the reason they do not."""
-    if not (isinstance(p1, torch.Tensor) and isinstance(p2, torch.Tensor)):
-        return "p1 and p2 must be torch.Tensors"
-    if not (p1.is_cuda and p2.is_cuda):
-        return f"p1 and p2 must be on a GPU (got {p1.device} and {p2.device}); there is no CPU path, see knn_points_host"
-    if p1.device != p2.device:
-        return f"p1 and p2 must be on one device (got {p1.device} and {p2.device})"
-    if p1.dtype != torch.float32 or p2.dtype != torch.float32:
-        return f"p1 and p2 must be float32 (got {p1.dtype} and {p2.dtype})"
-    if p1.dim() != 3 or p2.dim() != 3 or p1.shape[2] != 3 or p2.shape[2] != 3:
-        return f"p1 and p2 must be [N, P, 3] (got {list(p1.shape)} and {list(p2.shape)})"
+    why = (_takes.tensors((("p1", p1, torch.float32), ("p2", p2, torch.float32)), host="knn_points_host")
+           or _takes.shaped("p1", p1, "[N, P1, 3]", p1.dim() == 3 and p1.shape[2] == 3)
+           or _takes.shaped("p2", p2, "[N, P2, 3]", p2.dim() == 3 and p2.shape[2] == 3))
+    if why is not None:
+        return why
     if p1.shape[0] != p2.shape[0] or p1.shape[0] < 1:
         return f"p1 and p2 must have the same batch size N >= 1 (got {p1.shape[0]} and {p2.shape[0]})"
     if lengths1 is not None or lengths2 is not None:
@@ -132,11 +128,7 @@ def _why_not(p1, p2, lengths1, lengths2, norm, K) -> Optional[str]:
         return f"p2 has {p2.shape[1]} points, fewer than K = {K}"
     if p1.shape[1] > MAX_POINTS or p2.shape[1] > MAX_POINTS:
         return f"{p1.shape[1]} and {p2.shape[1]} points: at most 2^30 - 1 each"
-    from . import _lib
-
-    if _lib.capturing():
-        return "the current stream is capturing a graph (the call allocates its scratch)"
-    return None
+    return _takes.capturing("the call allocates its scratch")
 
 
 def knn_points_takes(p1, p2, lengths1=None, lengths2=None, norm=2, K=1, version=-1, return_nn=False, return_sorted=True) -> bool:
@@ -154,8 +146,8 @@ def _search(p1: torch.Tensor, p2: torch.Tensor, K: int):
     from . import _lib
 
     same = _same_view(p1, p2)
-    c1 = p1.detach().contiguous()
-    c2 = c1 if same else p2.detach().contiguous()
+    c1 = _takes.c(p1)
+    c2 = c1 if same else _takes.c(p2)
     N, P1, P2 = int(c1.shape[0]), int(c1.shape[1]), int(c2.shape[1])
     dists = torch.empty((N, P1, K), dtype=torch.float32, device=c1.device)
     idx = torch.empty((N, P1, K), dtype=torch.int64, device=c1.device)
@@ -216,30 +208,21 @@ def knn_points(p1, p2, lengths1=None, lengths2=None, norm: int = 2, K: int = 1, 
     by ``idx >= 0``).  Rows are always sorted (``return_sorted=False`` allows it);
     ``version`` is ignored.  Passing the same tensor twice is the self query, which needs no second sort.  A call
     :func:`knn_points_takes` rejects raises ``ValueError`` with the reason; queued on the current stream, no host synchronisation."""
-    why = _why_not(p1, p2, lengths1, lengths2, norm, K)
-    if why is not None:
-        raise ValueError("knn_points: " + why)
+    _takes.refuse("knn_points", _why_not(p1, p2, lengths1, lengths2, norm, K))
     return _taken(p1, p2, K, return_nn)
 
 
 def drop_in(original: Callable) -> Callable:
     """A ``knn_points`` that runs the kernels for the calls :func:`knn_points_takes` accepts and ``original`` (pytorch3d's, same
     signature) for every other: CPU tensors, ``lengths``, other norms, K above 16, and 2-D points
-    (``sugar_extractors/refined_mesh.py:147``).  ``autovfx_amd.install()`` builds it around ``pytorch3d.ops.knn.knn_points``.  The
-    library is loaded here, so that a missing one shows when the patch is made."""
-    from . import _lib  # noqa: F401
-
+    (``sugar_extractors/refined_mesh.py:147``).  ``autovfx_amd.install()`` builds it around ``pytorch3d.ops.knn.knn_points``."""
     def knn_points_drop_in(p1, p2, lengths1=None, lengths2=None, norm=2, K=1, version=-1, return_nn=False, return_sorted=True):
         if _why_not(p1, p2, lengths1, lengths2, norm, K) is not None:
             return original(p1, p2, lengths1=lengths1, lengths2=lengths2, norm=norm, K=K, version=version, return_nn=return_nn,
                             return_sorted=return_sorted)
         return _taken(p1, p2, K, return_nn)
 
-    knn_points_drop_in.__name__ = knn_points_drop_in.__qualname__ = "knn_points"
-    knn_points_drop_in.fallback = original
-    knn_points_drop_in.__doc__ = ("pytorch3d.ops.knn_points: HIP kernels where they apply (autovfx_amd/knn.py), "
-                                  f"{getattr(original, '__module__', '?')}.{getattr(original, '__name__', '?')} otherwise.")
-    return knn_points_drop_in
+    return _takes.dressed(knn_points_drop_in, "knn_points", original, "pytorch3d.ops.knn_points", "knn")
 
 
 def knn_points_host(p1, p2, K: int, chunk_elems: int = 1 << 23):

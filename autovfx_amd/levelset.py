@@ -29,6 +29,7 @@ from typing import Callable, Optional
 import numpy as np
 import torch
 
+from . import _takes
 from .field import MAX_COUNT, MAX_K, _host_inputs, _host_pairs, _sum_ascending, field_values_host
 
 MAX_S = 32
@@ -48,50 +49,28 @@ def _levels_why_not(levels, n_points_in_range) -> Optional[str]:
 
 def _why_not(origins, dirs, stds, idx, centers, inv_scaled_rotation, strengths, levels, n_points_in_range=21) -> Optional[str]:
     """None when the kernel takes the call, else the reason it does not."""
-    named = (("origins", origins), ("dirs", dirs), ("stds", stds), ("idx", idx), ("centers", centers),
-             ("inv_scaled_rotation", inv_scaled_rotation), ("strengths", strengths))
-    for name, t in named:
-        if not isinstance(t, torch.Tensor):
-            return f"{name} must be a torch.Tensor, not {type(t).__name__}"
-    for name, t in named:
-        if not t.is_cuda:
-            return f"{name} must be on a GPU (got {t.device}); there is no CPU path, see level_surface_host"
-        if t.device != origins.device:
-            return f"all tensors must be on one device ({name} is on {t.device}, origins on {origins.device})"
-        if t.dtype != (torch.int64 if name == "idx" else torch.float32):
-            return f"{name} must be {'int64' if name == 'idx' else 'float32'} (got {t.dtype})"
-    if origins.dim() != 2 or origins.shape[1] != 3:
-        return f"origins must be [n, 3] (got {list(origins.shape)})"
+    named = tuple((name, t, torch.int64 if name == "idx" else torch.float32) for name, t in (
+        ("origins", origins), ("dirs", dirs), ("stds", stds), ("idx", idx), ("centers", centers),
+        ("inv_scaled_rotation", inv_scaled_rotation), ("strengths", strengths)))
+    why = _takes.tensors(named, host="level_surface_host") or _takes.shaped("origins", origins, "[n, 3]", origins.dim() == 2 and origins.shape[1] == 3)
+    if why is not None:
+        return why
     n = origins.shape[0]
-    if tuple(dirs.shape) != (n, 3):
-        return f"dirs must be [n, 3] with n = {n} (got {list(dirs.shape)})"
-    if tuple(stds.shape) != (n,):
-        return f"stds must be [n] with n = {n} (got {list(stds.shape)})"
-    if idx.dim() != 2 or idx.shape[0] != n:
-        return f"idx must be [n, K] with n = {n} (got {list(idx.shape)})"
-    if not 1 <= idx.shape[1] <= MAX_K:
-        return f"K must be in 1..{MAX_K} (got {idx.shape[1]})"
-    if centers.dim() != 2 or centers.shape[1] != 3:
-        return f"centers must be [P, 3] (got {list(centers.shape)})"
-    P = centers.shape[0]
-    if tuple(inv_scaled_rotation.shape) != (P, 3, 3):
-        return f"inv_scaled_rotation must be [P, 3, 3] with P = {P} (got {list(inv_scaled_rotation.shape)})"
-    if tuple(strengths.shape) not in ((P,), (P, 1)):
-        return f"strengths must be [P] or [P, 1] with P = {P} (got {list(strengths.shape)})"
-    if n > MAX_COUNT or P > MAX_COUNT:
-        return f"{n} rays and {P} Gaussians: at most 2^30 - 1 each"
+    why = (_takes.shaped("dirs", dirs, f"[n, 3] with n = {n}", tuple(dirs.shape) == (n, 3))
+           or _takes.shaped("stds", stds, f"[n] with n = {n}", tuple(stds.shape) == (n,))
+           or _takes.gaussians(n, idx, centers, inv_scaled_rotation, strengths, MAX_K))
+    if why is not None:
+        return why
+    if n > MAX_COUNT or centers.shape[0] > MAX_COUNT:
+        return f"{n} rays and {centers.shape[0]} Gaussians: at most 2^30 - 1 each"
     why = _levels_why_not(levels, n_points_in_range)
     if why is not None:
         return why
     if torch.is_grad_enabled():
-        for name, t in named:
+        for name, t, _ in named:
             if t.requires_grad:
                 return f"{name} requires a gradient and autograd is on: the ray march has no backward (the extractor runs under no_grad)"
-    from . import _lib
-
-    if _lib.capturing():
-        return "the current stream is capturing a graph (the call allocates its scratch)"
-    return None
+    return _takes.capturing("the call allocates its scratch")
 
 
 def _host_number(name, v) -> Optional[str]:
@@ -117,13 +96,11 @@ def level_surface(origins, dirs, stds, idx, centers, inv_scaled_rotation, streng
     """The contract above on the current stream, no host synchronisation after the 4 S bytes of ``range`` went to the device:
     ``{"hit": bool [L, n], "t": [L, n], "points": [L, n, 3], "normals": [L, n, 3] or None, "densities": [n, S] or None}``, dense per
     level, rows of empty rays zero.  A call :func:`level_surface_takes` rejects raises ``ValueError`` with the reason."""
-    why = (_host_number("range_size", range_size) or _host_number("density_factor", density_factor)
-           or _why_not(origins, dirs, stds, idx, centers, inv_scaled_rotation, strengths, levels, n_points_in_range))
-    if why is not None:
-        raise ValueError("level_surface: " + why)
+    _takes.refuse("level_surface", _host_number("range_size", range_size) or _host_number("density_factor", density_factor)
+                  or _why_not(origins, dirs, stds, idx, centers, inv_scaled_rotation, strengths, levels, n_points_in_range))
     from . import _lib
 
-    o, v, sd, ix, cs, Ms, ss = (t.detach().contiguous() for t in (origins, dirs, stds, idx, centers, inv_scaled_rotation, strengths))
+    o, v, sd, ix, cs, Ms, ss = _takes.cs(origins, dirs, stds, idx, centers, inv_scaled_rotation, strengths)
     n, K, P, S, L = int(o.shape[0]), int(ix.shape[1]), int(cs.shape[0]), int(n_points_in_range), len(levels)
     dev = o.device
     hit = torch.empty((L, n), dtype=torch.uint8, device=dev)
@@ -226,8 +203,6 @@ def drop_in_compute_level_surface_points_from_camera_fast(original: Callable) ->
     state; should the tensors the model's own objects return turn out not to be the kernel's after the draw, the generator's state is
     put back before ``original`` runs.  ``quaternion_apply``, ``quaternion_invert``, ``RasterizationSettings`` and ``MeshRasterizer`` are the names the reference's
     own module imported, where it has them."""
-    from . import _lib
-
     names = original.__globals__
 
     def why_original(self, surface_levels, n_points_in_range, range_size, density_factor, compute_flat_normals,
@@ -247,9 +222,7 @@ def drop_in_compute_level_surface_points_from_camera_fast(original: Callable) ->
         K = getattr(self, "knn_to_track", None) or (knn_idx.shape[-1] if isinstance(knn_idx, torch.Tensor) else 0)
         if not 1 <= K <= MAX_K:
             return f"{K} neighbours"
-        if _lib.capturing():
-            return "graph capture"
-        return None
+        return _takes.capturing("the call allocates its scratch")
 
     def compute_level_surface_points_from_camera_fast(
             self, nerf_cameras=None, cam_idx=0, rasterizer=None, surface_levels=[0.1, 0.3, 0.5], n_surface_points=-1, primitive_types=None,
@@ -346,7 +319,5 @@ def drop_in_compute_level_surface_points_from_camera_fast(original: Callable) ->
             all_outputs[surface_level] = outputs
         return all_outputs
 
-    compute_level_surface_points_from_camera_fast.fallback = original
-    compute_level_surface_points_from_camera_fast.__doc__ = ("SuGaR.compute_level_surface_points_from_camera_fast: the fused HIP ray march "
-                                                             "where it applies (autovfx_amd/levelset.py), the reference's otherwise.")
-    return compute_level_surface_points_from_camera_fast
+    return _takes.dressed(compute_level_surface_points_from_camera_fast, "compute_level_surface_points_from_camera_fast", original,
+                          "SuGaR.compute_level_surface_points_from_camera_fast", "levelset")

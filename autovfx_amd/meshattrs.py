@@ -69,7 +69,7 @@ from typing import Callable, Optional, Tuple
 import numpy as np
 import torch
 
-from . import _mesh_host
+from . import _mesh_host, _takes
 
 MAX_COUNT = (1 << 31) - 1
 MAX_D = 65536
@@ -78,71 +78,40 @@ _F = np.float32
 
 # ---- which calls the kernels take -----------------------------------------------------------------------------------------------------
 
-def _capturing() -> Optional[str]:
-    from . import _lib
-
-    if _lib.capturing():
-        return "the current stream is capturing a graph (the call allocates its outputs; such a call is left to the original)"
-    return None
-
-
-def _float_on(name: str, t, like, shape_text: str, ok) -> Optional[str]:
-    """``t``: a CUDA float32 tensor on ``like``'s device (``like`` None: any GPU) whose shape ``ok(t)`` accepts."""
-    if not t.is_cuda:
-        return f"{name} must be on a GPU (got {t.device}); there is no CPU path, see the *_host functions"
-    if t.dtype != torch.float32:
-        return f"{name} must be float32 (got {t.dtype})"
-    if like is not None and t.device != like.device:
-        return f"{name} must be on {like.device} (got {t.device})"
-    if not ok(t):
-        return f"{name} must be {shape_text} (got {list(t.shape)})"
-    return None
-
-
-def _index_on(name: str, t, like, shape_text: str, ok) -> Optional[str]:
-    if t.dtype != torch.int64:
-        return f"{name} must be int64 (got {t.dtype})"
-    if not t.is_cuda or t.device != like.device:
-        return f"{name} must be on {like.device} (got {t.device})"
-    if not ok(t):
-        return f"{name} must be {shape_text} (got {list(t.shape)})"
-    return None
+ALLOCATES = "the call allocates its outputs; such a call is left to the original"
+_f32, _i64 = torch.float32, torch.int64
 
 
 def _why_not_faces(verts, faces, grad_areas=None, grad_normals=None, backward: bool = False) -> Optional[str]:
     """None when the kernels take the call, else the reason they do not."""
-    tensors = (verts, faces) + ((grad_areas, grad_normals) if backward else ())
-    if not all(isinstance(t, torch.Tensor) for t in tensors):
-        return "every argument must be a torch.Tensor"
-    why = (_float_on("verts", verts, None, "[V, 3]", lambda t: t.dim() == 2 and t.shape[1] == 3)
-           or _index_on("faces", faces, verts, "[F, 3]", lambda t: t.dim() == 2 and t.shape[1] == 3))
+    why = _takes.mesh(verts, faces)
     if why is None and backward:
         F = faces.shape[0]
-        why = (_float_on("grad_areas", grad_areas, verts, "[F]", lambda t: t.dim() == 1 and t.shape[0] == F)
-               or _float_on("grad_normals", grad_normals, verts, "[F, 3]", lambda t: t.dim() == 2 and tuple(t.shape) == (F, 3)))
+        why = (_takes.tensors((("grad_areas", grad_areas, _f32), ("grad_normals", grad_normals, _f32)), like=verts)
+               or _takes.shaped("grad_areas", grad_areas, "[F]", tuple(grad_areas.shape) == (F,))
+               or _takes.shaped("grad_normals", grad_normals, "[F, 3]", tuple(grad_normals.shape) == (F, 3)))
     if why is None and (verts.shape[0] > MAX_COUNT or faces.shape[0] > MAX_COUNT):
         why = f"{verts.shape[0]} vertices, {faces.shape[0]} faces: at most 2^31 - 1 of each"
-    return why or _capturing()
+    return why or _takes.capturing(ALLOCATES)
 
 
 def _why_not_interp(pix_to_face, bary, attrs, grad_out=None, backward: bool = False) -> Optional[str]:
     """None when the kernels take the call, else the reason they do not."""
-    tensors = (pix_to_face, bary, attrs) + ((grad_out,) if backward else ())
-    if not all(isinstance(t, torch.Tensor) for t in tensors):
-        return "every argument must be a torch.Tensor"
-    why = _float_on("face_attributes", attrs, None, "[F, 3, D] with D >= 1", lambda t: t.dim() == 3 and t.shape[1] == 3 and t.shape[2] >= 1)
+    why = _takes.tensors((("face_attributes", attrs, _f32), ("pix_to_face", pix_to_face, _i64), ("barycentric_coords", bary, _f32))
+                         + ((("grad_pix_attrs", grad_out, _f32),) if backward else ()))
+    if why is None:
+        why = _takes.shaped("face_attributes", attrs, "[F, 3, D] with D >= 1", attrs.dim() == 3 and attrs.shape[1] == 3 and attrs.shape[2] >= 1)
     if why is None and attrs.shape[2] > MAX_D:
         why = f"D = {attrs.shape[2]}: at most {MAX_D}"
     if why is None:
-        why = (_index_on("pix_to_face", pix_to_face, attrs, "[P] or [N, H, W, K]", lambda t: t.dim() >= 1)
-               or _float_on("barycentric_coords", bary, attrs, "pix_to_face's shape + [3]",
-                            lambda t: tuple(t.shape) == tuple(pix_to_face.shape) + (3,)))
-    if why is None and backward:
-        D = attrs.shape[2]
-        why = _float_on("grad_pix_attrs", grad_out, attrs, "pix_to_face's shape + [D]", lambda t: tuple(t.shape) == tuple(pix_to_face.shape) + (D,))
+        S = tuple(pix_to_face.shape)
+        why = (_takes.shaped("pix_to_face", pix_to_face, "[P] or [N, H, W, K]", len(S) >= 1)
+               or _takes.shaped("barycentric_coords", bary, "pix_to_face's shape + [3]", tuple(bary.shape) == S + (3,))
+               or (_takes.shaped("grad_pix_attrs", grad_out, "pix_to_face's shape + [D]", tuple(grad_out.shape) == S + (attrs.shape[2],))
+                   if backward else None))
     if why is None and (pix_to_face.numel() > MAX_COUNT or attrs.shape[0] > MAX_COUNT):
         why = f"{pix_to_face.numel()} slots, {attrs.shape[0]} faces: at most 2^31 - 1 of each"
-    return why or _capturing()
+    return why or _takes.capturing(ALLOCATES)
 
 
 def face_areas_normals_takes(verts, faces) -> bool:
@@ -169,14 +138,10 @@ def interpolate_face_attributes_backward_takes(pix_to_face, barycentric_coords, 
 
 # ---- the calls ------------------------------------------------------------------------------------------------------------------------
 
-def _c(t: torch.Tensor) -> torch.Tensor:
-    return t.detach().contiguous()
-
-
 def _faces_forward(verts, faces):
     from . import _lib
 
-    v, f = _c(verts), _c(faces)
+    v, f = _takes.cs(verts, faces)
     V, F = int(v.shape[0]), int(f.shape[0])
     areas = torch.empty((F,), dtype=torch.float32, device=v.device)
     normals = torch.empty((F, 3), dtype=torch.float32, device=v.device)
@@ -188,7 +153,7 @@ def _faces_forward(verts, faces):
 def _faces_backward(grad_areas, grad_normals, verts, faces):
     from . import _lib
 
-    v, f, ga, gn = _c(verts), _c(faces), _c(grad_areas), _c(grad_normals)
+    v, f, ga, gn = _takes.cs(verts, faces, grad_areas, grad_normals)
     V, F = int(v.shape[0]), int(f.shape[0])
     grad_verts = torch.empty((V, 3), dtype=torch.float32, device=v.device)
     with torch.cuda.device(v.device):
@@ -200,7 +165,7 @@ def _faces_backward(grad_areas, grad_normals, verts, faces):
 def _interp_forward(pix_to_face, bary, attrs):
     from . import _lib
 
-    p, w, a = _c(pix_to_face), _c(bary), _c(attrs)
+    p, w, a = _takes.cs(pix_to_face, bary, attrs)
     P, F, D = int(p.numel()), int(a.shape[0]), int(a.shape[2])
     out = torch.empty(tuple(p.shape) + (D,), dtype=torch.float32, device=a.device)
     with torch.cuda.device(a.device):
@@ -211,7 +176,7 @@ def _interp_forward(pix_to_face, bary, attrs):
 def _interp_backward(pix_to_face, bary, attrs, grad_out):
     from . import _lib
 
-    p, w, a, g = _c(pix_to_face), _c(bary), _c(attrs), _c(grad_out)
+    p, w, a, g = _takes.cs(pix_to_face, bary, attrs, grad_out)
     P, F, D = int(p.numel()), int(a.shape[0]), int(a.shape[2])
     grad_bary = torch.empty(tuple(p.shape) + (3,), dtype=torch.float32, device=a.device)
     grad_attrs = torch.empty((F, 3, D), dtype=torch.float32, device=a.device)
@@ -224,27 +189,21 @@ def _interp_backward(pix_to_face, bary, attrs, grad_out):
 def face_areas_normals_forward(verts, faces) -> Tuple[torch.Tensor, torch.Tensor]:
     """``pytorch3d._C.face_areas_normals_forward`` -> ``(areas [F], normals [F, 3])`` by the module's contract, queued on the current stream.
     Non-contiguous inputs are copied.  A call :func:`face_areas_normals_takes` rejects raises ``ValueError`` with the reason."""
-    why = _why_not_faces(verts, faces)
-    if why is not None:
-        raise ValueError("face_areas_normals_forward: " + why)
+    _takes.refuse("face_areas_normals_forward", _why_not_faces(verts, faces))
     return _faces_forward(verts, faces)
 
 
 def face_areas_normals_backward(grad_areas, grad_normals, verts, faces) -> torch.Tensor:
     """``pytorch3d._C.face_areas_normals_backward`` -> ``grad_verts [V, 3]`` by the module's contract (float atomics: the order of a vertex's
     sum is free).  A call :func:`face_areas_normals_backward_takes` rejects raises ``ValueError`` with the reason."""
-    why = _why_not_faces(verts, faces, grad_areas, grad_normals, backward=True)
-    if why is not None:
-        raise ValueError("face_areas_normals_backward: " + why)
+    _takes.refuse("face_areas_normals_backward", _why_not_faces(verts, faces, grad_areas, grad_normals, backward=True))
     return _faces_backward(grad_areas, grad_normals, verts, faces)
 
 
 def interpolate_face_attributes_forward(pix_to_face, barycentric_coords, face_attributes) -> torch.Tensor:
     """``pytorch3d._C.interpolate_face_attributes_forward`` -> ``pix_attrs``, ``pix_to_face``'s shape + ``[D]``, by the module's contract.  A call
     :func:`interpolate_face_attributes_takes` rejects raises ``ValueError`` with the reason."""
-    why = _why_not_interp(pix_to_face, barycentric_coords, face_attributes)
-    if why is not None:
-        raise ValueError("interpolate_face_attributes_forward: " + why)
+    _takes.refuse("interpolate_face_attributes_forward", _why_not_interp(pix_to_face, barycentric_coords, face_attributes))
     return _interp_forward(pix_to_face, barycentric_coords, face_attributes)
 
 
@@ -252,27 +211,19 @@ def interpolate_face_attributes_backward(pix_to_face, barycentric_coords, face_a
     """``pytorch3d._C.interpolate_face_attributes_backward`` -> ``(grad_barycentric_coords, grad_face_attributes [F, 3, D])``
     by the module's contract (float atomics into the second).  A call :func:`interpolate_face_attributes_backward_takes` rejects raises
     ``ValueError`` with the reason."""
-    why = _why_not_interp(pix_to_face, barycentric_coords, face_attributes, grad_pix_attrs, backward=True)
-    if why is not None:
-        raise ValueError("interpolate_face_attributes_backward: " + why)
+    _takes.refuse("interpolate_face_attributes_backward", _why_not_interp(pix_to_face, barycentric_coords, face_attributes, grad_pix_attrs, backward=True))
     return _interp_backward(pix_to_face, barycentric_coords, face_attributes, grad_pix_attrs)
 
 
 def _drop_in(name: str, original: Callable, why_not: Callable, taken: Callable) -> Callable:
     """An operator named ``name`` that runs ``taken`` for the calls ``why_not`` lets through and ``original`` with the caller's arguments for
-    every other.  The library is loaded here, so that a missing one shows when the patch is made."""
-    from . import _lib  # noqa: F401
-
+    every other."""
     def operator(*args, **kwargs):
         if not kwargs and why_not(*args) is None:     # (pytorch3d's Python calls positionally; a call by keyword is the original's)
             return taken(*args)
         return original(*args, **kwargs)
 
-    operator.__name__ = operator.__qualname__ = name
-    operator.fallback = original
-    operator.__doc__ = (f"pytorch3d._C.{name}: HIP kernels where they apply (autovfx_amd/meshattrs.py), "
-                        f"{getattr(original, '__module__', '?')}.{getattr(original, '__name__', '?')} otherwise.")
-    return operator
+    return _takes.dressed(operator, name, original, f"pytorch3d._C.{name}", "meshattrs")
 
 
 def _guarded(why_not: Callable, count: int, **fixed) -> Callable:

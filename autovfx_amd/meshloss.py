@@ -67,6 +67,7 @@ import numpy as np
 import torch
 from torch.autograd.function import once_differentiable
 
+from . import _takes
 from ._mesh_host import cross as _cross, dot as _dot, norm as _norm, verts_faces as _verts_faces
 
 MAX_INCIDENCES = 1 << 30
@@ -87,17 +88,13 @@ class NormalConsistencyPlan(NamedTuple):
 
 # ---- which calls the kernels take -----------------------------------------------------------------------------------------------------
 
+HOST = "mesh_normal_consistency_host"
+ALLOCATES = "the call allocates its scratch; such a call is left to the original"
+
+
 def _why_not(verts, faces, plan_=None, needs_faces: bool = False) -> Optional[str]:
     """None when the kernels take the call, else the reason they do not."""
-    if not (isinstance(verts, torch.Tensor) and isinstance(faces, torch.Tensor)):
-        return "verts and faces must be torch.Tensors"
-    if not verts.is_cuda:
-        return f"verts must be on a GPU (got {verts.device}); there is no CPU path, see mesh_normal_consistency_host"
-    if verts.dtype != torch.float32:
-        return f"verts must be float32 (got {verts.dtype})"
-    if verts.dim() != 2 or verts.shape[1] != 3:
-        return f"verts must be [V, 3] (got {list(verts.shape)})"
-    why = _why_not_faces(faces, verts.shape[0], verts.device)
+    why = _takes.mesh(verts, faces, HOST) or _why_not_counts(faces.shape[0], verts.shape[0])
     if why is not None:
         return why
     if needs_faces and faces.shape[0] < 1:
@@ -109,43 +106,29 @@ def _why_not(verts, faces, plan_=None, needs_faces: bool = False) -> Optional[st
             if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.device != faces.device or tuple(t.shape) != (count,) \
                     or not t.is_contiguous():
                 return f"plan.{name} must be a contiguous {dtype} [{count}] on {faces.device}: the plan of these faces"
-    return _capturing()
+    return _takes.capturing(ALLOCATES)
 
 
-def _why_not_faces(faces, V, device=None) -> Optional[str]:
-    if not isinstance(faces, torch.Tensor):
-        return "faces must be a torch.Tensor"
-    if faces.dtype != torch.int64:
-        return f"faces must be int64 (got {faces.dtype})"
-    if not faces.is_cuda or (device is not None and faces.device != device):
-        return f"faces must be on {device if device is not None else 'a GPU'} (got {faces.device})"
-    if faces.dim() != 2 or faces.shape[1] != 3:
-        return f"faces must be [F, 3] (got {list(faces.shape)})"
+def _why_not_faces(faces, V) -> Optional[str]:
+    """As :func:`_why_not`, for the faces alone and a ``V`` the caller states."""
+    return (_takes.tensors((("faces", faces, torch.int64),), host=HOST)
+            or _takes.shaped("faces", faces, "[F, 3]", faces.dim() == 2 and faces.shape[1] == 3) or _why_not_counts(faces.shape[0], V))
+
+
+def _why_not_counts(F, V) -> Optional[str]:
     if type(V) is not int or V < 0:
         return f"V must be a non-negative int (got {V!r})"
-    if 3 * faces.shape[0] >= MAX_INCIDENCES or V >= MAX_VERTS:
-        return f"{faces.shape[0]} faces, {V} vertices: 3 F below 2^30 and V below 2^31"
-    return None
-
-
-def _capturing() -> Optional[str]:
-    from . import _lib
-
-    if _lib.capturing():
-        return "the current stream is capturing a graph (the call allocates its scratch; such a call is left to the original)"
+    if 3 * F >= MAX_INCIDENCES or V >= MAX_VERTS:
+        return f"{F} faces, {V} vertices: 3 F below 2^30 and V below 2^31"
     return None
 
 
 # ---- the calls ------------------------------------------------------------------------------------------------------------------------
 
-def _c(t: torch.Tensor) -> torch.Tensor:
-    return t.detach().contiguous()
-
-
 def _plan(faces: torch.Tensor, V: int) -> NormalConsistencyPlan:
     from . import _lib
 
-    f = _c(faces)
+    f = _takes.c(faces)
     F = int(f.shape[0])
     order = torch.empty((3 * F,), dtype=torch.int32, device=f.device)
     partners = torch.empty((3 * F,), dtype=torch.int32, device=f.device)
@@ -188,7 +171,7 @@ class _NormalConsistency(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, verts, faces, order, partners, pairs):
-        v, f = _c(verts), _c(faces)
+        v, f = _takes.cs(verts, faces)
         p = NormalConsistencyPlan(order, partners, pairs)
         loss, _ = _forward(v, f, p)
         ctx.save_for_backward(v, f, order, partners, pairs)
@@ -204,9 +187,7 @@ class _NormalConsistency(torch.autograd.Function):
 def plan(faces, V: int) -> NormalConsistencyPlan:
     """The plan of a topology (the module's contract), queued on the current stream without a host read.  A caller whose faces do not
     change builds it once and passes it to :func:`mesh_normal_consistency`; the faces it is used with must be the ones it was built from."""
-    why = _why_not_faces(faces, V) or _capturing()
-    if why is not None:
-        raise ValueError("plan: " + why)
+    _takes.refuse("plan", _why_not_faces(faces, V) or _takes.capturing(ALLOCATES))
     return _plan(faces, V)
 
 
@@ -215,20 +196,16 @@ def mesh_normal_consistency(verts, faces, plan: Optional[NormalConsistencyPlan] 
     once in ``verts``, queued on the current stream with no host synchronisation.  ``plan``: what :func:`plan` returned for these faces and
     this ``V`` (the two sorts are then skipped); built per call when not given.  Non-contiguous inputs are copied.  ``F = 0`` gives 0.
     A call the kernels do not take raises ``ValueError`` with the reason."""
-    why = _why_not(verts, faces, plan)
-    if why is not None:
-        raise ValueError("mesh_normal_consistency: " + why)
+    _takes.refuse("mesh_normal_consistency", _why_not(verts, faces, plan))
     p = plan if plan is not None else _plan(faces, int(verts.shape[0]))
     return _NormalConsistency.apply(verts, faces, p.order, p.partners, p.pairs)
 
 
 def mesh_normal_consistency_terms(verts, faces, plan: Optional[NormalConsistencyPlan] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """``(loss, terms [3F])`` without autograd: the ``T_s`` of the contract beside the loss (for tests and diagnosis)."""
-    why = _why_not(verts, faces, plan)
-    if why is not None:
-        raise ValueError("mesh_normal_consistency_terms: " + why)
+    _takes.refuse("mesh_normal_consistency_terms", _why_not(verts, faces, plan))
     p = plan if plan is not None else _plan(faces, int(verts.shape[0]))
-    return _forward(_c(verts), _c(faces), p, want_terms=True)
+    return _forward(*_takes.cs(verts, faces), p, want_terms=True)
 
 
 def _packed(meshes):
@@ -247,10 +224,7 @@ def drop_in(original: Callable) -> Callable:
     ``faces_packed()`` int64 ``[F, 3]`` on the same device with ``F >= 1`` and no graph is being captured, and ``original`` (pytorch3d's)
     with the caller's arguments for every other call: batches, CPU meshes, an empty mesh, other dtypes, objects without those methods.
     The plan is built on every call: ``Meshes.__init__`` re-indexes the faces, so a tensor's identity proves nothing about the topology,
-    and checking the content would need the host round trip this replaces.  The library is loaded here, so that a missing one shows when
-    the patch is made."""
-    from . import _lib  # noqa: F401
-
+    and checking the content would need the host round trip this replaces."""
     def mesh_normal_consistency_drop_in(*args, **kwargs):
         taken = _packed(args[0]) if len(args) == 1 and not kwargs else None
         if taken is None:
@@ -259,11 +233,7 @@ def drop_in(original: Callable) -> Callable:
         p = _plan(faces, int(verts.shape[0]))
         return _NormalConsistency.apply(verts, faces, p.order, p.partners, p.pairs)
 
-    mesh_normal_consistency_drop_in.__name__ = mesh_normal_consistency_drop_in.__qualname__ = "mesh_normal_consistency"
-    mesh_normal_consistency_drop_in.fallback = original
-    mesh_normal_consistency_drop_in.__doc__ = ("pytorch3d.loss.mesh_normal_consistency: HIP kernels where they apply (autovfx_amd/meshloss.py), "
-                                               f"{getattr(original, '__module__', '?')}.{getattr(original, '__name__', '?')} otherwise.")
-    return mesh_normal_consistency_drop_in
+    return _takes.dressed(mesh_normal_consistency_drop_in, "mesh_normal_consistency", original, "pytorch3d.loss.mesh_normal_consistency", "meshloss")
 
 
 # ---- the contract in numpy ------------------------------------------------------------------------------------------------------------

@@ -66,6 +66,8 @@ from typing import NamedTuple, Optional, Tuple
 import numpy as np
 import torch
 
+from . import _takes
+
 MAX_FACES = (1 << 30) - 1
 MAX_VERTS = (1 << 31) - 1
 MAX_QUERIES = (1 << 31) - 1
@@ -459,44 +461,23 @@ class Plan:
         return self.buffer.device
 
 
+HOST = "closest_triangles_host"
+ALLOCATES = "the call allocates its buffers and outputs"
+
+
 def _why_not_mesh(verts, faces) -> Optional[str]:
-    if not (isinstance(verts, torch.Tensor) and isinstance(faces, torch.Tensor)):
-        return "verts and faces must be torch.Tensors"
-    if not (verts.is_cuda and faces.is_cuda):
-        return f"verts and faces must be on a GPU (got {verts.device} and {faces.device}); there is no CPU path, see closest_triangles_host"
-    if verts.device != faces.device:
-        return f"verts and faces must be on one device (got {verts.device} and {faces.device})"
-    if verts.dtype != torch.float32 or faces.dtype != torch.int64:
-        return f"verts must be float32 and faces int64 (got {verts.dtype} and {faces.dtype})"
-    if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
-        return f"verts must be [V, 3] and faces [F, 3] (got {list(verts.shape)} and {list(faces.shape)})"
-    if faces.shape[0] > MAX_FACES or verts.shape[0] > MAX_VERTS:
-        return f"{faces.shape[0]} faces and {verts.shape[0]} vertices: at most 2^30 - 1 and 2^31 - 1"
-    from . import _lib
-
-    if _lib.capturing():
-        return "the current stream is capturing a graph (the call allocates its buffers)"
-    return None
+    why = _takes.mesh(verts, faces, HOST)
+    if why is None and (faces.shape[0] > MAX_FACES or verts.shape[0] > MAX_VERTS):
+        why = f"{faces.shape[0]} faces and {verts.shape[0]} vertices: at most 2^30 - 1 and 2^31 - 1"
+    return why
 
 
-def _why_not_points(points, device) -> Optional[str]:
-    if not isinstance(points, torch.Tensor):
-        return "points must be a torch.Tensor"
-    if not points.is_cuda:
-        return f"points must be on a GPU (got {points.device}); there is no CPU path, see closest_triangles_host"
-    if points.device != device:
-        return f"points and the mesh must be on one device (got {points.device} and {device})"
-    if points.dtype != torch.float32:
-        return f"points must be float32 (got {points.dtype})"
-    if points.dim() != 2 or points.shape[1] != 3:
-        return f"points must be [n, 3] (got {list(points.shape)})"
-    if points.shape[0] > MAX_QUERIES:
-        return f"{points.shape[0]} points: at most 2^31 - 1"
-    from . import _lib
-
-    if _lib.capturing():
-        return "the current stream is capturing a graph (the call allocates its outputs)"
-    return None
+def _why_not_points(points, like, name: str = "points") -> Optional[str]:
+    why = (_takes.tensors(((name, points, torch.float32),), like, HOST)
+           or _takes.shaped(name, points, "[n, 3]", points.dim() == 2 and points.shape[1] == 3))
+    if why is None and points.shape[0] > MAX_QUERIES:
+        why = f"{points.shape[0]} {name}: at most 2^31 - 1"
+    return why
 
 
 def _why_not_plan(plan, verts, faces) -> Optional[str]:
@@ -514,13 +495,11 @@ def _why_not_plan(plan, verts, faces) -> Optional[str]:
     return None
 
 
-def _why_not_rays(origins, dirs, device) -> Optional[str]:
-    why = _why_not_points(origins, device) or _why_not_points(dirs, device)
-    if why is not None:
-        return why.replace("points", "origins and dirs")
-    if origins.shape[0] != dirs.shape[0]:
-        return f"{origins.shape[0]} origins and {dirs.shape[0]} dirs"
-    return None
+def _why_not_rays(origins, dirs, like) -> Optional[str]:
+    why = _why_not_points(origins, like, "origins") or _why_not_points(dirs, like, "dirs")
+    if why is None and origins.shape[0] != dirs.shape[0]:
+        why = f"{origins.shape[0]} origins and {dirs.shape[0]} dirs"
+    return why
 
 
 def _plan_bytes(F: int) -> int:
@@ -533,7 +512,7 @@ def _plan_bytes(F: int) -> int:
 def _build(verts: torch.Tensor, faces: torch.Tensor) -> Plan:
     from . import _lib
 
-    v, f = verts.detach().contiguous(), faces.detach().contiguous()
+    v, f = _takes.cs(verts, faces)
     V, F = int(v.shape[0]), int(f.shape[0])
     with torch.cuda.device(v.device):
         buffer, plan_bytes = _lib.scratch("gsr_closest_tri_plan_bytes", F, device=v.device)
@@ -546,9 +525,7 @@ def _build(verts: torch.Tensor, faces: torch.Tensor) -> Plan:
 def plan(verts: torch.Tensor, faces: torch.Tensor) -> Plan:
     """The tree over the mesh ``verts [V, 3]`` float32, ``faces [F, 3]`` int64 (both on one GPU), built on the current stream: pass it
     to :func:`closest_triangles` as often as the mesh is asked.  Raises ``ValueError`` with the reason for anything else."""
-    why = _why_not_mesh(verts, faces)
-    if why is not None:
-        raise ValueError("meshquery.plan: " + why)
+    _takes.refuse("meshquery.plan", _why_not_mesh(verts, faces) or _takes.capturing(ALLOCATES))
     return _build(verts, faces)
 
 
@@ -560,9 +537,8 @@ def closest_triangles(points: torch.Tensor, verts: torch.Tensor, faces: torch.Te
     same answers, much sooner unless the caller's order is coherent already).  Queued on the current stream, no host synchronisation;
     not differentiable; non-contiguous inputs are copied.  Raises ``ValueError`` with the reason for CPU tensors, other dtypes or shapes, devices that
     differ, a plan of another mesh or of another size than its ``F`` asks for, and under graph capture."""
-    why = _why_not_mesh(verts, faces) or _why_not_points(points, verts.device) or _why_not_plan(plan, verts, faces)
-    if why is not None:
-        raise ValueError("closest_triangles: " + why)
+    _takes.refuse("closest_triangles", _why_not_mesh(verts, faces) or _why_not_points(points, verts) or _why_not_plan(plan, verts, faces)
+                  or _takes.capturing(ALLOCATES))
     tree = plan if plan is not None else _build(verts, faces)
     return _query(points, tree, return_points)
 
@@ -597,7 +573,7 @@ def _query(points: torch.Tensor, tree: Plan, return_points: bool, sort_queries: 
     back in it, 215 ms asked as drawn; scripts/bench_meshquery.py).  So the queries are asked in Morton order and the answers put
     back; every answer is a function of its own query alone.  ``sort_queries=False`` (the tests, the benchmark) asks in the
     caller's order."""
-    pts = points.detach().contiguous()
+    pts = _takes.c(points)
     n = int(pts.shape[0])
     face_idx = torch.empty(n, dtype=torch.int64, device=pts.device)
     sq_dist = torch.empty(n, dtype=torch.float32, device=pts.device)
@@ -638,11 +614,10 @@ def first_hits(origins: torch.Tensor, dirs: torch.Tensor, verts: torch.Tensor, f
     answers put back; ``sort=False`` asks them as given, which is sooner when they come side by side already, as the pixels of a
     camera do (``_cast`` has the measurements).  The answers are the same either way.  Queued on the current stream, no host synchronisation; not differentiable; non-contiguous inputs are copied.  Raises
     ``ValueError`` with the reason for what :func:`closest_triangles` refuses."""
-    why = _why_not_mesh(verts, faces) or _why_not_rays(origins, dirs, verts.device) or _why_not_plan(plan, verts, faces)
-    if why is not None:
-        raise ValueError("first_hits: " + why)
+    _takes.refuse("first_hits", _why_not_mesh(verts, faces) or _why_not_rays(origins, dirs, verts) or _why_not_plan(plan, verts, faces)
+                  or _takes.capturing(ALLOCATES))
     tree = plan if plan is not None else _build(verts, faces)
-    o, d = origins.detach().contiguous(), dirs.detach().contiguous()
+    o, d = _takes.cs(origins, dirs)
     face_idx, t, bary = _cast(o, d, tree, return_bary, order=ray_order(o, d, verts) if sort and o.shape[0] >= SORT_FROM else None)
     out = [face_idx, t]
     if return_bary:

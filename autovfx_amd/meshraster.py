@@ -65,6 +65,8 @@ from typing import Callable, Optional, Tuple
 import numpy as np
 import torch
 
+from . import _takes
+
 MAX_K = 16
 MAX_SIDE = 16384
 MAX_FACES = (1 << 31) - 2
@@ -90,24 +92,19 @@ def _image_size(image_size) -> Optional[Tuple[int, int]]:
 def _why_not(face_verts, mesh_to_face_first_idx, num_faces_per_mesh, clipped_faces_neighbor_idx, image_size, blur_radius,
              faces_per_pixel) -> Optional[str]:
     """None when the kernels take the call, else the reason they do not."""
-    index = (mesh_to_face_first_idx, num_faces_per_mesh, clipped_faces_neighbor_idx)
-    if not isinstance(face_verts, torch.Tensor) or not all(isinstance(t, torch.Tensor) for t in index):
-        return "face_verts and the three index arguments must be torch.Tensors"
-    if not face_verts.is_cuda:
-        return f"face_verts must be on a GPU (got {face_verts.device}); there is no CPU path, see rasterize_face_verts_host"
-    if face_verts.dtype != torch.float32:
-        return f"face_verts must be float32 (got {face_verts.dtype})"
-    if face_verts.dim() != 3 or tuple(face_verts.shape[1:]) != (3, 3):
-        return f"face_verts must be [F, 3, 3] (got {list(face_verts.shape)})"
+    index = (("mesh_to_face_first_idx", mesh_to_face_first_idx, torch.int64), ("num_faces_per_mesh", num_faces_per_mesh, torch.int64),
+             ("clipped_faces_neighbor_idx", clipped_faces_neighbor_idx, torch.int64))
+    why = (_takes.tensors((("face_verts", face_verts, torch.float32),) + index, host="rasterize_face_verts_host")
+           or _takes.shaped("face_verts", face_verts, "[F, 3, 3]", face_verts.dim() == 3 and tuple(face_verts.shape[1:]) == (3, 3)))
+    if why is not None:
+        return why
     if not face_verts.is_contiguous():
         return "face_verts must be contiguous"
     if face_verts.shape[0] > MAX_FACES:
         return f"{face_verts.shape[0]} faces: at most 2^31 - 2"
-    for name, t in zip(("mesh_to_face_first_idx", "num_faces_per_mesh", "clipped_faces_neighbor_idx"), index):
-        if t.dtype != torch.int64 or t.dim() != 1 or not t.is_contiguous():
-            return f"{name} must be a contiguous 1-D int64 tensor (got {t.dtype} {list(t.shape)})"
-        if not t.is_cuda or t.device != face_verts.device:
-            return f"{name} must be on face_verts' device (got {t.device}, not {face_verts.device})"
+    for name, t, _ in index:
+        if t.dim() != 1 or not t.is_contiguous():
+            return _takes.shaped(name, t, "contiguous and 1-D", False)
     if mesh_to_face_first_idx.shape[0] != num_faces_per_mesh.shape[0]:
         return f"mesh_to_face_first_idx and num_faces_per_mesh must have one length (got {mesh_to_face_first_idx.shape[0]} and {num_faces_per_mesh.shape[0]})"
     if clipped_faces_neighbor_idx.shape[0] != face_verts.shape[0]:
@@ -121,11 +118,7 @@ def _why_not(face_verts, mesh_to_face_first_idx, num_faces_per_mesh, clipped_fac
         return f"faces_per_pixel must be an int in 1..{MAX_K} (got {faces_per_pixel!r})"
     if face_verts.requires_grad:   # (also inside pytorch3d's autograd.Function.forward, where the operator is called with grad mode off)
         return "face_verts requires a gradient (the backward stays pytorch3d's, which needs its own forward)"
-    from . import _lib
-
-    if _lib.capturing():
-        return "the current stream is capturing a graph (the call reads the pair total back and allocates its scratch)"
-    return None
+    return _takes.capturing("the call reads the pair total back and allocates its scratch")
 
 
 def rasterize_takes(face_verts, mesh_to_face_first_idx, num_faces_per_mesh, clipped_faces_neighbor_idx, image_size, blur_radius,
@@ -177,10 +170,8 @@ def rasterize_face_verts(face_verts, mesh_to_face_first_idx, num_faces_per_mesh,
     queued on the current stream; the call waits once for the device (the total length of the tile lists sizes its scratch).
     ``bin_size`` and ``max_faces_per_bin`` are ignored.  A call :func:`rasterize_takes` rejects raises ``ValueError`` with the reason, and so does
     one whose tile lists would hold 2^31 entries or more (:class:`TooManyPairs`, after the count step)."""
-    why = _why_not(face_verts, mesh_to_face_first_idx, num_faces_per_mesh, clipped_faces_neighbor_idx, image_size, blur_radius,
-                   faces_per_pixel)
-    if why is not None:
-        raise ValueError("rasterize_meshes: " + why)
+    _takes.refuse("rasterize_meshes", _why_not(face_verts, mesh_to_face_first_idx, num_faces_per_mesh, clipped_faces_neighbor_idx, image_size,
+                                               blur_radius, faces_per_pixel))
     return _taken(face_verts, mesh_to_face_first_idx, num_faces_per_mesh, clipped_faces_neighbor_idx, _image_size(image_size), faces_per_pixel,
                   perspective_correct, clip_barycentric_coords, cull_backfaces)
 
@@ -190,10 +181,7 @@ def drop_in(original: Callable) -> Callable:
     same positional arguments) for every other: CPU tensors, ``blur_radius > 0``, more than 16 faces per pixel, faces that need a gradient,
     graph capture, and a call whose tile lists turn out to need 2^31 entries or more (:class:`TooManyPairs`, found by the count step).
     ``autovfx_amd.install()`` builds it around ``pytorch3d._C.rasterize_meshes``; pytorch3d's Python looks the operator up on ``_C`` at every
-    call, so its ``clip_faces``, bin heuristics and ``convert_clipped_rasterization_to_original_faces`` run as they are around it.  The
-    library is loaded here, so that a missing one shows when the patch is made."""
-    from . import _lib  # noqa: F401
-
+    call, so its ``clip_faces``, bin heuristics and ``convert_clipped_rasterization_to_original_faces`` run as they are around it."""
     def rasterize_meshes_drop_in(face_verts, mesh_to_face_first_idx, num_faces_per_mesh, clipped_faces_neighbor_idx, image_size, blur_radius,
                                  faces_per_pixel, bin_size, max_faces_per_bin, perspective_correct, clip_barycentric_coords, cull_backfaces):
         if _why_not(face_verts, mesh_to_face_first_idx, num_faces_per_mesh, clipped_faces_neighbor_idx, image_size, blur_radius,
@@ -206,11 +194,7 @@ def drop_in(original: Callable) -> Callable:
         return original(face_verts, mesh_to_face_first_idx, num_faces_per_mesh, clipped_faces_neighbor_idx, image_size, blur_radius,
                         faces_per_pixel, bin_size, max_faces_per_bin, perspective_correct, clip_barycentric_coords, cull_backfaces)
 
-    rasterize_meshes_drop_in.__name__ = rasterize_meshes_drop_in.__qualname__ = "rasterize_meshes"
-    rasterize_meshes_drop_in.fallback = original
-    rasterize_meshes_drop_in.__doc__ = ("pytorch3d._C.rasterize_meshes: HIP kernels where they apply (autovfx_amd/meshraster.py), "
-                                        f"{getattr(original, '__module__', '?')}.{getattr(original, '__name__', '?')} otherwise.")
-    return rasterize_meshes_drop_in
+    return _takes.dressed(rasterize_meshes_drop_in, "rasterize_meshes", original, "pytorch3d._C.rasterize_meshes", "meshraster")
 
 
 # ---- the contract in numpy ------------------------------------------------------------------------------------------------------------

@@ -20,7 +20,7 @@ import torch
 import torch.nn.functional as F
 from torch.autograd.function import once_differentiable
 
-from . import _lib
+from . import _lib, _takes
 
 WINDOW_SIZE = 11
 SIGMA = 1.5
@@ -64,11 +64,7 @@ def ssim_restated(img1, img2, window_size=11, size_average=True):
 
 
 def _fused_takes(img1, img2, window_size, size_average) -> bool:
-    if not (isinstance(img1, torch.Tensor) and isinstance(img2, torch.Tensor)):
-        return False
-    if not (img1.is_cuda and img2.is_cuda and img1.device == img2.device):
-        return False
-    if img1.dtype != torch.float32 or img2.dtype != torch.float32 or img1.shape != img2.shape:
+    if _takes.tensors((("img1", img1, torch.float32), ("img2", img2, torch.float32))) is not None or img1.shape != img2.shape:
         return False
     if img1.dim() not in (3, 4) or type(window_size) is not int or window_size != WINDOW_SIZE:
         return False
@@ -86,7 +82,7 @@ def _dims(t: torch.Tensor):
 class _FusedSSIM(torch.autograd.Function):
     @staticmethod
     def forward(ctx, img1, img2, per_image, want_grad):
-        x, y = img1.detach().contiguous(), img2.detach().contiguous()
+        x, y = _takes.cs(img1, img2)
         n, c, h, w = _dims(x)
         with torch.cuda.device(x.device):
             out = torch.empty((n,) if per_image else (), dtype=torch.float32, device=x.device)
@@ -124,11 +120,7 @@ def drop_in(fallback: Callable) -> Callable:
         # (needs_input_grad does not see torch.no_grad(): the maps are written only when a gradient can be asked for)
         return _FusedSSIM.apply(img1, img2, not size_average, img1.requires_grad and torch.is_grad_enabled())
 
-    ssim.fallback = fallback
-    ssim.__doc__ = ("The reference's loss_utils.ssim: the mean SSIM of img1 against img2 (a 0-d tensor), or per image ([N]) with "
-                    "size_average=False; differentiable in img1.  Fused HIP kernels where they apply (autovfx_amd/ssim.py), "
-                    f"{getattr(fallback, '__module__', '?')}.{getattr(fallback, '__name__', '?')} otherwise.")
-    return ssim
+    return _takes.dressed(ssim, "ssim", fallback, "loss_utils.ssim, the mean SSIM of img1 against img2 (per image with size_average=False)", "ssim")
 
 
 ssim = drop_in(ssim_restated)

@@ -58,7 +58,7 @@ from typing import Callable, Optional
 import numpy as np
 import torch
 
-from . import _mesh_host
+from . import _mesh_host, _takes
 
 MAX_G = 8
 MIN_S, MAX_S = 4, 32
@@ -211,29 +211,12 @@ def new_owner(texture_size: int, device) -> torch.Tensor:
     return torch.full((int(texture_size) ** 2,), -1, dtype=torch.int32, device=device)
 
 
-def _tensors_why_not(named, device=None) -> Optional[str]:
-    """``named``: (name, tensor, dtype).  CUDA tensors of those dtypes on one device, not under graph capture."""
-    for name, t, _ in named:
-        if not isinstance(t, torch.Tensor):
-            return f"{name} must be a torch.Tensor, not {type(t).__name__}"
-    device = named[0][1].device if device is None else device
-    for name, t, dtype in named:
-        if not t.is_cuda:
-            return f"{name} must be on a GPU (got {t.device}); there is no CPU path, see the _host functions"
-        if t.device != device:
-            return f"all tensors must be on one device ({name} is on {t.device}, {named[0][0]} on {device})"
-        if t.dtype != dtype:
-            return f"{name} must be {str(dtype).replace('torch.', '')} (got {t.dtype})"
-    from . import _lib
-
-    if _lib.capturing():
-        return "the current stream is capturing a graph"
-    return None
+ALLOCATES = "the call allocates its outputs or copies of its inputs"
 
 
 def _view_why_not(pix_to_face, bary, zbuf, face_uvs) -> Optional[str]:
-    why = _tensors_why_not((("pix_to_face", pix_to_face, torch.int64), ("bary", bary, torch.float32), ("zbuf", zbuf, torch.float32),
-                            ("face_uvs", face_uvs, torch.float32)))
+    why = _takes.tensors((("pix_to_face", pix_to_face, torch.int64), ("bary", bary, torch.float32), ("zbuf", zbuf, torch.float32),
+                          ("face_uvs", face_uvs, torch.float32)))
     if why is not None:
         return why
     P = pix_to_face.numel()
@@ -242,7 +225,7 @@ def _view_why_not(pix_to_face, bary, zbuf, face_uvs) -> Optional[str]:
     if zbuf.numel() != P:
         return f"zbuf must hold one value per pixel of pix_to_face {list(pix_to_face.shape)} (got {list(zbuf.shape)})"
     if face_uvs.dim() != 3 or tuple(face_uvs.shape[1:]) != (3, 2):
-        return f"face_uvs must be [F, 3, 2] (got {list(face_uvs.shape)})"
+        return _takes.shaped("face_uvs", face_uvs, "[F, 3, 2]", False)
     if P > MAX_PIXELS:
         return f"{P} pixels: at most 2^32 - 2"
     return None
@@ -254,11 +237,10 @@ def texels_of_pixels(pix_to_face, bary, zbuf, face_uvs, texture_size: int) -> to
     why = _view_why_not(pix_to_face, bary, zbuf, face_uvs)
     if why is None and not (type(texture_size) is int and 1 <= texture_size <= MAX_T):
         why = f"texture_size must be an int in 1..{MAX_T} (got {texture_size!r})"
-    if why is not None:
-        raise ValueError("texels_of_pixels: " + why)
+    _takes.refuse("texels_of_pixels", why or _takes.capturing(ALLOCATES))
     from . import _lib
 
-    pix, w, z, uv = (t.detach().contiguous() for t in (pix_to_face, bary, zbuf, face_uvs))
+    pix, w, z, uv = _takes.cs(pix_to_face, bary, zbuf, face_uvs)
     out = torch.empty(pix.shape, dtype=torch.int32, device=pix.device)
     with torch.cuda.device(pix.device):
         _lib.call("gsr_texture_texels", pix.numel(), uv.shape[0], texture_size, _lib.ptr(pix), _lib.ptr(w), _lib.ptr(z), _lib.ptr(uv),
@@ -283,8 +265,8 @@ def bake_view(tex, count, owner, rgb, pix_to_face, bary, zbuf, face_uvs) -> None
     kernels do not take raises ``ValueError`` with the reason."""
     why = _view_why_not(pix_to_face, bary, zbuf, face_uvs)
     if why is None:
-        why = _tensors_why_not((("tex", tex, torch.float32), ("count", count, torch.float32), ("owner", owner, torch.int32),
-                                ("rgb", rgb, torch.float32)), pix_to_face.device)
+        why = _takes.tensors((("tex", tex, torch.float32), ("count", count, torch.float32), ("owner", owner, torch.int32),
+                              ("rgb", rgb, torch.float32)), like=pix_to_face)
     if why is None:
         T = tex.shape[0] if tex.dim() == 3 else 0
         if tex.dim() != 3 or tuple(tex.shape) != (T, T, 3) or not 1 <= T <= MAX_T:
@@ -297,11 +279,10 @@ def bake_view(tex, count, owner, rgb, pix_to_face, bary, zbuf, face_uvs) -> None
             why = "tex, count and owner are written in place and must be contiguous"
         elif rgb.dim() < 1 or rgb.shape[-1] != 3 or rgb.numel() != 3 * pix_to_face.numel():
             why = f"rgb must hold three values per pixel of pix_to_face {list(pix_to_face.shape)} (got {list(rgb.shape)})"
-    if why is not None:
-        raise ValueError("bake_view: " + why)
+    _takes.refuse("bake_view", why or _takes.capturing(ALLOCATES))
     from . import _lib
 
-    pix, w, z, uv = (t.detach().contiguous() for t in (pix_to_face, bary, zbuf, face_uvs))
+    pix, w, z, uv = _takes.cs(pix_to_face, bary, zbuf, face_uvs)
     colours, stride = _pixel_rows(rgb.detach())
     with torch.cuda.device(pix.device):
         _lib.call("gsr_texture_bake_view", pix.numel(), uv.shape[0], T, _lib.ptr(pix), _lib.ptr(w), _lib.ptr(z), _lib.ptr(uv),
@@ -312,19 +293,15 @@ def fill(verts, faces, centers, inv_scaled_rot, features, texel_offset, texel_ba
     """The initial atlas ``[T, T, 3]``, ``T = A S``: ``verts [V, 3]``, ``faces [F, 3]`` int64, ``centers [F G, 3]``, ``inv_scaled_rot
     [F G, 3, 3]``, ``features [F G, 3]``, the two tables of :func:`atlas`.  On the current stream, no host synchronisation.  A call the
     kernels do not take raises ``ValueError`` with the reason."""
-    why = _tensors_why_not((("verts", verts, torch.float32), ("faces", faces, torch.int64), ("centers", centers, torch.float32),
-                            ("inv_scaled_rot", inv_scaled_rot, torch.float32), ("features", features, torch.float32),
-                            ("texel_offset", texel_offset, torch.int32), ("texel_bary", texel_bary, torch.float32)))
+    why = _takes.mesh(verts, faces) or _takes.tensors((
+        ("centers", centers, torch.float32), ("inv_scaled_rot", inv_scaled_rot, torch.float32), ("features", features, torch.float32),
+        ("texel_offset", texel_offset, torch.int32), ("texel_bary", texel_bary, torch.float32)), like=verts)
     if why is None:
-        F = faces.shape[0] if faces.dim() == 2 else 0
+        F = faces.shape[0]
         n = texel_offset.shape[1] if texel_offset.dim() == 3 else 0
         G = centers.shape[0] // F if centers.dim() == 2 and F else 1
         if type(A) is not int or type(S) is not int or not MIN_S <= S <= MAX_S or A < 1 or A * S > MAX_T:
             why = f"A and S must be ints with S in {MIN_S}..{MAX_S}, A >= 1 and A * S <= {MAX_T} (got A = {A!r}, S = {S!r})"
-        elif verts.dim() != 2 or verts.shape[1] != 3:
-            why = f"verts must be [V, 3] (got {list(verts.shape)})"
-        elif faces.dim() != 2 or faces.shape[1] != 3:
-            why = f"faces must be [F, 3] (got {list(faces.shape)})"
         elif F > MAX_FACES or (F + 1) // 2 > A * A:
             why = f"{F} faces: at most 2^28 - 1, and two per square of the {A} x {A} atlas"
         elif centers.dim() != 2 or centers.shape[1] != 3 or centers.shape[0] != F * G:
@@ -338,11 +315,10 @@ def fill(verts, faces, centers, inv_scaled_rot, features, texel_offset, texel_ba
         elif tuple(texel_offset.shape) != (2, n, 2) or tuple(texel_bary.shape) != (2, n, 3) or not 1 <= n <= S * S:
             why = (f"texel_offset must be [2, n, 2] and texel_bary [2, n, 3] with 1 <= n <= S S (got {list(texel_offset.shape)}, "
                    f"{list(texel_bary.shape)})")
-    if why is not None:
-        raise ValueError("fill: " + why)
+    _takes.refuse("fill", why or _takes.capturing(ALLOCATES))
     from . import _lib
 
-    v, fc, c, M, ft, off, wt = (t.detach().contiguous() for t in (verts, faces, centers, inv_scaled_rot, features, texel_offset, texel_bary))
+    v, fc, c, M, ft, off, wt = _takes.cs(verts, faces, centers, inv_scaled_rot, features, texel_offset, texel_bary)
     T = A * S
     tex = torch.empty((T, T, 3), dtype=torch.float32, device=v.device)
     with torch.cuda.device(v.device):
@@ -358,12 +334,10 @@ def drop_in(original: Callable) -> Callable:
     ``4 <= square_size <= 32``, at most 8 Gaussians per triangle, autograd is off and no graph is being captured; every other call --
     ``square_size < 3`` and its ``ValueError`` among them -- runs ``original`` with the caller's arguments, decided before anything is
     consumed.  ``MeshRasterizer``, ``RasterizationSettings`` and ``Meshes`` are the reference module's own; no shader is built."""
-    from . import _lib
-
     names = getattr(original, "__globals__", {})
 
     def takes(rc, square_size, n_sh, texture_with_gaussian_renders) -> bool:
-        if not texture_with_gaussian_renders or torch.is_grad_enabled() or _lib.capturing():
+        if not texture_with_gaussian_renders or torch.is_grad_enabled() or _takes.capturing(ALLOCATES):
             return False
         if type(square_size) is not int or not MIN_S <= square_size <= MAX_S or type(n_sh) is not int:
             return False
@@ -415,7 +389,5 @@ def drop_in(original: Callable) -> Callable:
             bake_view(tex, count, owner, rgb_img[..., :3], fragments.pix_to_face, fragments.bary_coords, fragments.zbuf, face_uvs)
         return verts_uv, faces_uv, tex / count.clamp(min=1)
 
-    extract_texture_image_and_uv_from_gaussians.fallback = original
-    extract_texture_image_and_uv_from_gaussians.__doc__ = ("extract_texture_image_and_uv_from_gaussians: the HIP texture bake where it applies "
-                                                           "(autovfx_amd/texture.py), the reference's otherwise.")
-    return extract_texture_image_and_uv_from_gaussians
+    return _takes.dressed(extract_texture_image_and_uv_from_gaussians, "extract_texture_image_and_uv_from_gaussians", original,
+                          "extract_texture_image_and_uv_from_gaussians", "texture")

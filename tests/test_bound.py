@@ -13,6 +13,7 @@ import torch
 
 import bound_cases as BC
 from autovfx_amd import bound
+from helpers import OnGpu
 from meshattrs_cases import atomic_sum_check
 
 F32 = np.float32
@@ -173,26 +174,28 @@ def test_host_degenerate_rows():
 
 # ---- what the kernels refuse ----------------------------------------------------------------------------------------------------------
 
-def _args(case, **changed):
-    t = {k: torch.from_numpy(np.ascontiguousarray(case[k])) for k in ("verts", "faces", "bary", "complex", "log_scales", "thickness")}
+def _args(case, cls=torch.Tensor, **changed):
+    t = {k: torch.from_numpy(np.ascontiguousarray(case[k])).as_subclass(cls) for k in ("verts", "faces", "bary", "complex", "log_scales", "thickness")}
     t.update(changed)
     return [t[k] for k in ("verts", "faces", "bary", "complex", "log_scales", "thickness")]
 
 
 def test_refusals_raise_value_error_with_their_reason():
     case = BC.sized_case(4, 3, seed=1)
-    t = lambda k: torch.from_numpy(case[k])
-    for changed, reason in ((dict(), "must be on a GPU"),
-                            (dict(verts=t("verts").double()), "verts must be float32"),
+    with pytest.raises(ValueError, match="must be on a GPU"):
+        bound.bound_gaussians(*_args(case))
+    t = lambda k: torch.from_numpy(case[k]).as_subclass(OnGpu)     # a device is asked for before a dtype or a shape: these say they are on one
+    rand = lambda *shape: torch.rand(*shape).as_subclass(OnGpu)
+    for changed, reason in ((dict(verts=t("verts").double()), "verts must be float32"),
                             (dict(faces=t("faces").int()), "faces must be int64"),
                             (dict(verts=t("verts")[:, :2]), r"verts must be \[V, 3\]"),
                             (dict(complex=t("complex")[:-1]), r"complex must be \[F G, 2\]"),
                             (dict(log_scales=t("log_scales").reshape(-1)), r"log_scales must be \[F G, 2\]"),
-                            (dict(bary=torch.rand(9, 3), complex=torch.rand(36, 2), log_scales=torch.rand(36, 2)), "at most 8"),
-                            (dict(thickness=torch.rand(2)), "thickness must hold one element"),
+                            (dict(bary=rand(9, 3), complex=rand(36, 2), log_scales=rand(36, 2)), "at most 8"),
+                            (dict(thickness=rand(2)), "thickness must hold one element"),
                             (dict(thickness=3.7e-6), "must be a torch.Tensor")):
         with pytest.raises(ValueError, match=reason):
-            bound.bound_gaussians(*_args(case, **changed))
+            bound.bound_gaussians(*_args(case, OnGpu, **changed))
     with pytest.raises(ValueError, match="want must name"):
         bound.bound_gaussians(*_args(case), want=("normals",))
     with pytest.raises(ValueError, match="want must name"):

@@ -235,7 +235,7 @@ def test_mixed_devices_and_graph_capture_are_refused(monkeypatch):
     from autovfx_amd import _lib
     case = BC.sized_case(4, 3, seed=1)
     t = {k: torch.from_numpy(np.ascontiguousarray(case[k])).to(DEV) for k in INPUTS}
-    with pytest.raises(ValueError, match="complex must be on cuda"):
+    with pytest.raises(ValueError, match="complex must be on a GPU"):
         bound.bound_gaussians(*(t[k].cpu() if k == "complex" else t[k] for k in INPUTS))
     with pytest.raises(ValueError, match="must be on a GPU"):
         bound.bound_gaussians(*(t[k].cpu() for k in INPUTS))

@@ -11,6 +11,7 @@ import torch
 
 import field_cases as FC
 from autovfx_amd import field
+from helpers import fake_gpu as fake
 
 F = np.float32
 
@@ -96,14 +97,6 @@ def test_why_not_reasons():
     with pytest.raises(ValueError, match="host number"):
         field.field_values(x, idx, c, M, s, density_factor=torch.tensor(1.0))
     assert "torch.Tensor" in field._why_not(x.numpy(), idx, c, M, s)
-    meta = lambda *shape, dtype=torch.float32: torch.empty(*shape, dtype=dtype, device="meta")
-
-    class Cuda(torch.Tensor):       # shape / dtype checks without a device: a meta tensor that says it is on the GPU
-        is_cuda = True
-
-    def fake(*shape, dtype=torch.float32):
-        return meta(*shape, dtype=dtype).as_subclass(Cuda)
-
     good = dict(x=fake(5, 3), idx=fake(5, 4, dtype=torch.int64), centers=fake(7, 3), inv_scaled_rotation=fake(7, 3, 3), strengths=fake(7, 1))
     why = lambda **kw: field._why_not(**{**good, **kw})
     with mock.patch("torch.cuda.is_initialized", lambda: False):

@@ -11,6 +11,7 @@ import torch
 
 from autovfx_amd import hook, knn
 from autovfx_amd.knn import knn_points_host, knn_points_takes
+from helpers import fake_gpu as _gpu
 
 F = np.float32
 REL = 16 * 2.0 ** -24          # the bound tests/test_knn.py holds the same expression to
@@ -82,16 +83,6 @@ def test_a_nan_point_is_in_nobodys_row_and_has_an_empty_row():
     # fewer candidates than K: the rest of the row is (inf, -1)
     d, i = knn_points_host(pts[:12], pts[:12], 16)
     assert np.all(np.isfinite(d[0, :10])) and np.all(np.isposinf(d[0, 10:])) and np.all(i[0, 10:] == -1)
-
-
-class _OnGpu(torch.Tensor):
-    """A CPU tensor that says it lives on a GPU: what knn_points_takes looks at, on a machine without one."""
-    is_cuda = property(lambda self: True)
-    device = property(lambda self: torch.device("cuda:0"))
-
-
-def _gpu(*shape, dtype=torch.float32, requires_grad=False):
-    return torch.zeros(*shape, dtype=dtype).as_subclass(_OnGpu).requires_grad_(requires_grad)
 
 
 def test_which_calls_the_kernels_take():

@@ -12,6 +12,7 @@ import torch
 
 import levelset_cases as LC
 from autovfx_amd import levelset
+from helpers import fake_gpu as fake
 
 F = np.float32
 LEVELS = {1: [0.3], 3: [0.1, 0.3, 0.5], 8: [0.05, 0.1, 0.2, 0.3, 0.4, 0.5, 0.7, 0.9]}
@@ -136,14 +137,6 @@ def test_why_not_reasons():
     with pytest.raises(ValueError, match="host number"):
         levelset.level_surface(o, v, sd, idx, c, M, s, [0.3], range_size=torch.tensor(3.0))
     assert "torch.Tensor" in levelset._why_not(o.numpy(), v, sd, idx, c, M, s, [0.3])
-    meta = lambda *shape, dtype=torch.float32: torch.empty(*shape, dtype=dtype, device="meta")
-
-    class Cuda(torch.Tensor):       # shape / dtype checks without a device: a meta tensor that says it is on the GPU
-        is_cuda = True
-
-    def fake(*shape, dtype=torch.float32):
-        return meta(*shape, dtype=dtype).as_subclass(Cuda)
-
     good = dict(origins=fake(5, 3), dirs=fake(5, 3), stds=fake(5), idx=fake(5, 4, dtype=torch.int64), centers=fake(7, 3),
                 inv_scaled_rotation=fake(7, 3, 3), strengths=fake(7, 1), levels=[0.1, 0.3, 0.5])
     why = lambda **kw: levelset._why_not(**{**good, **kw})

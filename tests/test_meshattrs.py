@@ -14,6 +14,7 @@ import meshattrs_cases as cases
 from autovfx_amd import hook, meshattrs
 from autovfx_amd.meshattrs import (face_areas_normals_backward_host, face_areas_normals_host, interp_face_attrs_backward_host,
                                    interp_face_attrs_host)
+from helpers import OnOtherGpu as _OnOtherGpu, fake_gpu as _gpu
 
 F = np.float32
 OPERATORS = ("face_areas_normals_forward", "face_areas_normals_backward", "interpolate_face_attributes_forward",
@@ -184,20 +185,6 @@ def test_empty_slots_and_faces_past_the_end():
 
 
 # ---- which calls the kernels take ---------------------------------------------------------------------------------------------------
-
-class _OnGpu(torch.Tensor):
-    """A CPU tensor that says it lives on a GPU: enough for the checks, which read ``is_cuda`` and ``device`` and never the data."""
-    is_cuda = property(lambda self: True)
-    device = property(lambda self: torch.device("cuda:0"))
-
-
-class _OnOtherGpu(_OnGpu):
-    device = property(lambda self: torch.device("cuda:1"))
-
-
-def _gpu(*shape, dtype=torch.float32, cls=_OnGpu):
-    return torch.zeros(*shape, dtype=dtype).as_subclass(cls)
-
 
 def _faces_call(**over):
     args = dict(grad_areas=_gpu(5), grad_normals=_gpu(5, 3), verts=_gpu(7, 3), faces=_gpu(5, 3, dtype=torch.int64))

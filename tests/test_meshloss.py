@@ -12,6 +12,7 @@ import torch
 import meshloss_cases as cases
 from autovfx_amd import hook, meshloss
 from autovfx_amd.meshloss import mesh_normal_consistency_backward_host, mesh_normal_consistency_host, plan_host
+from helpers import OnOtherGpu as _OnOtherGpu, fake_gpu as _gpu
 
 F = np.float32
 
@@ -314,27 +315,13 @@ def test_the_tree_sum_is_the_contracts():
 
 # ---- which calls the kernels take, and the drop-in -----------------------------------------------------------------------------------------
 
-class _OnGpu(torch.Tensor):
-    """A CPU tensor that says it lives on a GPU: enough for the checks, which read ``is_cuda`` and ``device`` and never the data."""
-    is_cuda = property(lambda self: True)
-    device = property(lambda self: torch.device("cuda:0"))
-
-
-class _OnOtherGpu(_OnGpu):
-    device = property(lambda self: torch.device("cuda:1"))
-
-
-def _gpu(*shape, dtype=torch.float32, cls=_OnGpu):
-    return torch.zeros(*shape, dtype=dtype).as_subclass(cls)
-
-
 def test_direct_calls_say_why_not():
     verts, faces = _gpu(7, 3), _gpu(5, 3, dtype=torch.int64)
     assert meshloss._why_not(verts, faces) is None and meshloss._why_not(_gpu(3, 7).t(), _gpu(3, 5, dtype=torch.int64).t()) is None
     assert meshloss._why_not(_gpu(0, 3), _gpu(0, 3, dtype=torch.int64)) is None
     refused = (((torch.zeros(7, 3), faces), "GPU"), ((_gpu(7, 3, dtype=torch.float64), faces), "float32"), ((_gpu(7, 2), faces), r"\[V, 3\]"),
                ((_gpu(21), faces), r"\[V, 3\]"), ((verts, _gpu(5, 3, dtype=torch.int32)), "int64"), ((verts, _gpu(5, 4, dtype=torch.int64)), r"\[F, 3\]"),
-               ((verts, torch.zeros(5, 3, dtype=torch.int64)), "cuda:0"), ((verts, _gpu(5, 3, dtype=torch.int64, cls=_OnOtherGpu)), "cuda:0"),
+               ((verts, torch.zeros(5, 3, dtype=torch.int64)), "faces must be on a GPU"), ((verts, _gpu(5, 3, dtype=torch.int64, cls=_OnOtherGpu)), "cuda:0"),
                ((np.zeros((7, 3), F), faces), "torch.Tensor"), ((verts, None), "torch.Tensor"))
     for args, word in refused:
         with pytest.raises(ValueError, match=word):

@@ -14,6 +14,7 @@ from autovfx_amd import frame_loop, meshquery
 from autovfx_amd.meshquery import closest_triangles_host, triangle_distance_host
 
 import meshquery_cases as cases
+from helpers import fake_gpu as _gpu
 
 F32 = np.float32
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -360,16 +361,6 @@ def test_pruned_restatement_equals_the_brute_force(name):
     assert np.all(want[0][fine] >= 0) and np.all(want[0][~fine] == -1) and np.all(np.isposinf(want[1][-2:]))
 
 
-class _OnGpu(torch.Tensor):
-    """A CPU tensor that says it lives on a GPU: what the direct entry points look at, on a machine without one."""
-    is_cuda = property(lambda self: True)
-    device = property(lambda self: torch.device("cuda:0"))
-
-
-def _gpu(*shape, dtype=torch.float32):
-    return torch.zeros(*shape, dtype=dtype).as_subclass(_OnGpu)
-
-
 def test_direct_calls_raise_value_error_with_the_reason():
     v, f, p = _gpu(8, 3), _gpu(4, 3, dtype=torch.int64), _gpu(5, 3)
     with pytest.raises(ValueError, match="GPU"):
@@ -378,9 +369,9 @@ def test_direct_calls_raise_value_error_with_the_reason():
         meshquery.plan(torch.zeros(8, 3), torch.zeros(4, 3, dtype=torch.int64))
     with pytest.raises(ValueError, match="GPU"):
         meshquery.closest_triangles(torch.zeros(5, 3), v, f)
-    with pytest.raises(ValueError, match="float32 and faces int64"):
+    with pytest.raises(ValueError, match="faces must be int64"):
         meshquery.closest_triangles(p, v, _gpu(4, 3, dtype=torch.int32))
-    with pytest.raises(ValueError, match="float32 and faces int64"):
+    with pytest.raises(ValueError, match="verts must be float32"):
         meshquery.plan(_gpu(8, 3, dtype=torch.float64), f)
     with pytest.raises(ValueError, match=r"\[V, 3\]"):
         meshquery.plan(_gpu(8, 2), f)

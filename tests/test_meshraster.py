@@ -18,6 +18,7 @@ import meshraster_cases as cases
 from autovfx_amd import hook, meshraster
 from autovfx_amd.meshraster import rasterize_face_verts_host, rasterize_takes
 from meshraster_cases import one_mesh, tri_around
+from helpers import fake_gpu as _gpu
 
 F = np.float32
 
@@ -281,16 +282,6 @@ def test_no_faces():
     assert all(np.all(o == -1) for o in out)
     with pytest.raises(ValueError, match="blur_radius"):
         rasterize_face_verts_host(np.zeros((0, 3, 3), F), [0], [0], np.zeros(0, np.int64), (3, 5), 1e-4, 2)
-
-
-class _OnGpu(torch.Tensor):
-    """A CPU tensor that says it lives on a GPU: what rasterize_takes looks at, on a machine without one."""
-    is_cuda = property(lambda self: True)
-    device = property(lambda self: torch.device("cuda:0"))
-
-
-def _gpu(*shape, dtype=torch.float32, requires_grad=False):
-    return torch.zeros(*shape, dtype=dtype).as_subclass(_OnGpu).requires_grad_(requires_grad)
 
 
 def _call(F_=7, N=1, **over):
